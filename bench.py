@@ -5,7 +5,11 @@ One STEP = one pass of the hot path (extract + associate + vote + normal equatio
 BASELINE.json's metric unit) over a batch of synthetic KITTI-shape 64-ring scans that is already resident in
 HBM when the timed region starts.  `value` = scans processed by all ranks per second.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line.  --full adds what the headline figure does not need: the
+CPU baseline, the box calibration, per-kernel HIP-event times and the roofline, the per-slot self-check and the RCCL check.
+--dump-outputs DIR writes what the last timed step computed as .npy files, for comparing two builds output for output.
 
 N > 1: one process per GPU.  Started under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment) this
 process IS a rank; started as a plain command line it only LAUNCHES the N ranks as fresh child processes -- before it imports
@@ -496,6 +500,48 @@ def issue_from_profile(args, kernels, path=None):
         return None, "profiles/sq_issue.json unreadable: " + repr(e)[:80]
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SLOTS = 8            # slots whose feature clouds, correspondences and vote go into the dump (a fixed, seeded choice)
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy (float32 stays float32, anything else becomes float64)."""
+    arrays = {k: np.ascontiguousarray(v, np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def hot_path_outputs(ctx, batch):
+    """What a caller of the hot path receives for the slots 0 .. batch-1: every slot's pose, normal equations and counts; for a fixed
+    sample of slots also the four feature clouds, the correspondences and the vote (one row per entry, the slot in column 0)."""
+    S = [ctx.scan_info(i) for i in range(batch)]
+    Pi = [ctx.pair_info(i) for i in range(batch)]
+    ne = [ctx.normal_equations_result(i) for i in range(batch)]
+    out = {"pose": np.stack([ctx.pose(i) for i in range(batch)]),
+           "normal_equations_H": np.stack([x[0] for x in ne]), "normal_equations_g": np.stack([x[1] for x in ne]),
+           "normal_equations_cost": np.array([x[2] for x in ne]),
+           "scan_info": np.array([[getattr(s, f) for f, _ in s._fields_] for s in S], np.float64),
+           "pair_info": np.array([[getattr(p, f) for f, _ in p._fields_] for p in Pi], np.float64)}
+    slots = np.sort(np.random.default_rng(0x5EED).choice(batch, size=min(DUMP_SAMPLE_SLOTS, batch), replace=False))
+    rows = {k: [] for k in ("sharp", "less_sharp", "flat", "less_flat", "edge_corr", "plane_corr", "vote")}
+    for i in slots:
+        for k, v in ctx.features(int(i)).items():
+            rows[k].append(np.hstack([np.full((len(v), 1), i, np.float32), v]))
+        cols = [np.full(Pi[i].n_edge, i)] + list(ctx.edge_corr(int(i)))
+        rows["edge_corr"].append(np.stack(cols, axis=1).astype(np.float64))
+        cols = [np.full(Pi[i].n_plane, i)] + list(ctx.plane_corr(int(i)))
+        rows["plane_corr"].append(np.stack(cols, axis=1).astype(np.float64))
+        cols = [np.full(Pi[i].n_plane, i)] + list(ctx.vote_result(int(i)))
+        rows["vote"].append(np.stack(cols, axis=1).astype(np.float64))
+    out["sample_slots"] = slots.astype(np.float64)
+    out.update({"sample_" + k: np.concatenate(v) for k, v in rows.items()})
+    return out
+
+
 def launch_ranks(args, argv):
     """`python bench.py --gpus N` without a launcher: start N fresh child processes of this same command line, one per GPU, with
     RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set (what torch.distributed.run would set), relay rank 0's stdout --
@@ -565,6 +611,156 @@ def launch_ranks(args, argv):
     return rc
 
 
+def analyse_hot_path(args, ctx, step, prof, order, rank, world, elapsed):
+    """--full: the per-slot self-check of the timed work (every rank) and, on rank 0, (config entries, roofline) from the HIP-event
+    profile of the timed region `prof`, the run's actual counts and the stamped counter files under profiles/."""
+    # With LIGHTLOAM_TWO_STREAM=1 the timed region runs k_build_grid and k_associate side by side on two streams (ll_set_two_stream; off by
+    # default: measured, no gain), which the event profiler records as ONE interval.  Their own durations -- each kernel alone on the chip,
+    # what a roofline figure is defined on -- then come from a short pass on one stream behind the timed region (not part of `value`).
+    STAGE = "k_build_grid||k_associate"
+    stage_two_stream_ms = None
+    if STAGE in prof and prof[STAGE][1]:
+        stage_two_stream_ms = prof[STAGE][0] / prof[STAGE][1]
+        ctx.set_two_stream(False)
+        step(); ctx.synchronize(); ctx.profile_read(reset=True)
+        for _ in range(3):
+            step()
+        sprof = ctx.profile_read(reset=True)
+        ctx.set_two_stream(True)
+        for k in ("k_build_grid", "k_associate"):
+            prof[k] = sprof[k]
+        prof = {k: v for k, v in prof.items() if k != STAGE}
+    ctx.profile_enable(False)
+
+    # sanity on the result of the timed work (not timed): EVERY slot extracted (status 0),
+    # found correspondences and solved to a finite pose; slots that hold the same (previous, current) pair of scans and the
+    # same guess must give bit-identical poses (the batch cycles through `distinct`+1 scans)
+    ab = ctx.algorithmic_bytes(0, args.batch)
+    # per-kernel share of SURVEY.md section 8d's algorithmic bytes (every array counted once, at the kernel that must touch
+    # it), summed over the batch from the run's actual counts
+    tot = dict(n_in=0, n=0, feat=0, lsharp=0, lflat=0, q=0, ne=0, np_=0, nsel=0)
+    pose_of_pair = {}
+    bad = []
+    for i in range(args.batch):
+        si = ctx.scan_info(i); pi = ctx.pair_info(i); pose = ctx.pose(i)
+        if si.status != 0 or pi.n_edge <= 0 or pi.n_plane_selected <= 0 or not np.isfinite(pose).all():
+            bad.append((i, si.status, pi.n_edge, pi.n_plane_selected))
+        key = (order[i], order[i + 1])
+        if pose_of_pair.setdefault(key, pose).tobytes() != pose.tobytes():
+            bad.append((i, "pose differs from the slot with the same scan pair", key))
+        tot["n_in"] += si.n_in; tot["n"] += si.n
+        tot["feat"] += si.n_sharp + si.n_less_sharp + si.n_flat + si.n_less_flat
+        tot["lsharp"] += si.n_less_sharp; tot["lflat"] += si.n_less_flat; tot["q"] += si.n_sharp + si.n_flat
+        tot["ne"] += pi.n_edge; tot["np_"] += pi.n_plane; tot["nsel"] += pi.n_plane_selected
+    if bad and not os.environ.get("LL_BENCH_TIMING_BUILD"):     # set only by tools/ that time deliberately incomplete builds
+        raise SystemExit(f"bench self-check failed on rank {rank}: {len(bad)} slot(s), first {bad[:5]}")
+    kernel_bytes = {
+        "k_first_kept": 0.0, "k_offsets": 0.0, "k_gn_step": 0.0,
+        "k_organize": 4.0 * args.input_stride * tot["n_in"] + 16.0 * tot["n"],   # read the raw scan, write laserCloud (one pass)
+        "k_classify": 4.0 * args.input_stride * tot["n_in"],                            # (tile-parallel path of small calls) read the raw scan
+        "k_scatter": 16.0 * tot["n"],                                # (tile-parallel path) write laserCloud
+        # the ring stage is two launches since round 4 (ll_pick.hip, ll_features.hip)
+        "k_ring_pick": 17.0 * tot["n"],                               # read laserCloud, write labels (+ 352 B of lists per ring)
+        "k_ring_features": 16.0 * tot["n"] + 16.0 * tot["feat"],   # read laserCloud (again), write the four feature clouds
+        "k_build_grid": 16.0 * (tot["lsharp"] + tot["lflat"]),       # read the target clouds once
+        "k_associate": 16.0 * tot["q"] + 8.0 * tot["ne"] + 12.0 * tot["np_"],
+        "k_vote": 32.0 * tot["np_"] + 8.0 * tot["nsel"],
+        "k_normal_equations": 48.0 * tot["ne"] + 64.0 * tot["nsel"] + 216.0 * args.batch,
+    }
+
+    if rank != 0:
+        return None, None
+    # dominant kernel by summed HIP-event time (events on the library's own stream)
+    dom = max(prof, key=lambda k: prof[k][0])
+    dom_ms, dom_launches = prof[dom]
+    # launches of every kernel per step: one per chunk (the library's event pool holds ~800 steps; beyond that the
+    # recorded launches are a prefix of the run, so per-step figures come from the per-launch average, not the sum)
+    launches_per_step = 1 if args.chunk <= 0 else -(-args.batch // args.chunk)
+    bytes_per_launch = kernel_bytes[dom] / launches_per_step
+    avg_ms = dom_ms / max(1, dom_launches)
+    achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    traffic, traffic_note = traffic_from_profile(args, dom, launches_per_step)
+    ms_of = {k: v[0] / v[1] * launches_per_step for k, v in prof.items() if v[1]}
+    # the ring stage = what rounds 1-3 ran as ONE kernel: laserCloud counted once (SURVEY.md section 8d: 17 n + 16 feat)
+    stage_kernels = [k for k in ("k_ring_pick", "k_ring_features") if k in ms_of]
+    stage_ms = sum(ms_of[k] for k in stage_kernels)
+    stage_bytes = 17.0 * tot["n"] + 16.0 * tot["feat"]
+    stage_gbps = stage_bytes / (stage_ms * 1e-3) / 1e9 if stage_ms > 0 else 0.0
+    # which wall: vector / scalar instruction issue against bytes, from the stamped counter pass -- for EVERY kernel of the step, so
+    # that whichever kernel dominates (the ring kernels on 64 rings, k_associate on 128) is read against its own counters
+    all_kernels = [k for k in ms_of if kernel_bytes.get(k)]
+    issue, issue_note = issue_from_profile(args, all_kernels)
+    issue_out = {"source": issue_note}
+    bound = "unknown (no counter pass of this code, workload and batch: %s)" % issue_note
+    sr = stream_rates()
+    if issue is not None:
+        simd_slots = N_SIMD * CLOCK_GHZ * 1e9 / VALU_CYCLES                   # wave64 vector instructions per second, whole chip
+        scalar_slots = (N_SIMD / 4) * CLOCK_GHZ * 1e9                          # one scalar unit per CU, one instruction per cycle
+        for k in all_kernels:
+            t = ms_of[k] / launches_per_step * 1e-3
+            issue_out[k] = {"valu_wave_insts_per_launch": issue[k]["valu"], "salu_wave_insts_per_launch": issue[k]["salu"],
+                            "lds_wave_insts_per_launch": issue[k].get("lds"),
+                            "valu_busy": issue[k]["valu"] / (simd_slots * t), "salu_busy": issue[k]["salu"] / (scalar_slots * t),
+                            "hbm_frac": kernel_bytes[k] / launches_per_step / t / 1e9 / HBM_PEAK_GBS}
+        d = issue_out.get(dom)
+        # the kernel answers to the LARGEST of: vector issue, scalar issue, and the bytes it actually moves across the L2 <-> fabric
+        # boundary (counter traffic, not the algorithmic bytes: re-reads count) against what the chip streams (stream_rates(), else the peak)
+        t_dom = avg_ms * 1e-3
+        stream_ceiling = (sr.get("copy_GBps") or HBM_PEAK_GBS)
+        traffic_frac = (traffic / t_dom / 1e9 / HBM_PEAK_GBS) if (traffic and t_dom > 0) else None
+        traffic_of_stream = (traffic / t_dom / 1e9 / stream_ceiling) if (traffic and t_dom > 0) else None
+        if d:
+            byte_frac = max(d["hbm_frac"] * HBM_PEAK_GBS / stream_ceiling, traffic_of_stream or 0.0)
+            if max(d["valu_busy"], d["salu_busy"]) > byte_frac:
+                bound = "issue (vector %.0f %%, scalar %.0f %% busy; bytes %.0f %% of the HBM peak)" % (100 * d["valu_busy"], 100 * d["salu_busy"], 100 * d["hbm_frac"])
+            else:
+                bound = "hbm"
+        issue_out["decision"] = {"valu_busy": d["valu_busy"] if d else None, "salu_busy": d["salu_busy"] if d else None,
+                                 "algorithmic_bytes_frac_of_hbm_peak": d["hbm_frac"] if d else None,
+                                 "counter_traffic_frac_of_hbm_peak": traffic_frac,
+                                 "counter_traffic_frac_of_measured_stream_rate": traffic_of_stream,
+                                 "rule": "bound = hbm when the counter traffic's (or the algorithmic bytes') fraction of the measured streaming rate "
+                                         "(profiles/r05_stream_rate.json; the 8 TB/s peak without it) is the largest of the four, else issue; "
+                                         "unknown without a counter pass of this code",
+                                 "caveat": "the label names the LARGEST of the four fractions, not a saturated unit: below ~0.9 nothing is.  docs/rounds/r05.md 14.7: "
+                                           "k_ring_features got ~1 % faster for 15 % fewer bytes and again for 31 % fewer vector instructions; fewer "
+                                           "barriers bought 1-3 %"}
+        issue_out["model"] = ("valu_busy = SQ_INSTS_VALU / (%d SIMDs x %.1f GHz / %.1f cycles x launch time); salu_busy = SQ_INSTS_SALU / "
+                              "(%d scalar units x %.1f GHz x launch time)" % (N_SIMD, CLOCK_GHZ, VALU_CYCLES, N_SIMD // 4, CLOCK_GHZ))
+    whole_alg_bytes_per_step = ab["ext"] + ab["assoc"] + ab["vote"] + ab["rj"]
+    whole_alg_gbps = whole_alg_bytes_per_step * args.steps / elapsed / 1e9
+    counter_bytes_per_step = all_traffic_from_profile(args, all_kernels, launches_per_step)
+    config = {"distinct_scan_pairs": len(pose_of_pair),
+              "self_check": "every slot: status 0, correspondences > 0, finite pose; equal scan pairs -> bit-identical poses"}
+    roofline = {"bound": bound, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
+                "traffic_GBps": (traffic / (avg_ms * 1e-3) / 1e9) if (traffic and avg_ms > 0) else None,
+                "frac_of_measured_copy": achieved / (sr.get("copy_GBps") or HBM_COPY_GBS), "measured_copy_GBps": sr.get("copy_GBps") or HBM_COPY_GBS,
+                "measured_stream": sr,
+                "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": bytes_per_launch,
+                "whole_path_algorithmic_GBps": whole_alg_gbps,
+                # comparable across rounds (BASELINE.md's own definition: B x scans/s / peak, the whole path, every array counted once)
+                "frac_whole_path": whole_alg_gbps / HBM_PEAK_GBS,
+                # sum of the kernels' counter bytes / sum of the algorithmic bytes (1.0 = nothing re-read); null without a counter pass of this code
+                "wasted_traffic": (counter_bytes_per_step / whole_alg_bytes_per_step) if counter_bytes_per_step else None,
+                "issue": issue_out,
+                "ring_stage": {"kernels": stage_kernels, "ms_per_step": stage_ms, "algorithmic_bytes_per_step": stage_bytes,
+                               "achieved": stage_gbps, "frac": stage_gbps / HBM_PEAK_GBS,
+                               "note": "the stage rounds 1-3 ran as one kernel: laserCloud counted once (17 n + 16 features); each kernel's own "
+                                       "figure above counts what that launch must read and write"},
+                "kernel_ms_per_step": ms_of,
+                "association_stage": None if stage_two_stream_ms is None else {
+                    "schedule": "timed region: k_build_grid of one quarter of the batch beside k_associate of the quarter before it, two HIP "
+                                "streams ordered by events (LIGHTLOAM_TWO_STREAM=1 / ll_set_two_stream); kernel_ms_per_step's k_build_grid / "
+                                "k_associate: each kernel alone, from 3 one-stream steps behind the timed region",
+                    "two_stream_ms_per_step": stage_two_stream_ms * launches_per_step,
+                    "one_stream_ms_per_step": ms_of.get("k_build_grid", 0.0) + ms_of.get("k_associate", 0.0),
+                    "sum_of_kernel_ms_equals_ms_per_step_with": "the two-stream figure in place of the two kernels' own"},
+                "kernel_algorithmic_GBps": {k: kernel_bytes[k] / (v[0] / v[1] * launches_per_step * 1e-3) / 1e9
+                                            for k, v in prof.items() if v[1] and kernel_bytes.get(k)}}
+    return config, roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -586,7 +782,13 @@ def main():
     ap.add_argument("--input-stride", type=int, choices=[3, 4], default=4,
                     help="floats per resident raw point (ll_params.input_stride_floats): 4 = KITTI .bin / PointXYZ (the contract, default), "
                          "3 = x, y, z packed: the 4th float the reference never reads (scanRegistration.cpp:105-106) neither crosses PCIe nor is read from HBM")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="--mode hot: also measure and check what the headline figure does not need -- the CPU baseline (unless --no-cpu-baseline), "
+                         "the box calibration micro-run, per-kernel HIP-event times and the roofline, the per-slot self-check, the RCCL all-reduce check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--mode hot: after the timed steps, write what the hot path computed in its last step (rank 0) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--cpu-budget", type=float, default=24.0, help="seconds of CPU baseline, split over the 1 / 8 / 64 / all-cpu points of the sweep")
     ap.add_argument("--calibrate", action="store_true",
                     help="also launch k_calib_copy (1 GiB in + 1 GiB out) once: the known-byte launch tools/pmc_traffic.py "
@@ -613,6 +815,8 @@ def main():
     args.batch_defaulted = args.batch <= 0
     if args.share_gpu and args.backend != "gloo":
         raise SystemExit("--share-gpu puts every rank on device 0: RCCL cannot run there, use --backend gloo")
+    if args.dump_outputs and (args.mode != "hot" or args.stream_input):
+        raise SystemExit("--dump-outputs writes the hot path's outputs: --mode hot without --stream-input")
     if args.mode == "map" and (args.share_gpu or args.backend != "nccl"):
         raise SystemExit("--mode map runs its collectives on device buffers over RCCL: --backend nccl, one GPU per rank (no --share-gpu)")
     if args.workload == "hdl64":
@@ -657,7 +861,7 @@ def main():
     # every rank owns its own scans (different seed => different noise), same shape
     base, order, guesses = build_workload(args, args.batch, 0x5EED0000 + rank)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_host(args, 0x5EED0000 + rank)                              # before any HIP call in this process
 
     import torch
@@ -696,17 +900,21 @@ def main():
     def step():
         ctx.hot_path(0, args.batch, None, vote=True)     # pose restarts from the stored guess, device-to-device
 
-    # box calibration: a FIXED micro-run (the extract stage of the first 512 slots, three times, untimed warm-up first), HIP-event time
-    # of the ring kernels -- the boxes of the pool differ by up to 30 % in exactly these kernels (docs/rounds/r03.md 12.3a), so a slow
-    # draw shows here instead of looking like a regression of the headline
-    calib_n = min(512, args.batch)
-    ctx.extract(0, calib_n); ctx.synchronize()
-    ctx.profile_enable(True); ctx.profile_read(reset=True)
-    for _ in range(3):
-        ctx.extract(0, calib_n)
-    cprof = ctx.profile_read(reset=True)
-    ctx.profile_enable(False)
-    box_calibration_ms = sum(cprof[k][0] / max(1, cprof[k][1]) for k in ("k_ring_pick", "k_ring_features") if k in cprof and cprof[k][1])
+    box_calibration = {}
+    if args.full:
+        # box calibration: a FIXED micro-run (the extract stage of the first 512 slots, three times, untimed warm-up first), HIP-event time
+        # of the ring kernels -- the boxes of the pool differ by up to 30 % in exactly these kernels (docs/rounds/r03.md 12.3a), so a slow
+        # draw shows here instead of looking like a regression of the headline
+        calib_n = min(512, args.batch)
+        ctx.extract(0, calib_n); ctx.synchronize()
+        ctx.profile_enable(True); ctx.profile_read(reset=True)
+        for _ in range(3):
+            ctx.extract(0, calib_n)
+        cprof = ctx.profile_read(reset=True)
+        ctx.profile_enable(False)
+        box_calibration_ms = sum(cprof[k][0] / max(1, cprof[k][1]) for k in ("k_ring_pick", "k_ring_features") if k in cprof and cprof[k][1])
+        box_calibration = {"box_calibration_ms": box_calibration_ms,
+                           "box_calibration": "HIP-event time of the ring kernels over the first %d slots (fixed micro-run before the timed region)" % calib_n}
 
     def barrier():
         if dist is not None:
@@ -716,138 +924,30 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    ctx.profile_enable(True)
-    ctx.profile_read(reset=True)
+    if args.full:
+        ctx.profile_enable(True)
+        ctx.profile_read(reset=True)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
-    prof = ctx.profile_read(reset=True)
-    # With LIGHTLOAM_TWO_STREAM=1 the timed region runs k_build_grid and k_associate side by side on two streams (ll_set_two_stream; off by
-    # default: measured, no gain), which the event profiler records as ONE interval.  Their own durations -- each kernel alone on the chip,
-    # what a roofline figure is defined on -- then come from a short pass on one stream behind the timed region (not part of `value`).
-    STAGE = "k_build_grid||k_associate"
-    stage_two_stream_ms = None
-    if STAGE in prof and prof[STAGE][1]:
-        stage_two_stream_ms = prof[STAGE][0] / prof[STAGE][1]
-        ctx.set_two_stream(False)
-        step(); ctx.synchronize(); ctx.profile_read(reset=True)
-        for _ in range(3):
-            step()
-        sprof = ctx.profile_read(reset=True)
-        ctx.set_two_stream(True)
-        for k in ("k_build_grid", "k_associate"):
-            prof[k] = sprof[k]
-        prof = {k: v for k, v in prof.items() if k != STAGE}
-    ctx.profile_enable(False)
+    prof = ctx.profile_read(reset=True) if args.full else None
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, hot_path_outputs(ctx, args.batch))
 
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
     if dist is not None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
 
-    # sanity on the result of the timed work (not timed): EVERY slot extracted (status 0),
-    # found correspondences and solved to a finite pose; slots that hold the same (previous, current) pair of scans and the
-    # same guess must give bit-identical poses (the batch cycles through `distinct`+1 scans)
     info = ctx.scan_info(0)
-    ab = ctx.algorithmic_bytes(0, args.batch)
-    # per-kernel share of SURVEY.md section 8d's algorithmic bytes (every array counted once, at the kernel that must touch
-    # it), summed over the batch from the run's actual counts
-    tot = dict(n_in=0, n=0, feat=0, lsharp=0, lflat=0, q=0, ne=0, np_=0, nsel=0)
-    pose_of_pair = {}
-    bad = []
-    for i in range(args.batch):
-        si = ctx.scan_info(i); pi = ctx.pair_info(i); pose = ctx.pose(i)
-        if si.status != 0 or pi.n_edge <= 0 or pi.n_plane_selected <= 0 or not np.isfinite(pose).all():
-            bad.append((i, si.status, pi.n_edge, pi.n_plane_selected))
-        key = (order[i], order[i + 1])
-        if pose_of_pair.setdefault(key, pose).tobytes() != pose.tobytes():
-            bad.append((i, "pose differs from the slot with the same scan pair", key))
-        tot["n_in"] += si.n_in; tot["n"] += si.n
-        tot["feat"] += si.n_sharp + si.n_less_sharp + si.n_flat + si.n_less_flat
-        tot["lsharp"] += si.n_less_sharp; tot["lflat"] += si.n_less_flat; tot["q"] += si.n_sharp + si.n_flat
-        tot["ne"] += pi.n_edge; tot["np_"] += pi.n_plane; tot["nsel"] += pi.n_plane_selected
-    if bad and not os.environ.get("LL_BENCH_TIMING_BUILD"):     # set only by tools/ that time deliberately incomplete builds
-        raise SystemExit(f"bench self-check failed on rank {rank}: {len(bad)} slot(s), first {bad[:5]}")
-    kernel_bytes = {
-        "k_first_kept": 0.0, "k_offsets": 0.0, "k_gn_step": 0.0,
-        "k_organize": 4.0 * args.input_stride * tot["n_in"] + 16.0 * tot["n"],   # read the raw scan, write laserCloud (one pass)
-        "k_classify": 4.0 * args.input_stride * tot["n_in"],                            # (tile-parallel path of small calls) read the raw scan
-        "k_scatter": 16.0 * tot["n"],                                # (tile-parallel path) write laserCloud
-        # the ring stage is two launches since round 4 (ll_pick.hip, ll_features.hip)
-        "k_ring_pick": 17.0 * tot["n"],                               # read laserCloud, write labels (+ 352 B of lists per ring)
-        "k_ring_features": 16.0 * tot["n"] + 16.0 * tot["feat"],   # read laserCloud (again), write the four feature clouds
-        "k_build_grid": 16.0 * (tot["lsharp"] + tot["lflat"]),       # read the target clouds once
-        "k_associate": 16.0 * tot["q"] + 8.0 * tot["ne"] + 12.0 * tot["np_"],
-        "k_vote": 32.0 * tot["np_"] + 8.0 * tot["nsel"],
-        "k_normal_equations": 48.0 * tot["ne"] + 64.0 * tot["nsel"] + 216.0 * args.batch,
-    }
-
+    if args.full:
+        full_config, roofline = analyse_hot_path(args, ctx, step, prof, order, rank, world, elapsed)
     if rank == 0:
         total_scans = args.batch * world * args.steps
         value = total_scans / elapsed
-        # dominant kernel by summed HIP-event time (events on the library's own stream)
-        dom = max(prof, key=lambda k: prof[k][0])
-        dom_ms, dom_launches = prof[dom]
-        # launches of every kernel per step: one per chunk (the library's event pool holds ~800 steps; beyond that the
-        # recorded launches are a prefix of the run, so per-step figures come from the per-launch average, not the sum)
-        launches_per_step = 1 if args.chunk <= 0 else -(-args.batch // args.chunk)
-        bytes_per_launch = kernel_bytes[dom] / launches_per_step
-        avg_ms = dom_ms / max(1, dom_launches)
-        achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        traffic, traffic_note = traffic_from_profile(args, dom, launches_per_step)
-        ms_of = {k: v[0] / v[1] * launches_per_step for k, v in prof.items() if v[1]}
-        # the ring stage = what rounds 1-3 ran as ONE kernel: laserCloud counted once (17 n + 16 feat)
-        stage_kernels = [k for k in ("k_ring_pick", "k_ring_features") if k in ms_of]
-        stage_ms = sum(ms_of[k] for k in stage_kernels)
-        stage_bytes = 17.0 * tot["n"] + 16.0 * tot["feat"]
-        stage_gbps = stage_bytes / (stage_ms * 1e-3) / 1e9 if stage_ms > 0 else 0.0
-        # which wall: vector / scalar instruction issue against bytes, from the stamped counter pass -- for EVERY kernel of the step, so
-        # that whichever kernel dominates (the ring kernels on 64 rings, k_associate on 128) is read against its own counters
-        all_kernels = [k for k in ms_of if kernel_bytes.get(k)]
-        issue, issue_note = issue_from_profile(args, all_kernels)
-        issue_out = {"source": issue_note}
-        bound = "unknown (no counter pass of this code, workload and batch: %s)" % issue_note
-        sr = stream_rates()
-        if issue is not None:
-            simd_slots = N_SIMD * CLOCK_GHZ * 1e9 / VALU_CYCLES                   # wave64 vector instructions per second, whole chip
-            scalar_slots = (N_SIMD / 4) * CLOCK_GHZ * 1e9                          # one scalar unit per CU, one instruction per cycle
-            for k in all_kernels:
-                t = ms_of[k] / launches_per_step * 1e-3
-                issue_out[k] = {"valu_wave_insts_per_launch": issue[k]["valu"], "salu_wave_insts_per_launch": issue[k]["salu"],
-                                "lds_wave_insts_per_launch": issue[k].get("lds"),
-                                "valu_busy": issue[k]["valu"] / (simd_slots * t), "salu_busy": issue[k]["salu"] / (scalar_slots * t),
-                                "hbm_frac": kernel_bytes[k] / launches_per_step / t / 1e9 / HBM_PEAK_GBS}
-            d = issue_out.get(dom)
-            # the kernel answers to the LARGEST of: vector issue, scalar issue, and the bytes it actually moves across the L2 <-> fabric
-            # boundary (counter traffic, not the algorithmic bytes: re-reads count) against what the chip streams (stream_rates(), else the peak)
-            t_dom = avg_ms * 1e-3
-            stream_ceiling = (sr.get("copy_GBps") or HBM_PEAK_GBS)
-            traffic_frac = (traffic / t_dom / 1e9 / HBM_PEAK_GBS) if (traffic and t_dom > 0) else None
-            traffic_of_stream = (traffic / t_dom / 1e9 / stream_ceiling) if (traffic and t_dom > 0) else None
-            if d:
-                byte_frac = max(d["hbm_frac"] * HBM_PEAK_GBS / stream_ceiling, traffic_of_stream or 0.0)
-                if max(d["valu_busy"], d["salu_busy"]) > byte_frac:
-                    bound = "issue (vector %.0f %%, scalar %.0f %% busy; bytes %.0f %% of the HBM peak)" % (100 * d["valu_busy"], 100 * d["salu_busy"], 100 * d["hbm_frac"])
-                else:
-                    bound = "hbm"
-            issue_out["decision"] = {"valu_busy": d["valu_busy"] if d else None, "salu_busy": d["salu_busy"] if d else None,
-                                     "algorithmic_bytes_frac_of_hbm_peak": d["hbm_frac"] if d else None,
-                                     "counter_traffic_frac_of_hbm_peak": traffic_frac,
-                                     "counter_traffic_frac_of_measured_stream_rate": traffic_of_stream,
-                                     "rule": "bound = hbm when the counter traffic's (or the algorithmic bytes') fraction of the measured streaming rate "
-                                             "(profiles/r05_stream_rate.json; the 8 TB/s peak without it) is the largest of the four, else issue; "
-                                             "unknown without a counter pass of this code",
-                                     "caveat": "the label names the LARGEST of the four fractions, not a saturated unit: below ~0.9 nothing is.  docs/rounds/r05.md 14.7: "
-                                               "k_ring_features got ~1 % faster for 15 % fewer bytes and again for 31 % fewer vector instructions; fewer "
-                                               "barriers bought 1-3 %"}
-            issue_out["model"] = ("valu_busy = SQ_INSTS_VALU / (%d SIMDs x %.1f GHz / %.1f cycles x launch time); salu_busy = SQ_INSTS_SALU / "
-                                  "(%d scalar units x %.1f GHz x launch time)" % (N_SIMD, CLOCK_GHZ, VALU_CYCLES, N_SIMD // 4, CLOCK_GHZ))
-        whole_alg_bytes_per_step = ab["ext"] + ab["assoc"] + ab["vote"] + ab["rj"]
-        whole_alg_gbps = whole_alg_bytes_per_step * args.steps / elapsed / 1e9
-        counter_bytes_per_step = all_traffic_from_profile(args, all_kernels, launches_per_step)
         out = {
             "metric": metric_name(args),
             "value": value, "unit": "scans/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -857,47 +957,23 @@ def main():
             "config": {"workload": workload_name(args) + ", feature extraction + graph-match + one GN iteration per scan pair, inputs resident in HBM",
                        "workload_id": args.workload, "max_ring_points": args.max_ring_points or 2304,
                        "scans_per_gpu_per_step": args.batch, "chunk": args.chunk or args.batch,
-                       "distinct_scans": args.distinct + 1, "distinct_scan_pairs": len(pose_of_pair),
-                       "box_calibration_ms": box_calibration_ms,
-                       "box_calibration": "HIP-event time of the ring kernels over the first %d slots (fixed micro-run before the timed region)" % calib_n,
+                       "distinct_scans": args.distinct + 1,
                        "ring_pipeline": "k_ring_pick + k_ring_features; ring-strided less-flat cloud, no hand-over between the rings of a scan",
-                       "self_check": "every slot: status 0, correspondences > 0, finite pose; equal scan pairs -> bit-identical poses",
                        "points_per_scan_in": int(info.n_in), "points_per_scan_kept": int(info.n),
                        "input_bytes_per_point": 4 * args.input_stride,
                        "association": "k_associate in one traversal (per-ring minima collected while the nearest neighbour is searched)",
-                       "parallelism": f"scan-parallel x{world}, no data-path collective"},
-            "roofline": {"bound": bound, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
-                         "traffic_GBps": (traffic / (avg_ms * 1e-3) / 1e9) if (traffic and avg_ms > 0) else None,
-                         "frac_of_measured_copy": achieved / (sr.get("copy_GBps") or HBM_COPY_GBS), "measured_copy_GBps": sr.get("copy_GBps") or HBM_COPY_GBS,
-                         "measured_stream": sr,
-                         "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "whole_path_algorithmic_GBps": whole_alg_gbps,
-                         # comparable across rounds (BASELINE.md's own definition: B x scans/s / peak, the whole path, every array counted once)
-                         "frac_whole_path": whole_alg_gbps / HBM_PEAK_GBS,
-                         # sum of the kernels' counter bytes / sum of the algorithmic bytes (1.0 = nothing re-read); null without a counter pass of this code
-                         "wasted_traffic": (counter_bytes_per_step / whole_alg_bytes_per_step) if counter_bytes_per_step else None,
-                         "issue": issue_out,
-                         "ring_stage": {"kernels": stage_kernels, "ms_per_step": stage_ms, "algorithmic_bytes_per_step": stage_bytes,
-                                        "achieved": stage_gbps, "frac": stage_gbps / HBM_PEAK_GBS,
-                                        "note": "the stage rounds 1-3 ran as one kernel: laserCloud counted once (17 n + 16 features); each kernel's own "
-                                                "figure above counts what that launch must read and write"},
-                         "kernel_ms_per_step": ms_of,
-                         "association_stage": None if stage_two_stream_ms is None else {
-                             "schedule": "timed region: k_build_grid of one quarter of the batch beside k_associate of the quarter before it, two HIP "
-                                         "streams ordered by events (LIGHTLOAM_TWO_STREAM=1 / ll_set_two_stream); kernel_ms_per_step's k_build_grid / "
-                                         "k_associate: each kernel alone, from 3 one-stream steps behind the timed region",
-                             "two_stream_ms_per_step": stage_two_stream_ms * launches_per_step,
-                             "one_stream_ms_per_step": ms_of.get("k_build_grid", 0.0) + ms_of.get("k_associate", 0.0),
-                             "sum_of_kernel_ms_equals_ms_per_step_with": "the two-stream figure in place of the two kernels' own"},
-                         "kernel_algorithmic_GBps": {k: kernel_bytes[k] / (v[0] / v[1] * launches_per_step * 1e-3) / 1e9
-                                                     for k, v in prof.items() if v[1] and kernel_bytes.get(k)}},
+                       "parallelism": f"scan-parallel x{world}, no data-path collective"}
         }
+        if args.full:
+            out["config"].update(box_calibration, **full_config)
+            out["roofline"] = roofline
         if cpu is not None:
             out["cpu_baseline"] = cpu
-    # RCCL sanity on every run (also N = 1): the 28-double all-reduce of the row-parallel mode (21 + 6 + 1 unique values of
+    # --full: RCCL sanity (also N = 1): the 28-double all-reduce of the row-parallel mode (21 + 6 + 1 unique values of
     # JtJ, Jtr, cost) on a device buffer, checked against the closed form and timed.  Not part of `value`.
-    rccl = rccl_check(torch, dist, world, rank, local_rank) if args.backend == "nccl" else {"rccl_world": None, "backend": "gloo (RCCL not exercised)"}
+    rccl = {}
+    if args.full:
+        rccl = rccl_check(torch, dist, world, rank, local_rank) if args.backend == "nccl" else {"rccl_world": None, "backend": "gloo (RCCL not exercised)"}
     ctx.close()
     import torch.distributed as tdist
     if tdist.is_initialized():

@@ -70,6 +70,46 @@ def test_children_exit_code_is_relayed():
         assert "rank exit codes" in out.stderr
 
 
+def test_dump_outputs_are_float32_or_float64_and_bounded(tmp_path):
+    """--dump-outputs writes float32 as float32 and every other dtype as float64, and refuses more than 64 MB in all."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    bench.write_outputs(str(tmp_path / "d"), {"f": np.ones((3, 4), np.float32), "i": np.arange(5, dtype=np.int32), "b": np.array([True, False])})
+    got = {n: np.load(tmp_path / "d" / (n + ".npy")) for n in ("f", "i", "b")}
+    assert got["f"].dtype == np.float32 and got["i"].dtype == np.float64 and got["b"].dtype == np.float64
+    assert got["i"].tolist() == [0, 1, 2, 3, 4] and got["b"].tolist() == [1.0, 0.0]
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros((64 << 20) // 8 + 1)})
+    assert not (tmp_path / "big").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step_and_full_adds_the_analysis(tmp_path):
+    """A plain run prints the headline only; --dump-outputs gives the same arrays whatever --steps is; --full adds the roofline and the
+    self-check."""
+    import numpy as np
+    cmd = [sys.executable, BENCH, "--gpus", "1", "--batch", "64", "--distinct", "8"]
+    lines = {}
+    for name, extra in (("a", ["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")]),
+                        ("b", ["--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "b")]),
+                        ("full", ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])):
+        out = subprocess.run(cmd + extra, capture_output=True, text=True, env=_clean_env(), timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines[name] = json.loads(out.stdout.strip().splitlines()[-1])
+    a, full = lines["a"], lines["full"]
+    assert a["steps"] == 3 and a["warmup"] == 1 and abs(a["value"] - 64 / (a["ms_per_step"] * 1e-3)) < 1e-6 * a["value"]
+    assert "roofline" not in a and "cpu_baseline" not in a and "rccl_world" not in a
+    assert full["steps"] == 2 and "roofline" in full and full["config"]["self_check"] and "box_calibration_ms" in full["config"]
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir()) and "pose.npy" in names
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), n
+    pose = np.load(tmp_path / "a" / "pose.npy")
+    assert pose.shape == (64, 7) and np.isfinite(pose).all()
+
+
 @pytest.mark.gpu
 def test_self_launched_two_ranks_share_the_gpu_over_gloo():
     """The whole N = 2 path of `python bench.py --gpus 2` on a one-GPU box: parent launches two ranks, both on device 0, gloo for

@@ -17,6 +17,6 @@ for f in sorted(glob.glob('gpurun_out/r06_01_stream_*.json')):
         d=json.loads(open(f).read().strip().splitlines()[-1]); print(f, '%.0f scans/s' % d['value'], d['stream'])
     except Exception as e: print(f, 'failed', e)
 P
-timeout 300 python bench.py --input-stride 3 --steps 8 --warmup 2 --no-cpu-baseline 2>/dev/null | grep '^{"metric' > $O/r06_01_bench_stride3.json
+timeout 300 python bench.py --input-stride 3 --steps 8 --warmup 2 --full --no-cpu-baseline 2>/dev/null | grep '^{"metric' > $O/r06_01_bench_stride3.json
 python -c "
 import json; d=json.load(open('gpurun_out/r06_01_bench_stride3.json')); print('stride3 resident: %.0f scans/s' % d['value'], d['roofline']['kernel_ms_per_step'])"

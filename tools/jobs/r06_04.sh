@@ -8,6 +8,6 @@ fmt='import sys,json
 d=json.loads(sys.stdin.read()); a=d["roofline"].get("association_stage") or {}
 print("%.0f scans/s  %.2f ms/step | stage two-stream %s one-stream %s" % (d["value"], d["ms_per_step"], a.get("two_stream_ms_per_step"), a.get("one_stream_ms_per_step")))'
 for p in 2 3 4 6 8; do
-  printf "pieces %d: " $p; LIGHTLOAM_TWO_STREAM=1 LIGHTLOAM_TS_PIECES=$p timeout 600 python bench.py --steps 8 --warmup 2 --no-cpu-baseline 2>/dev/null | grep '^{"metric' | python -c "$fmt"
+  printf "pieces %d: " $p; LIGHTLOAM_TWO_STREAM=1 LIGHTLOAM_TS_PIECES=$p timeout 600 python bench.py --steps 8 --warmup 2 --full --no-cpu-baseline 2>/dev/null | grep '^{"metric' | python -c "$fmt"
 done | tee $O/r06_04_two_stream_pieces.log
-printf "one stream: " | tee -a $O/r06_04_two_stream_pieces.log; timeout 600 python bench.py --steps 8 --warmup 2 --no-cpu-baseline 2>/dev/null | grep '^{"metric' | python -c "$fmt" | tee -a $O/r06_04_two_stream_pieces.log
+printf "one stream: " | tee -a $O/r06_04_two_stream_pieces.log; timeout 600 python bench.py --steps 8 --warmup 2 --full --no-cpu-baseline 2>/dev/null | grep '^{"metric' | python -c "$fmt" | tee -a $O/r06_04_two_stream_pieces.log

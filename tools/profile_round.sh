@@ -54,18 +54,18 @@ python3 tools/sq_summary.py $O/pmc_sq_v > $O/${TAG}_sq_counters_s16.txt
 python3 tools/sq_issue.py $O/pmc_sq_v --batch 32768 --rings 16 --workload synthetic > $O/sq_issue_s16.json
 cp $O/pmc_traffic_s16.json profiles/pmc_traffic_s16.json
 cp $O/sq_issue_s16.json profiles/sq_issue_s16.json
-python3 bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python3 bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 # the self-launching N-rank path on the one GPU of this pool (two ranks on device 0, gloo for the timing reduction: RCCL cannot share a device)
-python3 bench.py --gpus 2 --backend gloo --share-gpu --batch 2048 --no-cpu-baseline > $O/${TAG}_bench_gpus2_gloo_share_gpu.json 2>/dev/null
+python3 bench.py --gpus 2 --backend gloo --share-gpu --batch 2048 --full --no-cpu-baseline > $O/${TAG}_bench_gpus2_gloo_share_gpu.json 2>/dev/null
 # 9 distinct scans (the default of rounds 1-3) beside the 65 of the headline: what slot-to-slot diversity costs
-python3 bench.py --distinct 8 --no-cpu-baseline > $O/${TAG}_bench_distinct8.json 2>/dev/null
+python3 bench.py --distinct 8 --full --no-cpu-baseline > $O/${TAG}_bench_distinct8.json 2>/dev/null
 # BASELINE config 3's stand-in (HDL-64E true laser table, ring capacity 4608): bench line + its kernel stats
-python3 bench.py --workload hdl64 --no-cpu-baseline > $O/${TAG}_bench_hdl64.json 2> $O/${TAG}_bench_hdl64.err
+python3 bench.py --workload hdl64 --full --no-cpu-baseline > $O/${TAG}_bench_hdl64.json 2> $O/${TAG}_bench_hdl64.err
 rocprofv3 --kernel-trace --stats -d $O/prof_${TAG}_hdl64 -o ${TAG}h -- python3 bench.py --workload hdl64 --steps 5 --warmup 1 --no-cpu-baseline > $O/prof_${TAG}_hdl64.log 2>&1
 python3 tools/rocpd_summary.py $O/prof_${TAG}_hdl64/${TAG}h_results.db > $O/${TAG}_kernel_stats_hdl64.txt
 # the other shapes and BASELINE config 5 (stream of scans over PCIe, 64 and 128 rings)
-python3 bench.py --rings 128 --no-cpu-baseline > $O/${TAG}_bench_s128.json 2>/dev/null
-python3 bench.py --rings 16 --no-cpu-baseline > $O/${TAG}_bench_s16.json 2>/dev/null
+python3 bench.py --rings 128 --full --no-cpu-baseline > $O/${TAG}_bench_s128.json 2>/dev/null
+python3 bench.py --rings 16 --full --no-cpu-baseline > $O/${TAG}_bench_s16.json 2>/dev/null
 # (12-byte points = ll_params.input_stride_floats 3: the 4th float of a .bin record never crosses PCIe; the 16-byte contract beside it)
 python3 bench.py --stream-input --input-stride 3 --no-cpu-baseline > $O/${TAG}_stream_input.json 2>/dev/null
 python3 bench.py --stream-input --input-stride 3 --rings 128 --no-cpu-baseline > $O/${TAG}_stream_input_s128.json 2>/dev/null
