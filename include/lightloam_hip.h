@@ -224,6 +224,27 @@ int ll_lm_solve_batch(ll_ctx *ctx, int first, int count, const ll_lm_options *op
  * The slots must have been extracted (ll_extract_batch).                                                             */
 int ll_odometry_frames(ll_ctx *ctx, int first, int count, const double *host_pose0, int n_outer, int first_frame_index,
                        const ll_lm_options *opt, double *host_poses_out);
+/* The same frame loop for S independent sequences side by side: frame k of every sequence advances in one set of launches.
+ * The frames live in a ring of rows, one row = S contiguous slots; frame row r of sequence q sits in slot
+ *     base + (r mod ring_rows) * S + q,
+ * and its target is the same sequence's frame at row r - 1 (modulo the ring).  Row row0 - 1 must hold every running
+ * sequence's previous frame, extracted (for a fresh sequence its frame 0).  Rows row0 .. row0 + n_rows - 1 run:
+ *   seq_rows[q]      rows sequence q runs in this call, 0..n_rows (NULL = n_rows for all); the slots of the rows it does
+ *                    not run are not touched (no pose, pair header, correspondence or LM state is written),
+ *   frame_index0[q]  the sequence's frame index of row row0: a frame votes when its index is > 5 (:794) (NULL = 1 for all),
+ *   host_pose0       [S][7] warm start of row row0; NULL = the pose held by row row0 - 1's slot, which continues a drive
+ *                    that streams through the ring: extract the next frames into the slots of finished rows, call again.
+ * The warm start of row r + 1 is row r's solution (:61-65).  Everything is enqueued on the context stream; the call
+ * synchronises only to fill host_poses_out ([n_rows][S][7], may be NULL; rows a sequence did not run are NaN).
+ * LL_ERR_ARG (nothing enqueued): S < 1, ring_rows < 2, base < 0, base + S * ring_rows > batch, n_rows outside
+ * 1..ring_rows - 1, seq_rows[q] outside 0..n_rows, n_outer outside 1..16, opt->max_num_iterations outside 0..64.   */
+typedef struct {
+    int base;        /* first slot of the ring */
+    int n_seq;       /* S: sequences side by side */
+    int ring_rows;   /* rows in the ring: slots [base, base + ring_rows * S) */
+} ll_seq_layout;
+int ll_odometry_sequences(ll_ctx *ctx, const ll_seq_layout *L, int row0, int n_rows, const int *seq_rows, const int *frame_index0,
+                          const double *host_pose0, int n_outer, const ll_lm_options *opt, double *host_poses_out);
 
 /* ---------------------------------------------------------------- laserMapping scan-to-submap (first stage)
  * The optimisation laserMapping runs per frame (laserMapping.cpp:1822-2095) for ONE scan against the corner / surf clouds

@@ -412,6 +412,17 @@ inline std::vector<double> odometry_frames(Context &c, int first, int count, con
     return rel;
 }
 
+/* laserOdometry for L.n_seq sequences side by side over rows [row0, row0 + n_rows) of a ring (ll_odometry_sequences): returns the
+ * [n_rows][S][7] relative poses, NaN for the rows a sequence did not run.  seq_rows / frame_index0 / pose0: NULL or S entries
+ * (pose0: S x 7; NULL continues from the poses on the device). */
+inline std::vector<double> odometry_sequences(Context &c, const ll_seq_layout &L, int row0, int n_rows, const int *seq_rows = nullptr,
+                                              const int *frame_index0 = nullptr, const double *pose0 = nullptr, int n_outer = 3)
+{
+    std::vector<double> rel((size_t)(n_rows > 0 ? n_rows : 0) * (size_t)(L.n_seq > 0 ? L.n_seq : 0) * 7);
+    c.check(ll_odometry_sequences(c.get(), &L, row0, n_rows, seq_rows, frame_index0, pose0, n_outer, nullptr, rel.data()));
+    return rel;
+}
+
 }  // namespace lightloam
 
 /* ------------------------------------------------------------------------------------------------------------------

@@ -23,7 +23,7 @@ EXPORTS = [
     "ll_download_edge_corr", "ll_download_plane_corr", "ll_vote_batch", "ll_download_vote",
     "ll_normal_equations_batch", "ll_download_normal_equations", "ll_gn_step_batch", "ll_download_pose",
     "ll_residual_jacobian", "ll_hot_path_batch", "ll_algorithmic_bytes", "ll_profile_enable", "ll_profile_read", "ll_set_pose_guess", "ll_debug_counters", "ll_vote_host", "ll_debug_calibration_copy", "ll_debug_launch_stage", "ll_debug_exact_math", "ll_upload_scan_async", "ll_upload_scans_async", "ll_upload_scans_async_strided", "ll_stream_record", "ll_stream_wait", "ll_hot_path_chain", "ll_synchronize_copy", "ll_host_alloc", "ll_host_free",
-    "ll_lm_default_options", "ll_lm_solve_batch", "ll_odometry_frames", "ll_set_two_stream",
+    "ll_lm_default_options", "ll_lm_solve_batch", "ll_odometry_frames", "ll_odometry_sequences", "ll_set_two_stream",
     "ll_map_create", "ll_map_destroy", "ll_map_last_error", "ll_map_set_map", "ll_map_set_scan", "ll_map_associate",
     "ll_map_residual_jacobian", "ll_map_get_counts", "ll_map_get_map_sizes", "ll_map_download_edges", "ll_map_download_planes", "ll_map_normal_equations", "ll_map_optimize",
     "ll_cubemap_create", "ll_cubemap_destroy", "ll_cubemap_last_error", "ll_cubemap_prepare", "ll_cubemap_optimize", "ll_cubemap_update",
@@ -59,6 +59,16 @@ class LmOptions(C.Structure):
 
 class PairInfo(C.Structure):
     _fields_ = [("n_edge", C.c_int), ("n_plane", C.c_int), ("n_plane_selected", C.c_int)]
+
+
+class SeqLayout(C.Structure):
+    """ll_seq_layout: S sequences side by side in a ring of `ring_rows` rows of S contiguous slots from slot `base`"""
+    _fields_ = [("base", C.c_int), ("n_seq", C.c_int), ("ring_rows", C.c_int)]
+
+
+def sequence_slot(layout, row, q):
+    """the slot of frame row `row` of sequence `q`: base + (row mod ring_rows) * n_seq + q"""
+    return layout.base + (row % layout.ring_rows) * layout.n_seq + q
 
 
 class LightLoamError(RuntimeError):
@@ -359,6 +369,19 @@ class Context:
         p0 = None if pose0 is None else np.ascontiguousarray(pose0, np.float64)
         self._ck(self.lib.ll_odometry_frames(self.h, first, count, _ptr(p0), n_outer, first_frame_index,
                                              None if opt is None else C.byref(opt), _ptr(out)))
+        return out
+
+    def odometry_sequences(self, n_seq, ring_rows, row0, n_rows, base=0, seq_rows=None, frame_index0=1, pose0=None, n_outer=3, opt=None):
+        """the frame loop of n_seq sequences side by side (ll_odometry_sequences); returns the (n_rows, n_seq, 7) relative poses,
+        NaN for the rows a sequence did not run.  frame_index0: one int or one per sequence; pose0: None (continue from the poses
+        on the device), one pose or (n_seq, 7)."""
+        L = SeqLayout(base, n_seq, ring_rows)
+        rows = None if seq_rows is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seq_rows, np.int32), (n_seq,)))
+        fidx = np.ascontiguousarray(np.broadcast_to(np.asarray(frame_index0, np.int32), (n_seq,)))
+        p0 = self._poses(pose0, n_seq)
+        out = np.zeros((n_rows, n_seq, 7))
+        self._ck(self.lib.ll_odometry_sequences(self.h, C.byref(L), int(row0), int(n_rows), _ptr(rows), _ptr(fidx), _ptr(p0), int(n_outer),
+                                                None if opt is None else C.byref(opt), _ptr(out)))
         return out
 
     def hot_path(self, first=0, count=1, pose=None, vote=True):

@@ -629,6 +629,102 @@ extern "C" int ll_odometry_frames(ll_ctx *ctx, int first, int count, const doubl
     return LL_OK;
 }
 
+/* ---- ll_odometry_sequences: S sequences side by side, one ring row (S contiguous slots) per frame step ---- */
+#define LL_SEQ_CHUNK 32            /* sequences per setup launch: their rows, frame indices and poses go down by value */
+struct LLSeqChunk {
+    int q0, nq, has_pose;
+    int rows[LL_SEQ_CHUNK];        /* rows this call runs per sequence */
+    int fidx[LL_SEQ_CHUNK];        /* frame index of row row0 */
+    double pose[LL_SEQ_CHUNK][7];  /* warm start of row row0 (has_pose) */
+};
+static_assert(sizeof(LLSeqChunk) + sizeof(LLView) + 32 <= 4096, "kernel arguments of k_seq_setup");
+__host__ __device__ __forceinline__ int ll_ring_row(long long r, int ring_rows) { const int m = (int)(r % ring_rows); return m < 0 ? m + ring_rows : m; }
+/* row_pred / row_mode of the chunk's sequences for the call's rows, and the starting pose of row row0 of those that run */
+__global__ void k_seq_setup(LLView V, int base, int S, int ring_rows, long long row0, int n_rows, LLSeqChunk c)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows * c.nq) return;
+    const int ri = i / c.nq, qi = i - ri * c.nq, q = c.q0 + qi;
+    const int slot = base + ll_ring_row(row0 + ri, ring_rows) * S + q;
+    const int pred = base + ll_ring_row(row0 + ri - 1, ring_rows) * S + q;
+    const int active = ri < c.rows[qi];
+    V.row_pred[slot] = pred;
+    V.row_mode[slot] = active | ((c.fidx[qi] + ri) > 5 ? 2 : 0);          /* now_frame > 5 (:794) */
+    if (ri == 0 && active)
+        for (int k = 0; k < 7; ++k) V.pose[(size_t)slot * 7 + k] = c.has_pose ? c.pose[qi][k] : V.pose[(size_t)pred * 7 + k];
+}
+
+extern "C" int ll_odometry_sequences(ll_ctx *ctx, const ll_seq_layout *L, int row0, int n_rows, const int *seq_rows, const int *frame_index0,
+                                     const double *host_pose0, int n_outer, const ll_lm_options *opt, double *host_poses_out)
+{
+    int rc = ll_enter(ctx); if (rc) return rc;
+    if (!L) { ctx->err = "no sequence layout"; return LL_ERR_ARG; }
+    const int S = L->n_seq, RR = L->ring_rows, base = L->base;
+    if (S < 1) { ctx->err = "n_seq must be >= 1"; return LL_ERR_ARG; }
+    if (RR < 2) { ctx->err = "ring_rows must be >= 2"; return LL_ERR_ARG; }
+    if (base < 0 || (long long)base + (long long)S * RR > ctx->p.batch) { ctx->err = "the ring does not fit in the batch"; return LL_ERR_ARG; }
+    if (n_rows < 1 || n_rows > RR - 1) { ctx->err = "n_rows must be in 1..ring_rows - 1"; return LL_ERR_ARG; }
+    int max_rows = n_rows;
+    if (seq_rows) {
+        max_rows = 0;
+        for (int q = 0; q < S; ++q) {
+            if (seq_rows[q] < 0 || seq_rows[q] > n_rows) { ctx->err = "seq_rows out of range"; return LL_ERR_ARG; }
+            max_rows = std::max(max_rows, seq_rows[q]);
+        }
+    }
+    if (n_outer < 1 || n_outer > 16) { ctx->err = "n_outer out of range"; return LL_ERR_ARG; }
+    const LLLmOpt o = ll_to_dev_opt(opt);
+    if (o.max_num_iterations < 0 || o.max_num_iterations > 64) { ctx->err = "max_num_iterations out of range"; return LL_ERR_ARG; }
+    LLView &V = ctx->V;
+    if (!V.row_pred) {
+        void *a = nullptr, *b = nullptr;
+        const size_t bytes = (size_t)V.B * sizeof(int);
+        if (hipMalloc(&a, bytes) != hipSuccess) { ctx->err = "hipMalloc failed (sequence tables)"; return LL_ERR_HIP; }
+        ctx->allocs.push_back(a);
+        if (hipMalloc(&b, bytes) != hipSuccess) { ctx->err = "hipMalloc failed (sequence tables)"; return LL_ERR_HIP; }
+        ctx->allocs.push_back(b);
+        V.row_pred = (int *)a; V.row_mode = (int *)b;
+    }
+    if (max_rows > 0) {
+        for (int q0 = 0; q0 < S; q0 += LL_SEQ_CHUNK) {
+            LLSeqChunk c;
+            std::memset(&c, 0, sizeof(c));
+            c.q0 = q0; c.nq = std::min(LL_SEQ_CHUNK, S - q0); c.has_pose = host_pose0 != nullptr;
+            for (int k = 0; k < c.nq; ++k) {
+                c.rows[k] = seq_rows ? seq_rows[q0 + k] : n_rows;
+                c.fidx[k] = frame_index0 ? frame_index0[q0 + k] : 1;
+                if (host_pose0) std::memcpy(c.pose[k], host_pose0 + (size_t)(q0 + k) * 7, 7 * sizeof(double));
+            }
+            const int n = n_rows * c.nq;
+            hipLaunchKernelGGL(k_seq_setup, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, V, base, S, RR, (long long)row0, n_rows, c);
+        }
+        for (int ri = 0; ri < max_rows; ++ri) {                              /* no sequence runs the rows past max_rows */
+            const int first = base + ll_ring_row((long long)row0 + ri, RR) * S;
+            const int succ = (ri + 1 < max_rows) ? base + ll_ring_row((long long)row0 + ri + 1, RR) * S : -1;
+            for (int outer = 0; outer < n_outer; ++outer) {                  /* :439 */
+                ll_launch_associate_rows(V, first, S, ctx->stream, &ctx->prof);
+                ll_launch_vote_lm_rows(V, first, S, outer == n_outer - 1 ? succ : -1, o, ctx->stream, &ctx->prof);
+            }
+        }
+        LL_HIP(hipGetLastError());
+    }
+    if (host_poses_out) {
+        /* the call's rows are n_rows consecutive ring rows: at most two contiguous pieces */
+        const int a = ll_ring_row(row0, RR), n1 = std::min(n_rows, RR - a);
+        const size_t row_d = (size_t)S * 7;
+        if (ll_read_back(host_poses_out, V.pose + (size_t)(base + a * S) * 7, (size_t)n1 * row_d * sizeof(double), ctx->stream) ||
+            (n1 < n_rows && ll_read_back(host_poses_out + (size_t)n1 * row_d, V.pose + (size_t)base * 7, (size_t)(n_rows - n1) * row_d * sizeof(double), ctx->stream))) {
+            ctx->err = "read-back failed"; return LL_ERR_HIP;
+        }
+        const double nan = std::nan("");
+        for (int ri = 0; ri < n_rows; ++ri)
+            for (int q = 0; q < S; ++q)
+                if (ri >= (seq_rows ? seq_rows[q] : n_rows))
+                    for (int k = 0; k < 7; ++k) host_poses_out[((size_t)ri * S + q) * 7 + k] = nan;
+    }
+    return LL_OK;
+}
+
 static int hot_path(ll_ctx *ctx, int first, int count, const double *host_pose_guess, int vote_enable, int chain);
 
 /* The association stage of a hot-path call on TWO streams -- built in round 6, measured, and OFF by default (ll_set_two_stream(ctx, 1) or

@@ -144,6 +144,10 @@ struct LLView {
                                     * Vote, factors and the solves read the target from here: a later call over a sub-range cannot disagree
                                     * with the association about whose points the correspondences name */
     unsigned long long *dbg;       /* [16] phase-timing counters (only written by -DLL_PHASE_TIMING builds) */
+    /* many sequences side by side (ll_odometry_sequences): per ring slot, written by the setup kernel of every call for the call's rows;
+     * allocated on the first such call (null until then).  Appended last so that no field above moves. */
+    int *row_pred;                 /* [B] the slot holding the same sequence's previous frame (the slot's target) */
+    int *row_mode;                 /* [B] bit 0: the slot runs in this call; bit 1: its frame votes (frame index > 5, laserOdometry.cpp:794) */
 };
 
 #define LL_NEQ_STRIDE 44
@@ -368,6 +372,11 @@ void ll_launch_pick(const LLView &V, int first, int count, hipStream_t st);
 void ll_launch_associate(const LLView &V, int first, int count, hipStream_t st, LLProfiler *prof);
 void ll_launch_build_grid(const LLView &V, int first, int count, int carry, hipStream_t st, LLProfiler *prof);
 void ll_launch_vote(const LLView &V, int first, int count, int enable, hipStream_t st, LLProfiler *prof);
+/* one row of ll_odometry_sequences: slots [first, first + count), those with row_mode bit 0 only; the target of slot s is row_pred[s] */
+void ll_launch_associate_rows(const LLView &V, int first, int count, hipStream_t st, LLProfiler *prof);
+/* vote + LM solve per active slot of a row in one launch; succ_first >= 0: also leave the solved pose in slot succ_first + i when that
+ * slot is active (the warm start of the next row) */
+void ll_launch_vote_lm_rows(const LLView &V, int first, int count, int succ_first, const LLLmOpt &o, hipStream_t st, LLProfiler *prof);
 void ll_launch_vote_points(const float4 *src, const float4 *tgt, int n, int regions, int *vc, uint8_t *vs, float *vw, hipStream_t st);
 void ll_launch_normal_equations(const LLView &V, int first, int count, int do_step, hipStream_t st, LLProfiler *prof);
 void ll_launch_gn_step(const LLView &V, int first, int count, hipStream_t st, LLProfiler *prof);
