@@ -384,6 +384,34 @@ int ll_cubemap_info(ll_cubemap *cm, int *cen3, int *counts4);
 int ll_cubemap_download_cloud(ll_cubemap *cm, int which, ll_point *out, int cap, int *n);
 int ll_cubemap_download_cube(ll_cubemap *cm, int surf, int cube_index, ll_point *out, int cap, int *n);
 
+/* ---------------------------------------------------------------- laserMapping's cube map for many sequences side by side
+ * S independent cube maps, each what an ll_cubemap created with the same parameters holds.  One call runs one frame of
+ * :1584-2165 for every running sequence in one set of launches per stage; the host synchronises five times per frame (the
+ * slots' headers -- not for host clouds --, prepare, the poses, the per-cube counts, the filtered sizes), plus one per voxel-filter or by-cube sort
+ * that is too large to stay inside its workgroups (clouds of more than 65 536 points), whatever S is.
+ * Contract: sequence q after any number of calls equals an ll_cubemap driven by ll_cubemap_process_slot / _process with
+ * the same frames, bit for bit: pose, ran, cen, the four clouds, every cube.  Tile and row shards are not supported.
+ * ll_cubemaps_process_slots: the scan of sequence q is the extracted slot slots[q] of the owning context (device to
+ * device); slots[q] = -1: sequence q does not run this frame -- its map, its pose_w7 row and ran[q] are not touched.
+ * pose_w7 [S][7]: in = the guess of transformAssociateToMap (:1581), out = the optimised parameters[]; ran [S] may be NULL.
+ * ll_cubemaps_process: the same from host clouds; a sequence whose two cloud pointers are NULL does not run.
+ * Errors: LL_ERR_ARG before anything is enqueued (n_seq < 1, a slot out of range, a slot used by two sequences, bad
+ * clouds); LL_ERR_STATE for a slot that holds no extracted scan, or a solve that leaves a NaN pose (last_error names the
+ * sequence); LL_ERR_CAPACITY when a pool would overflow -- decided for every sequence and both cloud types before any
+ * pair table changes, so no cube changes in that call and the call can be repeated.
+ * ll_cubemaps_stats: host synchronisations and frames since create.                                                 */
+typedef struct ll_cubemaps ll_cubemaps;
+int  ll_cubemaps_create(ll_ctx *ctx, int n_seq, float line_res, float plane_res, int max_scan_corner, int max_scan_surf, int pool_points, ll_cubemaps **out);
+void ll_cubemaps_destroy(ll_cubemaps *cms);
+const char *ll_cubemaps_last_error(const ll_cubemaps *cms);
+int  ll_cubemaps_process_slots(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran);
+int  ll_cubemaps_process(ll_cubemaps *cms, const ll_point *const *corner_last, const int *n_corner, const ll_point *const *surf_last,
+                         const int *n_surf, double *pose_w7, int *ran);
+int  ll_cubemaps_info(ll_cubemaps *cms, int q, int *cen3, int *counts4);
+int  ll_cubemaps_download_cloud(ll_cubemaps *cms, int q, int which, ll_point *out, int cap, int *n);
+int  ll_cubemaps_download_cube(ll_cubemaps *cms, int q, int surf, int cube_index, ll_point *out, int cap, int *n);
+int  ll_cubemaps_stats(const ll_cubemaps *cms, long long *syncs, long long *frames);
+
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),
  * everything device-resident, no host synchronisation inside.  `vote_enable` as above.                   */

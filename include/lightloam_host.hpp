@@ -335,6 +335,77 @@ private:
     static void mcheck(ll_map *m, int rc) { if (rc != LL_OK) throw Error(rc, ll_map_last_error(m)); }
     ll_cubemap *cm_ = nullptr;
     int world_ = 1;
+    friend class LaserMappingSequences;
+};
+
+/* laserMapping for S sequences side by side (ll_cubemaps): per sequence q the state of LaserMapping (parameters, q_wmap_wodom,
+ * t_wmap_wodom, rows of [S][7] / [S][4] / [S][3]) and the same formulas; one call runs frame k of every running sequence.
+ * Sequence q equals a LaserMapping fed the same frames, bit for bit. */
+class LaserMappingSequences {
+public:
+    LaserMappingSequences(Context &c, int n_seq, float lineRes = 0.4f, float planeRes = 0.8f, int max_scan_corner = 20000,
+                          int max_scan_surf = 200000, int pool_points = 1 << 22)
+        : S(n_seq), parameters((size_t)7 * n_seq), q_wmap_wodom((size_t)4 * n_seq), t_wmap_wodom((size_t)3 * n_seq, 0.0), ran((size_t)n_seq, 0) {
+        c.check(ll_cubemaps_create(c.get(), n_seq, lineRes, planeRes, max_scan_corner, max_scan_surf, pool_points, &cms_));
+        for (int q = 0; q < S; ++q) {
+            const double p0[7] = {0, 0, 0, 1, 0, 0, 0}, q0[4] = {0, 0, 0, 1};
+            std::copy(p0, p0 + 7, &parameters[(size_t)7 * q]); std::copy(q0, q0 + 4, &q_wmap_wodom[(size_t)4 * q]);
+        }
+    }
+    ~LaserMappingSequences() { ll_cubemaps_destroy(cms_); }
+    LaserMappingSequences(const LaserMappingSequences &) = delete;
+    LaserMappingSequences &operator=(const LaserMappingSequences &) = delete;
+
+    /* transformAssociateToMap / transformUpdate (:113-123) of every sequence q with run[q] (NULL: all); q_wodom_curr [S][4], t [S][3] */
+    void transformAssociateToMap(const double *q_wodom_curr, const double *t_wodom_curr, const int *run = nullptr) {
+        for (int q = 0; q < S; ++q) {
+            if (run && !run[q]) continue;
+            double *P = &parameters[(size_t)7 * q];
+            const double *qm = &q_wmap_wodom[(size_t)4 * q], *tm = &t_wmap_wodom[(size_t)3 * q];
+            LaserMapping::qmul(qm, q_wodom_curr + 4 * q, P);
+            double r[3]; LaserMapping::qrot(qm, t_wodom_curr + 3 * q, r);
+            for (int k = 0; k < 3; ++k) P[4 + k] = r[k] + tm[k];
+        }
+    }
+    void transformUpdate(const double *q_wodom_curr, const double *t_wodom_curr, const int *run = nullptr) {
+        for (int q = 0; q < S; ++q) {
+            if (run && !run[q]) continue;
+            const double *qc = q_wodom_curr + 4 * q, *P = &parameters[(size_t)7 * q];
+            double *qm = &q_wmap_wodom[(size_t)4 * q], *tm = &t_wmap_wodom[(size_t)3 * q];
+            const double n2 = qc[0] * qc[0] + qc[1] * qc[1] + qc[2] * qc[2] + qc[3] * qc[3];
+            const double inv[4] = {-qc[0] / n2, -qc[1] / n2, -qc[2] / n2, qc[3] / n2};
+            LaserMapping::qmul(P, inv, qm);
+            double r[3]; LaserMapping::qrot(qm, t_wodom_curr + 3 * q, r);
+            for (int k = 0; k < 3; ++k) tm[k] = P[4 + k] - r[k];
+        }
+    }
+    /* :1584-2165 for every sequence q with slots[q] >= 0 (its scan: that extracted slot of the context); parameters rows in: the
+     * guesses, out: the optimised poses; ran[q] as LaserMapping::process_slot returns it */
+    void process_slots(const std::vector<int> &slots) {
+        if ((int)slots.size() != S) throw Error(LL_ERR_ARG, "one slot per sequence");
+        check(ll_cubemaps_process_slots(cms_, slots.data(), parameters.data(), ran.data()));
+    }
+    /* the same from host clouds; an empty pair of clouds with run[q] == 0 (or both pointers NULL) skips sequence q */
+    void process(const std::vector<const std::vector<PointXYZI> *> &corner_last, const std::vector<const std::vector<PointXYZI> *> &surf_last) {
+        if ((int)corner_last.size() != S || (int)surf_last.size() != S) throw Error(LL_ERR_ARG, "one cloud pair per sequence");
+        std::vector<const ll_point *> c((size_t)S, nullptr), s((size_t)S, nullptr);
+        std::vector<int> nc((size_t)S, 0), ns((size_t)S, 0);
+        static const ll_point empty = {0, 0, 0, 0};
+        for (int q = 0; q < S; ++q) {
+            if (!corner_last[q] && !surf_last[q]) continue;
+            c[q] = corner_last[q] && !corner_last[q]->empty() ? (const ll_point *)corner_last[q]->data() : &empty;
+            s[q] = surf_last[q] && !surf_last[q]->empty() ? (const ll_point *)surf_last[q]->data() : &empty;
+            nc[q] = corner_last[q] ? (int)corner_last[q]->size() : 0; ns[q] = surf_last[q] ? (int)surf_last[q]->size() : 0;
+        }
+        check(ll_cubemaps_process(cms_, c.data(), nc.data(), s.data(), ns.data(), parameters.data(), ran.data()));
+    }
+    const int S;
+    std::vector<double> parameters, q_wmap_wodom, t_wmap_wodom;   /* [S][7], [S][4], [S][3] */
+    std::vector<int> ran;                                       /* [S] */
+    ll_cubemaps *get() const { return cms_; }
+private:
+    void check(int rc) { if (rc != LL_OK) throw Error(rc, ll_cubemaps_last_error(cms_)); }
+    ll_cubemaps *cms_ = nullptr;
 };
 
 /* ---- I/O surface ---------------------------------------------------------------------------------- */

@@ -33,6 +33,8 @@ EXPORTS = [
     "ll_map_evaluate_dev", "ll_map_lm_begin_dev", "ll_map_lm_propose_dev", "ll_map_lm_accept_dev", "ll_map_knn_partial_dev",
     "ll_map_associate_merged_dev", "ll_map_solve_dev",
     "ll_voxel_grid", "ll_map_set_pose", "ll_map_get_pose", "ll_map_evaluate", "ll_map_lm_begin", "ll_map_lm_propose", "ll_map_lm_accept",
+    "ll_cubemaps_create", "ll_cubemaps_destroy", "ll_cubemaps_last_error", "ll_cubemaps_process_slots", "ll_cubemaps_process",
+    "ll_cubemaps_info", "ll_cubemaps_download_cloud", "ll_cubemaps_download_cube", "ll_cubemaps_stats",
 ]
 
 
@@ -702,3 +704,91 @@ class CubeMap:
         out = np.zeros((cap, 4), np.float32); n = C.c_int(0)
         self._ck(self.lib.ll_cubemap_download_cube(self.h, int(surf), int(index), _ptr(out), len(out), C.byref(n)))
         return out[:n.value].copy()
+
+
+class CubeMaps:
+    """One ll_cubemaps: n_seq cube maps side by side, frame k of every running sequence in one set of launches per stage.
+    Sequence q equals a CubeMap with the same parameters driven by process_slot / process with the same frames, bit for bit."""
+
+    def __init__(self, ctx, n_seq, max_scan_corner, max_scan_surf, pool_points=1 << 20, line_res=0.4, plane_res=0.8):
+        self.ctx = ctx; self.lib = ctx.lib; self.n_seq = int(n_seq)
+        self.lib.ll_cubemaps_last_error.restype = C.c_char_p
+        self.lib.ll_cubemaps_last_error.argtypes = [C.c_void_p]
+        self.lib.ll_cubemaps_destroy.argtypes = [C.c_void_p]
+        self.h = C.c_void_p()
+        rc = self.lib.ll_cubemaps_create(ctx.h, int(n_seq), C.c_float(line_res), C.c_float(plane_res), int(max_scan_corner),
+                                         int(max_scan_surf), int(pool_points), C.byref(self.h))
+        if rc != LL_OK:
+            raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ll_cubemaps_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_cubemaps_last_error(self.h).decode())
+
+    def _poses(self, pose_w):
+        p = np.ascontiguousarray(pose_w, np.float64).reshape(self.n_seq, 7).copy()
+        return p, np.zeros(self.n_seq, np.int32)
+
+    def process_slots(self, pose_w, slots):
+        """pose_w [S, 7], slots [S] (-1: the sequence does not run) -> (poses [S, 7], ran [S] bool)"""
+        p, ran = self._poses(pose_w)
+        s = np.ascontiguousarray(slots, np.int32)
+        if s.shape != (self.n_seq,):
+            raise ValueError("slots must have one entry per sequence")
+        self._ck(self.lib.ll_cubemaps_process_slots(self.h, _ptr(s), _ptr(p), _ptr(ran)))
+        return p, ran.astype(bool)
+
+    def process(self, pose_w, corners, surfs):
+        """corners / surfs: one (n, 4) float32 cloud per sequence, None for a sequence that does not run"""
+        p, ran = self._poses(pose_w)
+        keep = []
+        cp = (C.c_void_p * self.n_seq)(); sp = (C.c_void_p * self.n_seq)()
+        nc = np.zeros(self.n_seq, np.int32); ns = np.zeros(self.n_seq, np.int32)
+        for q in range(self.n_seq):
+            if corners[q] is None and surfs[q] is None:
+                continue
+            c = np.ascontiguousarray(np.zeros((0, 4)) if corners[q] is None else corners[q], np.float32).reshape(-1, 4)
+            s_ = np.ascontiguousarray(np.zeros((0, 4)) if surfs[q] is None else surfs[q], np.float32).reshape(-1, 4)
+            keep += [c, s_]
+            cp[q] = c.ctypes.data if c.size else C.addressof(_EMPTY)
+            sp[q] = s_.ctypes.data if s_.size else C.addressof(_EMPTY)
+            nc[q] = len(c); ns[q] = len(s_)
+        self._ck(self.lib.ll_cubemaps_process(self.h, cp, _ptr(nc), sp, _ptr(ns), _ptr(p), _ptr(ran)))
+        return p, ran.astype(bool)
+
+    def info(self, q):
+        cen = (C.c_int * 3)(); cnt = (C.c_int * 4)()
+        self._ck(self.lib.ll_cubemaps_info(self.h, int(q), cen, cnt))
+        return tuple(cen), tuple(cnt)
+
+    def cloud(self, q, which):
+        _, cnt = self.info(q)
+        out = np.zeros((max(cnt[which], 1), 4), np.float32); n = C.c_int(0)
+        self._ck(self.lib.ll_cubemaps_download_cloud(self.h, int(q), which, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def cube(self, q, surf, index, cap=1 << 18):
+        out = np.zeros((cap, 4), np.float32); n = C.c_int(0)
+        self._ck(self.lib.ll_cubemaps_download_cube(self.h, int(q), int(surf), int(index), _ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def stats(self):
+        """(host synchronisations, frames) since create"""
+        s = C.c_longlong(0); f = C.c_longlong(0)
+        self._ck(self.lib.ll_cubemaps_stats(self.h, C.byref(s), C.byref(f)))
+        return s.value, f.value
+
+
+_EMPTY = (C.c_float * 4)()      # a non-NULL address for an empty cloud of a running sequence

@@ -1,0 +1,765 @@
+/*
+ * ll_cubemaps.hip -- laserMapping's per-frame body (laserMapping.cpp:1584-2165) for S cube maps side by side.
+ * Sequence q is an ll_cubemap (ll_cubemap.h) whose pools are the q-th region of shared allocations and whose ll_map is its own;
+ * its pair tables, centre and pool tops are host state exactly as for one cube map.  Frame k of every running sequence goes
+ * through one set of launches per stage, and the host synchronises a fixed number of times per frame, whatever S is:
+ *   slots      the scan headers of the running slots (ll_cubemaps_process_slots only)
+ *   prepare    shift loops and valid cubes on the host; ONE k_cms_copy gathers every sequence's valid cubes and scans, one
+ *              ll_voxel_grid_segments call per cloud type down-sizes every scan (a segment per sequence), k_cms_bbox boxes every
+ *              search cloud; then the boxes and the stack sizes of all sequences come back together
+ *   optimize   :1822 gate per sequence; 2 x {k_cms_knn (ll_map_knn_one per stack point over a block table of (sequence, cloud
+ *              type, first point)), k_cms_compact (one workgroup per sequence and type), k_cms_lm (one workgroup per sequence
+ *              for the whole ceres::Solve)}; all poses come back once
+ *   update     k_cms_assign (k_cm_assign's body over a block table), a stable sort by cube per sequence, then the per-cube
+ *              counts of all sequences; one ll_voxel_grid_segments call per type over every valid cube of every sequence,
+ *              then the filtered sizes; the capacity decision for all sequences, the commit, one k_cms_copy for all clouds.
+ * No kernel here waits on another workgroup.  k_cms_lm runs k_map_lm_solve's LL_NEQ_NB x 256-thread partition of the blocks as
+ * LL_NEQ_NB passes of one 256-thread workgroup, with the same per-partial reduction tree and the same order of the partials:
+ * the normal equations, and so the poses, are bit for bit those of ll_cubemap_process_slot.  The grids of the search clouds
+ * are still built per sequence (ll_map_rebuild_finish: a handful of launches each, no synchronisation).
+ */
+#include "ll_cubemap.h"
+#include "ll_factor_math.h"
+#include "ll_lm_step.h"
+#include "ll_map_search.h"
+#include <cmath>
+
+int ll_sort_pairs(unsigned long long *keys, int *vals, unsigned long long *tmp_keys, int *tmp_vals, int n, int *hist, int *tile_sum,
+                  unsigned long long *or_and_dev, hipStream_t st);
+
+/* dst[i] = index ? src[index[i]] : src[i], i < cnt */
+struct CmsCopy { const float4 *src; const int *index; float4 *dst; int cnt, pad; };
+/* one bounding box: 6 ordered ints (min xyz, max xyz) of pts[0, n) */
+struct CmsBox { const float4 *pts; int *out; int n, pad; };
+/* k_cm_assign's arguments for one (sequence, cloud type) */
+struct CmsAssign { const float4 *stk; const double *pose; float4 *tp; unsigned long long *keys; int *vals; int *addcnt; int n, cen[3]; };
+
+/* ------------------------------------------------------------------ kernels */
+__global__ __launch_bounds__(256) void k_cms_copy(const CmsCopy *ops, int per)
+{
+    const CmsCopy op = ops[blockIdx.x / per];
+    for (int i = (blockIdx.x % per) * 256 + threadIdx.x; i < op.cnt; i += per * 256) op.dst[i] = op.index ? op.src[op.index[i]] : op.src[i];
+}
+
+/* k_map_bbox for many clouds: one workgroup per cloud, no atomics (min / max do not depend on the order) */
+__global__ __launch_bounds__(256) void k_cms_bbox(const CmsBox *boxes)
+{
+    const CmsBox B = boxes[blockIdx.x];
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = threadIdx.x; i < B.n; i += 256) {
+        const float4 p = B.pts[i];
+        mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
+        mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
+    }
+    for (int o = 32; o > 0; o >>= 1)
+        for (int k = 0; k < 3; ++k) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], o)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o)); }
+    __shared__ float red[4][6];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) for (int k = 0; k < 3; ++k) { red[wave][k] = mn[k]; red[wave][3 + k] = mx[k]; }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        float v = red[0][threadIdx.x];
+        for (int w = 1; w < 4; ++w) v = threadIdx.x < 3 ? fminf(v, red[w][threadIdx.x]) : fmaxf(v, red[w][threadIdx.x]);
+        B.out[threadIdx.x] = ll_f2ord(v);
+    }
+}
+
+/* the search + fit of k_map_knn; block b covers the LL_KNNB stack points from blk[b].z of cloud type blk[b].y of view blk[b].x */
+__global__ __launch_bounds__(LL_KNNB) void k_cms_knn(const LLMapView *views, const int4 *blk)
+{
+    const int4 b = blk[blockIdx.x];
+    const LLMapView &M = views[b.x];
+    if (b.y == 0) ll_map_knn_one<true>(M, b.z + threadIdx.x);
+    else ll_map_knn_one<false>(M, b.z + threadIdx.x);
+}
+
+/* k_map_compact's result (residual blocks in stack order) for one (view, cloud type) per workgroup, chunk after chunk */
+__global__ __launch_bounds__(256) void k_cms_compact(const LLMapView *views)
+{
+    __shared__ int sc[4];
+    const LLMapView &M = views[blockIdx.x >> 1];
+    const int which = blockIdx.x & 1, tid = threadIdx.x;
+    const int n = M.n_stk[which];
+    int base = 0;
+    for (int c0 = 0; c0 < n; c0 += 256) {
+        const int i = c0 + tid;
+        const bool ok = i < n && M.ok[which][i];
+        int total;
+        const int pos = base + ll_block_exscan_n<4>(ok ? 1 : 0, sc, total);
+        if (ok) {
+            M.src[which][pos] = i;
+            if (which == 0) for (int k = 0; k < 3; ++k) { M.fa[(size_t)pos * 3 + k] = M.qa[(size_t)i * 3 + k]; M.fb[(size_t)pos * 3 + k] = M.qb[(size_t)i * 3 + k]; }
+            else { for (int k = 0; k < 3; ++k) M.fn[(size_t)pos * 3 + k] = M.qn[(size_t)i * 3 + k]; M.fd[pos] = M.qd[i]; }
+        }
+        base += total;
+    }
+    if (tid == 0) M.counts[which] = base;
+}
+
+/* one ceres::Solve per view on one workgroup: k_map_lm_solve's rounds, its LL_NEQ_NB workgroups' partial sums taken as
+ * LL_NEQ_NB passes (thread tid of pass b does what thread tid of workgroup b does), summed in workgroup order */
+__global__ __launch_bounds__(256) void k_cms_lm(const LLMapView *views, LLLmOpt o)
+{
+    const LLMapView &M = views[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int gsz = LL_NEQ_NB * 256;
+    const int n_e = M.counts[0], n_p = M.counts[1];
+    __shared__ double red[4][LL_NACC];
+    __shared__ double sp[7], sneq[LL_NEQ_STRIDE], sL[LL_LM_STRIDE], stot[LL_NACC], spart[LL_NEQ_NB * LL_NACC];
+    for (int k = tid; k < LL_LM_STRIDE; k += 256) sL[k] = 0.0;
+    if (tid < 7) sp[tid] = M.pose[tid];
+    __syncthreads();
+    for (int round = 0; round <= o.max_num_iterations; ++round) {
+        Pose P;
+        for (int k = 0; k < 4; ++k) P.q[k] = sp[k];
+        for (int k = 0; k < 3; ++k) P.t[k] = sp[4 + k];
+        for (int wg = 0; wg < LL_NEQ_NB; ++wg) {
+            const int gtid = wg * 256 + tid;
+            double acc[LL_NACC];
+#pragma unroll
+            for (int k = 0; k < LL_NACC; ++k) acc[k] = 0.0;
+            for (int i = gtid; i < n_e; i += gsz) {
+                double r[3], Jq[3][4], Jt[3][3];
+                ll_edge_d(P, M.stk[0][M.src[0][i]], &M.fa[(size_t)i * 3], &M.fb[(size_t)i * 3], r, Jq, Jt);
+                const double sc = ll_huber_scale(r[0] * r[0] + r[1] * r[1] + r[2] * r[2], M.huber, acc[27]);
+                for (int row = 0; row < 3; ++row) {
+                    double J[6];
+                    ll_to_local(P, Jq[row], J);
+                    J[3] = Jt[row][0]; J[4] = Jt[row][1]; J[5] = Jt[row][2];
+                    for (int k = 0; k < 6; ++k) J[k] *= sc;
+                    ll_acc_row(acc, J, r[row] * sc);
+                }
+            }
+            for (int i = gtid; i < n_p; i += gsz) {
+                double r, Jq[4], Jt[3], J[6];
+                ll_plane_norm(P, M.stk[1][M.src[1][i]], &M.fn[(size_t)i * 3], M.fd[i], r, Jq, Jt);
+                const double sc = ll_huber_scale(r * r, M.huber, acc[27]);
+                ll_to_local(P, Jq, J);
+                J[3] = Jt[0]; J[4] = Jt[1]; J[5] = Jt[2];
+                for (int k = 0; k < 6; ++k) J[k] *= sc;
+                ll_acc_row(acc, J, r * sc);
+            }
+#pragma unroll
+            for (int k = 0; k < LL_NACC; ++k) {
+                double v = acc[k];
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+                if (lane == 0) red[wave][k] = v;
+            }
+            __syncthreads();
+            if (tid < LL_NACC) spart[wg * LL_NACC + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+            __syncthreads();
+        }
+        if (tid < LL_NACC) {
+            double v = 0.0;
+            for (int b = 0; b < LL_NEQ_NB; ++b) v += spart[b * LL_NACC + tid];
+            stot[tid] = v;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int k = 0;
+            for (int a = 0; a < 6; ++a) for (int b = a; b < 6; ++b) { sneq[a * 6 + b] = stot[k]; sneq[b * 6 + a] = stot[k]; ++k; }
+            for (int a = 0; a < 6; ++a) sneq[36 + a] = stot[21 + a];
+            sneq[42] = stot[27];
+            sneq[43] = (double)(3 * n_e + n_p);
+            if (round == 0) ll_lm_begin_one(sL, sneq, sp, o); else ll_lm_accept_one(sL, sneq, sp, o);
+            if (round < o.max_num_iterations) ll_lm_propose_one(sL, sp, o);
+        }
+        __syncthreads();
+    }
+    if (tid < 7) M.pose[tid] = sp[tid];
+    for (int k = tid; k < LL_NEQ_STRIDE; k += 256) M.neq[k] = sneq[k];
+    for (int k = tid; k < LL_LM_STRIDE; k += 256) M.lm[k] = sL[k];
+}
+
+/* k_cm_assign (one cube map, no tile shard) for the 256 stack points from blk[b].y of record blk[b].x */
+__global__ __launch_bounds__(256) void k_cms_assign(const CmsAssign *recs, const int2 *blk)
+{
+    const int2 b = blk[blockIdx.x];
+    const CmsAssign &A = recs[b.x];
+    const int i = b.y + threadIdx.x;
+    int cube = -1;
+    if (i < A.n) {
+        const float4 po = A.stk[i];
+        const double *pose = A.pose;
+        const double ux = pose[0], uy = pose[1], uz = pose[2], w = pose[3];
+        const double v[3] = {(double)po.x, (double)po.y, (double)po.z};
+        double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
+        uvx += uvx; uvy += uvy; uvz += uvz;
+        const float sx = (float)(((v[0] + w * uvx) + (uy * uvz - uz * uvy)) + pose[4]);
+        const float sy = (float)(((v[1] + w * uvy) + (uz * uvx - ux * uvz)) + pose[5]);
+        const float sz = (float)(((v[2] + w * uvz) + (ux * uvy - uy * uvx)) + pose[6]);
+        A.tp[i] = make_float4(sx, sy, sz, po.w);
+        int ci = (int)(((double)sx + 25.0) / 50.0) + A.cen[0], cj = (int)(((double)sy + 25.0) / 50.0) + A.cen[1], ck = (int)(((double)sz + 25.0) / 50.0) + A.cen[2];
+        if ((double)sx + 25.0 < 0) ci--;
+        if ((double)sy + 25.0 < 0) cj--;
+        if ((double)sz + 25.0 < 0) ck--;
+        if (ci >= 0 && ci < CM_W && cj >= 0 && cj < CM_H && ck >= 0 && ck < CM_D) cube = ci + CM_W * cj + CM_W * CM_H * ck;
+        A.keys[i] = (unsigned long long)(cube >= 0 ? cube : CM_N);
+        A.vals[i] = i;
+    }
+    unsigned long long todo = __ballot(cube >= 0);
+    while (todo) {
+        const int c0 = __shfl(cube, __ffsll((long long)todo) - 1);
+        const unsigned long long same = __ballot(cube == c0);
+        if ((threadIdx.x & 63) == __ffsll((long long)same) - 1) atomicAdd(&A.addcnt[c0], __popcll(same));
+        todo &= ~same;
+    }
+}
+
+/* ------------------------------------------------------------------ host side */
+/* the per-call tables go up through page-locked memory: arena `par` of a call is written only after the call before the previous
+ * one has synchronised, so no copy of it can still be in flight; a table that does not fit moves to a larger arena (the old one
+ * is kept until destroy: copies and kernels of this call may still read it) */
+struct CmsArena { unsigned char *h = nullptr, *d = nullptr; size_t cap = 0, used = 0; };
+
+struct ll_cubemaps {
+    ll_ctx *ctx = nullptr;
+    int S = 0;
+    float leaf[2] = {0.4f, 0.8f};
+    int cap_last[2] = {0, 0}, cap_work = 0;
+    size_t cap_pool = 0;
+    std::vector<ll_cubemap *> cm;                 /* sequence q: pools = region q of pool_mem, its own ll_map */
+    float4 *pool_mem[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    float4 *d_last[2] = {nullptr, nullptr}, *d_stk_out[2] = {nullptr, nullptr}, *d_tp[2] = {nullptr, nullptr};   /* [S][cap_last[w]] */
+    unsigned long long *d_keys[2] = {nullptr, nullptr}; int *d_vals[2] = {nullptr, nullptr};
+    float4 *d_work[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};                                   /* [S][cap_work] */
+    int *d_addcnt = nullptr, *d_nout = nullptr, *d_bbox = nullptr;
+    double *d_pose = nullptr;                     /* [S][7]: the pose every stage of a frame reads */
+    LLVoxWork W[2], WS;                           /* per cloud type: prepare's and update's filters; WS: the by-cube sort */
+    CmsArena ar[2]; int par = 0;
+    std::vector<void *> allocs, host_allocs;
+    long long syncs = 0, frames = 0;
+    std::string err;
+};
+
+#define CMS_HIP(call)                                                                        \
+    do {                                                                                     \
+        hipError_t e_ = (call);                                                              \
+        if (e_ != hipSuccess) { cms->err = std::string(#call) + ": " + hipGetErrorString(e_); return LL_ERR_HIP; } \
+    } while (0)
+
+template <typename T>
+static bool cms_alloc(ll_cubemaps *cms, T *&ptr, size_t count)
+{
+    void *p = nullptr;
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    if (hipMalloc(&p, bytes) != hipSuccess) { cms->err = "hipMalloc failed (" + std::to_string(bytes) + " bytes)"; return false; }
+    cms->allocs.push_back(p);
+    ptr = (T *)p;
+    return true;
+}
+
+/* host bytes -> device: through the call's page-locked arena; dst == nullptr: into the arena's device half (returned) */
+static void *cms_stage(ll_cubemaps *cms, const void *src, size_t bytes, void *dst = nullptr)
+{
+    CmsArena &A = cms->ar[cms->par];
+    const size_t need = (bytes + 255) & ~(size_t)255;
+    if (A.used + need > A.cap) {
+        const size_t cap = std::max<size_t>(std::max<size_t>(2 * A.cap, need), (size_t)1 << 20);
+        void *h = nullptr, *d = nullptr;
+        if (hipHostMalloc(&h, cap, hipHostMallocDefault) != hipSuccess) { cms->err = "hipHostMalloc failed"; return nullptr; }
+        cms->host_allocs.push_back(h);
+        if (hipMalloc(&d, cap) != hipSuccess) { cms->err = "hipMalloc failed"; return nullptr; }
+        cms->allocs.push_back(d);
+        A.h = (unsigned char *)h; A.d = (unsigned char *)d; A.cap = cap; A.used = 0;
+    }
+    unsigned char *h = A.h + A.used, *d = A.d + A.used;
+    A.used += need;
+    if (bytes) std::memcpy(h, src, bytes);
+    if (!dst) dst = d;
+    if (bytes && hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, cms->ctx->stream) != hipSuccess) { cms->err = "upload failed"; return nullptr; }
+    return dst;
+}
+
+/* device -> the arena's host half, then one synchronisation; returns the host copy */
+static int cms_sync(ll_cubemaps *cms)
+{
+    CMS_HIP(hipStreamSynchronize(cms->ctx->stream));
+    ++cms->syncs;
+    return LL_OK;
+}
+
+static int cms_copy(ll_cubemaps *cms, const std::vector<CmsCopy> &ops)
+{
+    if (ops.empty()) return LL_OK;
+    int mx = 1;
+    for (const CmsCopy &o : ops) mx = std::max(mx, o.cnt);
+    const CmsCopy *d = (const CmsCopy *)cms_stage(cms, ops.data(), ops.size() * sizeof(CmsCopy));
+    if (!d) return LL_ERR_HIP;
+    const int per = std::min(64, (mx + 255) / 256);
+    hipLaunchKernelGGL(k_cms_copy, dim3((unsigned)(ops.size() * per)), dim3(256), 0, cms->ctx->stream, d, per);
+    return LL_OK;
+}
+
+/* the voxel filter's sort reads back once when it cannot stay inside the workgroups (ll_voxel.hip): counted with the syncs */
+static int cms_voxel(ll_cubemaps *cms, int w, const float4 *pts, const std::vector<int> &seg_off, float4 *out, int *n_out_dev)
+{
+    const int nseg = (int)seg_off.size() - 1, n = seg_off.back();
+    int max_seg = 0;
+    for (int s = 0; s < nseg; ++s) max_seg = std::max(max_seg, seg_off[(size_t)s + 1] - seg_off[(size_t)s]);
+    if (!cms_stage(cms, seg_off.data(), seg_off.size() * sizeof(int), cms->W[w].seg_off)) return LL_ERR_HIP;
+    if (!(nseg > 1 && max_seg <= 8192) && n > 65536) ++cms->syncs;
+    if (ll_voxel_grid_segments(pts, n, nseg, cms->leaf[w], cms->W[w], out, n_out_dev, cms->ctx->stream, nseg > 1 ? max_seg : 0)) { cms->err = "voxel filter: read-back failed"; return LL_ERR_HIP; }
+    return LL_OK;
+}
+
+extern "C" void ll_cubemaps_destroy(ll_cubemaps *cms)
+{
+    if (!cms) return;
+    if (cms->ctx) { (void)hipSetDevice(cms->ctx->device); (void)hipStreamSynchronize(cms->ctx->stream); }
+    for (ll_cubemap *cm : cms->cm) ll_cubemap_destroy(cm);
+    for (void *p : cms->allocs) (void)hipFree(p);
+    for (void *p : cms->host_allocs) (void)hipHostFree(p);
+    delete cms;
+}
+
+extern "C" const char *ll_cubemaps_last_error(const ll_cubemaps *cms) { return cms ? cms->err.c_str() : "null cube maps"; }
+
+extern "C" int ll_cubemaps_create(ll_ctx *ctx, int n_seq, float line_res, float plane_res, int max_scan_corner, int max_scan_surf, int pool_points, ll_cubemaps **out)
+{
+    if (!ctx || !out) return LL_ERR_ARG;
+    *out = nullptr;
+    if (n_seq < 1 || n_seq > 4096 || !(line_res > 0.0f) || !(plane_res > 0.0f) || max_scan_corner < 1 || max_scan_surf < 1 || pool_points < 4096 || pool_points > (1 << 26)) {
+        ctx->err = "bad cube maps parameters"; return LL_ERR_ARG;
+    }
+    const int cap_from_map = std::min(pool_points, 1 << 24), mx_last = std::max(max_scan_corner, max_scan_surf);
+    if (cap_from_map < mx_last) { ctx->err = "pool_points must be at least the scan capacity"; return LL_ERR_ARG; }
+    if ((size_t)n_seq * (size_t)cap_from_map > (size_t)(INT_MAX / 2)) { ctx->err = "n_seq x pool_points too large for one filter call"; return LL_ERR_ARG; }
+    LL_HIP(hipSetDevice(ctx->device));
+    ll_cubemaps *cms = new ll_cubemaps();
+    cms->ctx = ctx; cms->S = n_seq;
+    cms->leaf[0] = line_res; cms->leaf[1] = plane_res;
+    cms->cap_last[0] = max_scan_corner; cms->cap_last[1] = max_scan_surf;
+    cms->cap_pool = (size_t)pool_points; cms->cap_work = cap_from_map;
+    const size_t S = (size_t)n_seq;
+    bool ok = true;
+    for (int w = 0; w < 2 && ok; ++w) {
+        ok = ok && cms_alloc(cms, cms->pool_mem[w][0], S * cms->cap_pool) && cms_alloc(cms, cms->pool_mem[w][1], S * cms->cap_pool);
+        ok = ok && cms_alloc(cms, cms->d_last[w], S * cms->cap_last[w]) && cms_alloc(cms, cms->d_stk_out[w], S * cms->cap_last[w]) &&
+             cms_alloc(cms, cms->d_tp[w], S * cms->cap_last[w]) && cms_alloc(cms, cms->d_keys[w], S * cms->cap_last[w]) &&
+             cms_alloc(cms, cms->d_vals[w], S * cms->cap_last[w]);
+        ok = ok && cms_alloc(cms, cms->d_work[w], S * cap_from_map) && cms_alloc(cms, cms->d_out[w], S * cap_from_map);
+    }
+    ok = ok && cms_alloc(cms, cms->d_addcnt, S * 2 * (CM_N + 1)) && cms_alloc(cms, cms->d_nout, 4) && cms_alloc(cms, cms->d_bbox, S * 12) &&
+         cms_alloc(cms, cms->d_pose, S * 7);
+    for (int w = 0; w < 2 && ok; ++w) {
+        unsigned char *p = nullptr;
+        ok = cms_alloc(cms, p, ll_vox_work_bytes((int)(S * cap_from_map), (int)(S * 125)));
+        if (ok) ll_vox_work_carve(p, (int)(S * cap_from_map), (int)(S * 125), &cms->W[w]);
+    }
+    if (ok) {
+        unsigned char *p = nullptr;
+        ok = cms_alloc(cms, p, ll_vox_work_bytes(mx_last, 1));
+        if (ok) ll_vox_work_carve(p, mx_last, 1, &cms->WS);
+    }
+    for (int q = 0; q < n_seq && ok; ++q) {
+        ll_cubemap *cm = new ll_cubemap();
+        cms->cm.push_back(cm);
+        cm->ctx = ctx;
+        cm->leaf[0] = line_res; cm->leaf[1] = plane_res;
+        cm->cap_last[0] = max_scan_corner; cm->cap_last[1] = max_scan_surf;
+        cm->cap_pool = cms->cap_pool; cm->cap_work = cap_from_map;
+        for (int w = 0; w < 2; ++w) {
+            for (int b = 0; b < 2; ++b) cm->pool[w][b] = cms->pool_mem[w][b] + (size_t)q * cms->cap_pool;
+            cm->off[w].assign(CM_N, 0); cm->cnt[w].assign(CM_N, 0);
+        }
+        if (ll_map_create(ctx, cap_from_map, cap_from_map, max_scan_corner, max_scan_surf, &cm->map) != LL_OK) { cms->err = ctx->err; ok = false; }
+    }
+    if (!ok) { ctx->err = cms->err; ll_cubemaps_destroy(cms); return LL_ERR_HIP; }
+    *out = cms;
+    return LL_OK;
+}
+
+/* one frame for the running sequences run[r]: their scans are src[w][r] (device, n_in[w][r] points; nullptr with flat_slot[r] >= 0:
+ * the less-flat cloud of that extracted slot is flattened into place) */
+static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::vector<const float4 *> src[2], const std::vector<int> n_in[2],
+                     const std::vector<int> &flat_slot, double *pose_w7, int *ran)
+{
+    ll_ctx *ctx = cms->ctx;
+    hipStream_t st = ctx->stream;
+    const int R = (int)run.size();
+    for (int r = 0; r < R; ++r)
+        if (n_in[0][r] > cms->cap_last[0] || n_in[1][r] > cms->cap_last[1]) {
+            cms->err = "sequence " + std::to_string(run[r]) + ": scan cloud larger than the capacity given to ll_cubemaps_create"; return LL_ERR_CAPACITY;
+        }
+    /* ---------------- prepare (:1584-1821) */
+    std::vector<CmsCopy> ops;
+    std::vector<int> n_from[2] = {std::vector<int>(R), std::vector<int>(R)};
+    for (int r = 0; r < R; ++r) {
+        ll_cubemap *cm = cms->cm[run[r]];
+        const double *t_w3 = pose_w7 + 7 * run[r] + 4;
+        const int dim[3] = {CM_W, CM_H, CM_D};
+        int cc[3];
+        for (int k = 0; k < 3; ++k) {
+            cc[k] = (int)((t_w3[k] + 25.0) / 50.0) + cm->cen[k];                   /* :1584-1586 */
+            if (t_w3[k] + 25.0 < 0) cc[k]--;                                       /* :1588-1593 */
+        }
+        for (int k = 0; k < 3; ++k) {
+            while (cc[k] < 3) { cm_shift(cm, k, +1); cc[k]++; cm->cen[k]++; }      /* :1595-1625 and the J, K twins */
+            while (cc[k] >= dim[k] - 3) { cm_shift(cm, k, -1); cc[k]--; cm->cen[k]--; }
+        }
+        cm->n_valid = 0;
+        for (int i = cc[0] - 2; i <= cc[0] + 2; i++) for (int j = cc[1] - 2; j <= cc[1] + 2; j++) for (int k = cc[2] - 1; k <= cc[2] + 1; k++)   /* :1783-1801 */
+            if (i >= 0 && i < CM_W && j >= 0 && j < CM_H && k >= 0 && k < CM_D) cm->valid[cm->n_valid++] = i + CM_W * j + CM_W * CM_H * k;
+        for (int w = 0; w < 2; ++w) {                                              /* :1803-1808 */
+            size_t tot = 0;
+            for (int v = 0; v < cm->n_valid; ++v) {
+                const int c = cm->valid[v];
+                if (cm->cnt[w][c] > 0) { ops.push_back({cm->pool[w][cm->cur[w]] + cm->off[w][c], nullptr, cm->map->d_map[w] + tot, cm->cnt[w][c], 0}); tot += (size_t)cm->cnt[w][c]; }
+            }
+            if (tot > (size_t)cm->map->cap_map[w]) { cms->err = "sequence " + std::to_string(run[r]) + ": the valid cubes hold more points than the search cloud capacity"; return LL_ERR_CAPACITY; }
+            n_from[w][r] = (int)tot;
+        }
+    }
+    std::vector<int> seg_off[2];
+    for (int w = 0; w < 2; ++w) {                                                  /* the scans back to back, one segment each */
+        seg_off[w].assign(R + 1, 0);
+        for (int r = 0; r < R; ++r) {
+            float4 *dst = cms->d_last[w] + seg_off[w][r];
+            if (n_in[w][r] > 0) {
+                if (src[w][r]) ops.push_back({src[w][r], nullptr, dst, n_in[w][r], 0});
+                else ll_launch_lflat_flatten(ctx->V, flat_slot[r], dst, st);
+            }
+            seg_off[w][r + 1] = seg_off[w][r] + n_in[w][r];
+        }
+    }
+    int rc = cms_copy(cms, ops); if (rc) return rc;
+    std::vector<CmsBox> boxes;
+    for (int r = 0; r < R; ++r)
+        for (int w = 0; w < 2; ++w) boxes.push_back({cms->cm[run[r]]->map->d_map[w], cms->d_bbox + 12 * r + 6 * w, n_from[w][r], 0});
+    const CmsBox *d_boxes = (const CmsBox *)cms_stage(cms, boxes.data(), boxes.size() * sizeof(CmsBox));
+    if (!d_boxes) return LL_ERR_HIP;
+    hipLaunchKernelGGL(k_cms_bbox, dim3(2 * R), dim3(256), 0, st, d_boxes);
+    for (int w = 0; w < 2; ++w)                                                    /* laserCloudCornerStack / SurfStack (:1813-1821) */
+        if (seg_off[w][R] > 0) { rc = cms_voxel(cms, w, cms->d_last[w], seg_off[w], cms->d_stk_out[w], cms->d_nout + w); if (rc) return rc; }
+    /* ONE synchronisation: every box and every stack size */
+    std::vector<int> bbox((size_t)R * 12), n_stk[2] = {std::vector<int>(R, 0), std::vector<int>(R, 0)};
+    {
+        int *pin = (int *)ll_pinned_scratch((size_t)R * 14 * sizeof(int));
+        if (!pin) { cms->err = "no page-locked scratch"; return LL_ERR_HIP; }
+        CMS_HIP(hipMemcpyAsync(pin, cms->d_bbox, (size_t)R * 12 * sizeof(int), hipMemcpyDeviceToHost, st));
+        for (int w = 0; w < 2; ++w)
+            if (seg_off[w][R] > 0) CMS_HIP(hipMemcpyAsync(pin + (size_t)R * (12 + w), cms->W[w].seg_count, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, st));
+        rc = cms_sync(cms); if (rc) return rc;
+        std::memcpy(bbox.data(), pin, (size_t)R * 12 * sizeof(int));
+        for (int w = 0; w < 2; ++w)
+            if (seg_off[w][R] > 0) for (int r = 0; r < R; ++r) n_stk[w][r] = n_in[w][r] > 0 ? pin[(size_t)R * (12 + w) + r] : 0;
+    }
+    ops.clear();
+    for (int r = 0; r < R; ++r) {
+        ll_map *m = cms->cm[run[r]]->map;
+        for (int w = 0; w < 2; ++w) { m->M.n_map[w] = n_from[w][r]; m->M.n_stk[w] = n_stk[w][r]; }
+        ll_map_rebuild_finish(m, bbox.data() + 12 * r);                            /* kdtree setInputCloud (:1826-1827) */
+    }
+    for (int w = 0; w < 2; ++w) {
+        int at = 0;
+        for (int r = 0; r < R; ++r) {
+            if (n_stk[w][r] > 0) ops.push_back({cms->d_stk_out[w] + at, nullptr, cms->cm[run[r]]->map->d_stk[w], n_stk[w][r], 0});
+            at += n_stk[w][r];
+        }
+    }
+    rc = cms_copy(cms, ops); if (rc) return rc;
+    CMS_HIP(hipGetLastError());
+
+    /* ---------------- optimize (:1822-2100) */
+    if (!cms_stage(cms, pose_w7, (size_t)cms->S * 7 * sizeof(double), cms->d_pose)) return LL_ERR_HIP;
+    std::vector<int> opt_r;
+    for (int r = 0; r < R; ++r) {
+        const LLMapView &M = cms->cm[run[r]]->map->M;
+        if (M.n_map[0] > 10 && M.n_map[1] > 50) opt_r.push_back(r);               /* :1822 */
+    }
+    const int O = (int)opt_r.size();
+    if (O > 0) {
+        std::vector<LLMapView> views;
+        std::vector<int4> blk;
+        for (int k = 0; k < O; ++k) {
+            LLMapView V = cms->cm[run[opt_r[k]]]->map->M;
+            V.pose = cms->d_pose + 7 * run[opt_r[k]];
+            views.push_back(V);
+            for (int w = 0; w < 2; ++w) for (int f = 0; f < V.n_stk[w]; f += LL_KNNB) blk.push_back(make_int4(k, w, f, 0));
+        }
+        const LLMapView *d_views = (const LLMapView *)cms_stage(cms, views.data(), views.size() * sizeof(LLMapView));
+        const int4 *d_blk = blk.empty() ? nullptr : (const int4 *)cms_stage(cms, blk.data(), blk.size() * sizeof(int4));
+        if (!d_views || (!blk.empty() && !d_blk)) return LL_ERR_HIP;
+        const LLLmOpt o = ll_to_dev_opt(nullptr);
+        for (int it = 0; it < 2; ++it) {                                           /* :1832 */
+            if (!blk.empty()) hipLaunchKernelGGL(k_cms_knn, dim3((unsigned)blk.size()), dim3(LL_KNNB), 0, st, d_views, d_blk);
+            hipLaunchKernelGGL(k_cms_compact, dim3(2 * O), dim3(256), 0, st, d_views);
+            hipLaunchKernelGGL(k_cms_lm, dim3(O), dim3(256), 0, st, d_views, o);
+        }
+        CMS_HIP(hipGetLastError());
+        double *pin = (double *)ll_pinned_scratch((size_t)cms->S * 7 * sizeof(double));
+        if (!pin) { cms->err = "no page-locked scratch"; return LL_ERR_HIP; }
+        CMS_HIP(hipMemcpyAsync(pin, cms->d_pose, (size_t)cms->S * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+        rc = cms_sync(cms); if (rc) return rc;
+        for (int k = 0; k < O; ++k) std::memcpy(pose_w7 + 7 * run[opt_r[k]], pin + 7 * run[opt_r[k]], 7 * sizeof(double));
+    }
+    int bad = -1;
+    for (int r = 0, k = 0; r < R; ++r) {
+        const bool opt = k < O && opt_r[k] == r;
+        bool nan = false;
+        if (opt) { ++k; for (int j = 0; j < 7; ++j) nan = nan || std::isnan(pose_w7[7 * run[r] + j]); }
+        if (ran) ran[run[r]] = opt && !nan;
+        if (nan && bad < 0) bad = run[r];
+    }
+    if (bad >= 0) {
+        cms->err = "sequence " + std::to_string(bad) + ": the mapping solve returned an undefined pose (the input pose was NaN): set a pose and solve again";
+        return LL_ERR_STATE;
+    }
+
+    /* ---------------- update (:2103-2165) */
+    CMS_HIP(hipMemsetAsync(cms->d_addcnt, 0, (size_t)R * 2 * (CM_N + 1) * sizeof(int), st));
+    std::vector<CmsAssign> recs;
+    std::vector<int2> ablk;
+    std::vector<int> toff[2] = {std::vector<int>(R + 1, 0), std::vector<int>(R + 1, 0)};
+    for (int w = 0; w < 2; ++w)
+        for (int r = 0; r < R; ++r) {
+            ll_cubemap *cm = cms->cm[run[r]];
+            const int ns = cm->map->M.n_stk[w], at = toff[w][r];
+            toff[w][r + 1] = at + ns;
+            if (ns <= 0) continue;
+            CmsAssign A;
+            A.stk = cm->map->d_stk[w]; A.pose = cms->d_pose + 7 * run[r];
+            A.tp = cms->d_tp[w] + at; A.keys = cms->d_keys[w] + at; A.vals = cms->d_vals[w] + at;
+            A.addcnt = cms->d_addcnt + ((size_t)r * 2 + w) * (CM_N + 1);
+            A.n = ns; for (int k = 0; k < 3; ++k) A.cen[k] = cm->cen[k];
+            for (int f = 0; f < ns; f += 256) ablk.push_back(make_int2((int)recs.size(), f));
+            recs.push_back(A);
+        }
+    if (!recs.empty()) {
+        const CmsAssign *d_recs = (const CmsAssign *)cms_stage(cms, recs.data(), recs.size() * sizeof(CmsAssign));
+        const int2 *d_ablk = (const int2 *)cms_stage(cms, ablk.data(), ablk.size() * sizeof(int2));
+        if (!d_recs || !d_ablk) return LL_ERR_HIP;
+        hipLaunchKernelGGL(k_cms_assign, dim3((unsigned)ablk.size()), dim3(256), 0, st, d_recs, d_ablk);
+        for (const CmsAssign &A : recs) {                                          /* by cube, stack order kept */
+            if (A.n > 65536) ++cms->syncs;
+            if (ll_sort_pairs(A.keys, A.vals, cms->WS.keys, cms->WS.vals, A.n, cms->WS.hist, cms->WS.tile_sum, cms->WS.or_and, st)) { cms->err = "sort by cube: read-back failed"; return LL_ERR_HIP; }
+        }
+    }
+    std::vector<int> addcnt_all((size_t)R * 2 * (CM_N + 1));
+    {
+        int *pin = (int *)ll_pinned_scratch(addcnt_all.size() * sizeof(int));
+        if (!pin) { cms->err = "no page-locked scratch"; return LL_ERR_HIP; }
+        CMS_HIP(hipMemcpyAsync(pin, cms->d_addcnt, addcnt_all.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+        rc = cms_sync(cms); if (rc) return rc;
+        std::memcpy(addcnt_all.data(), pin, addcnt_all.size() * sizeof(int));
+    }
+    /* one voxel-grid segment per valid cube of every sequence: its cloud, then its new points (:2119-2125, :2151-2165) */
+    std::vector<std::vector<int>> goff(2 * R);
+    std::vector<int> useg[2], seg0[2] = {std::vector<int>(R + 1, 0), std::vector<int>(R + 1, 0)};
+    ops.clear();
+    for (int w = 0; w < 2; ++w) {
+        useg[w].assign(1, 0);
+        for (int r = 0; r < R; ++r) {
+            ll_cubemap *cm = cms->cm[run[r]];
+            const int *addcnt = addcnt_all.data() + ((size_t)r * 2 + w) * (CM_N + 1);
+            std::vector<int> &g = goff[2 * r + w];
+            g.assign(CM_N + 2, 0);
+            for (int c = 0; c < CM_N; ++c) g[c + 1] = g[c] + addcnt[c];
+            const size_t start = (size_t)useg[w].back();
+            size_t tot = start;
+            seg0[w][r] = (int)useg[w].size() - 1;
+            for (int v = 0; v < cm->n_valid; ++v) {
+                const int c = cm->valid[v];
+                if (cm->cnt[w][c] > 0) { ops.push_back({cm->pool[w][cm->cur[w]] + cm->off[w][c], nullptr, cms->d_work[w] + tot, cm->cnt[w][c], 0}); tot += (size_t)cm->cnt[w][c]; }
+                if (addcnt[c] > 0) { ops.push_back({cms->d_tp[w] + toff[w][r], cms->d_vals[w] + toff[w][r] + g[c], cms->d_work[w] + tot, addcnt[c], 0}); tot += (size_t)addcnt[c]; }
+                useg[w].push_back((int)tot);
+            }
+            if (tot - start > (size_t)cms->cap_work) { cms->err = "sequence " + std::to_string(run[r]) + ": the valid cubes hold more points than the filter workspace"; return LL_ERR_CAPACITY; }
+        }
+        seg0[w][R] = (int)useg[w].size() - 1;
+    }
+    rc = cms_copy(cms, ops); if (rc) return rc;
+    for (int w = 0; w < 2; ++w)
+        if (useg[w].back() > 0) { rc = cms_voxel(cms, w, cms->d_work[w], useg[w], cms->d_out[w], cms->d_nout + 2 + w); if (rc) return rc; }
+    std::vector<int> seg_count[2];
+    {
+        const size_t n0 = useg[0].size() - 1, n1 = useg[1].size() - 1;
+        int *pin = (int *)ll_pinned_scratch((n0 + n1 + 2) * sizeof(int));
+        if (!pin) { cms->err = "no page-locked scratch"; return LL_ERR_HIP; }
+        if (useg[0].back() > 0 && n0) CMS_HIP(hipMemcpyAsync(pin, cms->W[0].seg_count, n0 * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (useg[1].back() > 0 && n1) CMS_HIP(hipMemcpyAsync(pin + n0, cms->W[1].seg_count, n1 * sizeof(int), hipMemcpyDeviceToHost, st));
+        rc = cms_sync(cms); if (rc) return rc;
+        seg_count[0].assign(n0, 0); seg_count[1].assign(n1, 0);
+        if (useg[0].back() > 0) std::memcpy(seg_count[0].data(), pin, n0 * sizeof(int));
+        if (useg[1].back() > 0) std::memcpy(seg_count[1].data(), pin + n0, n1 * sizeof(int));
+    }
+    /* Will it fit?  Decided for every sequence and both cloud types before any pair table changes (ll_cubemap_update's rule) */
+    std::vector<size_t> need((size_t)R * 2), nout((size_t)R * 2), out_at((size_t)R * 2);
+    std::vector<char> is_valid(CM_N, 0);
+    for (int w = 0; w < 2; ++w) {
+        size_t at = 0;
+        for (int r = 0; r < R; ++r) {
+            ll_cubemap *cm = cms->cm[run[r]];
+            const int *addcnt = addcnt_all.data() + ((size_t)r * 2 + w) * (CM_N + 1);
+            size_t n = 0;
+            for (int v = 0; v < cm->n_valid; ++v) n += (size_t)seg_count[w][(size_t)seg0[w][r] + v];
+            out_at[(size_t)2 * r + w] = at; nout[(size_t)2 * r + w] = n; at += n;
+            for (int v = 0; v < cm->n_valid; ++v) is_valid[cm->valid[v]] = 1;
+            size_t nd = n;
+            for (int c = 0; c < CM_N; ++c) if (!is_valid[c] && addcnt[c] > 0) nd += (size_t)cm->cnt[w][c] + (size_t)addcnt[c];
+            need[(size_t)2 * r + w] = nd;
+            bool full = false;
+            if (cm->top[w] + nd > cm->cap_pool * 3 / 4) {
+                size_t live = 0;
+                for (int c = 0; c < CM_N; ++c) if (!is_valid[c]) live += (size_t)cm->cnt[w][c];
+                full = live + nd > cm->cap_pool;
+            }
+            for (int v = 0; v < cm->n_valid; ++v) is_valid[cm->valid[v]] = 0;
+            if (full) { cms->err = "sequence " + std::to_string(run[r]) + ": cube map pool exhausted (pool_points too small)"; return LL_ERR_CAPACITY; }
+        }
+    }
+    /* ---- commit: from here on a failure leaves the pair tables half-updated (the sequences are marked unusable) ---- */
+    for (int r = 0; r < R; ++r) cms->cm[run[r]]->broken = true;
+    ops.clear();
+    for (int r = 0; r < R; ++r) {
+        ll_cubemap *cm = cms->cm[run[r]];
+        for (int v = 0; v < cm->n_valid; ++v) is_valid[cm->valid[v]] = 1;
+        for (int w = 0; w < 2; ++w) {
+            const int *addcnt = addcnt_all.data() + ((size_t)r * 2 + w) * (CM_N + 1);
+            const std::vector<int> &g = goff[2 * r + w];
+            for (int v = 0; v < cm->n_valid; ++v) cm->cnt[w][cm->valid[v]] = 0;
+            rc = cm_reserve(cm, w, need[(size_t)2 * r + w]);
+            if (rc) { cms->err = "sequence " + std::to_string(run[r]) + ": " + cm->err; return rc; }
+            float4 *pool = cm->pool[w][cm->cur[w]];
+            const size_t n = nout[(size_t)2 * r + w];
+            if (n > 0) ops.push_back({cms->d_out[w] + out_at[(size_t)2 * r + w], nullptr, pool + cm->top[w], (int)n, 0});
+            size_t at = cm->top[w];
+            for (int v = 0; v < cm->n_valid; ++v) {
+                const int c = cm->valid[v], k = seg_count[w][(size_t)seg0[w][r] + v];
+                cm->off[w][c] = (int)at; cm->cnt[w][c] = k; at += (size_t)k;
+            }
+            for (int c = 0; c < CM_N; ++c)
+                if (!is_valid[c] && addcnt[c] > 0) {
+                    if (cm->cnt[w][c] > 0) ops.push_back({pool + cm->off[w][c], nullptr, pool + at, cm->cnt[w][c], 0});
+                    ops.push_back({cms->d_tp[w] + toff[w][r], cms->d_vals[w] + toff[w][r] + g[c], pool + at + (size_t)cm->cnt[w][c], addcnt[c], 0});
+                    cm->off[w][c] = (int)at; cm->cnt[w][c] += addcnt[c]; at += (size_t)cm->cnt[w][c];
+                }
+            cm->top[w] = at;
+        }
+        for (int v = 0; v < cm->n_valid; ++v) is_valid[cm->valid[v]] = 0;
+    }
+    rc = cms_copy(cms, ops); if (rc) return rc;                                   /* after every compaction above: stream order */
+    CMS_HIP(hipGetLastError());
+    for (int r = 0; r < R; ++r) cms->cm[run[r]]->broken = false;
+    ++cms->frames;
+    return LL_OK;
+}
+
+static int cms_check_common(ll_cubemaps *cms, const std::vector<int> &run)
+{
+    for (int q : run)
+        if (cms->cm[q]->broken) { cms->err = "sequence " + std::to_string(q) + ": unusable, an earlier update failed half-way"; return LL_ERR_STATE; }
+    return LL_OK;
+}
+
+extern "C" int ll_cubemaps_process_slots(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran)
+{
+    if (!cms || !slots || !pose_w7) return LL_ERR_ARG;
+    ll_ctx *ctx = cms->ctx;
+    std::vector<int> run;
+    std::vector<char> used(ctx->p.batch, 0);
+    for (int q = 0; q < cms->S; ++q) {
+        const int s = slots[q];
+        if (s == -1) continue;
+        if (s < -1 || s >= ctx->p.batch) { cms->err = "sequence " + std::to_string(q) + ": slot out of range"; return LL_ERR_ARG; }
+        if (used[s]) { cms->err = "sequence " + std::to_string(q) + ": slot " + std::to_string(s) + " is used by two sequences"; return LL_ERR_ARG; }
+        used[s] = 1;
+        run.push_back(q);
+    }
+    int rc = cms_check_common(cms, run); if (rc) return rc;
+    if (run.empty()) return LL_OK;
+    CMS_HIP(hipSetDevice(ctx->device));
+    cms->par ^= 1; cms->ar[cms->par].used = 0;
+    const int R = (int)run.size();
+    std::vector<ScanHdr> h(R);
+    {
+        ScanHdr *pin = (ScanHdr *)ll_pinned_scratch((size_t)R * sizeof(ScanHdr));
+        if (!pin) { cms->err = "no page-locked scratch"; return LL_ERR_HIP; }
+        for (int r = 0; r < R; ++r) CMS_HIP(hipMemcpyAsync(pin + r, ctx->V.hdr + slots[run[r]], sizeof(ScanHdr), hipMemcpyDeviceToHost, ctx->stream));
+        rc = cms_sync(cms); if (rc) return rc;
+        std::memcpy(h.data(), pin, (size_t)R * sizeof(ScanHdr));
+    }
+    std::vector<const float4 *> src[2] = {std::vector<const float4 *>(R), std::vector<const float4 *>(R)};
+    std::vector<int> n_in[2] = {std::vector<int>(R), std::vector<int>(R)}, flat(R, -1);
+    const LLView &V = ctx->V;
+    for (int r = 0; r < R; ++r) {
+        const int s = slots[run[r]];
+        if (h[r].status != 0) { cms->err = "sequence " + std::to_string(run[r]) + ": the slot holds no extracted scan"; return LL_ERR_STATE; }
+        src[0][r] = V.lsharp + (size_t)s * V.cap_lsharp; n_in[0][r] = h[r].n_less_sharp;
+        n_in[1][r] = h[r].n_less_flat;
+        if (h[r].lf_strided) { src[1][r] = nullptr; flat[r] = s; } else src[1][r] = V.lflat + (size_t)s * V.LFS;
+    }
+    return cms_frame(cms, run, src, n_in, flat, pose_w7, ran);
+}
+
+extern "C" int ll_cubemaps_process(ll_cubemaps *cms, const ll_point *const *corner_last, const int *n_corner, const ll_point *const *surf_last,
+                                   const int *n_surf, double *pose_w7, int *ran)
+{
+    if (!cms || !corner_last || !n_corner || !surf_last || !n_surf || !pose_w7) return LL_ERR_ARG;
+    std::vector<int> run;
+    for (int q = 0; q < cms->S; ++q) {
+        if (n_corner[q] < 0 || n_surf[q] < 0 || (!corner_last[q] && n_corner[q] > 0) || (!surf_last[q] && n_surf[q] > 0)) {
+            cms->err = "sequence " + std::to_string(q) + ": bad scan clouds"; return LL_ERR_ARG;
+        }
+        if (corner_last[q] || surf_last[q]) run.push_back(q);
+    }
+    int rc = cms_check_common(cms, run); if (rc) return rc;
+    if (run.empty()) return LL_OK;
+    CMS_HIP(hipSetDevice(cms->ctx->device));
+    cms->par ^= 1; cms->ar[cms->par].used = 0;
+    const int R = (int)run.size();
+    std::vector<const float4 *> src[2] = {std::vector<const float4 *>(R), std::vector<const float4 *>(R)};
+    std::vector<int> n_in[2] = {std::vector<int>(R), std::vector<int>(R)}, flat(R, -1);
+    for (int r = 0; r < R; ++r) {
+        const int q = run[r];
+        n_in[0][r] = n_corner[q]; n_in[1][r] = n_surf[q];
+        for (int w = 0; w < 2; ++w) {
+            if (n_in[w][r] > cms->cap_last[w]) { cms->err = "sequence " + std::to_string(q) + ": scan cloud larger than the capacity given to ll_cubemaps_create"; return LL_ERR_CAPACITY; }
+            const ll_point *p = w ? surf_last[q] : corner_last[q];
+            src[w][r] = n_in[w][r] > 0 ? (const float4 *)cms_stage(cms, p, (size_t)n_in[w][r] * sizeof(ll_point)) : nullptr;
+            if (n_in[w][r] > 0 && !src[w][r]) return LL_ERR_HIP;
+        }
+    }
+    return cms_frame(cms, run, src, n_in, flat, pose_w7, ran);
+}
+
+static int cms_seq(ll_cubemaps *cms, int q)
+{
+    if (q < 0 || q >= cms->S) { cms->err = "sequence index out of range"; return LL_ERR_ARG; }
+    return LL_OK;
+}
+
+extern "C" int ll_cubemaps_info(ll_cubemaps *cms, int q, int *cen3, int *counts4)
+{
+    if (!cms) return LL_ERR_ARG;
+    int rc = cms_seq(cms, q); if (rc) return rc;
+    return ll_cubemap_info(cms->cm[q], cen3, counts4);
+}
+
+extern "C" int ll_cubemaps_download_cloud(ll_cubemaps *cms, int q, int which, ll_point *out, int cap, int *n)
+{
+    if (!cms) return LL_ERR_ARG;
+    int rc = cms_seq(cms, q); if (rc) return rc;
+    rc = ll_cubemap_download_cloud(cms->cm[q], which, out, cap, n);
+    if (rc) cms->err = cms->cm[q]->err;
+    return rc;
+}
+
+extern "C" int ll_cubemaps_download_cube(ll_cubemaps *cms, int q, int surf, int cube_index, ll_point *out, int cap, int *n)
+{
+    if (!cms) return LL_ERR_ARG;
+    int rc = cms_seq(cms, q); if (rc) return rc;
+    rc = ll_cubemap_download_cube(cms->cm[q], surf, cube_index, out, cap, n);
+    if (rc) cms->err = cms->cm[q]->err;
+    return rc;
+}
+
+/* host synchronisations and frames since create (a frame = one process call that ran at least one sequence) */
+extern "C" int ll_cubemaps_stats(const ll_cubemaps *cms, long long *syncs, long long *frames)
+{
+    if (!cms) return LL_ERR_ARG;
+    if (syncs) *syncs = cms->syncs;
+    if (frames) *frames = cms->frames;
+    return LL_OK;
+}
