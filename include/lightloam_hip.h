@@ -411,6 +411,54 @@ int  ll_cubemaps_info(ll_cubemaps *cms, int q, int *cen3, int *counts4);
 int  ll_cubemaps_download_cloud(ll_cubemaps *cms, int q, int which, ll_point *out, int cap, int *n);
 int  ll_cubemaps_download_cube(ll_cubemaps *cms, int q, int surf, int cube_index, ll_point *out, int cap, int *n);
 int  ll_cubemaps_stats(const ll_cubemaps *cms, long long *syncs, long long *frames);
+/* sequence q back to what ll_cubemaps_create gave it (centre, counts, pool cursors, pair tables); the others are untouched */
+int  ll_cubemaps_reset(ll_cubemaps *cms, int q);
+
+/* ---------------------------------------------------------------- whole drives side by side
+ * S lanes; each runs one drive at a time through registration (ll_extract_batch), odometry (ll_odometry_sequences, one
+ * row) and mapping (ll_cubemaps), the single-drive chain of ll_odometry_kitti with mapping = 1 for every lane at once.
+ * The object uses slots [base, base + 2 S) of the context as two rows of S: one step reads lane q's raw scan from
+ * ll_drives_slots()[q] (upload it there first, with any upload entry point), and advances every running lane by one frame:
+ *   LL_DRIVE_IDLE   the lane does nothing; a drive ends when its lane goes idle
+ *   LL_DRIVE_RUN    the next frame of the lane's drive; only after a step on which the lane ran (no pause inside a drive)
+ *   LL_DRIVE_START  frame 0 of a new drive: a fresh cube map (ll_cubemaps_reset), identity world-odometry and map-to-odom
+ *                   poses; pose0[q] (NULL: identity) is the odometry warm start of the drive's frame 1
+ * Per step: extract over the row, odometry of the RUN lanes (frame index counted per lane, frame 1 = first odometry frame),
+ * then on the device the world pose (laserOdometry.cpp:830-831), transformAssociateToMap (laserMapping.cpp:113-117), the
+ * mapping frame (:1584-2165) and transformUpdate (:119-123).  The host synchronises only where the cube-map frame does.
+ * This is a batch runner: every frame is mapped (laserMapping.cpp:1572-1576 drops buffered frames to keep real time).
+ * Outputs ([S][7] / [S], each may be NULL; rows of lanes that did not run are NaN / 0):
+ *   odom_w7    laserOdometry's q_w_curr, t_w_curr;   mapped_w7   laserMapping's parameters[] after the frame;
+ *   ran        as ll_cubemaps_process_slots gives it.
+ * Lane q equals, bit for bit, its drive run alone through ll_odometry_frames, WorldPose and an ll_cubemap.
+ * keep_registered = 1: each step also keeps every running lane's full-resolution scan moved into the map frame
+ * (/velodyne_cloud_registered, :2203-2213), in laserCloud order; ll_drives_registered copies one lane's out.
+ * Errors: LL_ERR_ARG before anything is enqueued (a cmd outside 0..2, RUN on a lane that did not run on the previous step,
+ * a non-finite pose0 row of a START lane; at create: base + 2 S beyond the batch, n_outer outside 1..16).  LL_ERR_STATE
+ * for a scan the registration refused (status other than OK / EMPTY), LL_ERR_CAPACITY / LL_ERR_STATE from the mapping
+ * stage: the step is lost for every lane that ran, and those lanes are stopped -- their next command must be IDLE or
+ * START.  last_error names the lane at fault.  There is no retry protocol.
+ * ll_drives_stats: host synchronisations inside steps, and steps that ran at least one lane.                          */
+typedef struct ll_drives ll_drives;
+typedef struct {
+    int   n_lanes;                          /* S */
+    int   base;                             /* the object uses slots [base, base + 2 S) of the context */
+    float line_res, plane_res;              /* as ll_cubemaps_create (0.4, 0.8) */
+    int   max_scan_corner, max_scan_surf, pool_points;
+    int   n_outer;                          /* odometry outer iterations, 1..16 (3) */
+    int   keep_registered;                  /* 1: each step keeps every running lane's registered full-resolution cloud */
+} ll_drives_params;
+#define LL_DRIVE_IDLE  0
+#define LL_DRIVE_RUN   1
+#define LL_DRIVE_START 2
+int  ll_drives_create(ll_ctx *ctx, const ll_drives_params *p, ll_drives **out);
+void ll_drives_destroy(ll_drives *d);
+const char *ll_drives_last_error(const ll_drives *d);
+int  ll_drives_slots(ll_drives *d, int *slots);   /* [S]: the slot the next step reads lane q's raw scan from */
+int  ll_drives_step(ll_drives *d, const int *cmd, const double *pose0, double *odom_w7, double *mapped_w7, int *ran);
+int  ll_drives_registered(ll_drives *d, int lane, ll_point *out, int cap, int *n);   /* the last step's cloud of that lane (n = 0: it did not run) */
+int  ll_drives_stats(const ll_drives *d, long long *syncs, long long *frames);
+ll_cubemaps *ll_drives_cubemaps(ll_drives *d);    /* borrowed: info / cloud / cube of each lane's map */
 
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),

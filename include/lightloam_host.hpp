@@ -494,6 +494,61 @@ inline std::vector<double> odometry_sequences(Context &c, const ll_seq_layout &L
     return rel;
 }
 
+/* Whole drives side by side (ll_drives): S lanes, each running one drive at a time through registration -> odometry -> mapping,
+ * the chain of tools/ll_odometry_kitti with mapping = 1 for every lane in one step.  Upload lane q's raw scan into slots()[q], then
+ * step(cmd) with LL_DRIVE_IDLE / LL_DRIVE_RUN / LL_DRIVE_START per lane; odom / mapped ([S][7], NaN for lanes that did not run)
+ * and ran ([S]) hold the step's results.  Lane q equals its drive run alone through odometry_frames, WorldPose and a LaserMapping. */
+class Drives {
+public:
+    Drives(Context &c, int n_lanes, int max_scan_corner, int max_scan_surf, int pool_points = 1 << 22, int base = 0, bool keep_registered = false,
+           float lineRes = 0.4f, float planeRes = 0.8f, int n_outer = 3)
+        : S(n_lanes), odom((size_t)7 * (n_lanes > 0 ? n_lanes : 0)), mapped((size_t)7 * (n_lanes > 0 ? n_lanes : 0)), ran((size_t)(n_lanes > 0 ? n_lanes : 0), 0) {
+        ll_drives_params p;
+        p.n_lanes = n_lanes; p.base = base; p.line_res = lineRes; p.plane_res = planeRes;
+        p.max_scan_corner = max_scan_corner; p.max_scan_surf = max_scan_surf; p.pool_points = pool_points;
+        p.n_outer = n_outer; p.keep_registered = keep_registered ? 1 : 0;
+        c.check(ll_drives_create(c.get(), &p, &d_));
+    }
+    ~Drives() { ll_drives_destroy(d_); }
+    Drives(const Drives &) = delete;
+    Drives &operator=(const Drives &) = delete;
+
+    std::vector<int> slots() {
+        std::vector<int> s((size_t)S);
+        check(ll_drives_slots(d_, s.data()));
+        return s;
+    }
+    /* cmd: one command per lane; pose0: NULL or [S][7] (the rows of START lanes: the odometry warm start of frame 1) */
+    void step(const std::vector<int> &cmd, const double *pose0 = nullptr) {
+        if ((int)cmd.size() != S) throw Error(LL_ERR_ARG, "one command per lane");
+        check(ll_drives_step(d_, cmd.data(), pose0, odom.data(), mapped.data(), ran.data()));
+    }
+    /* lane q's mapped pose of the last step, as the trajectory file takes it */
+    WorldPose mapped_pose(int q) const {
+        WorldPose w;
+        for (int i = 0; i < 4; ++i) w.q[i] = mapped[(size_t)7 * q + i];
+        for (int i = 0; i < 3; ++i) w.t[i] = mapped[(size_t)7 * q + 4 + i];
+        return w;
+    }
+    /* /velodyne_cloud_registered of lane q from the last step (keep_registered) */
+    std::vector<PointXYZI> registered(int q) {
+        int n = 0;
+        check(ll_drives_registered(d_, q, nullptr, 0, &n));
+        std::vector<PointXYZI> out((size_t)n);
+        check(ll_drives_registered(d_, q, (ll_point *)out.data(), n, &n));
+        return out;
+    }
+    void stats(long long &syncs, long long &frames) const { check(ll_drives_stats(d_, &syncs, &frames)); }
+    ll_cubemaps *cubemaps() const { return ll_drives_cubemaps(d_); }
+    ll_drives *get() const { return d_; }
+    const int S;
+    std::vector<double> odom, mapped;   /* [S][7] */
+    std::vector<int> ran;               /* [S] */
+private:
+    void check(int rc) const { if (rc != LL_OK) throw Error(rc, ll_drives_last_error(d_)); }
+    ll_drives *d_ = nullptr;
+};
+
 }  // namespace lightloam
 
 /* ------------------------------------------------------------------------------------------------------------------

@@ -35,6 +35,8 @@ EXPORTS = [
     "ll_voxel_grid", "ll_map_set_pose", "ll_map_get_pose", "ll_map_evaluate", "ll_map_lm_begin", "ll_map_lm_propose", "ll_map_lm_accept",
     "ll_cubemaps_create", "ll_cubemaps_destroy", "ll_cubemaps_last_error", "ll_cubemaps_process_slots", "ll_cubemaps_process",
     "ll_cubemaps_info", "ll_cubemaps_download_cloud", "ll_cubemaps_download_cube", "ll_cubemaps_stats",
+    "ll_cubemaps_reset", "ll_drives_create", "ll_drives_destroy", "ll_drives_last_error", "ll_drives_slots", "ll_drives_step",
+    "ll_drives_registered", "ll_drives_stats", "ll_drives_cubemaps",
 ]
 
 
@@ -789,6 +791,104 @@ class CubeMaps:
         s = C.c_longlong(0); f = C.c_longlong(0)
         self._ck(self.lib.ll_cubemaps_stats(self.h, C.byref(s), C.byref(f)))
         return s.value, f.value
+
+    def reset(self, q):
+        """sequence q back to a freshly created cube map; the others are untouched"""
+        self._ck(self.lib.ll_cubemaps_reset(self.h, int(q)))
+
+
+class DrivesParams(C.Structure):
+    _fields_ = [("n_lanes", C.c_int), ("base", C.c_int), ("line_res", C.c_float), ("plane_res", C.c_float),
+                ("max_scan_corner", C.c_int), ("max_scan_surf", C.c_int), ("pool_points", C.c_int), ("n_outer", C.c_int),
+                ("keep_registered", C.c_int)]
+
+
+IDLE, RUN, START = 0, 1, 2
+
+
+class Drives:
+    """One ll_drives: n_lanes lanes, each running one drive at a time through registration -> odometry -> mapping.  Upload lane q's
+    raw scan into slots()[q], then step(cmd): IDLE (0), RUN (1: the next frame, only after a step the lane ran) or START (2: frame 0
+    of a new drive).  Lane q equals its drive run alone through ll_odometry_frames, WorldPose and a CubeMap, bit for bit."""
+
+    def __init__(self, ctx, n_lanes, max_scan_corner, max_scan_surf, pool_points=1 << 20, base=0, line_res=0.4, plane_res=0.8,
+                 n_outer=3, keep_registered=False):
+        self.ctx = ctx; self.lib = ctx.lib; self.n_lanes = int(n_lanes)
+        self.lib.ll_drives_last_error.restype = C.c_char_p
+        self.lib.ll_drives_last_error.argtypes = [C.c_void_p]
+        self.lib.ll_drives_destroy.argtypes = [C.c_void_p]
+        self.lib.ll_drives_cubemaps.restype = C.c_void_p
+        self.lib.ll_drives_cubemaps.argtypes = [C.c_void_p]
+        self.params = DrivesParams(self.n_lanes, int(base), line_res, plane_res, int(max_scan_corner), int(max_scan_surf),
+                                   int(pool_points), int(n_outer), int(bool(keep_registered)))
+        self.h = C.c_void_p()
+        rc = self.lib.ll_drives_create(ctx.h, C.byref(self.params), C.byref(self.h))
+        if rc != LL_OK:
+            raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
+        ctx._children.add(self)
+        self._cms_h = C.c_void_p(self.lib.ll_drives_cubemaps(self.h))
+
+    @property
+    def cubemaps(self):
+        """the lanes' cube maps (borrowed CubeMaps: info / cloud / cube per lane)"""
+        return _BorrowedCubeMaps(self._cms_h, self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ll_drives_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_drives_last_error(self.h).decode())
+
+    def slots(self):
+        """[S]: the slot the next step reads each lane's raw scan from"""
+        s = np.zeros(self.n_lanes, np.int32)
+        self._ck(self.lib.ll_drives_slots(self.h, _ptr(s)))
+        return s
+
+    def step(self, cmd, pose0=None):
+        """cmd [S] of IDLE / RUN / START; pose0: None or [S, 7] (the rows of START lanes are read) -> (odom [S, 7], mapped [S, 7],
+        ran [S] bool); rows of lanes that did not run are NaN / False"""
+        c = np.ascontiguousarray(cmd, np.int32)
+        if c.shape != (self.n_lanes,):
+            raise ValueError("cmd must have one entry per lane")
+        p0 = None if pose0 is None else np.ascontiguousarray(pose0, np.float64).reshape(self.n_lanes, 7)
+        odom = np.zeros((self.n_lanes, 7)); mapped = np.zeros((self.n_lanes, 7)); ran = np.zeros(self.n_lanes, np.int32)
+        self._ck(self.lib.ll_drives_step(self.h, _ptr(c), _ptr(p0), _ptr(odom), _ptr(mapped), _ptr(ran)))
+        return odom, mapped, ran.astype(bool)
+
+    def registered(self, lane):
+        """the last step's registered full-resolution cloud of `lane` ((n, 4) float32, laserCloud order; empty if it did not run)"""
+        n = C.c_int(0)
+        self._ck(self.lib.ll_drives_registered(self.h, int(lane), None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 4), np.float32)
+        self._ck(self.lib.ll_drives_registered(self.h, int(lane), _ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def stats(self):
+        """(host synchronisations inside steps, steps that ran at least one lane) since create"""
+        s = C.c_longlong(0); f = C.c_longlong(0)
+        self._ck(self.lib.ll_drives_stats(self.h, C.byref(s), C.byref(f)))
+        return s.value, f.value
+
+
+class _BorrowedCubeMaps(CubeMaps):
+    """the CubeMaps interface over the handle an ll_drives owns; closing it does nothing"""
+
+    def __init__(self, handle, owner):
+        self.ctx = owner.ctx; self.lib = owner.lib; self.n_seq = owner.n_lanes; self.h = handle
+        self._owner = owner                           # keeps the drives object (and so the handle) alive
+
+    def close(self):
+        self.h = None
 
 
 _EMPTY = (C.c_float * 4)()      # a non-NULL address for an empty cloud of a running sequence

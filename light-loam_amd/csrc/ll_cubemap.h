@@ -78,3 +78,14 @@ static void cm_shift(ll_cubemap *cm, int axis, int dir)
 /* ll_cubemap.hip: live clouds of type w -> the other pool, back to back; room for `need` more points (compacting when 3/4 full) */
 int cm_compact(ll_cubemap *cm, int w);
 int cm_reserve(ll_cubemap *cm, int w, size_t need);
+
+/* ll_cubemaps.hip's internals that ll_drives.hip drives (not exported from the library): a frame opens with llcms_begin (the
+ * staging arena of the call), may stage tables through it, and maps from the guesses the caller left in llcms_dev_pose [S][7] */
+#define LL_HIDDEN __attribute__((visibility("hidden")))
+LL_HIDDEN void llcms_begin(ll_cubemaps *cms);
+LL_HIDDEN void *llcms_stage(ll_cubemaps *cms, const void *src, size_t bytes);
+LL_HIDDEN double *llcms_dev_pose(ll_cubemaps *cms);
+LL_HIDDEN long long llcms_syncs(const ll_cubemaps *cms);
+LL_HIDDEN const std::string &llcms_err(const ll_cubemaps *cms);
+LL_HIDDEN int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran, const void *extra_dev, void *extra_host,
+                                      size_t extra_bytes, ScanHdr *hdr_out);

@@ -763,3 +763,73 @@ extern "C" int ll_cubemaps_stats(const ll_cubemaps *cms, long long *syncs, long 
     if (frames) *frames = cms->frames;
     return LL_OK;
 }
+
+/* sequence q back to what ll_cubemaps_create gave it: centre, pair tables, pool cursors, gathered-cloud counts (the pools' contents
+ * are dead: nothing reads a pool beyond its tables) */
+extern "C" int ll_cubemaps_reset(ll_cubemaps *cms, int q)
+{
+    if (!cms) return LL_ERR_ARG;
+    int rc = cms_seq(cms, q); if (rc) return rc;
+    ll_cubemap *cm = cms->cm[q];
+    cm->cen[0] = 10; cm->cen[1] = 10; cm->cen[2] = 5;
+    for (int w = 0; w < 2; ++w) {
+        cm->top[w] = 0; cm->cur[w] = 0;
+        std::fill(cm->off[w].begin(), cm->off[w].end(), 0); std::fill(cm->cnt[w].begin(), cm->cnt[w].end(), 0);
+        cm->map->M.n_map[w] = 0; cm->map->M.n_stk[w] = 0;
+    }
+    cm->n_valid = 0;
+    cm->broken = false;
+    return LL_OK;
+}
+
+/* ------------------------------------------------------------------ for ll_drives (ll_drives.hip), not exported */
+void llcms_begin(ll_cubemaps *cms) { cms->par ^= 1; cms->ar[cms->par].used = 0; }
+void *llcms_stage(ll_cubemaps *cms, const void *src, size_t bytes) { return cms_stage(cms, src, bytes); }
+double *llcms_dev_pose(ll_cubemaps *cms) { return cms->d_pose; }
+long long llcms_syncs(const ll_cubemaps *cms) { return cms->syncs; }
+const std::string &llcms_err(const ll_cubemaps *cms) { return cms->err; }
+
+/* ll_cubemaps_process_slots with the guesses already in d_pose (rows of the running sequences; llcms_begin called): they come to
+ * the host with the slot headers, in the same synchronisation, together with extra_bytes from extra_dev into extra_host.  A slot
+ * whose extract status is LL_ERR_EMPTY maps with empty clouds.  hdr_out[q]: the header of slots[q] (running sequences). */
+int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran, const void *extra_dev, void *extra_host,
+                            size_t extra_bytes, ScanHdr *hdr_out)
+{
+    ll_ctx *ctx = cms->ctx;
+    std::vector<int> run;
+    for (int q = 0; q < cms->S; ++q)
+        if (slots[q] >= 0) run.push_back(q);
+    int rc = cms_check_common(cms, run); if (rc) return rc;
+    const int R = (int)run.size();
+    const size_t pose_bytes = (size_t)cms->S * 7 * sizeof(double), hdr_at = (pose_bytes + extra_bytes + 15) & ~(size_t)15;
+    std::vector<ScanHdr> h(R);
+    {
+        unsigned char *pin = (unsigned char *)ll_pinned_scratch(hdr_at + (size_t)R * sizeof(ScanHdr));
+        if (!pin) { cms->err = "no page-locked scratch"; return LL_ERR_HIP; }
+        CMS_HIP(hipMemcpyAsync(pin, cms->d_pose, pose_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (extra_bytes) CMS_HIP(hipMemcpyAsync(pin + pose_bytes, extra_dev, extra_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        for (int r = 0; r < R; ++r)
+            CMS_HIP(hipMemcpyAsync(pin + hdr_at + (size_t)r * sizeof(ScanHdr), ctx->V.hdr + slots[run[r]], sizeof(ScanHdr), hipMemcpyDeviceToHost, ctx->stream));
+        rc = cms_sync(cms); if (rc) return rc;
+        std::memcpy(pose_w7, pin, pose_bytes);
+        if (extra_bytes) std::memcpy(extra_host, pin + pose_bytes, extra_bytes);
+        std::memcpy(h.data(), pin + hdr_at, (size_t)R * sizeof(ScanHdr));
+    }
+    if (R == 0) return LL_OK;
+    std::vector<const float4 *> src[2] = {std::vector<const float4 *>(R), std::vector<const float4 *>(R)};
+    std::vector<int> n_in[2] = {std::vector<int>(R), std::vector<int>(R)}, flat(R, -1);
+    const LLView &V = ctx->V;
+    for (int r = 0; r < R; ++r) {
+        const int s = slots[run[r]];
+        hdr_out[run[r]] = h[r];
+        if (h[r].status != 0 && h[r].status != LL_ERR_EMPTY) {
+            cms->err = "sequence " + std::to_string(run[r]) + ": the scan registration refused the slot's scan (status " + std::to_string(h[r].status) + ")";
+            return LL_ERR_STATE;
+        }
+        const bool empty = h[r].status == LL_ERR_EMPTY;
+        src[0][r] = V.lsharp + (size_t)s * V.cap_lsharp; n_in[0][r] = empty ? 0 : h[r].n_less_sharp;
+        n_in[1][r] = empty ? 0 : h[r].n_less_flat;
+        if (h[r].lf_strided) { src[1][r] = nullptr; flat[r] = s; } else src[1][r] = V.lflat + (size_t)s * V.LFS;
+    }
+    return cms_frame(cms, run, src, n_in, flat, pose_w7, ran);
+}

@@ -1,0 +1,94 @@
+// Many KITTI drives side by side: the directories of velodyne scans (*.bin, float32 x, y, z, reflectance) queued over `lanes`
+// lanes of one lightloam::Drives (ll_drives), each through registration -> odometry -> mapping -- the many-drive twin of
+//   ll_odometry_kitti <dir> <result_path> <scan_line> <first guess tx> 1 <max_ring_points>
+// A lane starts the next directory of the queue when its drive ends.  Directory i's mapped trajectory goes to <result_dir>/<i>.txt
+// in the reference's trajectory-file format (laserMapping.cpp:2284-2325), byte for byte what ll_odometry_kitti writes for it.
+//
+//   ll_kitti_drives <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...
+//
+// Build:  g++ -O2 -std=c++14 -I include tools/ll_kitti_drives.cpp -L light-loam_amd -llightloam_hip -o ll_kitti_drives
+#include <algorithm>
+#include <cstdlib>
+#include <dirent.h>
+#include <iostream>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "lightloam_host.hpp"
+
+static std::vector<std::string> bin_files(const std::string &dir)
+{
+    std::vector<std::string> files;
+    if (DIR *d = opendir(dir.c_str())) {
+        while (dirent *e = readdir(d)) {
+            const std::string n = e->d_name;
+            if (n.size() > 4 && n.substr(n.size() - 4) == ".bin") files.push_back(dir + "/" + n);
+        }
+        closedir(d);
+    }
+    std::sort(files.begin(), files.end());
+    return files;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc < 7) { std::cerr << "usage: ll_kitti_drives <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
+    const std::string result_dir = argv[1];
+    const int scan_line = std::atoi(argv[2]);
+    const double tx0 = std::atof(argv[3]);
+    const int max_ring_points = std::atoi(argv[4]), lanes = std::atoi(argv[5]);
+    if (lanes < 1) { std::cerr << "lanes must be >= 1\n"; return 2; }
+    std::vector<std::vector<std::string>> drives;
+    for (int a = 6; a < argc; ++a) {
+        drives.push_back(bin_files(argv[a]));
+        if (drives.back().size() < 2) { std::cerr << "need at least two .bin scans in " << argv[a] << "\n"; return 2; }
+    }
+    try {
+        using namespace lightloam;
+        Context ctx(scan_line, 2 * lanes, 0, -1.0, -24.9f, 2.0f, 0, max_ring_points, 3);   /* as ll_odometry_kitti: x, y, z resident */
+        Drives d(ctx, lanes, scan_line * 120 + 64, 400000, 1 << 22);                      /* ll_odometry_kitti's mapping capacities */
+        const double p0[7] = {0, 0, 0, 1, tx0, 0, 0};
+        std::vector<double> pose0((size_t)7 * lanes);
+        for (int q = 0; q < lanes; ++q) std::copy(p0, p0 + 7, &pose0[(size_t)7 * q]);
+        std::vector<int> drive_of(lanes, -1), frame(lanes, 0);                             /* per lane: the drive it runs, its next frame */
+        std::vector<std::unique_ptr<TrajectoryWriter>> out(drives.size());
+        size_t next = 0;
+        long long steps = 0;
+        for (;;) {
+            std::vector<int> cmd(lanes, LL_DRIVE_IDLE);
+            for (int q = 0; q < lanes; ++q) {
+                if (drive_of[q] >= 0 && frame[q] < (int)drives[drive_of[q]].size()) { cmd[q] = LL_DRIVE_RUN; continue; }
+                drive_of[q] = -1;
+                if (next < drives.size()) {                                                 /* the lane takes the next drive of the queue */
+                    drive_of[q] = (int)next++; frame[q] = 0; cmd[q] = LL_DRIVE_START;
+                    const std::string path = result_dir + "/" + std::to_string(drive_of[q]) + ".txt";
+                    std::remove(path.c_str());
+                    out[drive_of[q]].reset(new TrajectoryWriter(path));
+                }
+            }
+            if (std::all_of(cmd.begin(), cmd.end(), [](int c) { return c == LL_DRIVE_IDLE; })) break;
+            const std::vector<int> slots = d.slots();
+            for (int q = 0; q < lanes; ++q) {
+                if (cmd[q] == LL_DRIVE_IDLE) continue;
+                const std::vector<float> pts = read_lidar_data(drives[drive_of[q]][frame[q]]);
+                ctx.check(ll_upload_scan(ctx.get(), slots[q], pts.data(), 4, (int)(pts.size() / 4)));
+            }
+            d.step(cmd, pose0.data());
+            ++steps;
+            for (int q = 0; q < lanes; ++q) {
+                if (cmd[q] == LL_DRIVE_IDLE) continue;
+                out[drive_of[q]]->append(d.mapped_pose(q));
+                ++frame[q];
+            }
+        }
+        long long syncs = 0, frames = 0;
+        d.stats(syncs, frames);
+        std::cout << "wrote " << drives.size() << " mapped trajectories to " << result_dir << " in " << steps << " steps over " << lanes
+                  << " lanes (" << syncs << " host synchronisations)\n";
+    } catch (const lightloam::Error &e) {
+        std::cerr << "lightloam error " << e.code << ": " << e.what() << "\n";
+        return 1;
+    }
+    return 0;
+}
