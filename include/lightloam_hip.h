@@ -414,6 +414,40 @@ int  ll_cubemaps_stats(const ll_cubemaps *cms, long long *syncs, long long *fram
 /* sequence q back to what ll_cubemaps_create gave it (centre, counts, pool cursors, pair tables); the others are untouched */
 int  ll_cubemaps_reset(ll_cubemaps *cms, int q);
 
+/* ---------------------------------------------------------------- map export: laserCloudSurround and laserCloudMap
+ * laserMapping's two map publications -- the surround cloud every 5th frame (laserMapping.cpp:2173-2188) and the whole map
+ * every 20th (:2190-2203) -- for any subset of the S sequences in one call: the host lists the selected clouds from its pair
+ * tables, ONE gather kernel packs them on the device, ONE copy brings them to `out`, and the host synchronises ONCE, whatever
+ * S and the number of cubes are.  which [S] selects per sequence what it contributes; `out` may be host memory (pageable or
+ * page-locked) or device memory (the gather then writes to it directly).
+ * Order: the sequences back to back in sequence order; inside one sequence the cubes in list order (LL_MAP_SURROUND: the i, j,
+ * k loop order of :1784-1801; LL_MAP_ALL: cube index 0 .. 4850), per cube the corner cloud, then the surf cloud, each in the
+ * cube's own point order -- the concatenation of ll_cubemaps_download_cube(q, 0, c), (q, 1, c) over the list, byte for byte.
+ * Surround set: the valid cubes of the last frame that sequence ran, read after that frame's update, as in the reference (the
+ * list is made at :1784-1801, the cubes are read at :2176-2181, after the filters of :2150-2168).  A sequence that has not
+ * run a frame since create or ll_cubemaps_reset exports 0 points in either mode.
+ * Read-only: an export changes no pool, pair table, pose or counter of the maps other than ll_cubemaps_stats' syncs; it may be
+ * called between any two frames, and through ll_drives_cubemaps(d) between any two ll_drives_step calls.
+ * Host synchronisations: ll_cubemaps_export / ll_cubemap_export exactly one per successful call (added to syncs; the first
+ * calls also allocate the device staging buffer, which grows to the need and never beyond the pools' live points);
+ * ll_cubemaps_export_sizes none -- it is host bookkeeping, with no launch.
+ * offset [S + 1]: sequence q's points are out[offset[q] .. offset[q + 1]); totals are long long (128 maps can pass 2^31 bytes).
+ * Errors: LL_ERR_ARG before anything is enqueued (NULL handle / which, a value outside -1 .. 1, negative cap, out == NULL with
+ * a non-zero total); LL_ERR_CAPACITY when the total exceeds cap -- offset is still filled, out is not touched, nothing is
+ * launched; LL_ERR_STATE when a SELECTED sequence's map is unusable (an update failed half-way; last_error names it) -- one
+ * that is not selected does not stop the others; LL_ERR_HIP when the staging buffer cannot be allocated (last_error has the
+ * size; the object stays usable).  A tile-sharded single map (ll_cubemap_set_shard) exports the cubes it owns.
+ * ll_cubemaps_export_timing: the last export's table build (host clock), gather and copy (device events) in ms, and its
+ * points, segments (non-empty clouds) and tiles (workgroups of the gather); either pointer may be NULL.               */
+#define LL_MAP_NONE     (-1)   /* the sequence is left out */
+#define LL_MAP_SURROUND   0    /* the cubes of laserCloudSurroundInd of the sequence's last frame (:1784-1801), as :2175-2181 adds them */
+#define LL_MAP_ALL        1    /* all 4851 cubes, as :2192-2197 adds them */
+int  ll_cubemaps_export_sizes(ll_cubemaps *cms, const int *which /* [S] */, long long *offset /* [S + 1] */);
+int  ll_cubemaps_export(ll_cubemaps *cms, const int *which /* [S] */, ll_point *out, long long cap, long long *offset /* [S + 1], may be NULL */);
+int  ll_cubemaps_export_timing(const ll_cubemaps *cms, double *ms3, long long *counts3);
+/* the same for the single cube map (the ROS node's map); n (may be NULL): the points of the selection, also on LL_ERR_CAPACITY */
+int  ll_cubemap_export(ll_cubemap *cm, int which, ll_point *out, long long cap, long long *n);
+
 /* ---------------------------------------------------------------- whole drives side by side
  * S lanes; each runs one drive at a time through registration (ll_extract_batch), odometry (ll_odometry_sequences, one
  * row) and mapping (ll_cubemaps), the single-drive chain of ll_odometry_kitti with mapping = 1 for every lane at once.

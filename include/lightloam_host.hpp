@@ -316,6 +316,16 @@ public:
         check(ll_cubemap_update(cm_, parameters));                                        /* local to the rank: no collective behind it in this frame */
         return ran;
     }
+    /* laserCloudSurround (LL_MAP_SURROUND, :2173-2181: the cubes of the last frame's laserCloudSurroundInd) or laserCloudMap
+     * (LL_MAP_ALL, :2190-2197: all 4851 cubes), per cube the corner cloud then the surf cloud: one gather, one copy */
+    void export_map(int which, std::vector<PointXYZI> &out) {
+        long long n = 0;
+        ll_point none;
+        const int rc = ll_cubemap_export(cm_, which, &none, 0, &n);                       /* the size: with points to write nothing is launched */
+        if (rc != LL_ERR_CAPACITY) check(rc);
+        out.resize((size_t)n);
+        if (n > 0) check(ll_cubemap_export(cm_, which, (ll_point *)out.data(), n, &n));
+    }
     double parameters[7] = {0, 0, 0, 1, 0, 0, 0};                 /* :81-83 */
     double q_wmap_wodom[4] = {0, 0, 0, 1}, t_wmap_wodom[3] = {0, 0, 0};   /* :88-89 */
     ll_cubemap *get() const { return cm_; }
@@ -398,6 +408,21 @@ public:
             nc[q] = corner_last[q] ? (int)corner_last[q]->size() : 0; ns[q] = surf_last[q] ? (int)surf_last[q]->size() : 0;
         }
         check(ll_cubemaps_process(cms_, c.data(), nc.data(), s.data(), ns.data(), parameters.data(), ran.data()));
+    }
+    /* the map publications (:2173-2203) of the sequences which[q] selects (LL_MAP_NONE / LL_MAP_SURROUND / LL_MAP_ALL), back to
+     * back in sequence order: sequence q is out[offset[q] .. offset[q + 1]).  One gather, one copy, one synchronisation */
+    void export_maps(const std::vector<int> &which, std::vector<PointXYZI> &out, std::vector<long long> &offset) {
+        if ((int)which.size() != S) throw Error(LL_ERR_ARG, "one selection per sequence");
+        const int rc = export_from(cms_, S, which.data(), out, offset);
+        if (rc != LL_OK) check(rc);
+    }
+    /* the same on a borrowed handle (Drives::export_maps); returns the status, the text is the handle's last error */
+    static int export_from(ll_cubemaps *cms, int n_seq, const int *which, std::vector<PointXYZI> &out, std::vector<long long> &offset) {
+        offset.assign((size_t)n_seq + 1, 0);
+        int rc = ll_cubemaps_export_sizes(cms, which, offset.data());
+        if (rc != LL_OK) return rc;
+        out.resize((size_t)offset[(size_t)n_seq]);
+        return ll_cubemaps_export(cms, which, (ll_point *)out.data(), (long long)out.size(), offset.data());
     }
     const int S;
     std::vector<double> parameters, q_wmap_wodom, t_wmap_wodom;   /* [S][7], [S][4], [S][3] */
@@ -537,6 +562,12 @@ public:
         std::vector<PointXYZI> out((size_t)n);
         check(ll_drives_registered(d_, q, (ll_point *)out.data(), n, &n));
         return out;
+    }
+    /* LaserMappingSequences::export_maps of the lanes' maps, between any two steps */
+    void export_maps(const std::vector<int> &which, std::vector<PointXYZI> &out, std::vector<long long> &offset) {
+        if ((int)which.size() != S) throw Error(LL_ERR_ARG, "one selection per lane");
+        const int rc = LaserMappingSequences::export_from(cubemaps(), S, which.data(), out, offset);
+        if (rc != LL_OK) throw Error(rc, ll_cubemaps_last_error(cubemaps()));
     }
     void stats(long long &syncs, long long &frames) const { check(ll_drives_stats(d_, &syncs, &frames)); }
     ll_cubemaps *cubemaps() const { return ll_drives_cubemaps(d_); }

@@ -37,7 +37,10 @@ EXPORTS = [
     "ll_cubemaps_info", "ll_cubemaps_download_cloud", "ll_cubemaps_download_cube", "ll_cubemaps_stats",
     "ll_cubemaps_reset", "ll_drives_create", "ll_drives_destroy", "ll_drives_last_error", "ll_drives_slots", "ll_drives_step",
     "ll_drives_registered", "ll_drives_stats", "ll_drives_cubemaps",
+    "ll_cubemaps_export_sizes", "ll_cubemaps_export", "ll_cubemaps_export_timing", "ll_cubemap_export",
 ]
+
+MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
 
 
 class Params(C.Structure):
@@ -101,6 +104,10 @@ def load_library():
         _lib.ll_host_alloc.restype = C.c_void_p
         _lib.ll_host_alloc.argtypes = [C.c_size_t]
         _lib.ll_host_free.argtypes = [C.c_void_p]
+        _lib.ll_cubemaps_export_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ll_cubemaps_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+        _lib.ll_cubemaps_export_timing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ll_cubemap_export.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
     return _lib
 
 
@@ -707,6 +714,18 @@ class CubeMap:
         self._ck(self.lib.ll_cubemap_download_cube(self.h, int(surf), int(index), _ptr(out), len(out), C.byref(n)))
         return out[:n.value].copy()
 
+    def export(self, which):
+        """laserCloudSurround (MAP_SURROUND) or laserCloudMap (MAP_ALL) of this map: (n, 4) float32, per cube corner then surf;
+        one gather, one copy, one synchronisation"""
+        n = C.c_longlong(0); out = np.zeros((1, 4), np.float32)
+        rc = self.lib.ll_cubemap_export(self.h, int(which), out.ctypes.data, 0, C.byref(n))   # the size: nothing is launched
+        if rc not in (LL_OK, -4):
+            self._ck(rc)
+        if n.value > 0:
+            out = np.empty((n.value, 4), np.float32)
+            self._ck(self.lib.ll_cubemap_export(self.h, int(which), out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value]
+
 
 class CubeMaps:
     """One ll_cubemaps: n_seq cube maps side by side, frame k of every running sequence in one set of launches per stage.
@@ -786,6 +805,39 @@ class CubeMaps:
         self._ck(self.lib.ll_cubemaps_download_cube(self.h, int(q), int(surf), int(index), _ptr(out), len(out), C.byref(n)))
         return out[:n.value].copy()
 
+    def _which(self, which):
+        w = np.full(self.n_seq, which, np.int32) if np.ndim(which) == 0 else np.ascontiguousarray(which, np.int32)
+        if w.shape != (self.n_seq,):
+            raise ValueError("which must be one value or one per sequence")
+        return w
+
+    def export_sizes(self, which):
+        """offset [S + 1] int64 of export(which): host bookkeeping, no launch, no synchronisation"""
+        w = self._which(which)
+        off = np.zeros(self.n_seq + 1, np.int64)
+        self._ck(self.lib.ll_cubemaps_export_sizes(self.h, w.ctypes.data, off.ctypes.data))
+        return off
+
+    def export(self, which, out=None):
+        """which: MAP_NONE / MAP_SURROUND / MAP_ALL, one for all sequences or one per sequence -> (points [N, 4] float32,
+        offset [S + 1] int64); sequence q is points[offset[q]:offset[q + 1]], per cube corner then surf.  One gather, one copy,
+        one synchronisation.  out: a preallocated (n, 4) float32 array to fill instead (page-locked memory copies faster)"""
+        w = self._which(which)
+        off = self.export_sizes(w)
+        n = int(off[-1])
+        if out is None:
+            out = np.empty((max(n, 1), 4), np.float32)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.size < 4 * n:
+            raise ValueError("out must be a C-contiguous float32 array of at least N x 4")
+        self._ck(self.lib.ll_cubemaps_export(self.h, w.ctypes.data, out.ctypes.data, out.size // 4, off.ctypes.data))
+        return out.reshape(-1, 4)[:n], off
+
+    def export_timing(self):
+        """the last export: ((table build ms, gather ms, copy ms), (points, segments, tiles))"""
+        ms = np.zeros(3); cnt = np.zeros(3, np.int64)
+        self._ck(self.lib.ll_cubemaps_export_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
+        return tuple(ms), tuple(int(c) for c in cnt)
+
     def stats(self):
         """(host synchronisations, frames) since create"""
         s = C.c_longlong(0); f = C.c_longlong(0)
@@ -832,6 +884,10 @@ class Drives:
     def cubemaps(self):
         """the lanes' cube maps (borrowed CubeMaps: info / cloud / cube per lane)"""
         return _BorrowedCubeMaps(self._cms_h, self)
+
+    def export_maps(self, which):
+        """CubeMaps.export of the lanes' maps: (points [N, 4], offset [S + 1]); between any two steps"""
+        return self.cubemaps.export(which)
 
     def close(self):
         if getattr(self, "h", None):

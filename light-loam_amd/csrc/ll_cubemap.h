@@ -23,6 +23,19 @@ __host__ __device__ __forceinline__ int cm_owner(int wi, int wj, int wk, int wor
 }
 #define CM_GID_SHIFT 20                  /* global id = position in the valid list << 20 | position in the cube */
 
+/* map export (ll_map_export.hip): one non-empty cloud of the output.  dst: its first point in the output; tile0: the tiles of
+ * the segments before it */
+struct LLExpSeg { const float4 *src; long long dst; int cnt; unsigned tile0; };
+/* what an exporting object keeps between calls: the device staging buffer of the gathered cloud (grown to the need), the
+ * page-locked / device pair the single map's table goes through, the events around the gather and the copy of the last call */
+struct LLMapExport {
+    float4 *d_dst = nullptr; size_t cap_dst = 0;
+    unsigned char *h_tab = nullptr, *d_tab = nullptr; size_t cap_tab = 0;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; bool have_ev = false;
+    double ms[3] = {0.0, 0.0, 0.0};               /* the last export: table build (host clock), gather, copy (events) */
+    long long points = 0, segments = 0, tiles = 0;
+};
+
 struct ll_cubemap {
     ll_ctx *ctx = nullptr;
     ll_map *map = nullptr;
@@ -45,6 +58,7 @@ struct ll_cubemap {
     void *vox_mem = nullptr; LLVoxWork W;         /* prepare's filters and update's corner filter */
     void *vox_mem2 = nullptr; LLVoxWork W2;       /* update's surface filter */
     void *sort_mem = nullptr; LLVoxWork WS;       /* scratch of the by-cube sort (same layout, stack-sized) */
+    LLMapExport X;                                /* ll_cubemap_export's buffers (not used by the maps inside an ll_cubemaps) */
     std::vector<void *> allocs;
     std::string err;
     bool broken = false;                          /* an update failed half-way: the pair tables no longer describe the pools */
@@ -79,9 +93,19 @@ static void cm_shift(ll_cubemap *cm, int axis, int dir)
 int cm_compact(ll_cubemap *cm, int w);
 int cm_reserve(ll_cubemap *cm, int w, size_t need);
 
+#define LL_HIDDEN __attribute__((visibility("hidden")))
+/* ll_map_export.hip: the tile size of this call; the segments of one map in output order (returns its points; segs == nullptr:
+ * sizes only); the single map's table upload; the gather + copy + the one synchronisation; the last call's figures */
+LL_HIDDEN int llx_tile();
+LL_HIDDEN long long llx_segments(const ll_cubemap *cm, int which, long long dst0, int tile_points, unsigned long long *tile, std::vector<LLExpSeg> *segs);
+LL_HIDDEN const LLExpSeg *llx_stage(LLMapExport &X, const std::vector<LLExpSeg> &segs, hipStream_t st, std::string &err);
+LL_HIDDEN int llx_gather(LLMapExport &X, ll_ctx *ctx, const LLExpSeg *d_segs, size_t nseg, unsigned long long ntiles, long long total, size_t limit,
+                         int tile_points, ll_point *out, std::string &err);
+LL_HIDDEN void llx_free(LLMapExport &X);
+LL_HIDDEN void llx_timing(const LLMapExport &X, double *ms3, long long *counts3);
+
 /* ll_cubemaps.hip's internals that ll_drives.hip drives (not exported from the library): a frame opens with llcms_begin (the
  * staging arena of the call), may stage tables through it, and maps from the guesses the caller left in llcms_dev_pose [S][7] */
-#define LL_HIDDEN __attribute__((visibility("hidden")))
 LL_HIDDEN void llcms_begin(ll_cubemaps *cms);
 LL_HIDDEN void *llcms_stage(ll_cubemaps *cms, const void *src, size_t bytes);
 LL_HIDDEN double *llcms_dev_pose(ll_cubemaps *cms);

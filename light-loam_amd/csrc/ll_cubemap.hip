@@ -90,6 +90,7 @@ extern "C" void ll_cubemap_destroy(ll_cubemap *cm)
     if (cm->ctx) { (void)hipSetDevice(cm->ctx->device); (void)hipStreamSynchronize(cm->ctx->stream); }
     if (cm->map) ll_map_destroy(cm->map);
     for (void *p : cm->allocs) (void)hipFree(p);
+    llx_free(cm->X);
     delete cm;
 }
 

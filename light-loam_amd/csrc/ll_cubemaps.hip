@@ -22,6 +22,7 @@
 #include "ll_factor_math.h"
 #include "ll_lm_step.h"
 #include "ll_map_search.h"
+#include <chrono>
 #include <cmath>
 
 int ll_sort_pairs(unsigned long long *keys, int *vals, unsigned long long *tmp_keys, int *tmp_vals, int n, int *hist, int *tile_sum,
@@ -227,6 +228,7 @@ struct ll_cubemaps {
     double *d_pose = nullptr;                     /* [S][7]: the pose every stage of a frame reads */
     LLVoxWork W[2], WS;                           /* per cloud type: prepare's and update's filters; WS: the by-cube sort */
     CmsArena ar[2]; int par = 0;
+    LLMapExport X;                                /* ll_cubemaps_export's staging buffer and events */
     std::vector<void *> allocs, host_allocs;
     long long syncs = 0, frames = 0;
     std::string err;
@@ -310,6 +312,7 @@ extern "C" void ll_cubemaps_destroy(ll_cubemaps *cms)
     for (ll_cubemap *cm : cms->cm) ll_cubemap_destroy(cm);
     for (void *p : cms->allocs) (void)hipFree(p);
     for (void *p : cms->host_allocs) (void)hipHostFree(p);
+    llx_free(cms->X);
     delete cms;
 }
 
@@ -779,6 +782,62 @@ extern "C" int ll_cubemaps_reset(ll_cubemaps *cms, int q)
     }
     cm->n_valid = 0;
     cm->broken = false;
+    return LL_OK;
+}
+
+/* ------------------------------------------------------------------ map export (:2173-2203 for any subset of the sequences)
+ * Host bookkeeping: the sizes of the selected clouds.  segs != nullptr: also the segment table of the gather */
+static int cms_export_table(ll_cubemaps *cms, const int *which, long long *offset, int tile_points, unsigned long long *ntiles, std::vector<LLExpSeg> *segs, long long *total)
+{
+    for (int q = 0; q < cms->S; ++q) {
+        if (which[q] < LL_MAP_NONE || which[q] > LL_MAP_ALL) { cms->err = "sequence " + std::to_string(q) + ": which must be LL_MAP_NONE, LL_MAP_SURROUND or LL_MAP_ALL"; return LL_ERR_ARG; }
+        if (which[q] != LL_MAP_NONE && cms->cm[q]->broken) { cms->err = "sequence " + std::to_string(q) + ": unusable, an earlier update failed half-way"; return LL_ERR_STATE; }
+    }
+    long long at = 0;
+    for (int q = 0; q < cms->S; ++q) {
+        if (offset) offset[q] = at;
+        at += llx_segments(cms->cm[q], which[q], at, tile_points, ntiles, segs);
+    }
+    if (offset) offset[cms->S] = at;
+    *total = at;
+    return LL_OK;
+}
+
+extern "C" int ll_cubemaps_export_sizes(ll_cubemaps *cms, const int *which, long long *offset)
+{
+    if (!cms || !which || !offset) return LL_ERR_ARG;
+    long long total = 0;
+    return cms_export_table(cms, which, offset, 0, nullptr, nullptr, &total);
+}
+
+extern "C" int ll_cubemaps_export(ll_cubemaps *cms, const int *which, ll_point *out, long long cap, long long *offset)
+{
+    if (!cms || !which) return LL_ERR_ARG;
+    if (cap < 0) { cms->err = "map export: negative capacity"; return LL_ERR_ARG; }
+    const auto t0 = std::chrono::steady_clock::now();
+    const int tile_points = llx_tile();
+    std::vector<LLExpSeg> segs;
+    unsigned long long ntiles = 0;
+    long long total = 0;
+    int rc = cms_export_table(cms, which, offset, tile_points, &ntiles, &segs, &total); if (rc) return rc;
+    if (total > 0 && !out) { cms->err = "map export: out is NULL"; return LL_ERR_ARG; }
+    if (total > cap) { cms->err = "map export: " + std::to_string(total) + " points, room for " + std::to_string(cap); return LL_ERR_CAPACITY; }
+    if (ntiles > 0x7fffffffull) { cms->err = "map export: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+    CMS_HIP(hipSetDevice(cms->ctx->device));
+    cms->par ^= 1; cms->ar[cms->par].used = 0;                                     /* the last frame's copies may still read the other arena */
+    const LLExpSeg *d_segs = nullptr;
+    if (total > 0) { d_segs = (const LLExpSeg *)cms_stage(cms, segs.data(), segs.size() * sizeof(LLExpSeg)); if (!d_segs) return LL_ERR_HIP; }
+    cms->X.ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    rc = llx_gather(cms->X, cms->ctx, d_segs, segs.size(), ntiles, total, (size_t)cms->S * 2 * cms->cap_pool, tile_points, out, cms->err);
+    if (rc == LL_OK) ++cms->syncs;
+    return rc;
+}
+
+/* the last ll_cubemaps_export: ms3 = table build (host clock), gather, copy to out (device events); counts3 = points, segments, tiles */
+extern "C" int ll_cubemaps_export_timing(const ll_cubemaps *cms, double *ms3, long long *counts3)
+{
+    if (!cms) return LL_ERR_ARG;
+    llx_timing(cms->X, ms3, counts3);
     return LL_OK;
 }
 

@@ -43,9 +43,6 @@
 
 namespace {
 
-const int laserCloudWidth = 21, laserCloudHeight = 21, laserCloudDepth = 11;                       /* :48-50 */
-const int laserCloudNum = laserCloudWidth * laserCloudHeight * laserCloudDepth;                     /* :53 */
-
 std::queue<sensor_msgs::PointCloud2ConstPtr> cornerLastBuf, surfLastBuf, fullResBuf;                /* :94-96 */
 std::queue<nav_msgs::Odometry::ConstPtr> odometryBuf;                                               /* :97 */
 std::mutex mBuf;                                                                                    /* :98 */
@@ -111,21 +108,6 @@ void laserOdometryHandler(const nav_msgs::Odometry::ConstPtr &laserOdometry)    
     pubOdomAftMappedHighFrec.publish(odomAftMapped);
 }
 
-/* the clouds of the cubes `ind`, corner then surf per cube, like the `+=` loops of :2173-2178 / :2191-2195 */
-void gather_cubes(const std::vector<int> &ind, std::vector<lightloam::PointXYZI> &out)
-{
-    out.clear();
-    std::vector<lightloam::PointXYZI> buf;
-    for (int cube : ind)
-        for (int surf = 0; surf < 2; ++surf) {
-            int n = 0;
-            if (ll_cubemap_download_cube(g_lm->get(), surf, cube, nullptr, 1 << 30, &n) != LL_OK || n == 0) continue;
-            buf.resize((size_t)n);
-            if (ll_cubemap_download_cube(g_lm->get(), surf, cube, (ll_point *)buf.data(), n, &n) != LL_OK) continue;
-            out.insert(out.end(), buf.begin(), buf.end());
-        }
-}
-
 void publish_cloud(ros::Publisher &pub, const std::vector<lightloam::PointXYZI> &pts, double stamp)
 {
     sensor_msgs::PointCloud2 out;
@@ -171,46 +153,31 @@ void process()                                                                  
             const auto &P = mOdom->pose.pose;
             const double q_wodom_curr[4] = {P.orientation.x, P.orientation.y, P.orientation.z, P.orientation.w};
             const double t_wodom_curr[3] = {P.position.x, P.position.y, P.position.z};
-            double guess_t[3];
-            int cen[3] = {0, 0, 0};
             try {
                 /* mBuf is held around the queue pops only, as in the reference (:1505-1578): the subscriber callbacks -- the
                  * high-frequency republish of laserOdometryHandler among them -- keep running during the device work.
                  * q_wmap_wodom / t_wmap_wodom are written by this thread alone (transformUpdate) and read by that callback:
                  * their own small mutex covers the write */
                 g_lm->transformAssociateToMap(q_wodom_curr, t_wodom_curr);                          /* :1581 */
-                for (int k = 0; k < 3; ++k) guess_t[k] = g_lm->parameters[4 + k];
                 g_lm->process(cornerLast, surfLast);                                                /* :1584-2165 */
                 { std::lock_guard<std::mutex> l(mPose); g_lm->transformUpdate(q_wodom_curr, t_wodom_curr); }   /* :2101 */
-                if (ll_cubemap_info(g_lm->get(), cen, nullptr) != LL_OK) throw lightloam::Error(LL_ERR_STATE, "cube map info");
             } catch (const lightloam::Error &e) {
                 ROS_ERROR("laser mapping: %s (code %d)", e.what(), e.code);
                 continue;
             }
             const double *q_w_curr = g_lm->parameters, *t_w_curr = g_lm->parameters + 4;
             if (frameCount % 5 == 0) {                                                              /* :2171-2186 */
-                /* laserCloudSurroundInd: the cubes centerCube +-2, +-2, +-1 inside the grid, in the loop order of :1784-1801;
-                 * the centre cube comes from the pose guess of :1581, after the shift loops moved it with the grid */
-                int c[3];
-                for (int k = 0; k < 3; ++k) {
-                    c[k] = int((guess_t[k] + 25.0) / 50.0) + cen[k];                                /* :1584-1593 */
-                    if (guess_t[k] + 25.0 < 0) c[k]--;
-                }
-                std::vector<int> ind;
-                for (int i = c[0] - 2; i <= c[0] + 2; i++)
-                    for (int j = c[1] - 2; j <= c[1] + 2; j++)
-                        for (int k = c[2] - 1; k <= c[2] + 1; k++)
-                            if (i >= 0 && i < laserCloudWidth && j >= 0 && j < laserCloudHeight && k >= 0 && k < laserCloudDepth)
-                                ind.push_back(i + laserCloudWidth * j + laserCloudWidth * laserCloudHeight * k);
+                /* laserCloudSurroundInd: the cubes centerCube +-2, +-2, +-1 inside the grid, in the loop order of :1784-1801, which
+                 * the cube map kept from this frame; corner then surf per cube, like the `+=` loops of :2173-2178 -- one gather */
                 std::vector<lightloam::PointXYZI> surround;
-                gather_cubes(ind, surround);
+                try { g_lm->export_map(LL_MAP_SURROUND, surround); }
+                catch (const lightloam::Error &e) { ROS_ERROR("laser mapping: %s (code %d)", e.what(), e.code); surround.clear(); }
                 publish_cloud(pubLaserCloudSurround, surround, timeLaserOdometry);
             }
             if (frameCount % 20 == 0) {                                                             /* :2188-2201 */
-                std::vector<int> all((size_t)laserCloudNum);
-                for (int i = 0; i < laserCloudNum; ++i) all[(size_t)i] = i;
-                std::vector<lightloam::PointXYZI> map;
-                gather_cubes(all, map);
+                std::vector<lightloam::PointXYZI> map;                                              /* all 4851 cubes (:2191-2195) */
+                try { g_lm->export_map(LL_MAP_ALL, map); }
+                catch (const lightloam::Error &e) { ROS_ERROR("laser mapping: %s (code %d)", e.what(), e.code); map.clear(); }
                 publish_cloud(pubLaserCloudMap, map, timeLaserOdometry);
             }
             for (auto &p : fullRes) {                                                               /* pointAssociateToMap (:125-133), :2203-2207 */

@@ -4,11 +4,17 @@
 // A lane starts the next directory of the queue when its drive ends.  Directory i's mapped trajectory goes to <result_dir>/<i>.txt
 // in the reference's trajectory-file format (laserMapping.cpp:2284-2325), byte for byte what ll_odometry_kitti writes for it.
 //
-//   ll_kitti_drives <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...
+//   ll_kitti_drives [--maps] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...
+//
+// --maps: when a drive ends, its final map (laserCloudMap, laserMapping.cpp:2190-2197: all cubes, corner then surf per cube) is
+// also written, as <result_dir>/<i>_map.bin in the layout of the scans (float32 x, y, z, intensity: read_lidar_data reads it back).
+// Lanes whose drives end on the same step are read in one export.  Without --maps the output is what it was.
 //
 // Build:  g++ -O2 -std=c++14 -I include tools/ll_kitti_drives.cpp -L light-loam_amd -llightloam_hip -o ll_kitti_drives
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <dirent.h>
 #include <iostream>
 #include <memory>
@@ -33,7 +39,9 @@ static std::vector<std::string> bin_files(const std::string &dir)
 
 int main(int argc, char **argv)
 {
-    if (argc < 7) { std::cerr << "usage: ll_kitti_drives <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
+    const bool maps = argc > 1 && std::strcmp(argv[1], "--maps") == 0;
+    if (maps) { --argc; ++argv; }
+    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
     const std::string result_dir = argv[1];
     const int scan_line = std::atoi(argv[2]);
     const double tx0 = std::atof(argv[3]);
@@ -80,6 +88,25 @@ int main(int argc, char **argv)
                 if (cmd[q] == LL_DRIVE_IDLE) continue;
                 out[drive_of[q]]->append(d.mapped_pose(q));
                 ++frame[q];
+            }
+            if (maps) {                                                                     /* the drives that just ended: their maps, before a START clears them */
+                std::vector<int> which(lanes, LL_MAP_NONE);
+                bool any = false;
+                for (int q = 0; q < lanes; ++q)
+                    if (cmd[q] != LL_DRIVE_IDLE && frame[q] == (int)drives[drive_of[q]].size()) { which[q] = LL_MAP_ALL; any = true; }
+                if (any) {
+                    std::vector<PointXYZI> pts;
+                    std::vector<long long> off;
+                    d.export_maps(which, pts, off);
+                    for (int q = 0; q < lanes; ++q) {
+                        if (which[q] != LL_MAP_ALL) continue;
+                        const std::string path = result_dir + "/" + std::to_string(drive_of[q]) + "_map.bin";
+                        std::FILE *f = std::fopen(path.c_str(), "wb");
+                        const size_t n = (size_t)(off[(size_t)q + 1] - off[(size_t)q]);
+                        if (!f || std::fwrite(pts.data() + off[(size_t)q], sizeof(PointXYZI), n, f) != n) { if (f) std::fclose(f); throw Error(LL_ERR_ARG, "cannot write " + path); }
+                        std::fclose(f);
+                    }
+                }
             }
         }
         long long syncs = 0, frames = 0;
