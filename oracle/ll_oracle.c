@@ -1,7 +1,8 @@
 /*
  * ll_oracle.c -- CPU ORACLE (test infrastructure; see ll_oracle.h header comment).
- * PARITY UNPINNED: restatement of /root/reference sources + published third-party algorithms;
- * no reference-held golden vectors exist and the reference cannot be built here.
+ * Restatement of /root/reference sources + published third-party algorithms.  a1-a3 are PINNED to the reference's own
+ * scanRegistration.cpp built against declared doubles (oracle/ref.py); the rest is PARITY UNPINNED: no reference-held
+ * golden vectors exist and those translation units cannot be built here.
  *
  * Build: gcc -O2 -ffp-contract=off -fno-fast-math (baseline x86-64: f32 stays f32, no FMA),
  * matching the reference build (CMakeLists.txt:4-6: -O3, no -march).

@@ -5,10 +5,22 @@
  * and bench.py's cpu_baseline leg may load it.  The product path (light-loam_amd/) never
  * links, imports or calls anything in oracle/ and has no CPU fallback.
  *
- * PARITY UNPINNED: the reference (BrenYi/Light-LOAM) ships no tests, golden vectors or
- * fixtures, and none of its translation units can be compiled in this image (every TU
- * needs ROS1 + PCL, and the odometry path also Eigen + Ceres; none are installed and no
- * stand-in headers are written for them).  This file is therefore a *restatement* of the
+ * PINNED (a1-a3 and the less-flat selection: orc_organize, orc_curvature, orc_pick up to the
+ * VoxelGrid input): scanRegistration.cpp uses no Eigen / Ceres / FLANN / OpenCV symbol, so
+ * oracle/ref.py compiles the reference's own file unchanged, at the reference's flags
+ * (-std=c++14 -O3 -g), against declared container doubles (oracle/ref_standins/,
+ * tests/native/ros_double/) into oracle/_ref/, and tests/test_ref_scan_registration.py holds
+ * this oracle -- tests/test_gpu_ref_extract.py the kernels -- to that binary bitwise, with
+ * this toolchain's g++ / libstdc++ (std::sort) and glibc.  The doubles replace, and so pin
+ * nothing of: PCL VoxelGrid (a4's centroids and order), removeNaNFromPointCloud, the message
+ * conversions.  Assumption A1 (float overloads at :139) is measured against the double
+ * variant there; DESIGN section 6 has the figures.
+ *
+ * PARITY UNPINNED (everything else: a4's filter, a5-a10, f1, f2): the reference
+ * (BrenYi/Light-LOAM) ships no tests, golden vectors or fixtures, and laserOdometry.cpp,
+ * laserMapping.cpp and lidarFactor.hpp cannot be compiled in this image (Eigen and Ceres types
+ * run through all of them; neither is installed, and a stand-in for them would restate
+ * third-party arithmetic and pin nothing).  For those rows this file is a *restatement* of the
  * reference algorithm, each function citing the reference file:line it follows; the
  * third-party arithmetic on the path (PCL 1.10 VoxelGrid / KdTreeFLANN->FLANN L2_Simple,
  * Eigen 3.3 Quaternion slerp/_transformVector/cross/normalize, Ceres 2.x Jet, HuberLoss,

@@ -1,7 +1,8 @@
 """ctypes binding of the CPU oracle (oracle/ll_oracle.c).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.
-The product package (light-loam_amd/) never imports this module.  PARITY UNPINNED -- see ll_oracle.h.
+The product package (light-loam_amd/) never imports this module.  a1-a3 are pinned to the reference's own scan registration
+(oracle/ref.py); the rest is PARITY UNPINNED -- see ll_oracle.h.
 """
 import ctypes as C
 import os
@@ -24,6 +25,8 @@ def build(force=False):
     src = [os.path.join(_HERE, f) for f in ("ll_oracle.c", "ll_oracle.h", "Makefile")]
     if force or not os.path.exists(_LIB) or any(os.path.getmtime(s) > os.path.getmtime(_LIB) for s in src):
         subprocess.check_call(["make", "-C", _HERE, "-s"])
+    from oracle import ref
+    ref.build(force)                 # the reference's own scan registration -> oracle/_ref/ (a no-op where the reference is absent)
     return _LIB
 
 

@@ -2,9 +2,9 @@
 independent cross-checks of the restated third-party arithmetic (finite differences, a second derivation in
 torch float64 autograd), and the edge cases the reference code paths contain.
 
-The reference ships no tests or golden vectors and cannot be built in this image, so these do
-NOT pin the oracle to the reference ("parity unpinned", see oracle/ll_oracle.h); they pin it to the behaviour we
-read out of the cited lines.
+The reference ships no tests or golden vectors, so these do NOT pin the oracle to the reference
+("parity unpinned", see oracle/ll_oracle.h); they pin it to the behaviour we read out of the cited lines.  The extract
+stage (a1-a3) IS held to the reference's own compiled scan registration, in tests/test_ref_scan_registration.py.
 """
 import numpy as np
 import pytest
