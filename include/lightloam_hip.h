@@ -448,13 +448,41 @@ int  ll_cubemaps_export_timing(const ll_cubemaps *cms, double *ms3, long long *c
 /* the same for the single cube map (the ROS node's map); n (may be NULL): the points of the selection, also on LL_ERR_CAPACITY */
 int  ll_cubemap_export(ll_cubemap *cm, int which, ll_point *out, long long cap, long long *n);
 
+/* ---------------------------------------------------------------- map import: the export's inverse
+ * ll_cubemaps_layout (host bookkeeping: no launch, no synchronisation) gives what an LL_MAP_ALL export does not say about map q:
+ * the centre cen3, the per-cube point counts counts [2][4851] (corner, then surf), and the valid list of the last frame
+ * (valid [125], *n_valid entries) that LL_MAP_SURROUND reads.  Together with the LL_MAP_ALL cloud this is the complete state
+ * of the map; where the clouds lie inside the pools is not part of it (nothing reads a pool except through its tables).
+ * Any out pointer may be NULL.  LL_ERR_STATE for an unusable map.
+ * ll_cubemaps_import puts such state back.  `points` is exactly the byte layout ll_cubemaps_export(.., LL_MAP_ALL) writes --
+ * the sequences back to back (sequence q at points[offset[q] .. offset[q + 1])), cubes 0 .. 4850, per cube the corner cloud,
+ * then the surf cloud -- in host memory (pageable or page-locked) or in device memory.  sel [S] (0 / 1) selects the sequences to
+ * load; cen3 [S][3], counts [S][2][4851], valid [S][125] and n_valid [S] are read for the selected ones only.  For any S and
+ * any number of cubes: ONE upload of the points (none when they are on the device), one table upload, ONE scatter kernel and
+ * ONE host synchronisation, added to ll_cubemaps_stats' syncs.
+ * A selected map is replaced whole, as if ll_cubemaps_reset had run first (ll_cubemaps_info's four cloud sizes are 0 until its
+ * next frame); its pools end compact, in cube order.  A map that is not selected is untouched.
+ * Errors, all decided before anything is enqueued or any table changes: LL_ERR_ARG for a NULL pointer, a sel outside 0 / 1,
+ * an offset that is not ascending, counts that do not add up to the sequence's share of offset, a negative count, a centre
+ * beyond +-2^24 (the centre is the array index of the world's origin cube and legitimately leaves 0 .. 20 on any long drive,
+ * so only values the cube arithmetic cannot hold are refused), n_valid outside 0 .. 125 or a valid entry outside 0 .. 4850 or
+ * listed twice; LL_ERR_CAPACITY when one type's points exceed pool_points (last_error names the sequence); LL_ERR_HIP when
+ * the staging buffer cannot be allocated (the object stays usable).
+ * ll_cubemap_layout / ll_cubemap_import: the same for the single map (n: the points of the cloud); a tile-sharded map accepts
+ * only counts in cubes it owns (LL_ERR_ARG otherwise).                                                                       */
+int  ll_cubemaps_layout(ll_cubemaps *cms, int q, int *cen3, int *counts /* [2][4851] */, int *valid /* [125] */, int *n_valid);
+int  ll_cubemaps_import(ll_cubemaps *cms, const int *sel /* [S] */, const ll_point *points, const long long *offset /* [S + 1] */,
+                        const int *cen3 /* [S][3] */, const int *counts /* [S][2][4851] */, const int *valid /* [S][125] */, const int *n_valid /* [S] */);
+int  ll_cubemap_layout(ll_cubemap *cm, int *cen3, int *counts, int *valid, int *n_valid);
+int  ll_cubemap_import(ll_cubemap *cm, const ll_point *points, long long n, const int *cen3, const int *counts, const int *valid, int n_valid);
+
 /* ---------------------------------------------------------------- whole drives side by side
  * S lanes; each runs one drive at a time through registration (ll_extract_batch), odometry (ll_odometry_sequences, one
  * row) and mapping (ll_cubemaps), the single-drive chain of ll_odometry_kitti with mapping = 1 for every lane at once.
  * The object uses slots [base, base + 2 S) of the context as two rows of S: one step reads lane q's raw scan from
  * ll_drives_slots()[q] (upload it there first, with any upload entry point), and advances every running lane by one frame:
  *   LL_DRIVE_IDLE   the lane does nothing; a drive ends when its lane goes idle
- *   LL_DRIVE_RUN    the next frame of the lane's drive; only after a step on which the lane ran (no pause inside a drive)
+ *   LL_DRIVE_RUN    the next frame of the lane's drive; only after a step on which the lane ran, or a restore (lane checkpoints, below)
  *   LL_DRIVE_START  frame 0 of a new drive: a fresh cube map (ll_cubemaps_reset), identity world-odometry and map-to-odom
  *                   poses; pose0[q] (NULL: identity) is the odometry warm start of the drive's frame 1
  * Per step: extract over the row, odometry of the RUN lanes (frame index counted per lane, frame 1 = first odometry frame),
@@ -493,6 +521,52 @@ int  ll_drives_step(ll_drives *d, const int *cmd, const double *pose0, double *o
 int  ll_drives_registered(ll_drives *d, int lane, ll_point *out, int cap, int *n);   /* the last step's cloud of that lane (n = 0: it did not run) */
 int  ll_drives_stats(const ll_drives *d, long long *syncs, long long *frames);
 ll_cubemaps *ll_drives_cubemaps(ll_drives *d);    /* borrowed: info / cloud / cube of each lane's map */
+
+/* ---------------------------------------------------------------- lane checkpoints
+ * A lane's state between two steps is its cube map (ll_cubemaps_layout + the LL_MAP_ALL cloud), its world-odometry and
+ * map-to-odom poses, its frame counter (the vote switches on at frame 6) and the previous row's slot: the four feature clouds
+ * and the solved pose, the target and the warm start of the lane's next odometry frame.  ll_drives_save writes that for the
+ * selected lanes (lanes [S], 0 / 1) into one self-describing blob (INTEGRATION.md documents the format); ll_drives_restore
+ * puts record r of a blob into lane into[r] (-1: the record is skipped) of this object -- another lane index, another
+ * ll_drives with another S and base, a fresh context, another process.  The restored lane counts as having run: its next
+ * command may be RUN (the drive continues, bit for bit as if it had never stopped), IDLE or START.
+ * ll_drives_save_size: the blob's bytes, from host bookkeeping (no launch, no synchronisation); a negative value is an error code.
+ * ll_drives_save: ONE pack launch (the export gather's tiles, the ring-strided less-flat cloud closed up in
+ * ll_download_features' order, the poses and the counter), ONE copy and ONE synchronisation whatever the selection; `blob` may
+ * be host memory or (16-byte aligned) device memory; *bytes (may be NULL) is filled whenever the selection is valid.  The call
+ * is read-only: the run continues exactly as if it had not saved, apart from the syncs counters (ll_drives_stats and
+ * ll_cubemaps_stats rise by one).  A lane can be saved when it ran on the previous step, or was restored and has not stepped
+ * since; LL_ERR_STATE otherwise.  LL_ERR_CAPACITY when cap is too small: blob is not touched.  The pack launch checks every
+ * ring-strided less-flat cloud against the size in its scan header; a mismatch is LL_ERR_STATE and the blob gets no header.
+ * ll_drives_restore (blob in host memory): ONE upload, one import scatter, one small state kernel, the search grids of the
+ * restored slots as ll_upload_features builds them (one launch per run of neighbouring lanes: one when all lanes or a
+ * contiguous block are restored) and ONE synchronisation.  The lane's previous-row slot receives the
+ * feature clouds the way ll_upload_features leaves a slot.  Every refusal is made before any lane changes: LL_ERR_ARG (last_error names the
+ * field) for a wrong magic or version, a truncated or inconsistent blob, n_scans, distortion, line_res or plane_res that differ
+ * from the destination's, an into entry that is no lane, two records into one lane; LL_ERR_CAPACITY when pool_points or a
+ * per-scan feature capacity of the destination is too small.
+ * ll_checkpoint_describe: pure host code, no device and no context: validates a blob and returns its header fields and, in
+ * info->records (caller's array of info->cap_records entries, may be NULL), the per-record sizes.  LL_ERR_ARG as above.    */
+typedef struct {
+    int       lane;                          /* the lane the record was saved from */
+    int       frame_index;                   /* of the lane's last frame (0: only frame 0 has run) */
+    long long n_corner, n_surf;              /* map points per type */
+    int       n_features[4];                 /* sharp, less sharp, flat, less flat of the previous-row slot */
+    long long offset, bytes;                 /* the record's device payload inside the blob */
+} ll_checkpoint_record;
+typedef struct {
+    int       version, n_records;
+    long long total_bytes;
+    int       n_scans, distortion, voxel_sort_ranks;
+    float     line_res, plane_res;
+    int       need_features[4];              /* the per-scan feature capacities a destination needs */
+    ll_checkpoint_record *records;           /* in: the caller's array or NULL */
+    int       cap_records;                   /* in: its entries */
+} ll_checkpoint_info;
+long long ll_drives_save_size(ll_drives *d, const int *lanes /* [S] */);
+int  ll_drives_save(ll_drives *d, const int *lanes /* [S] */, void *blob, long long cap, long long *bytes);
+int  ll_drives_restore(ll_drives *d, const int *into /* [records] */, const void *blob, long long bytes);
+int  ll_checkpoint_describe(const void *blob, long long bytes, ll_checkpoint_info *info);
 
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),

@@ -348,6 +348,14 @@ private:
     friend class LaserMappingSequences;
 };
 
+/* ll_cubemaps_layout of one map: the centre, the per-cube point counts [2][4851] (corner, then surf) and the valid list of its
+ * last frame */
+struct MapLayout {
+    enum { N_COUNTS = 2 * 4851 };
+    int cen[3] = {10, 10, 5};
+    std::vector<int> counts = std::vector<int>((size_t)N_COUNTS, 0), valid = std::vector<int>(125, 0);
+};
+
 /* laserMapping for S sequences side by side (ll_cubemaps): per sequence q the state of LaserMapping (parameters, q_wmap_wodom,
  * t_wmap_wodom, rows of [S][7] / [S][4] / [S][3]) and the same formulas; one call runs frame k of every running sequence.
  * Sequence q equals a LaserMapping fed the same frames, bit for bit. */
@@ -416,6 +424,37 @@ public:
         const int rc = export_from(cms_, S, which.data(), out, offset);
         if (rc != LL_OK) check(rc);
     }
+    /* what an LL_MAP_ALL export does not say about map q (ll_cubemaps_layout: host bookkeeping, no launch); with that cloud the
+     * complete state of the map */
+    MapLayout layout(int q) {
+        MapLayout L;
+        int n = 0;
+        check(ll_cubemaps_layout(cms_, q, L.cen, L.counts.data(), L.valid.data(), &n));
+        L.valid.resize((size_t)n);
+        return L;
+    }
+    /* the export's inverse (ll_cubemaps_import): points / offset as export_maps(LL_MAP_ALL) gave them, layouts[q] == nullptr leaves
+     * map q alone.  One upload, one scatter, one synchronisation */
+    void import_maps(const std::vector<PointXYZI> &points, const std::vector<long long> &offset, const std::vector<const MapLayout *> &layouts) {
+        if ((int)layouts.size() != S || (int)offset.size() != S + 1) throw Error(LL_ERR_ARG, "one layout per sequence and S + 1 offsets");
+        if (offset[(size_t)S] > (long long)points.size()) throw Error(LL_ERR_ARG, "points is shorter than offset[S]");
+        const int rc = import_into(cms_, S, points.data(), offset.data(), layouts);
+        if (rc != LL_OK) check(rc);
+    }
+    static int import_into(ll_cubemaps *cms, int n_seq, const PointXYZI *points, const long long *offset, const std::vector<const MapLayout *> &layouts) {
+        const size_t S_ = (size_t)n_seq;
+        std::vector<int> sel(S_, 0), cen(3 * S_, 0), counts(S_ * MapLayout::N_COUNTS, 0), valid(S_ * 125, 0), nv(S_, 0);
+        for (size_t q = 0; q < S_; ++q) {
+            const MapLayout *L = layouts[q];
+            if (!L) continue;
+            if (L->counts.size() != (size_t)MapLayout::N_COUNTS || L->valid.size() > 125) return LL_ERR_ARG;
+            sel[q] = 1; nv[q] = (int)L->valid.size();
+            std::copy(L->cen, L->cen + 3, &cen[3 * q]);
+            std::copy(L->counts.begin(), L->counts.end(), &counts[q * MapLayout::N_COUNTS]);
+            std::copy(L->valid.begin(), L->valid.end(), &valid[q * 125]);
+        }
+        return ll_cubemaps_import(cms, sel.data(), (const ll_point *)points, offset, cen.data(), counts.data(), valid.data(), nv.data());
+    }
     /* the same on a borrowed handle (Drives::export_maps); returns the status, the text is the handle's last error */
     static int export_from(ll_cubemaps *cms, int n_seq, const int *which, std::vector<PointXYZI> &out, std::vector<long long> &offset) {
         offset.assign((size_t)n_seq + 1, 0);
@@ -479,6 +518,10 @@ struct WorldPose {
 class TrajectoryWriter {
 public:
     explicit TrajectoryWriter(const std::string &result_path) : path_(result_path) {}
+    /* a trajectory continued in another process (lane checkpoints): H_init [12] of the file's first pose, as init() gave it */
+    TrajectoryWriter(const std::string &result_path, const double *H_init) : path_(result_path), init_flag_(false) { std::copy(H_init, H_init + 12, Hinit_); }
+    bool started() const { return !init_flag_; }
+    const double *init() const { return Hinit_; }
     void append(const WorldPose &p) {
         double H[12]; p.matrix(H);
         if (init_flag_) { for (int i = 0; i < 12; ++i) Hinit_[i] = H[i]; init_flag_ = false; }
@@ -568,6 +611,26 @@ public:
         if ((int)which.size() != S) throw Error(LL_ERR_ARG, "one selection per lane");
         const int rc = LaserMappingSequences::export_from(cubemaps(), S, which.data(), out, offset);
         if (rc != LL_OK) throw Error(rc, ll_cubemaps_last_error(cubemaps()));
+    }
+    /* the checkpoint of the lanes with lanes[q] != 0 (ll_drives_save: one pack launch, one copy, one synchronisation; read-only).
+     * A lane can be saved when it ran on the previous step, or was restored and has not stepped since */
+    std::vector<unsigned char> save(const std::vector<int> &lanes) {
+        if ((int)lanes.size() != S) throw Error(LL_ERR_ARG, "one selection per lane");
+        const long long n = ll_drives_save_size(d_, lanes.data());
+        if (n < 0) check((int)n);
+        std::vector<unsigned char> blob((size_t)n);
+        long long got = 0;
+        check(ll_drives_save(d_, lanes.data(), blob.data(), n, &got));
+        blob.resize((size_t)got);
+        return blob;
+    }
+    /* record r of the checkpoint into lane into[r] (-1: skipped): the lane may then RUN on, bit for bit as if it had never stopped */
+    void restore(const std::vector<unsigned char> &blob, const std::vector<int> &into) {
+        ll_checkpoint_info info;
+        std::memset(&info, 0, sizeof(info));
+        if (ll_checkpoint_describe(blob.data(), (long long)blob.size(), &info) == LL_OK && (int)into.size() != info.n_records)
+            throw Error(LL_ERR_ARG, "one destination per record");
+        check(ll_drives_restore(d_, into.data(), blob.data(), (long long)blob.size()));
     }
     void stats(long long &syncs, long long &frames) const { check(ll_drives_stats(d_, &syncs, &frames)); }
     ll_cubemaps *cubemaps() const { return ll_drives_cubemaps(d_); }

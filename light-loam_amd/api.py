@@ -38,9 +38,12 @@ EXPORTS = [
     "ll_cubemaps_reset", "ll_drives_create", "ll_drives_destroy", "ll_drives_last_error", "ll_drives_slots", "ll_drives_step",
     "ll_drives_registered", "ll_drives_stats", "ll_drives_cubemaps",
     "ll_cubemaps_export_sizes", "ll_cubemaps_export", "ll_cubemaps_export_timing", "ll_cubemap_export",
+    "ll_cubemaps_layout", "ll_cubemaps_import", "ll_cubemap_layout", "ll_cubemap_import",
+    "ll_drives_save_size", "ll_drives_save", "ll_drives_restore", "ll_checkpoint_describe",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
+N_CUBES = 4851                  # laserCloudNum: 21 x 21 x 11
 
 
 class Params(C.Structure):
@@ -108,6 +111,15 @@ def load_library():
         _lib.ll_cubemaps_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
         _lib.ll_cubemaps_export_timing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ll_cubemap_export.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
+        _lib.ll_cubemaps_layout.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ll_cubemaps_import.argtypes = [C.c_void_p] * 8
+        _lib.ll_cubemap_layout.argtypes = [C.c_void_p] * 5
+        _lib.ll_cubemap_import.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        _lib.ll_drives_save_size.restype = C.c_longlong
+        _lib.ll_drives_save_size.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.ll_drives_save.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+        _lib.ll_drives_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+        _lib.ll_checkpoint_describe.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
     return _lib
 
 
@@ -727,6 +739,23 @@ class CubeMap:
         return out[:n.value]
 
 
+    def layout(self):
+        """(cen (3,), counts [2, 4851] int32, valid [n_valid] int32): with export(MAP_ALL) the complete state of the map"""
+        cen = np.zeros(3, np.int32); counts = np.zeros((2, N_CUBES), np.int32); valid = np.zeros(125, np.int32); n = C.c_int(0)
+        self._ck(self.lib.ll_cubemap_layout(self.h, cen.ctypes.data, counts.ctypes.data, valid.ctypes.data, C.addressof(n)))
+        return cen, counts, valid[:n.value].copy()
+
+    def import_map(self, points, layout):
+        """replace the map by an export(MAP_ALL) cloud and its layout (cen, counts, valid): one upload, one scatter, one synchronisation"""
+        cen, counts, valid = layout
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        cen = np.ascontiguousarray(cen, np.int32); counts = np.ascontiguousarray(counts, np.int32); valid = np.ascontiguousarray(valid, np.int32)
+        if cen.shape != (3,) or counts.shape != (2, N_CUBES) or len(valid) > 125:
+            raise ValueError("layout must be (cen [3], counts [2, 4851], valid [<= 125])")
+        v = np.zeros(125, np.int32); v[:len(valid)] = valid
+        self._ck(self.lib.ll_cubemap_import(self.h, pts.ctypes.data, len(pts), cen.ctypes.data, counts.ctypes.data, v.ctypes.data, len(valid)))
+
+
 class CubeMaps:
     """One ll_cubemaps: n_seq cube maps side by side, frame k of every running sequence in one set of launches per stage.
     Sequence q equals a CubeMap with the same parameters driven by process_slot / process with the same frames, bit for bit."""
@@ -838,6 +867,40 @@ class CubeMaps:
         self._ck(self.lib.ll_cubemaps_export_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
         return tuple(ms), tuple(int(c) for c in cnt)
 
+    def layout(self, q):
+        """(cen (3,), counts [2, 4851] int32, valid [n_valid] int32) of map q: host bookkeeping, no launch, no synchronisation.
+        With export(MAP_ALL) the complete state of the map"""
+        cen = np.zeros(3, np.int32); counts = np.zeros((2, N_CUBES), np.int32); valid = np.zeros(125, np.int32); n = C.c_int(0)
+        self._ck(self.lib.ll_cubemaps_layout(self.h, int(q), cen.ctypes.data, counts.ctypes.data, valid.ctypes.data, C.addressof(n)))
+        return cen, counts, valid[:n.value].copy()
+
+    def import_maps(self, points, offset, layouts, device_ptr=None):
+        """put maps back: points [N, 4] float32 in the layout export(MAP_ALL) writes, offset [S + 1], layouts: per sequence
+        None (the map is left alone) or (cen, counts, valid) as layout() gives it.  One upload, one scatter kernel, one
+        synchronisation.  device_ptr: the address of the same cloud in device memory (points is then not read)"""
+        S = self.n_seq
+        if len(layouts) != S:
+            raise ValueError("layouts must have one entry per sequence")
+        off = np.ascontiguousarray(offset, np.int64)
+        if off.shape != (S + 1,):
+            raise ValueError("offset must have S + 1 entries")
+        sel = np.zeros(S, np.int32); cen = np.zeros((S, 3), np.int32); counts = np.zeros((S, 2, N_CUBES), np.int32)
+        valid = np.zeros((S, 125), np.int32); nv = np.zeros(S, np.int32)
+        for q, lay in enumerate(layouts):
+            if lay is None:
+                continue
+            c, k, v = lay
+            sel[q] = 1; cen[q] = c; counts[q] = k; nv[q] = len(v); valid[q, :len(v)] = v
+        if device_ptr is None:
+            pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+            if len(pts) < int(off[-1]):
+                raise ValueError("points is shorter than offset[S]")
+            ptr = pts.ctypes.data
+        else:
+            ptr = int(device_ptr)
+        self._ck(self.lib.ll_cubemaps_import(self.h, sel.ctypes.data, ptr, off.ctypes.data, cen.ctypes.data, counts.ctypes.data,
+                                             valid.ctypes.data, nv.ctypes.data))
+
     def stats(self):
         """(host synchronisations, frames) since create"""
         s = C.c_longlong(0); f = C.c_longlong(0)
@@ -929,6 +992,40 @@ class Drives:
         self._ck(self.lib.ll_drives_registered(self.h, int(lane), _ptr(out), len(out), C.byref(n)))
         return out[:n.value].copy()
 
+    def _lanes(self, lanes):
+        sel = np.ascontiguousarray(lanes).astype(np.int32)
+        if sel.shape != (self.n_lanes,):
+            raise ValueError("lanes must be a 0 / 1 mask with one entry per lane")
+        return sel
+
+    def save_size(self, lanes):
+        """bytes of save(lanes): host bookkeeping, no launch, no synchronisation.  lanes: a 0 / 1 mask [S]"""
+        n = self.lib.ll_drives_save_size(self.h, self._lanes(lanes).ctypes.data)
+        if n < 0:
+            self._ck(int(n))
+        return int(n)
+
+    def save(self, lanes, out=None):
+        """the checkpoint of the selected lanes: bytes, or the filled uint8 array `out`.  One pack launch, one copy, one
+        synchronisation; the run goes on as if it had not saved"""
+        sel = self._lanes(lanes)
+        n = self.save_size(sel)
+        buf = np.empty(n, np.uint8) if out is None else out
+        if buf.dtype != np.uint8 or not buf.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous uint8 array")
+        got = C.c_longlong(0)
+        self._ck(self.lib.ll_drives_save(self.h, sel.ctypes.data, buf.ctypes.data, buf.size, C.addressof(got)))
+        return buf[:got.value].tobytes() if out is None else buf[:got.value]
+
+    def restore(self, blob, into):
+        """record r of the checkpoint goes into lane into[r] (-1: skipped); the lane may then RUN on"""
+        raw = np.frombuffer(blob, np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, np.uint8)
+        dst = np.ascontiguousarray(into, np.int32)
+        n = _checkpoint_records(raw)                                 # the header's count: the library validates the blob itself, once
+        if n is not None and dst.shape != (n,):
+            raise ValueError(f"into must have one entry per record ({n})")
+        self._ck(self.lib.ll_drives_restore(self.h, dst.ctypes.data, raw.ctypes.data, raw.size))
+
     def stats(self):
         """(host synchronisations inside steps, steps that ran at least one lane) since create"""
         s = C.c_longlong(0); f = C.c_longlong(0)
@@ -945,6 +1042,43 @@ class _BorrowedCubeMaps(CubeMaps):
 
     def close(self):
         self.h = None
+
+
+class CheckpointRecord(C.Structure):
+    _fields_ = [("lane", C.c_int), ("frame_index", C.c_int), ("n_corner", C.c_longlong), ("n_surf", C.c_longlong),
+                ("n_features", C.c_int * 4), ("offset", C.c_longlong), ("bytes", C.c_longlong)]
+
+
+class CheckpointInfo(C.Structure):
+    _fields_ = [("version", C.c_int), ("n_records", C.c_int), ("total_bytes", C.c_longlong), ("n_scans", C.c_int),
+                ("distortion", C.c_int), ("voxel_sort_ranks", C.c_int), ("line_res", C.c_float), ("plane_res", C.c_float),
+                ("need_features", C.c_int * 4), ("records", C.POINTER(CheckpointRecord)), ("cap_records", C.c_int)]
+
+
+def _checkpoint_records(raw):
+    """n_records as the header states it (bytes 24..28), None for a blob too short or too large to be believed"""
+    if raw.size < 28:
+        return None
+    n = int(raw[24:28].view("<u4")[0])
+    return n if n <= 4096 else None
+
+
+def describe_checkpoint(blob, lib=None):
+    """validate a checkpoint (bytes or uint8 array) on the host -- no device, no context -- and return its header fields and
+    per-record sizes as a dict; LightLoamError(LL_ERR_ARG) for a blob this library cannot read"""
+    lib = lib or load_library()
+    raw = np.frombuffer(blob, np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, np.uint8)
+    info = CheckpointInfo()
+    recs = (CheckpointRecord * max(_checkpoint_records(raw) or 0, 1))()
+    info.records = C.cast(recs, C.POINTER(CheckpointRecord)); info.cap_records = len(recs)
+    rc = lib.ll_checkpoint_describe(raw.ctypes.data if raw.size else None, raw.size, C.addressof(info))
+    if rc != LL_OK:
+        raise LightLoamError(rc, "not a readable checkpoint")
+    out = {k: getattr(info, k) for k in ("version", "n_records", "total_bytes", "n_scans", "distortion", "voxel_sort_ranks", "line_res", "plane_res")}
+    out["need_features"] = tuple(info.need_features)
+    out["records"] = [dict(lane=r.lane, frame_index=r.frame_index, n_corner=r.n_corner, n_surf=r.n_surf, n_features=tuple(r.n_features),
+                           offset=r.offset, bytes=r.bytes) for r in recs[:info.n_records]]
+    return out
 
 
 _EMPTY = (C.c_float * 4)()      # a non-NULL address for an empty cloud of a running sequence

@@ -98,11 +98,37 @@ int cm_reserve(ll_cubemap *cm, int w, size_t need);
  * sizes only); the single map's table upload; the gather + copy + the one synchronisation; the last call's figures */
 LL_HIDDEN int llx_tile();
 LL_HIDDEN long long llx_segments(const ll_cubemap *cm, int which, long long dst0, int tile_points, unsigned long long *tile, std::vector<LLExpSeg> *segs);
+LL_HIDDEN const void *llx_stage_bytes(LLMapExport &X, const void *data, size_t bytes, hipStream_t st, std::string &err);
 LL_HIDDEN const LLExpSeg *llx_stage(LLMapExport &X, const std::vector<LLExpSeg> &segs, hipStream_t st, std::string &err);
 LL_HIDDEN int llx_gather(LLMapExport &X, ll_ctx *ctx, const LLExpSeg *d_segs, size_t nseg, unsigned long long ntiles, long long total, size_t limit,
                          int tile_points, ll_point *out, std::string &err);
 LL_HIDDEN void llx_free(LLMapExport &X);
 LL_HIDDEN void llx_timing(const LLMapExport &X, double *ms3, long long *counts3);
+
+/* map import (ll_map_export.hip), the export's inverse: one non-empty cloud of the input.  src: its first point in the input;
+ * dst: where it goes (a pool, or a feature cloud of a slot); tile0: the tiles of the segments before it */
+struct LLImpSeg { float4 *dst; long long src; int cnt; unsigned tile0; };
+/* lane checkpoints (ll_drives.hip): what the pack launch reads of one lane beyond plain segments -- the ring-strided less-flat
+ * cloud of its previous-row slot (lflat == nullptr: the cloud is contiguous and went in as a segment) and the lane's state:
+ * the slot's pose, d_odom, d_m2o [7] each and fidx, 22 doubles = LL_CK_STATE_PTS points at dst_state.  Offsets in points.
+ * bad: set to 1 when the rings' prefix table does not add up to n_lflat, the size the host planned the record with. */
+#define LL_CK_STATE_PTS 11
+struct LLCkRec { const float4 *lflat; const int *lf_pre; long long dst_lflat; int n_lflat, ring_cap; const double *pose, *odom, *m2o; const int *fidx; long long dst_state; int *bad; };
+
+/* ll_map_export.hip, import side.  llx_import_check: the host-side refusals of one map's layout (LL_ERR_ARG / LL_ERR_CAPACITY, err
+ * filled; n_points: what counts must add up to, < 0: not checked); llx_import_segments: its non-empty clouds in input order from
+ * point src0 on, each into pool 0 of its type, back to back in cube order (no table changes); llx_import_commit: the map's
+ * tables as ll_cubemaps_reset leaves them, then the imported layout; llx_reserve: the staging buffer grown to n points;
+ * llx_scatter: the upload of n_up points from host memory (up == nullptr: none) and the one scatter launch over src -- no
+ * synchronisation; llx_pack: the export gather's launch with the checkpoint records beside the tiles, into dst -- no copy, no
+ * synchronisation */
+LL_HIDDEN bool llx_is_device(const void *p);
+LL_HIDDEN int llx_import_check(const ll_cubemap *cm, const int *cen3, const int *counts, const int *valid, int n_valid, long long n_points, std::string &err);
+LL_HIDDEN void llx_import_segments(const ll_cubemap *cm, const int *counts, long long src0, int tile_points, unsigned long long *tile, std::vector<LLImpSeg> *segs);
+LL_HIDDEN void llx_import_commit(ll_cubemap *cm, const int *cen3, const int *counts, const int *valid, int n_valid);
+LL_HIDDEN float4 *llx_reserve(LLMapExport &X, size_t n, std::string &err);
+LL_HIDDEN int llx_scatter(ll_ctx *ctx, const LLImpSeg *d_segs, size_t nseg, unsigned long long ntiles, float4 *src, const void *up, size_t n_up, int tile_points, std::string &err);
+LL_HIDDEN int llx_pack(ll_ctx *ctx, const LLExpSeg *d_segs, size_t nseg, unsigned long long ntiles, const LLCkRec *d_rec, int nrec, int R, int tile_points, float4 *dst, std::string &err);
 
 /* ll_cubemaps.hip's internals that ll_drives.hip drives (not exported from the library): a frame opens with llcms_begin (the
  * staging arena of the call), may stage tables through it, and maps from the guesses the caller left in llcms_dev_pose [S][7] */
@@ -111,5 +137,10 @@ LL_HIDDEN void *llcms_stage(ll_cubemaps *cms, const void *src, size_t bytes);
 LL_HIDDEN double *llcms_dev_pose(ll_cubemaps *cms);
 LL_HIDDEN long long llcms_syncs(const ll_cubemaps *cms);
 LL_HIDDEN const std::string &llcms_err(const ll_cubemaps *cms);
+/* for the lane checkpoints: lane q's map, the export's staging state, a table staged straight to dst, one more counted sync */
+LL_HIDDEN ll_cubemap *llcms_map(ll_cubemaps *cms, int q);
+LL_HIDDEN LLMapExport &llcms_export_state(ll_cubemaps *cms);
+LL_HIDDEN void *llcms_stage_to(ll_cubemaps *cms, const void *src, size_t bytes, void *dst);
+LL_HIDDEN int llcms_sync(ll_cubemaps *cms);
 LL_HIDDEN int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran, const void *extra_dev, void *extra_host,
                                       size_t extra_bytes, ScanHdr *hdr_out);

@@ -841,12 +841,72 @@ extern "C" int ll_cubemaps_export_timing(const ll_cubemaps *cms, double *ms3, lo
     return LL_OK;
 }
 
+/* ------------------------------------------------------------------ map import: what an LL_MAP_ALL export and the layout hold, put back
+ * Host bookkeeping: with an LL_MAP_ALL export the complete state of map q */
+extern "C" int ll_cubemaps_layout(ll_cubemaps *cms, int q, int *cen3, int *counts, int *valid, int *n_valid)
+{
+    if (!cms) return LL_ERR_ARG;
+    int rc = cms_seq(cms, q); if (rc) return rc;
+    if (cms->cm[q]->broken) { cms->err = "sequence " + std::to_string(q) + ": unusable, an earlier update failed half-way"; return LL_ERR_STATE; }
+    return ll_cubemap_layout(cms->cm[q], cen3, counts, valid, n_valid);
+}
+
+extern "C" int ll_cubemaps_import(ll_cubemaps *cms, const int *sel, const ll_point *points, const long long *offset, const int *cen3,
+                                  const int *counts, const int *valid, const int *n_valid)
+{
+    if (!cms) return LL_ERR_ARG;
+    if (!sel || !offset || !cen3 || !counts || !valid || !n_valid) { cms->err = "map import: NULL argument"; return LL_ERR_ARG; }
+    const int S = cms->S;
+    /* every refusal before anything is enqueued or any table changes */
+    long long lo = -1, hi = -1;
+    for (int q = 0; q < S; ++q) {
+        if (sel[q] != 0 && sel[q] != 1) { cms->err = "sequence " + std::to_string(q) + ": sel must be 0 or 1"; return LL_ERR_ARG; }
+        if (offset[q] < 0 || offset[q + 1] < offset[q]) { cms->err = "sequence " + std::to_string(q) + ": offset is not ascending"; return LL_ERR_ARG; }
+        if (!sel[q]) continue;
+        std::string why;
+        const int rc = llx_import_check(cms->cm[q], cen3 + 3 * q, counts + (size_t)q * 2 * CM_N, valid + (size_t)q * 125, n_valid[q], offset[q + 1] - offset[q], why);
+        if (rc) { cms->err = "sequence " + std::to_string(q) + ": " + why; return rc; }
+        if (offset[q + 1] > offset[q]) { if (lo < 0) lo = offset[q]; hi = offset[q + 1]; }
+    }
+    const long long n_up = lo < 0 ? 0 : hi - lo;
+    if (n_up > 0 && !points) { cms->err = "map import: points is NULL"; return LL_ERR_ARG; }
+    const int tile_points = llx_tile();
+    std::vector<LLImpSeg> segs;
+    unsigned long long ntiles = 0;
+    for (int q = 0; q < S; ++q)
+        if (sel[q]) llx_import_segments(cms->cm[q], counts + (size_t)q * 2 * CM_N, offset[q] - (lo < 0 ? 0 : lo), tile_points, &ntiles, &segs);
+    if (ntiles > 0x7fffffffull) { cms->err = "map import: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+    CMS_HIP(hipSetDevice(cms->ctx->device));
+    const bool direct = n_up > 0 && llx_is_device(points);
+    float4 *src = direct ? (float4 *)points + lo : nullptr;
+    if (n_up > 0 && !direct) {
+        std::string why;
+        src = llx_reserve(cms->X, (size_t)n_up, why);
+        if (!src) { cms->err = "map import: " + why; return LL_ERR_HIP; }
+    }
+    cms->par ^= 1; cms->ar[cms->par].used = 0;
+    const LLImpSeg *d_segs = nullptr;
+    if (!segs.empty()) { d_segs = (const LLImpSeg *)cms_stage(cms, segs.data(), segs.size() * sizeof(LLImpSeg)); if (!d_segs) return LL_ERR_HIP; }
+    /* ---- from here on a failure leaves the selected maps' pools half-written ---- */
+    for (int q = 0; q < S; ++q) if (sel[q]) cms->cm[q]->broken = true;
+    int rc = llx_scatter(cms->ctx, d_segs, segs.size(), ntiles, src, direct ? nullptr : (const void *)(points + lo), (size_t)n_up, tile_points, cms->err);
+    if (rc) return rc;
+    rc = cms_sync(cms); if (rc) return rc;                                         /* the ONE synchronisation: the caller's points may go away */
+    for (int q = 0; q < S; ++q)
+        if (sel[q]) llx_import_commit(cms->cm[q], cen3 + 3 * q, counts + (size_t)q * 2 * CM_N, valid + (size_t)q * 125, n_valid[q]);
+    return LL_OK;
+}
+
 /* ------------------------------------------------------------------ for ll_drives (ll_drives.hip), not exported */
 void llcms_begin(ll_cubemaps *cms) { cms->par ^= 1; cms->ar[cms->par].used = 0; }
 void *llcms_stage(ll_cubemaps *cms, const void *src, size_t bytes) { return cms_stage(cms, src, bytes); }
 double *llcms_dev_pose(ll_cubemaps *cms) { return cms->d_pose; }
 long long llcms_syncs(const ll_cubemaps *cms) { return cms->syncs; }
 const std::string &llcms_err(const ll_cubemaps *cms) { return cms->err; }
+ll_cubemap *llcms_map(ll_cubemaps *cms, int q) { return cms->cm[q]; }
+LLMapExport &llcms_export_state(ll_cubemaps *cms) { return cms->X; }
+void *llcms_stage_to(ll_cubemaps *cms, const void *src, size_t bytes, void *dst) { return cms_stage(cms, src, bytes, dst); }
+int llcms_sync(ll_cubemaps *cms) { return cms_sync(cms); }
 
 /* ll_cubemaps_process_slots with the guesses already in d_pose (rows of the running sequences; llcms_begin called): they come to
  * the host with the slot headers, in the same synchronisation, together with extra_bytes from extra_dev into extra_host.  A slot

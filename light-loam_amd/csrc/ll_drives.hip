@@ -105,15 +105,30 @@ __global__ __launch_bounds__(256) void k_drives_register(LLView V, const DrvReg 
     out[(size_t)L.lane * V.CS + off + i] = make_float4(sx, sy, sz, p.w);
 }
 
+/* ll_drives_restore: the state of one record out of the uploaded blob -- the slot's pose and header (as ll_upload_features
+ * leaves one), the lane's two poses and frame counter */
+struct DrvRestore { long long src_state; int slot, lane; ScanHdr hdr; };
+__global__ __launch_bounds__(64) void k_drives_restore(const DrvRestore *tab, const float4 *src, double *vpose, double *odom, double *m2o, int *fidx, ScanHdr *hdr)
+{
+    const DrvRestore R = tab[blockIdx.x];
+    const double *in = (const double *)(src + R.src_state);
+    const int t = threadIdx.x;
+    if (t < 7) { vpose[(size_t)R.slot * 7 + t] = in[t]; odom[(size_t)R.lane * 7 + t] = in[7 + t]; m2o[(size_t)R.lane * 7 + t] = in[14 + t]; }
+    if (t == 0) { fidx[R.lane] = ((const int *)(in + 21))[0]; hdr[R.slot] = R.hdr; }
+}
+
 /* ------------------------------------------------------------------ host side */
+struct DrvFeat { int n[4] = {0, 0, 0, 0}; int strided = 0; };   /* sharp, less sharp, flat, less flat; the less-flat cloud's layout */
 struct ll_drives {
     ll_ctx *ctx = nullptr;
     ll_cubemaps *cms = nullptr;
     int S = 0, base = 0, n_outer = 3, keep_registered = 0;
     int row = 0;                                  /* the row the next step reads */
     std::vector<int> ran_prev, fidx, reg_n;       /* per lane: ran on the last step, frame index of its last frame, registered points */
+    std::vector<DrvFeat> feat;                    /* per lane: the feature counts of its previous-row slot (from the step's header read-back, or a restore) */
     double *d_odom = nullptr, *d_m2o = nullptr;   /* [S][7] each */
     int *d_fidx = nullptr;                        /* [S]: the frame counter, mirrored on the device */
+    int *d_ck_bad = nullptr;                      /* [1]: ll_drives_save's pack launch found a less-flat table that disagrees with its header */
     float4 *d_reg = nullptr;                      /* [S][CS] registered clouds (keep_registered) */
     std::vector<void *> allocs;
     long long syncs = 0, frames = 0;
@@ -164,8 +179,8 @@ extern "C" int ll_drives_create(ll_ctx *ctx, const ll_drives_params *p, ll_drive
     if (rc) return rc;
     ll_drives *d = new ll_drives();
     d->ctx = ctx; d->cms = cms; d->S = S; d->base = p->base; d->n_outer = p->n_outer; d->keep_registered = p->keep_registered;
-    d->ran_prev.assign(S, 0); d->fidx.assign(S, 0); d->reg_n.assign(S, 0);
-    bool ok = drv_alloc(d, d->d_odom, (size_t)S * 7) && drv_alloc(d, d->d_m2o, (size_t)S * 7) && drv_alloc(d, d->d_fidx, (size_t)S);
+    d->ran_prev.assign(S, 0); d->fidx.assign(S, 0); d->reg_n.assign(S, 0); d->feat.assign(S, DrvFeat());
+    bool ok = drv_alloc(d, d->d_odom, (size_t)S * 7) && drv_alloc(d, d->d_m2o, (size_t)S * 7) && drv_alloc(d, d->d_fidx, (size_t)S) && drv_alloc(d, d->d_ck_bad, 1);
     if (ok && d->keep_registered) ok = drv_alloc(d, d->d_reg, (size_t)S * (size_t)ctx->V.CS);
     if (!ok) { ctx->err = d->err; ll_drives_destroy(d); return LL_ERR_HIP; }
     *out = d;
@@ -234,6 +249,13 @@ static int drv_run(ll_drives *d, const int *cmd, const std::vector<double> &p0, 
     if (rc) { d->err = "mapping: " + drv_lane_msg(llcms_err(d->cms)); return rc; }
     hipLaunchKernelGGL(k_drives_update, dim3(nb), dim3(64), 0, st, S, d_cmd, d->d_odom, d->d_m2o, (const double *)d_map_pose);
     DRV_HIP(hipGetLastError());
+    for (int q = 0; q < S; ++q) {                                                       /* what a checkpoint of the lane will hold of this slot */
+        if (cmd[q] == LL_DRIVE_IDLE) continue;
+        const bool ok = hdr[q].status == 0;                                             /* an empty scan is a target without points (ll_targets) */
+        DrvFeat &f = d->feat[q];
+        f.n[0] = ok ? hdr[q].n_sharp : 0; f.n[1] = ok ? hdr[q].n_less_sharp : 0; f.n[2] = ok ? hdr[q].n_flat : 0; f.n[3] = ok ? hdr[q].n_less_flat : 0;
+        f.strided = ok ? hdr[q].lf_strided : 0;
+    }
     if (d->keep_registered) {
         std::vector<DrvReg> tab;
         for (int q = 0; q < S; ++q) {
@@ -316,5 +338,328 @@ extern "C" int ll_drives_registered(ll_drives *d, int lane, ll_point *out, int c
     if (!out) return LL_OK;
     if (cap < cnt) { d->err = "registered cloud capacity too small"; return LL_ERR_CAPACITY; }
     if (cnt > 0 && ll_read_back(out, d->d_reg + (size_t)lane * d->ctx->V.CS, (size_t)cnt * sizeof(float4), d->ctx->stream)) { d->err = "read-back failed"; return LL_ERR_HIP; }
+    return LL_OK;
+}
+
+/* ------------------------------------------------------------------ lane checkpoints
+ * A lane's state between two steps: its cube map (centre, per-cube counts, the two pools' live points, the valid list of its
+ * last frame), d_odom, d_m2o, fidx, and the previous row's slot -- the four feature clouds and the solved pose, the target and
+ * the warm start of its next odometry frame.  Pool offsets are not part of it: nothing reads a pool except through (off, cnt).
+ * The blob (INTEGRATION.md has the table): CkHeader, n CkRecord, per record the counts [2][4851] and the valid list [125]
+ * (host bookkeeping), then from a 256-byte boundary per record the device payload in 16-byte points: the LL_MAP_ALL cloud, sharp,
+ * less sharp, flat, less flat (contiguous), LL_CK_STATE_PTS points of state.  Little-endian, as the hosts this library runs on. */
+#define LL_CK_MAGIC 0x4B434C4Cu                  /* "LLCK" */
+#define LL_CK_VERSION 1u
+struct CkHeader {
+    uint32_t magic, version, header_bytes, record_bytes;
+    uint64_t total_bytes;
+    uint32_t n_records; int32_t n_scans, distortion, voxel_sort_ranks;
+    float line_res, plane_res;
+    int32_t need[4];                             /* the largest sharp / less sharp / flat / less flat cloud of any record */
+};
+struct CkRecord {
+    uint64_t tab_offset, offset, bytes;          /* counts + valid list; the device payload and its size */
+    int64_t n_pts[2];                            /* corner, surf points of the map */
+    int32_t lane, fidx, cen[3], n_valid, n_feat[4], rsv[4];
+};
+static_assert(sizeof(CkHeader) == 64 && sizeof(CkRecord) == 96, "the blob's fixed layout");
+#define CK_COUNTS_BYTES ((size_t)((2 * CM_N * 4 + 15) / 16 * 16))
+#define CK_TAB_BYTES (CK_COUNTS_BYTES + 512)
+#define CK_MAX_RECORDS 4096
+
+struct CkView { CkHeader h; std::vector<CkRecord> rec; };
+
+static long long ck_payload_points(const CkRecord &r)
+{
+    return r.n_pts[0] + r.n_pts[1] + (long long)r.n_feat[0] + r.n_feat[1] + r.n_feat[2] + r.n_feat[3] + LL_CK_STATE_PTS;
+}
+
+/* every refusal a blob can earn on its own (LL_ERR_ARG, err names the field) */
+static int ck_parse(const void *blob, long long bytes, CkView &v, std::string &err)
+{
+    if (!blob || bytes < 0) { err = "checkpoint: no blob"; return LL_ERR_ARG; }
+    const unsigned char *b = (const unsigned char *)blob;
+    uint32_t w = 0;
+    if (bytes < 4) { err = "checkpoint: truncated before magic"; return LL_ERR_ARG; }
+    std::memcpy(&w, b, 4);
+    if (w != LL_CK_MAGIC) { err = "checkpoint: magic is not LLCK"; return LL_ERR_ARG; }
+    if (bytes < 8) { err = "checkpoint: truncated before version"; return LL_ERR_ARG; }
+    std::memcpy(&w, b + 4, 4);
+    if (w != LL_CK_VERSION) { err = "checkpoint: version " + std::to_string(w) + ", this library reads " + std::to_string(LL_CK_VERSION); return LL_ERR_ARG; }
+    if ((size_t)bytes < sizeof(CkHeader)) { err = "checkpoint: truncated inside the header"; return LL_ERR_ARG; }
+    std::memcpy(&v.h, b, sizeof(CkHeader));
+    const CkHeader &h = v.h;
+    if (h.header_bytes != sizeof(CkHeader) || h.record_bytes != sizeof(CkRecord)) { err = "checkpoint: header_bytes / record_bytes do not match version 1"; return LL_ERR_ARG; }
+    if (h.total_bytes != (uint64_t)bytes) { err = "checkpoint: total_bytes = " + std::to_string(h.total_bytes) + ", bytes = " + std::to_string(bytes) + (h.total_bytes > (uint64_t)bytes ? " (truncated)" : ""); return LL_ERR_ARG; }
+    if (h.n_records > CK_MAX_RECORDS) { err = "checkpoint: n_records out of range"; return LL_ERR_ARG; }
+    const uint64_t tab0 = sizeof(CkHeader) + (uint64_t)h.n_records * sizeof(CkRecord);
+    if (tab0 > h.total_bytes) { err = "checkpoint: the record table runs past the end"; return LL_ERR_ARG; }
+    if (h.n_scans < 1 || h.n_scans > LL_MAX_RINGS || !(h.line_res > 0.0f) || !(h.plane_res > 0.0f)) { err = "checkpoint: n_scans / line_res / plane_res out of range"; return LL_ERR_ARG; }
+    v.rec.resize(h.n_records);
+    if (h.n_records) std::memcpy(v.rec.data(), b + sizeof(CkHeader), (size_t)h.n_records * sizeof(CkRecord));
+    std::vector<int> counts(2 * CM_N);
+    /* the regions in the order a save writes them, none overlapping another: header, records, every record's tables, every record's payload */
+    uint64_t tab_end = tab0;
+    for (uint32_t r = 0; r < h.n_records; ++r) {
+        const CkRecord &R = v.rec[r];
+        if (R.tab_offset < tab_end || R.tab_offset > h.total_bytes || h.total_bytes - R.tab_offset < CK_TAB_BYTES) { err = "checkpoint: record " + std::to_string(r) + ": tab_offset overlaps what lies before it or runs past the end"; return LL_ERR_ARG; }
+        tab_end = R.tab_offset + CK_TAB_BYTES;
+    }
+    uint64_t pay_end = tab_end;
+    for (uint32_t r = 0; r < h.n_records; ++r) {
+        const CkRecord &R = v.rec[r];
+        const std::string who = "checkpoint: record " + std::to_string(r) + ": ";
+        if (R.offset < pay_end || (R.offset & 15) || R.offset > h.total_bytes || h.total_bytes - R.offset < R.bytes) { err = who + "offset / bytes overlap what lies before them or run past the end"; return LL_ERR_ARG; }
+        pay_end = R.offset + R.bytes;
+        for (int k = 0; k < 4; ++k) if (R.n_feat[k] < 0) { err = who + "negative feature count"; return LL_ERR_ARG; }
+        if (R.n_pts[0] < 0 || R.n_pts[1] < 0 || R.n_pts[0] > (1 << 26) || R.n_pts[1] > (1 << 26)) { err = who + "n_pts out of range"; return LL_ERR_ARG; }
+        if ((uint64_t)ck_payload_points(R) * 16 != R.bytes) { err = who + "bytes does not match the counts"; return LL_ERR_ARG; }
+        if (R.fidx < 0 || R.n_valid < 0 || R.n_valid > 125) { err = who + "fidx / n_valid out of range"; return LL_ERR_ARG; }
+        std::memcpy(counts.data(), b + R.tab_offset, counts.size() * sizeof(int));
+        long long tot[2] = {0, 0};
+        for (int wv = 0; wv < 2; ++wv)
+            for (int c = 0; c < CM_N; ++c) { if (counts[(size_t)wv * CM_N + c] < 0) { err = who + "negative cube count"; return LL_ERR_ARG; } tot[wv] += counts[(size_t)wv * CM_N + c]; }
+        if (tot[0] != R.n_pts[0] || tot[1] != R.n_pts[1]) { err = who + "the cube counts do not add up to n_pts"; return LL_ERR_ARG; }
+    }
+    return LL_OK;
+}
+
+extern "C" int ll_checkpoint_describe(const void *blob, long long bytes, ll_checkpoint_info *info)
+{
+    if (!info) return LL_ERR_ARG;
+    CkView v; std::string err;
+    const int rc = ck_parse(blob, bytes, v, err);
+    if (rc) return rc;
+    info->version = (int)v.h.version; info->n_records = (int)v.h.n_records; info->total_bytes = (long long)v.h.total_bytes;
+    info->n_scans = v.h.n_scans; info->distortion = v.h.distortion; info->voxel_sort_ranks = v.h.voxel_sort_ranks;
+    info->line_res = v.h.line_res; info->plane_res = v.h.plane_res;
+    for (int k = 0; k < 4; ++k) info->need_features[k] = v.h.need[k];
+    if (info->records)
+        for (int r = 0; r < (int)v.h.n_records && r < info->cap_records; ++r) {
+            const CkRecord &R = v.rec[r];
+            ll_checkpoint_record &o = info->records[r];
+            o.lane = R.lane; o.frame_index = R.fidx; o.n_corner = R.n_pts[0]; o.n_surf = R.n_pts[1];
+            for (int k = 0; k < 4; ++k) o.n_features[k] = R.n_feat[k];
+            o.offset = (long long)R.offset; o.bytes = (long long)R.bytes;
+        }
+    return LL_OK;
+}
+
+/* the blob of the selected lanes: header, records, and where the device payload starts; host bookkeeping only */
+static int ck_plan(ll_drives *d, const int *lanes, CkHeader &h, std::vector<CkRecord> &rec, uint64_t *dev_off)
+{
+    if (!lanes) { d->err = "checkpoint: no lane selection"; return LL_ERR_ARG; }
+    rec.clear();
+    for (int q = 0; q < d->S; ++q) {
+        if (lanes[q] != 0 && lanes[q] != 1) { d->err = "lane " + std::to_string(q) + ": the selection must be 0 or 1"; return LL_ERR_ARG; }
+        if (!lanes[q]) continue;
+        if (!d->ran_prev[q]) { d->err = "lane " + std::to_string(q) + ": nothing to save (the lane neither ran on the previous step nor was restored since)"; return LL_ERR_STATE; }
+        const ll_cubemap *cm = llcms_map(d->cms, q);
+        if (cm->broken) { d->err = "lane " + std::to_string(q) + ": its map is unusable"; return LL_ERR_STATE; }
+        CkRecord R;
+        std::memset(&R, 0, sizeof(R));
+        for (int w = 0; w < 2; ++w) for (int c = 0; c < CM_N; ++c) R.n_pts[w] += cm->cnt[w][c];
+        R.lane = q; R.fidx = d->fidx[q]; R.n_valid = cm->n_valid;
+        for (int k = 0; k < 3; ++k) R.cen[k] = cm->cen[k];
+        for (int k = 0; k < 4; ++k) R.n_feat[k] = d->feat[q].n[k];
+        R.bytes = (uint64_t)ck_payload_points(R) * 16;
+        rec.push_back(R);
+    }
+    std::memset(&h, 0, sizeof(h));
+    h.magic = LL_CK_MAGIC; h.version = LL_CK_VERSION; h.header_bytes = sizeof(CkHeader); h.record_bytes = sizeof(CkRecord);
+    h.n_records = (uint32_t)rec.size();
+    h.n_scans = d->ctx->p.n_scans; h.distortion = d->ctx->p.distortion; h.voxel_sort_ranks = d->ctx->p.voxel_sort_ranks;
+    const ll_cubemap *cm0 = llcms_map(d->cms, 0);
+    h.line_res = cm0->leaf[0]; h.plane_res = cm0->leaf[1];
+    uint64_t at = sizeof(CkHeader) + rec.size() * sizeof(CkRecord);
+    for (CkRecord &R : rec) { R.tab_offset = at; at += CK_TAB_BYTES; for (int k = 0; k < 4; ++k) h.need[k] = std::max(h.need[k], R.n_feat[k]); }
+    at = (at + 255) & ~(uint64_t)255;
+    *dev_off = at;
+    for (CkRecord &R : rec) { R.offset = at; at += R.bytes; }
+    h.total_bytes = at;
+    return LL_OK;
+}
+
+extern "C" long long ll_drives_save_size(ll_drives *d, const int *lanes)
+{
+    if (!d) return LL_ERR_ARG;
+    CkHeader h; std::vector<CkRecord> rec; uint64_t dev_off = 0;
+    const int rc = ck_plan(d, lanes, h, rec, &dev_off);
+    return rc ? (long long)rc : (long long)h.total_bytes;
+}
+
+extern "C" int ll_drives_save(ll_drives *d, const int *lanes, void *blob, long long cap, long long *bytes)
+{
+    if (!d) return LL_ERR_ARG;
+    CkHeader h; std::vector<CkRecord> rec; uint64_t dev_off = 0;
+    int rc = ck_plan(d, lanes, h, rec, &dev_off); if (rc) return rc;
+    if (bytes) *bytes = (long long)h.total_bytes;
+    if (cap < 0 || (uint64_t)cap < h.total_bytes) { d->err = "checkpoint: " + std::to_string(h.total_bytes) + " bytes, room for " + std::to_string(cap); return LL_ERR_CAPACITY; }
+    if (!blob) { d->err = "checkpoint: blob is NULL"; return LL_ERR_ARG; }
+    ll_ctx *ctx = d->ctx;
+    const LLView &V = ctx->V;
+    const int S = d->S, prev = d->base + (d->row ^ 1) * S, tile_points = llx_tile();
+    /* the host part, and the tables of the one pack launch */
+    std::vector<unsigned char> host((size_t)dev_off, 0);
+    std::memcpy(host.data(), &h, sizeof(h));
+    if (!rec.empty()) std::memcpy(host.data() + sizeof(h), rec.data(), rec.size() * sizeof(CkRecord));
+    std::vector<LLExpSeg> segs;
+    std::vector<LLCkRec> recs;
+    unsigned long long ntiles = 0;
+    auto seg = [&](const float4 *src, long long at, int cnt) {
+        if (cnt <= 0) return;
+        segs.push_back({src, at, cnt, (unsigned)ntiles});
+        ntiles += (unsigned long long)((cnt + tile_points - 1) / tile_points);
+    };
+    for (const CkRecord &R : rec) {
+        const int q = R.lane, slot = prev + q;
+        const ll_cubemap *cm = llcms_map(d->cms, q);
+        for (int w = 0; w < 2; ++w) std::memcpy(host.data() + R.tab_offset + (size_t)w * CM_N * sizeof(int), cm->cnt[w].data(), CM_N * sizeof(int));
+        std::memcpy(host.data() + R.tab_offset + CK_COUNTS_BYTES, cm->valid, (size_t)cm->n_valid * sizeof(int));
+        long long at = (long long)((R.offset - dev_off) / 16);
+        at += llx_segments(cm, LL_MAP_ALL, at, tile_points, &ntiles, &segs);
+        seg(V.sharp + (size_t)slot * V.cap_sharp, at, R.n_feat[0]); at += R.n_feat[0];
+        seg(V.lsharp + (size_t)slot * V.cap_lsharp, at, R.n_feat[1]); at += R.n_feat[1];
+        seg(V.flat + (size_t)slot * V.cap_flat, at, R.n_feat[2]); at += R.n_feat[2];
+        LLCkRec C;
+        std::memset(&C, 0, sizeof(C));
+        const float4 *lflat = V.lflat + (size_t)slot * V.LFS;
+        if (d->feat[q].strided) { C.lflat = lflat; C.lf_pre = V.lf_pre + (size_t)slot * (V.R + 1); C.dst_lflat = at; C.n_lflat = R.n_feat[3]; C.ring_cap = V.ring_cap; }
+        else seg(lflat, at, R.n_feat[3]);
+        at += R.n_feat[3];
+        C.pose = V.pose + (size_t)slot * 7; C.odom = d->d_odom + (size_t)q * 7; C.m2o = d->d_m2o + (size_t)q * 7; C.fidx = d->d_fidx + q; C.dst_state = at; C.bad = d->d_ck_bad;
+        recs.push_back(C);
+    }
+    if (ntiles > 0x7fffffffull) { d->err = "checkpoint: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+    DRV_HIP(hipSetDevice(ctx->device));
+    const size_t n_pts = (size_t)((h.total_bytes - dev_off) / 16);
+    const bool direct = llx_is_device(blob);
+    if (direct && ((uintptr_t)blob & 15)) { d->err = "checkpoint: a device blob must be 16-byte aligned"; return LL_ERR_ARG; }
+    float4 *dst = direct ? (float4 *)((unsigned char *)blob + dev_off) : nullptr;
+    if (!direct && n_pts > 0) {
+        std::string why;
+        dst = llx_reserve(llcms_export_state(d->cms), n_pts, why);
+        if (!dst) { d->err = "checkpoint: " + why; return LL_ERR_HIP; }
+    }
+    llcms_begin(d->cms);
+    const LLExpSeg *d_segs = segs.empty() ? nullptr : (const LLExpSeg *)llcms_stage(d->cms, segs.data(), segs.size() * sizeof(LLExpSeg));
+    const LLCkRec *d_recs = recs.empty() ? nullptr : (const LLCkRec *)llcms_stage(d->cms, recs.data(), recs.size() * sizeof(LLCkRec));
+    if ((!segs.empty() && !d_segs) || (!recs.empty() && !d_recs)) { d->err = llcms_err(d->cms); return LL_ERR_HIP; }
+    int *bad = (int *)ll_pinned_scratch(sizeof(int));
+    if (!bad) { d->err = "no page-locked scratch"; return LL_ERR_HIP; }
+    DRV_HIP(hipMemsetAsync(d->d_ck_bad, 0, sizeof(int), ctx->stream));
+    rc = llx_pack(ctx, d_segs, segs.size(), ntiles, d_recs, (int)recs.size(), V.R, tile_points, dst, d->err); if (rc) return rc;
+    DRV_HIP(hipMemcpyAsync(bad, d->d_ck_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (direct) { if (!llcms_stage_to(d->cms, host.data(), host.size(), blob)) { d->err = llcms_err(d->cms); return LL_ERR_HIP; } }
+    else if (n_pts > 0) DRV_HIP(hipMemcpyAsync((unsigned char *)blob + dev_off, dst, n_pts * 16, hipMemcpyDeviceToHost, ctx->stream));
+    rc = llcms_sync(d->cms);
+    if (rc) { d->err = llcms_err(d->cms); return rc; }
+    ++d->syncs;
+    if (*bad && direct) { (void)hipMemsetAsync(blob, 0, sizeof(CkHeader), ctx->stream); (void)hipStreamSynchronize(ctx->stream); }   /* no header: no checkpoint */
+    if (*bad) { d->err = "checkpoint: a lane's less-flat cloud does not add up to the size in its scan header: nothing valid was written"; return LL_ERR_STATE; }
+    if (!direct) std::memcpy(blob, host.data(), host.size());
+    return LL_OK;
+}
+
+extern "C" int ll_drives_restore(ll_drives *d, const int *into, const void *blob, long long bytes)
+{
+    if (!d) return LL_ERR_ARG;
+    if (!into) { d->err = "checkpoint: no lane mapping"; return LL_ERR_ARG; }
+    if (blob && llx_is_device(blob)) { d->err = "checkpoint: restore reads the blob from host memory"; return LL_ERR_ARG; }
+    CkView v;
+    int rc = ck_parse(blob, bytes, v, d->err); if (rc) return rc;
+    ll_ctx *ctx = d->ctx;
+    LLView &V = ctx->V;
+    const CkHeader &h = v.h;
+    const ll_cubemap *cm0 = llcms_map(d->cms, 0);
+    if (h.n_scans != ctx->p.n_scans) { d->err = "checkpoint: n_scans = " + std::to_string(h.n_scans) + ", the context has " + std::to_string(ctx->p.n_scans); return LL_ERR_ARG; }
+    if (h.distortion != ctx->p.distortion) { d->err = "checkpoint: distortion = " + std::to_string(h.distortion) + ", the context has " + std::to_string(ctx->p.distortion); return LL_ERR_ARG; }
+    if (h.line_res != cm0->leaf[0] || h.plane_res != cm0->leaf[1]) { d->err = "checkpoint: line_res / plane_res differ from the destination's"; return LL_ERR_ARG; }
+    const int S = d->S, prev = d->base + (d->row ^ 1) * S, tile_points = llx_tile();
+    const unsigned char *b = (const unsigned char *)blob;
+    std::vector<char> taken(S, 0);
+    std::vector<std::vector<int>> tabs(v.rec.size());
+    uint64_t lo = ~(uint64_t)0, hi = 0;
+    const int cap_feat[4] = {V.cap_sharp, V.cap_lsharp, V.cap_flat, V.NP};
+    const char *feat_name[4] = {"sharp", "less sharp", "flat", "less flat"};
+    for (size_t r = 0; r < v.rec.size(); ++r) {
+        const int q = into[r];
+        if (q == -1) continue;
+        const CkRecord &R = v.rec[r];
+        if (q < 0 || q >= S) { d->err = "checkpoint: into[" + std::to_string(r) + "] = " + std::to_string(q) + " is no lane"; return LL_ERR_ARG; }
+        if (taken[q]) { d->err = "checkpoint: two records go into lane " + std::to_string(q); return LL_ERR_ARG; }
+        taken[q] = 1;
+        tabs[r].assign(2 * CM_N + 125, 0);
+        std::memcpy(tabs[r].data(), b + R.tab_offset, 2 * CM_N * sizeof(int));
+        std::memcpy(tabs[r].data() + 2 * CM_N, b + R.tab_offset + CK_COUNTS_BYTES, 125 * sizeof(int));
+        std::string why;
+        rc = llx_import_check(llcms_map(d->cms, q), R.cen, tabs[r].data(), tabs[r].data() + 2 * CM_N, R.n_valid, R.n_pts[0] + R.n_pts[1], why);
+        if (rc) { d->err = "checkpoint: record " + std::to_string(r) + " into lane " + std::to_string(q) + ": " + why; return rc; }
+        for (int k = 0; k < 4; ++k)
+            if (R.n_feat[k] > cap_feat[k]) { d->err = "checkpoint: record " + std::to_string(r) + ": " + std::to_string(R.n_feat[k]) + " " + feat_name[k] + " points, the context holds " + std::to_string(cap_feat[k]) + " per scan"; return LL_ERR_CAPACITY; }
+        lo = std::min(lo, R.offset); hi = std::max(hi, R.offset + R.bytes);
+    }
+    if (hi <= lo) return LL_OK;                                                         /* every record skipped */
+    std::vector<LLImpSeg> segs;
+    std::vector<DrvRestore> tab;
+    unsigned long long ntiles = 0;
+    auto seg = [&](float4 *dst, long long at, int cnt) {
+        if (cnt <= 0) return;
+        segs.push_back({dst, at, cnt, (unsigned)ntiles});
+        ntiles += (unsigned long long)((cnt + tile_points - 1) / tile_points);
+    };
+    for (size_t r = 0; r < v.rec.size(); ++r) {
+        const int q = into[r];
+        if (q < 0) continue;
+        const CkRecord &R = v.rec[r];
+        const int slot = prev + q;
+        long long at = (long long)((R.offset - lo) / 16);
+        llx_import_segments(llcms_map(d->cms, q), tabs[r].data(), at, tile_points, &ntiles, &segs);
+        at += R.n_pts[0] + R.n_pts[1];
+        seg(V.sharp + (size_t)slot * V.cap_sharp, at, R.n_feat[0]); at += R.n_feat[0];
+        seg(V.lsharp + (size_t)slot * V.cap_lsharp, at, R.n_feat[1]); at += R.n_feat[1];
+        seg(V.flat + (size_t)slot * V.cap_flat, at, R.n_feat[2]); at += R.n_feat[2];
+        seg(V.lflat + (size_t)slot * V.LFS, at, R.n_feat[3]); at += R.n_feat[3];
+        DrvRestore T;
+        std::memset(&T, 0, sizeof(T));
+        T.src_state = at; T.slot = slot; T.lane = q;
+        T.hdr.first_kept = 0; T.hdr.last_kept = -1;                                     /* ll_upload_features' header */
+        T.hdr.n_sharp = R.n_feat[0]; T.hdr.n_less_sharp = R.n_feat[1]; T.hdr.n_flat = R.n_feat[2]; T.hdr.n_less_flat = R.n_feat[3];
+        tab.push_back(T);
+    }
+    if (ntiles > 0x7fffffffull) { d->err = "checkpoint: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+    DRV_HIP(hipSetDevice(ctx->device));
+    const size_t n_up = (size_t)((hi - lo) / 16);
+    std::string why;
+    float4 *src = llx_reserve(llcms_export_state(d->cms), n_up, why);
+    if (!src) { d->err = "checkpoint: " + why; return LL_ERR_HIP; }
+    llcms_begin(d->cms);
+    const LLImpSeg *d_segs = segs.empty() ? nullptr : (const LLImpSeg *)llcms_stage(d->cms, segs.data(), segs.size() * sizeof(LLImpSeg));
+    const DrvRestore *d_tab = (const DrvRestore *)llcms_stage(d->cms, tab.data(), tab.size() * sizeof(DrvRestore));
+    if ((!segs.empty() && !d_segs) || !d_tab) { d->err = llcms_err(d->cms); return LL_ERR_HIP; }
+    /* ---- from here on a failure loses the lanes being restored ---- */
+    for (const DrvRestore &T : tab) { llcms_map(d->cms, T.lane)->broken = true; d->ran_prev[T.lane] = 0; d->reg_n[T.lane] = 0; }
+    rc = llx_scatter(ctx, d_segs, segs.size(), ntiles, src, b + lo, n_up, tile_points, d->err); if (rc) return rc;
+    hipLaunchKernelGGL(k_drives_restore, dim3((unsigned)tab.size()), dim3(64), 0, ctx->stream, d_tab, (const float4 *)src, V.pose, d->d_odom, d->d_m2o, d->d_fidx, V.hdr);
+    for (size_t a = 0; a < tab.size();) {                                               /* the slots serve as targets: their search grids, one launch per run of neighbouring lanes */
+        size_t e = a + 1;                                                               /* (tab is in record order: a save lists the lanes ascending) */
+        while (e < tab.size() && tab[e].slot == tab[e - 1].slot + 1) ++e;
+        ll_launch_build_grid(V, tab[a].slot, (int)(e - a), 0, ctx->stream, nullptr);
+        a = e;
+    }
+    DRV_HIP(hipGetLastError());
+    rc = llcms_sync(d->cms);
+    if (rc) { d->err = llcms_err(d->cms); return rc; }
+    ++d->syncs;
+    for (size_t r = 0; r < v.rec.size(); ++r) {
+        const int q = into[r];
+        if (q < 0) continue;
+        const CkRecord &R = v.rec[r];
+        llx_import_commit(llcms_map(d->cms, q), R.cen, tabs[r].data(), tabs[r].data() + 2 * CM_N, R.n_valid);
+        d->ran_prev[q] = 1; d->fidx[q] = R.fidx;
+        for (int k = 0; k < 4; ++k) d->feat[q].n[k] = R.n_feat[k];
+        d->feat[q].strided = 0;
+        if ((size_t)(prev + q) < ctx->n_in_host.size()) ctx->n_in_host[prev + q] = 0;
+    }
     return LL_OK;
 }

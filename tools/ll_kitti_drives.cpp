@@ -4,7 +4,15 @@
 // A lane starts the next directory of the queue when its drive ends.  Directory i's mapped trajectory goes to <result_dir>/<i>.txt
 // in the reference's trajectory-file format (laserMapping.cpp:2284-2325), byte for byte what ll_odometry_kitti writes for it.
 //
-//   ll_kitti_drives [--maps] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...
+//   ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] <result_dir> <scan_line> <first-guess tx>
+//                   <max_ring_points> <lanes> <dir>...
+//
+// --checkpoint FILE --checkpoint-at N: after step N (N >= 1 steps done) the lanes that ran on it are saved (ll_drives_save) to FILE
+// together with the tool's own queue state -- per lane the drive it runs, its next frame and the first pose of its trajectory
+// file --, and the run carries on.  --resume FILE (same lanes, same directories in the same order): the lanes are restored and the
+// run continues with the frames after step N, appending to the pose files the first run began: a drive cut over several
+// commands gives, byte for byte, the files of one uninterrupted command.  Both may be given: resume, then checkpoint again at a
+// later step (N counts from the first run's start).
 //
 // --maps: when a drive ends, its final map (laserCloudMap, laserMapping.cpp:2190-2197: all cubes, corner then surf per cube) is
 // also written, as <result_dir>/<i>_map.bin in the layout of the scans (float32 x, y, z, intensity: read_lidar_data reads it back).
@@ -37,11 +45,53 @@ static std::vector<std::string> bin_files(const std::string &dir)
     return files;
 }
 
+/* the checkpoint file: the tool's queue state in front of the library's blob */
+struct LaneState { int drive, frame, started; double H_init[12]; };
+static const char CK_TAG[8] = {'L', 'L', 'K', 'D', '1', 0, 0, 0};
+
+static void write_checkpoint(const std::string &path, long long steps, int next, const std::vector<LaneState> &lanes, const std::vector<unsigned char> &blob)
+{
+    std::FILE *f = std::fopen(path.c_str(), "wb");
+    const int n = (int)lanes.size();
+    const long long bytes = (long long)blob.size();
+    const bool ok = f && std::fwrite(CK_TAG, 1, 8, f) == 8 && std::fwrite(&steps, sizeof(steps), 1, f) == 1 && std::fwrite(&next, sizeof(next), 1, f) == 1 &&
+                    std::fwrite(&n, sizeof(n), 1, f) == 1 && std::fwrite(lanes.data(), sizeof(LaneState), lanes.size(), f) == lanes.size() &&
+                    std::fwrite(&bytes, sizeof(bytes), 1, f) == 1 && std::fwrite(blob.data(), 1, blob.size(), f) == blob.size();
+    if (f) std::fclose(f);
+    if (!ok) throw lightloam::Error(LL_ERR_ARG, "cannot write " + path);
+}
+
+static void read_checkpoint(const std::string &path, long long &steps, int &next, std::vector<LaneState> &lanes, std::vector<unsigned char> &blob)
+{
+    std::FILE *f = std::fopen(path.c_str(), "rb");
+    char tag[8];
+    int n = 0;
+    long long bytes = -1;
+    bool ok = f && std::fread(tag, 1, 8, f) == 8 && std::memcmp(tag, CK_TAG, 8) == 0 && std::fread(&steps, sizeof(steps), 1, f) == 1 &&
+              std::fread(&next, sizeof(next), 1, f) == 1 && std::fread(&n, sizeof(n), 1, f) == 1 && n >= 1 && n <= 4096;
+    if (ok) { lanes.resize((size_t)n); ok = std::fread(lanes.data(), sizeof(LaneState), lanes.size(), f) == lanes.size() && std::fread(&bytes, sizeof(bytes), 1, f) == 1 && bytes >= 0 && bytes < (1LL << 40); }
+    if (ok) { blob.resize((size_t)bytes); ok = std::fread(blob.data(), 1, blob.size(), f) == blob.size(); }
+    if (f) std::fclose(f);
+    if (!ok) throw lightloam::Error(LL_ERR_ARG, path + " is no ll_kitti_drives checkpoint");
+}
+
 int main(int argc, char **argv)
 {
-    const bool maps = argc > 1 && std::strcmp(argv[1], "--maps") == 0;
-    if (maps) { --argc; ++argv; }
-    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
+    bool maps = false;
+    std::string ck_path, resume_path;
+    long long ck_at = -1;
+    while (argc > 1 && std::strncmp(argv[1], "--", 2) == 0) {
+        const std::string opt = argv[1];
+        if (opt == "--maps") { maps = true; --argc; ++argv; continue; }
+        if (argc < 3) { std::cerr << opt << " needs a value\n"; return 2; }
+        if (opt == "--checkpoint") ck_path = argv[2];
+        else if (opt == "--checkpoint-at") ck_at = std::atoll(argv[2]);
+        else if (opt == "--resume") resume_path = argv[2];
+        else { std::cerr << "unknown option " << opt << "\n"; return 2; }
+        argc -= 2; argv += 2;
+    }
+    if (ck_path.empty() != (ck_at < 1)) { std::cerr << "--checkpoint FILE and --checkpoint-at N (>= 1) go together\n"; return 2; }
+    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
     const std::string result_dir = argv[1];
     const int scan_line = std::atoi(argv[2]);
     const double tx0 = std::atof(argv[3]);
@@ -63,6 +113,23 @@ int main(int argc, char **argv)
         std::vector<std::unique_ptr<TrajectoryWriter>> out(drives.size());
         size_t next = 0;
         long long steps = 0;
+        if (!resume_path.empty()) {                                                        /* the lanes as the saving run left them */
+            std::vector<LaneState> st;
+            std::vector<unsigned char> blob;
+            int nxt = 0;
+            read_checkpoint(resume_path, steps, nxt, st, blob);
+            if ((int)st.size() != lanes || nxt < 0 || nxt > (int)drives.size()) throw Error(LL_ERR_ARG, resume_path + " was written for other lanes or directories");
+            next = (size_t)nxt;
+            std::vector<int> into;
+            for (int q = 0; q < lanes; ++q) {
+                if (st[q].drive < 0) continue;
+                if (st[q].drive >= (int)drives.size() || st[q].frame < 1 || st[q].frame > (int)drives[st[q].drive].size() || !st[q].started)
+                    throw Error(LL_ERR_ARG, resume_path + " was written for other lanes or directories");
+                drive_of[q] = st[q].drive; frame[q] = st[q].frame; into.push_back(q);
+                out[drive_of[q]].reset(new TrajectoryWriter(result_dir + "/" + std::to_string(drive_of[q]) + ".txt", st[q].H_init));
+            }
+            d.restore(blob, into);
+        }
         for (;;) {
             std::vector<int> cmd(lanes, LL_DRIVE_IDLE);
             for (int q = 0; q < lanes; ++q) {
@@ -88,6 +155,18 @@ int main(int argc, char **argv)
                 if (cmd[q] == LL_DRIVE_IDLE) continue;
                 out[drive_of[q]]->append(d.mapped_pose(q));
                 ++frame[q];
+            }
+            if (steps == ck_at) {                                                           /* the lanes that ran on this step, and the queue */
+                std::vector<LaneState> st((size_t)lanes);
+                std::vector<int> sel(lanes, 0);
+                for (int q = 0; q < lanes; ++q) {
+                    std::memset(&st[q], 0, sizeof(LaneState));
+                    st[q].drive = -1;
+                    if (cmd[q] == LL_DRIVE_IDLE) continue;
+                    sel[q] = 1; st[q].drive = drive_of[q]; st[q].frame = frame[q]; st[q].started = out[drive_of[q]]->started() ? 1 : 0;
+                    std::copy(out[drive_of[q]]->init(), out[drive_of[q]]->init() + 12, st[q].H_init);
+                }
+                write_checkpoint(ck_path, steps, (int)next, st, d.save(sel));
             }
             if (maps) {                                                                     /* the drives that just ended: their maps, before a START clears them */
                 std::vector<int> which(lanes, LL_MAP_NONE);
