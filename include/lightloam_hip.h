@@ -568,6 +568,55 @@ int  ll_drives_save(ll_drives *d, const int *lanes /* [S] */, void *blob, long l
 int  ll_drives_restore(ll_drives *d, const int *into /* [records] */, const void *blob, long long bytes);
 int  ll_checkpoint_describe(const void *blob, long long bytes, ll_checkpoint_info *info);
 
+/* ---------------------------------------------------------------- localisation against frozen cube maps
+ * ll_cubemaps_localize_slots: one READ-ONLY frame for every running sequence, :1584-1593, :1783-1821 and :1822-2100 without
+ * the update (:2103-2165): poses in a map's frame while no pool, pair table, cen, valid list, broken flag or frame counter of
+ * any map changes (map m's LL_MAP_SURROUND set stays that of the last frame that mapped into it).  Conventions are those of
+ * ll_cubemaps_process_slots: slots[q] = -1: sequence q sits out, its pose_w7, ran and fit rows are not touched; otherwise it
+ * reads the extracted slot slots[q] and localises against map map_of[q] (NULL: its own map q), any of the S maps, which several
+ * sequences may share; its workspace (search clouds, stacks, grids: what ll_cubemaps_download_cloud(q, ..) shows) is its own.
+ * map_of entries of sequences that sit out are not read.
+ * No shift loops (:1595-1781): a shared map cannot be re-indexed for one reader.  The centre cube comes from the guess's
+ * translation and the map's cen as in a mapping frame; the cubes i +-2, j +-2, k +-1 around it that lie inside the 21 x 21 x 11
+ * array are gathered in that loop order, a cube outside the array holds nothing.  CONDITION: this equals, cloud for cloud and
+ * bit for bit, a private copy of the map that runs the shift loops as long as that copy's shifts push no non-empty cube off
+ * the array (a shift only translates indices and brings in empty cubes).  Where a private copy would have shifted occupied
+ * cubes away, laserMapping forgets them and this call still reads those of them that lie inside the array.
+ * Then per sequence the :1813-1821 filters, the search grids and 2 x {knn, compact, LM} under the :1822 gate; ran as today.
+ * fit (may be NULL: then neither of the following is launched): for every sequence that optimised, one more association pass
+ * at the final pose and one reduction kernel fill
+ *   n_edge, n_plane     the residual blocks there, as ll_map_get_counts after ll_map_associate(final pose)
+ *   cost                ll_map_normal_equations' cost there (HuberLoss(0.1))
+ *   sq_edge, sq_plane   the sums of squares of ll_map_residual_jacobian's residuals there, loss not applied: the 3 n_edge edge
+ *                       rows, the n_plane plane rows
+ * and zeros for a running sequence that did not optimise.  sqrt(sq_plane / n_plane) is the RMS point-to-plane distance in
+ * metres; a vehicle that leaves the map shows falling counts and, at the edge of the array, ran = 0.
+ * Host synchronisations: three per call whatever S is (the slots' headers, prepare, poses + fit in one copy), plus the voxel
+ * filter's read-back for clouds above 65 536 points; added to ll_cubemaps_stats' syncs.  frames does not rise.
+ * Errors, all decided before any kernel is enqueued: LL_ERR_ARG (NULL handle, slots or pose; a slot out of range or used twice; a
+ * map_of entry outside 0..S-1); LL_ERR_STATE (a selected slot without an extracted scan; a read map that is broken);
+ * LL_ERR_CAPACITY (a scan larger than the create-time capacity; gathered cubes larger than the reader's search-cloud capacity).
+ * LL_ERR_STATE also for a NaN pose out of a solve (last_error names the sequence).  A failed call changes no map.
+ *
+ * ll_drives_set_localize: map_of[q] = -1: lane q maps into its own map (the state after create); m >= 0: lane q localises
+ * against lane m's map.  The mode holds until the next call and may change between any two steps, also for a running lane.  For
+ * a localising lane LL_DRIVE_START resets no map: world-odometry = identity, map-to-odom (q_wmap_wodom, t_wmap_wodom) =
+ * start_w7[q] (NULL: identity), where the drive begins in the map; LL_DRIVE_RUN is odometry, the world pose and
+ * transformAssociateToMap as ever, then the read-only frame above instead of the mapping frame, then transformUpdate on the
+ * localised pose.  mapped_w7 is the localised pose; odom_w7, ran and keep_registered (the cloud lands in the map's frame) as
+ * for mapping lanes.  One step may hold both kinds: at most 5 (mapping lanes) + 3 (localising lanes) synchronisations, plus
+ * filter read-backs, whatever S is.  The call itself uploads start_w7 and synchronises once (not counted: it is outside a step).
+ * A step that would write a map another running lane reads -- cmd[m] != IDLE with map_of[m] = -1 while a running lane q != m
+ * has map_of[q] = m -- is LL_ERR_ARG before anything is enqueued; last_error names both lanes.  LL_ERR_ARG also for a map_of
+ * entry outside -1..S-1 or a non-finite start row of a localising lane.
+ * A lane's mode is not part of a checkpoint: a restored lane continues in the mode ll_drives_set_localize gives it.
+ * ll_drives_fit: the last step's records [S]; zeros for lanes that mapped, sat out or did not optimise.                    */
+typedef struct { int n_edge, n_plane; double cost, sq_edge, sq_plane; } ll_localize_fit;
+int  ll_cubemaps_localize_slots(ll_cubemaps *cms, const int *slots /* [S] */, const int *map_of /* [S], NULL: own map */,
+                                double *pose_w7 /* [S][7] */, int *ran /* [S], may be NULL */, ll_localize_fit *fit /* [S], may be NULL */);
+int  ll_drives_set_localize(ll_drives *d, const int *map_of /* [S] */, const double *start_w7 /* [S][7], may be NULL */);
+int  ll_drives_fit(ll_drives *d, ll_localize_fit *fit /* [S] */);
+
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),
  * everything device-resident, no host synchronisation inside.  `vote_enable` as above.                   */

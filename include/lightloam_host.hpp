@@ -403,6 +403,16 @@ public:
         if ((int)slots.size() != S) throw Error(LL_ERR_ARG, "one slot per sequence");
         check(ll_cubemaps_process_slots(cms_, slots.data(), parameters.data(), ran.data()));
     }
+    /* a READ-ONLY frame (ll_cubemaps_localize_slots): sequence q with slots[q] >= 0 localises that extracted slot against map
+     * map_of[q] (an empty map_of: its own map) from the guess in its parameters row; no map changes, several sequences may read
+     * one map.  parameters / ran as process_slots leaves them; with want_fit, fit[q] says how the pose fits the map (zeros for a
+     * sequence that did not optimise; rows of sequences that sat out keep what they held) */
+    void localize_slots(const std::vector<int> &slots, const std::vector<int> &map_of = std::vector<int>(), bool want_fit = true) {
+        if ((int)slots.size() != S || (!map_of.empty() && (int)map_of.size() != S)) throw Error(LL_ERR_ARG, "one slot (and one map) per sequence");
+        if (want_fit && fit.empty()) fit.assign((size_t)S, ll_localize_fit());
+        check(ll_cubemaps_localize_slots(cms_, slots.data(), map_of.empty() ? nullptr : map_of.data(), parameters.data(), ran.data(),
+                                         want_fit ? fit.data() : nullptr));
+    }
     /* the same from host clouds; an empty pair of clouds with run[q] == 0 (or both pointers NULL) skips sequence q */
     void process(const std::vector<const std::vector<PointXYZI> *> &corner_last, const std::vector<const std::vector<PointXYZI> *> &surf_last) {
         if ((int)corner_last.size() != S || (int)surf_last.size() != S) throw Error(LL_ERR_ARG, "one cloud pair per sequence");
@@ -466,6 +476,7 @@ public:
     const int S;
     std::vector<double> parameters, q_wmap_wodom, t_wmap_wodom;   /* [S][7], [S][4], [S][3] */
     std::vector<int> ran;                                       /* [S] */
+    std::vector<ll_localize_fit> fit;                           /* [S] once localize_slots has asked for it */
     ll_cubemaps *get() const { return cms_; }
 private:
     void check(int rc) { if (rc != LL_OK) throw Error(rc, ll_cubemaps_last_error(cms_)); }
@@ -590,6 +601,19 @@ public:
     void step(const std::vector<int> &cmd, const double *pose0 = nullptr) {
         if ((int)cmd.size() != S) throw Error(LL_ERR_ARG, "one command per lane");
         check(ll_drives_step(d_, cmd.data(), pose0, odom.data(), mapped.data(), ran.data()));
+    }
+    /* map_of[q] = -1: lane q maps into its own map (the state after construction); m >= 0: it localises against lane m's map and
+     * writes none, from the next step on.  start: NULL or [S][7], the map-to-odom pose LL_DRIVE_START gives a localising lane --
+     * where its drive begins in the map.  A step that would map into a map a running lane reads is refused (LL_ERR_ARG) */
+    void set_localize(const std::vector<int> &map_of, const double *start = nullptr) {
+        if ((int)map_of.size() != S) throw Error(LL_ERR_ARG, "one map per lane");
+        check(ll_drives_set_localize(d_, map_of.data(), start));
+    }
+    /* the last step's fit records [S]: zeros for lanes that mapped, sat out or did not optimise */
+    std::vector<ll_localize_fit> fit() {
+        std::vector<ll_localize_fit> f((size_t)S);
+        check(ll_drives_fit(d_, f.data()));
+        return f;
     }
     /* lane q's mapped pose of the last step, as the trajectory file takes it */
     WorldPose mapped_pose(int q) const {

@@ -40,6 +40,7 @@ EXPORTS = [
     "ll_cubemaps_export_sizes", "ll_cubemaps_export", "ll_cubemaps_export_timing", "ll_cubemap_export",
     "ll_cubemaps_layout", "ll_cubemaps_import", "ll_cubemap_layout", "ll_cubemap_import",
     "ll_drives_save_size", "ll_drives_save", "ll_drives_restore", "ll_checkpoint_describe",
+    "ll_cubemaps_localize_slots", "ll_drives_set_localize", "ll_drives_fit",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -69,6 +70,11 @@ class LmOptions(C.Structure):
 
 class PairInfo(C.Structure):
     _fields_ = [("n_edge", C.c_int), ("n_plane", C.c_int), ("n_plane_selected", C.c_int)]
+
+
+class LocalizeFit(C.Structure):
+    """ll_localize_fit: how a localised pose fits the frozen map (residual blocks, Huber cost, sums of squared residuals)"""
+    _fields_ = [("n_edge", C.c_int), ("n_plane", C.c_int), ("cost", C.c_double), ("sq_edge", C.c_double), ("sq_plane", C.c_double)]
 
 
 class SeqLayout(C.Structure):
@@ -119,6 +125,9 @@ def load_library():
         _lib.ll_drives_save_size.argtypes = [C.c_void_p, C.c_void_p]
         _lib.ll_drives_save.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
         _lib.ll_drives_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+        _lib.ll_cubemaps_localize_slots.argtypes = [C.c_void_p] * 6
+        _lib.ll_drives_set_localize.argtypes = [C.c_void_p] * 3
+        _lib.ll_drives_fit.argtypes = [C.c_void_p] * 2
         _lib.ll_checkpoint_describe.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
     return _lib
 
@@ -800,6 +809,22 @@ class CubeMaps:
         self._ck(self.lib.ll_cubemaps_process_slots(self.h, _ptr(s), _ptr(p), _ptr(ran)))
         return p, ran.astype(bool)
 
+    def localize_slots(self, pose_w, slots, map_of=None, fit=True):
+        """A read-only frame: sequence q localises the extracted slot slots[q] (-1: it sits out) against map map_of[q] (None: its
+        own) from the guess pose_w[q]; no map changes -> (poses [S, 7], ran [S] bool, fit: a LocalizeFit array [S], or None with
+        fit=False -- then the extra association pass and the reduction are not launched)"""
+        p, ran = self._poses(pose_w)
+        s = np.ascontiguousarray(slots, np.int32)
+        if s.shape != (self.n_seq,):
+            raise ValueError("slots must have one entry per sequence")
+        m = None if map_of is None else np.ascontiguousarray(map_of, np.int32)
+        if m is not None and m.shape != (self.n_seq,):
+            raise ValueError("map_of must have one entry per sequence")
+        rec = (LocalizeFit * self.n_seq)() if fit else None
+        self._ck(self.lib.ll_cubemaps_localize_slots(self.h, s.ctypes.data, None if m is None else m.ctypes.data, p.ctypes.data,
+                                                     ran.ctypes.data, C.addressof(rec) if fit else None))
+        return p, ran.astype(bool), rec
+
     def process(self, pose_w, corners, surfs):
         """corners / surfs: one (n, 4) float32 cloud per sequence, None for a sequence that does not run"""
         p, ran = self._poses(pose_w)
@@ -983,6 +1008,21 @@ class Drives:
         odom = np.zeros((self.n_lanes, 7)); mapped = np.zeros((self.n_lanes, 7)); ran = np.zeros(self.n_lanes, np.int32)
         self._ck(self.lib.ll_drives_step(self.h, _ptr(c), _ptr(p0), _ptr(odom), _ptr(mapped), _ptr(ran)))
         return odom, mapped, ran.astype(bool)
+
+    def set_localize(self, map_of, start=None):
+        """map_of [S]: -1 = the lane maps into its own map, m >= 0 = it localises against lane m's map, from the next step on;
+        start: None or [S, 7], the map-to-odom pose START gives a localising lane (where its drive begins in the map)"""
+        m = np.ascontiguousarray(map_of, np.int32)
+        if m.shape != (self.n_lanes,):
+            raise ValueError("map_of must have one entry per lane")
+        st = None if start is None else np.ascontiguousarray(start, np.float64).reshape(self.n_lanes, 7)
+        self._ck(self.lib.ll_drives_set_localize(self.h, m.ctypes.data, None if st is None else st.ctypes.data))
+
+    def fit(self):
+        """the last step's LocalizeFit records [S]: zeros for lanes that mapped, sat out or did not optimise"""
+        rec = (LocalizeFit * self.n_lanes)()
+        self._ck(self.lib.ll_drives_fit(self.h, C.addressof(rec)))
+        return rec
 
     def registered(self, lane):
         """the last step's registered full-resolution cloud of `lane` ((n, 4) float32, laserCloud order; empty if it did not run)"""

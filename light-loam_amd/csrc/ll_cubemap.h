@@ -144,3 +144,8 @@ LL_HIDDEN void *llcms_stage_to(ll_cubemaps *cms, const void *src, size_t bytes, 
 LL_HIDDEN int llcms_sync(ll_cubemaps *cms);
 LL_HIDDEN int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran, const void *extra_dev, void *extra_host,
                                       size_t extra_bytes, ScanHdr *hdr_out);
+/* the same for ll_cubemaps_localize_slots (map_of [S], read for the running sequences; fit [S], rows of the running sequences) */
+LL_HIDDEN int llcms_localize_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit,
+                                       const void *extra_dev, void *extra_host, size_t extra_bytes, ScanHdr *hdr_out);
+/* ll_localize.hip: one k_cms_fit workgroup per view; view v's record goes to d_fit[(views[v].pose - d_pose0) / 7] */
+LL_HIDDEN void ll_launch_cms_fit(const LLMapView *d_views, int n_views, const double *d_pose0, ll_localize_fit *d_fit, hipStream_t st);

@@ -17,6 +17,9 @@
  * LL_NEQ_NB passes of one 256-thread workgroup, with the same per-partial reduction tree and the same order of the partials:
  * the normal equations, and so the poses, are bit for bit those of ll_cubemap_process_slot.  The grids of the search clouds
  * are still built per sequence (ll_map_rebuild_finish: a handful of launches each, no synchronisation).
+ * ll_cubemaps_localize_slots is the same frame read-only: slots, prepare without the shift loops (the map may be another
+ * sequence's and shared: cms_localize), optimize, no update -- three synchronisations; with a fit record, one more knn + compact
+ * pass at the final poses and k_cms_fit (ll_localize.hip) before the poses' copy, which then carries the records too.
  */
 #include "ll_cubemap.h"
 #include "ll_factor_math.h"
@@ -211,6 +214,7 @@ __global__ __launch_bounds__(256) void k_cms_assign(const CmsAssign *recs, const
 /* the per-call tables go up through page-locked memory: arena `par` of a call is written only after the call before the previous
  * one has synchronised, so no copy of it can still be in flight; a table that does not fit moves to a larger arena (the old one
  * is kept until destroy: copies and kernels of this call may still read it) */
+static_assert(sizeof(ll_localize_fit) == 4 * sizeof(double), "the fit records lie behind the poses as 4 doubles each");
 struct CmsArena { unsigned char *h = nullptr, *d = nullptr; size_t cap = 0, used = 0; };
 
 struct ll_cubemaps {
@@ -226,6 +230,7 @@ struct ll_cubemaps {
     float4 *d_work[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};                                   /* [S][cap_work] */
     int *d_addcnt = nullptr, *d_nout = nullptr, *d_bbox = nullptr;
     double *d_pose = nullptr;                     /* [S][7]: the pose every stage of a frame reads */
+    ll_localize_fit *d_fit = nullptr;             /* [S], right behind d_pose: one copy brings both to the host */
     LLVoxWork W[2], WS;                           /* per cloud type: prepare's and update's filters; WS: the by-cube sort */
     CmsArena ar[2]; int par = 0;
     LLMapExport X;                                /* ll_cubemaps_export's staging buffer and events */
@@ -344,7 +349,8 @@ extern "C" int ll_cubemaps_create(ll_ctx *ctx, int n_seq, float line_res, float 
         ok = ok && cms_alloc(cms, cms->d_work[w], S * cap_from_map) && cms_alloc(cms, cms->d_out[w], S * cap_from_map);
     }
     ok = ok && cms_alloc(cms, cms->d_addcnt, S * 2 * (CM_N + 1)) && cms_alloc(cms, cms->d_nout, 4) && cms_alloc(cms, cms->d_bbox, S * 12) &&
-         cms_alloc(cms, cms->d_pose, S * 7);
+         cms_alloc(cms, cms->d_pose, S * 7 + S * (sizeof(ll_localize_fit) / sizeof(double)));
+    if (ok) cms->d_fit = (ll_localize_fit *)(cms->d_pose + S * 7);
     for (int w = 0; w < 2 && ok; ++w) {
         unsigned char *p = nullptr;
         ok = cms_alloc(cms, p, ll_vox_work_bytes((int)(S * cap_from_map), (int)(S * 125)));
@@ -373,47 +379,58 @@ extern "C" int ll_cubemaps_create(ll_ctx *ctx, int n_seq, float line_res, float 
     return LL_OK;
 }
 
-/* one frame for the running sequences run[r]: their scans are src[w][r] (device, n_in[w][r] points; nullptr with flat_slot[r] >= 0:
- * the less-flat cloud of that extracted slot is flattened into place) */
-static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::vector<const float4 *> src[2], const std::vector<int> n_in[2],
-                     const std::vector<int> &flat_slot, double *pose_w7, int *ran)
+/* the cube the guess's translation falls into, in the indices of map cm (:1584-1593) */
+static void cms_centre(const ll_cubemap *cm, const double *t_w3, int cc[3])
+{
+    for (int k = 0; k < 3; ++k) {
+        cc[k] = (int)((t_w3[k] + 25.0) / 50.0) + cm->cen[k];                       /* :1584-1586 */
+        if (t_w3[k] + 25.0 < 0) cc[k]--;                                           /* :1588-1593 */
+    }
+}
+
+/* the cubes around cc that lie inside the array, in laserMapping's loop order (:1783-1801) */
+static int cms_valid_cubes(const int cc[3], int *valid)
+{
+    int n = 0;
+    for (int i = cc[0] - 2; i <= cc[0] + 2; i++) for (int j = cc[1] - 2; j <= cc[1] + 2; j++) for (int k = cc[2] - 1; k <= cc[2] + 1; k++)
+        if (i >= 0 && i < CM_W && j >= 0 && j < CM_H && k >= 0 && k < CM_D) valid[n++] = i + CM_W * j + CM_W * CM_H * k;
+    return n;
+}
+
+/* the copies that gather those cubes of map cm into the search clouds of sequence q's own ll_map (:1803-1808); n_from[w]: their sizes */
+static int cms_gather(ll_cubemaps *cms, int q, const ll_cubemap *cm, const int *valid, int n_valid, std::vector<CmsCopy> &ops, int n_from[2])
+{
+    ll_map *m = cms->cm[q]->map;
+    for (int w = 0; w < 2; ++w) {
+        size_t tot = 0;
+        for (int v = 0; v < n_valid; ++v) {
+            const int c = valid[v];
+            if (cm->cnt[w][c] > 0) { ops.push_back({cm->pool[w][cm->cur[w]] + cm->off[w][c], nullptr, m->d_map[w] + tot, cm->cnt[w][c], 0}); tot += (size_t)cm->cnt[w][c]; }
+        }
+        if (tot > (size_t)m->cap_map[w]) { cms->err = "sequence " + std::to_string(q) + ": the valid cubes hold more points than the search cloud capacity"; return LL_ERR_CAPACITY; }
+        n_from[w] = (int)tot;
+    }
+    return LL_OK;
+}
+
+static int cms_check_scans(ll_cubemaps *cms, const std::vector<int> &run, const std::vector<int> n_in[2])
+{
+    for (int r = 0; r < (int)run.size(); ++r)
+        if (n_in[0][r] > cms->cap_last[0] || n_in[1][r] > cms->cap_last[1]) {
+            cms->err = "sequence " + std::to_string(run[r]) + ": scan cloud larger than the capacity given to ll_cubemaps_create"; return LL_ERR_CAPACITY;
+        }
+    return LL_OK;
+}
+
+/* the rest of prepare once `ops` holds every running sequence's gather (n_from[w][r] points): the scans (src[w][r], device,
+ * n_in[w][r] points; nullptr with flat_slot[r] >= 0: the less-flat cloud of that extracted slot is flattened into place) join the
+ * one copy launch, the boxes, the :1813-1821 filters, ONE synchronisation, then the grids and the stacks of every ll_map */
+static int cms_prepare_finish(ll_cubemaps *cms, const std::vector<int> &run, const std::vector<const float4 *> src[2], const std::vector<int> n_in[2],
+                              const std::vector<int> &flat_slot, std::vector<CmsCopy> &ops, const std::vector<int> n_from[2])
 {
     ll_ctx *ctx = cms->ctx;
     hipStream_t st = ctx->stream;
     const int R = (int)run.size();
-    for (int r = 0; r < R; ++r)
-        if (n_in[0][r] > cms->cap_last[0] || n_in[1][r] > cms->cap_last[1]) {
-            cms->err = "sequence " + std::to_string(run[r]) + ": scan cloud larger than the capacity given to ll_cubemaps_create"; return LL_ERR_CAPACITY;
-        }
-    /* ---------------- prepare (:1584-1821) */
-    std::vector<CmsCopy> ops;
-    std::vector<int> n_from[2] = {std::vector<int>(R), std::vector<int>(R)};
-    for (int r = 0; r < R; ++r) {
-        ll_cubemap *cm = cms->cm[run[r]];
-        const double *t_w3 = pose_w7 + 7 * run[r] + 4;
-        const int dim[3] = {CM_W, CM_H, CM_D};
-        int cc[3];
-        for (int k = 0; k < 3; ++k) {
-            cc[k] = (int)((t_w3[k] + 25.0) / 50.0) + cm->cen[k];                   /* :1584-1586 */
-            if (t_w3[k] + 25.0 < 0) cc[k]--;                                       /* :1588-1593 */
-        }
-        for (int k = 0; k < 3; ++k) {
-            while (cc[k] < 3) { cm_shift(cm, k, +1); cc[k]++; cm->cen[k]++; }      /* :1595-1625 and the J, K twins */
-            while (cc[k] >= dim[k] - 3) { cm_shift(cm, k, -1); cc[k]--; cm->cen[k]--; }
-        }
-        cm->n_valid = 0;
-        for (int i = cc[0] - 2; i <= cc[0] + 2; i++) for (int j = cc[1] - 2; j <= cc[1] + 2; j++) for (int k = cc[2] - 1; k <= cc[2] + 1; k++)   /* :1783-1801 */
-            if (i >= 0 && i < CM_W && j >= 0 && j < CM_H && k >= 0 && k < CM_D) cm->valid[cm->n_valid++] = i + CM_W * j + CM_W * CM_H * k;
-        for (int w = 0; w < 2; ++w) {                                              /* :1803-1808 */
-            size_t tot = 0;
-            for (int v = 0; v < cm->n_valid; ++v) {
-                const int c = cm->valid[v];
-                if (cm->cnt[w][c] > 0) { ops.push_back({cm->pool[w][cm->cur[w]] + cm->off[w][c], nullptr, cm->map->d_map[w] + tot, cm->cnt[w][c], 0}); tot += (size_t)cm->cnt[w][c]; }
-            }
-            if (tot > (size_t)cm->map->cap_map[w]) { cms->err = "sequence " + std::to_string(run[r]) + ": the valid cubes hold more points than the search cloud capacity"; return LL_ERR_CAPACITY; }
-            n_from[w][r] = (int)tot;
-        }
-    }
     std::vector<int> seg_off[2];
     for (int w = 0; w < 2; ++w) {                                                  /* the scans back to back, one segment each */
         seg_off[w].assign(R + 1, 0);
@@ -463,8 +480,17 @@ static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::v
     }
     rc = cms_copy(cms, ops); if (rc) return rc;
     CMS_HIP(hipGetLastError());
+    return LL_OK;
+}
 
-    /* ---------------- optimize (:1822-2100) */
+/* optimize (:1822-2100) for the prepared sequences: the :1822 gate, 2 x {knn, compact, LM}, all poses back in ONE synchronisation.
+ * fit != nullptr: the residual blocks once more at the final poses and k_cms_fit (ll_localize.hip); the records come back in the
+ * poses' copy -- rows of the running sequences, zeros where the gate was shut */
+static int cms_optimize(ll_cubemaps *cms, const std::vector<int> &run, double *pose_w7, int *ran, ll_localize_fit *fit)
+{
+    hipStream_t st = cms->ctx->stream;
+    const int R = (int)run.size();
+    int rc;
     if (!cms_stage(cms, pose_w7, (size_t)cms->S * 7 * sizeof(double), cms->d_pose)) return LL_ERR_HIP;
     std::vector<int> opt_r;
     for (int r = 0; r < R; ++r) {
@@ -472,6 +498,7 @@ static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::v
         if (M.n_map[0] > 10 && M.n_map[1] > 50) opt_r.push_back(r);               /* :1822 */
     }
     const int O = (int)opt_r.size();
+    if (fit) for (int r = 0; r < R; ++r) std::memset(fit + run[r], 0, sizeof(ll_localize_fit));
     if (O > 0) {
         std::vector<LLMapView> views;
         std::vector<int4> blk;
@@ -490,12 +517,19 @@ static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::v
             hipLaunchKernelGGL(k_cms_compact, dim3(2 * O), dim3(256), 0, st, d_views);
             hipLaunchKernelGGL(k_cms_lm, dim3(O), dim3(256), 0, st, d_views, o);
         }
+        if (fit) {                                                                 /* the blocks at the final pose, reduced */
+            if (!blk.empty()) hipLaunchKernelGGL(k_cms_knn, dim3((unsigned)blk.size()), dim3(LL_KNNB), 0, st, d_views, d_blk);
+            hipLaunchKernelGGL(k_cms_compact, dim3(2 * O), dim3(256), 0, st, d_views);
+            ll_launch_cms_fit(d_views, O, cms->d_pose, cms->d_fit, st);
+        }
         CMS_HIP(hipGetLastError());
-        double *pin = (double *)ll_pinned_scratch((size_t)cms->S * 7 * sizeof(double));
+        const size_t pose_bytes = (size_t)cms->S * 7 * sizeof(double), bytes = pose_bytes + (fit ? (size_t)cms->S * sizeof(ll_localize_fit) : 0);
+        double *pin = (double *)ll_pinned_scratch(bytes);
         if (!pin) { cms->err = "no page-locked scratch"; return LL_ERR_HIP; }
-        CMS_HIP(hipMemcpyAsync(pin, cms->d_pose, (size_t)cms->S * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+        CMS_HIP(hipMemcpyAsync(pin, cms->d_pose, bytes, hipMemcpyDeviceToHost, st));
         rc = cms_sync(cms); if (rc) return rc;
         for (int k = 0; k < O; ++k) std::memcpy(pose_w7 + 7 * run[opt_r[k]], pin + 7 * run[opt_r[k]], 7 * sizeof(double));
+        if (fit) for (int k = 0; k < O; ++k) std::memcpy(fit + run[opt_r[k]], (const unsigned char *)pin + pose_bytes + (size_t)run[opt_r[k]] * sizeof(ll_localize_fit), sizeof(ll_localize_fit));
     }
     int bad = -1;
     for (int r = 0, k = 0; r < R; ++r) {
@@ -509,6 +543,38 @@ static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::v
         cms->err = "sequence " + std::to_string(bad) + ": the mapping solve returned an undefined pose (the input pose was NaN): set a pose and solve again";
         return LL_ERR_STATE;
     }
+    return LL_OK;
+}
+
+/* one frame for the running sequences run[r]: their scans are src[w][r] (device, n_in[w][r] points; nullptr with flat_slot[r] >= 0:
+ * the less-flat cloud of that extracted slot is flattened into place) */
+static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::vector<const float4 *> src[2], const std::vector<int> n_in[2],
+                     const std::vector<int> &flat_slot, double *pose_w7, int *ran)
+{
+    ll_ctx *ctx = cms->ctx;
+    hipStream_t st = ctx->stream;
+    const int R = (int)run.size();
+    int rc = cms_check_scans(cms, run, n_in); if (rc) return rc;
+    /* ---------------- prepare (:1584-1821) */
+    std::vector<CmsCopy> ops;
+    std::vector<int> n_from[2] = {std::vector<int>(R), std::vector<int>(R)};
+    for (int r = 0; r < R; ++r) {
+        ll_cubemap *cm = cms->cm[run[r]];
+        const int dim[3] = {CM_W, CM_H, CM_D};
+        int cc[3], nf[2];
+        cms_centre(cm, pose_w7 + 7 * run[r] + 4, cc);
+        for (int k = 0; k < 3; ++k) {
+            while (cc[k] < 3) { cm_shift(cm, k, +1); cc[k]++; cm->cen[k]++; }      /* :1595-1625 and the J, K twins */
+            while (cc[k] >= dim[k] - 3) { cm_shift(cm, k, -1); cc[k]--; cm->cen[k]--; }
+        }
+        cm->n_valid = cms_valid_cubes(cc, cm->valid);
+        rc = cms_gather(cms, run[r], cm, cm->valid, cm->n_valid, ops, nf); if (rc) return rc;
+        n_from[0][r] = nf[0]; n_from[1][r] = nf[1];
+    }
+    rc = cms_prepare_finish(cms, run, src, n_in, flat_slot, ops, n_from); if (rc) return rc;
+
+    /* ---------------- optimize (:1822-2100) */
+    rc = cms_optimize(cms, run, pose_w7, ran, nullptr); if (rc) return rc;
 
     /* ---------------- update (:2103-2165) */
     CMS_HIP(hipMemsetAsync(cms->d_addcnt, 0, (size_t)R * 2 * (CM_N + 1) * sizeof(int), st));
@@ -727,6 +793,83 @@ extern "C" int ll_cubemaps_process(ll_cubemaps *cms, const ll_point *const *corn
     return cms_frame(cms, run, src, n_in, flat, pose_w7, ran);
 }
 
+/* one READ-ONLY frame: sequence run[r] localises against map map_of[run[r]].  No shift loops: the centre cube in the indices the
+ * map has, the cubes around it that lie inside the array (cms_valid_cubes skips the others: they hold nothing), the shared
+ * prepare and optimize, no update.  Nothing of any ll_cubemap is written: the valid list is a local, the workspace is the
+ * reader's ll_map.  Every refusal comes before the first launch. */
+static int cms_localize(ll_cubemaps *cms, const std::vector<int> &run, const int *map_of, const std::vector<const float4 *> src[2],
+                        const std::vector<int> n_in[2], const std::vector<int> &flat_slot, double *pose_w7, int *ran, ll_localize_fit *fit)
+{
+    const int R = (int)run.size();
+    int rc = cms_check_scans(cms, run, n_in); if (rc) return rc;
+    std::vector<CmsCopy> ops;
+    std::vector<int> n_from[2] = {std::vector<int>(R), std::vector<int>(R)};
+    for (int r = 0; r < R; ++r) {
+        const ll_cubemap *cm = cms->cm[map_of ? map_of[run[r]] : run[r]];
+        int cc[3], nf[2], valid[125];
+        cms_centre(cm, pose_w7 + 7 * run[r] + 4, cc);
+        const int n_valid = cms_valid_cubes(cc, valid);
+        rc = cms_gather(cms, run[r], cm, valid, n_valid, ops, nf); if (rc) return rc;
+        n_from[0][r] = nf[0]; n_from[1][r] = nf[1];
+    }
+    rc = cms_prepare_finish(cms, run, src, n_in, flat_slot, ops, n_from); if (rc) return rc;
+    return cms_optimize(cms, run, pose_w7, ran, fit);
+}
+
+/* the maps the running sequences read: inside 0..S-1 and usable */
+static int cms_check_read_maps(ll_cubemaps *cms, const std::vector<int> &run, const int *map_of)
+{
+    for (int q : run) {
+        const int m = map_of ? map_of[q] : q;
+        if (m < 0 || m >= cms->S) { cms->err = "sequence " + std::to_string(q) + ": map_of = " + std::to_string(m) + " is no map"; return LL_ERR_ARG; }
+    }
+    for (int q : run) {
+        const int m = map_of ? map_of[q] : q;
+        if (cms->cm[m]->broken) { cms->err = "sequence " + std::to_string(q) + ": map " + std::to_string(m) + " is unusable, an earlier update failed half-way"; return LL_ERR_STATE; }
+    }
+    return LL_OK;
+}
+
+extern "C" int ll_cubemaps_localize_slots(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit)
+{
+    if (!cms || !slots || !pose_w7) return LL_ERR_ARG;
+    ll_ctx *ctx = cms->ctx;
+    std::vector<int> run;
+    std::vector<char> used(ctx->p.batch, 0);
+    for (int q = 0; q < cms->S; ++q) {
+        const int s = slots[q];
+        if (s == -1) continue;
+        if (s < -1 || s >= ctx->p.batch) { cms->err = "sequence " + std::to_string(q) + ": slot out of range"; return LL_ERR_ARG; }
+        if (used[s]) { cms->err = "sequence " + std::to_string(q) + ": slot " + std::to_string(s) + " is used by two sequences"; return LL_ERR_ARG; }
+        used[s] = 1;
+        run.push_back(q);
+    }
+    int rc = cms_check_read_maps(cms, run, map_of); if (rc) return rc;
+    if (run.empty()) return LL_OK;
+    CMS_HIP(hipSetDevice(ctx->device));
+    cms->par ^= 1; cms->ar[cms->par].used = 0;
+    const int R = (int)run.size();
+    std::vector<ScanHdr> h(R);
+    {
+        ScanHdr *pin = (ScanHdr *)ll_pinned_scratch((size_t)R * sizeof(ScanHdr));
+        if (!pin) { cms->err = "no page-locked scratch"; return LL_ERR_HIP; }
+        for (int r = 0; r < R; ++r) CMS_HIP(hipMemcpyAsync(pin + r, ctx->V.hdr + slots[run[r]], sizeof(ScanHdr), hipMemcpyDeviceToHost, ctx->stream));
+        rc = cms_sync(cms); if (rc) return rc;
+        std::memcpy(h.data(), pin, (size_t)R * sizeof(ScanHdr));
+    }
+    std::vector<const float4 *> src[2] = {std::vector<const float4 *>(R), std::vector<const float4 *>(R)};
+    std::vector<int> n_in[2] = {std::vector<int>(R), std::vector<int>(R)}, flat(R, -1);
+    const LLView &V = ctx->V;
+    for (int r = 0; r < R; ++r) {
+        const int s = slots[run[r]];
+        if (h[r].status != 0) { cms->err = "sequence " + std::to_string(run[r]) + ": the slot holds no extracted scan"; return LL_ERR_STATE; }
+        src[0][r] = V.lsharp + (size_t)s * V.cap_lsharp; n_in[0][r] = h[r].n_less_sharp;
+        n_in[1][r] = h[r].n_less_flat;
+        if (h[r].lf_strided) { src[1][r] = nullptr; flat[r] = s; } else src[1][r] = V.lflat + (size_t)s * V.LFS;
+    }
+    return cms_localize(cms, run, map_of, src, n_in, flat, pose_w7, ran, fit);
+}
+
 static int cms_seq(ll_cubemaps *cms, int q)
 {
     if (q < 0 || q >= cms->S) { cms->err = "sequence index out of range"; return LL_ERR_ARG; }
@@ -908,17 +1051,18 @@ LLMapExport &llcms_export_state(ll_cubemaps *cms) { return cms->X; }
 void *llcms_stage_to(ll_cubemaps *cms, const void *src, size_t bytes, void *dst) { return cms_stage(cms, src, bytes, dst); }
 int llcms_sync(ll_cubemaps *cms) { return cms_sync(cms); }
 
-/* ll_cubemaps_process_slots with the guesses already in d_pose (rows of the running sequences; llcms_begin called): they come to
- * the host with the slot headers, in the same synchronisation, together with extra_bytes from extra_dev into extra_host.  A slot
- * whose extract status is LL_ERR_EMPTY maps with empty clouds.  hdr_out[q]: the header of slots[q] (running sequences). */
-int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran, const void *extra_dev, void *extra_host,
-                            size_t extra_bytes, ScanHdr *hdr_out)
+/* ll_cubemaps_process_slots (map_of == nullptr) or ll_cubemaps_localize_slots with the guesses already in d_pose (rows of the
+ * running sequences; llcms_begin called): they come to the host with the slot headers, in the same synchronisation, together
+ * with extra_bytes from extra_dev into extra_host.  A slot whose extract status is LL_ERR_EMPTY runs with empty clouds.
+ * hdr_out[q]: the header of slots[q] (running sequences). */
+static int cms_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit,
+                         const void *extra_dev, void *extra_host, size_t extra_bytes, ScanHdr *hdr_out)
 {
     ll_ctx *ctx = cms->ctx;
     std::vector<int> run;
     for (int q = 0; q < cms->S; ++q)
         if (slots[q] >= 0) run.push_back(q);
-    int rc = cms_check_common(cms, run); if (rc) return rc;
+    int rc = map_of ? cms_check_read_maps(cms, run, map_of) : cms_check_common(cms, run); if (rc) return rc;
     const int R = (int)run.size();
     const size_t pose_bytes = (size_t)cms->S * 7 * sizeof(double), hdr_at = (pose_bytes + extra_bytes + 15) & ~(size_t)15;
     std::vector<ScanHdr> h(R);
@@ -950,5 +1094,17 @@ int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double *pose_w7,
         n_in[1][r] = empty ? 0 : h[r].n_less_flat;
         if (h[r].lf_strided) { src[1][r] = nullptr; flat[r] = s; } else src[1][r] = V.lflat + (size_t)s * V.LFS;
     }
-    return cms_frame(cms, run, src, n_in, flat, pose_w7, ran);
+    return map_of ? cms_localize(cms, run, map_of, src, n_in, flat, pose_w7, ran, fit) : cms_frame(cms, run, src, n_in, flat, pose_w7, ran);
+}
+
+int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran, const void *extra_dev, void *extra_host,
+                            size_t extra_bytes, ScanHdr *hdr_out)
+{
+    return cms_slots_dev(cms, slots, nullptr, pose_w7, ran, nullptr, extra_dev, extra_host, extra_bytes, hdr_out);
+}
+
+int llcms_localize_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit,
+                             const void *extra_dev, void *extra_host, size_t extra_bytes, ScanHdr *hdr_out)
+{
+    return cms_slots_dev(cms, slots, map_of, pose_w7, ran, fit, extra_dev, extra_host, extra_bytes, hdr_out);
 }

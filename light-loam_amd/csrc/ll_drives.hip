@@ -10,6 +10,9 @@
  * The pose arithmetic restates lightloam::WorldPose::compose and LaserMapping::qmul / qrot (lightloam_host.hpp) in their
  * operation order, in double; the library is built with -ffp-contract=off, so it is bit for bit the host's.  No fma(), no
  * reassociation here.
+ * A lane may instead localise against another lane's frozen map (ll_drives_set_localize): the same chain with the read-only frame
+ * of ll_cubemaps_localize_slots in place of the mapping frame; a step runs the mapping lanes' frame, then the localising lanes',
+ * and refuses beforehand any command set in which one would write what the other reads.
  */
 #include "ll_cubemap.h"
 #include <cmath>
@@ -31,9 +34,10 @@ __device__ __forceinline__ void drv_qmul(const double *a, const double *b, doubl
     o[2] = aw * bz + ax * by - ay * bx + az * bw; o[3] = aw * bw - ax * bx - ay * by - az * bz;
 }
 
-/* per lane: odom [S][7] = q_w_curr, t_w_curr (laserOdometry); m2o [S][7] = q_wmap_wodom, t_wmap_wodom (laserMapping) */
-__global__ __launch_bounds__(64) void k_drives_associate(double *vpose, int first, int S, const int *cmd, const double *pose0, double *odom,
-                                                          double *m2o, int *fidx, double *map_pose)
+/* per lane: odom [S][7] = q_w_curr, t_w_curr (laserOdometry); m2o [S][7] = q_wmap_wodom, t_wmap_wodom (laserMapping);
+ * start [S][7] = what START sets m2o to (ll_drives_set_localize; identity rows for mapping lanes) */
+__global__ __launch_bounds__(64) void k_drives_associate(double *vpose, int first, int S, const int *cmd, const double *pose0, const double *start,
+                                                          double *odom, double *m2o, int *fidx, double *map_pose)
 {
     const int q = blockIdx.x * 64 + threadIdx.x;
     if (q >= S) return;
@@ -41,7 +45,7 @@ __global__ __launch_bounds__(64) void k_drives_associate(double *vpose, int firs
     if (c == LL_DRIVE_IDLE) return;
     double *W = odom + (size_t)q * 7, *M = m2o + (size_t)q * 7, *slot_pose = vpose + (size_t)(first + q) * 7;
     if (c == LL_DRIVE_START) {
-        for (int k = 0; k < 7; ++k) { W[k] = k == 3 ? 1.0 : 0.0; M[k] = k == 3 ? 1.0 : 0.0; }
+        for (int k = 0; k < 7; ++k) { W[k] = k == 3 ? 1.0 : 0.0; M[k] = start[(size_t)q * 7 + k]; }   /* identity for a mapping lane; where a localising lane's drive begins in the map */
         for (int k = 0; k < 7; ++k) slot_pose[k] = pose0[(size_t)q * 7 + k];     /* the warm start of frame 1 (:61-65) */
         fidx[q] = 0;
     } else {                                                                      /* WorldPose::compose (:830-831) */
@@ -127,6 +131,9 @@ struct ll_drives {
     std::vector<int> ran_prev, fidx, reg_n;       /* per lane: ran on the last step, frame index of its last frame, registered points */
     std::vector<DrvFeat> feat;                    /* per lane: the feature counts of its previous-row slot (from the step's header read-back, or a restore) */
     double *d_odom = nullptr, *d_m2o = nullptr;   /* [S][7] each */
+    double *d_start = nullptr;                    /* [S][7]: the map-to-odom pose START gives a lane (identity unless ll_drives_set_localize said otherwise) */
+    std::vector<int> map_of;                      /* per lane: -1 maps into its own map; m >= 0 localises against lane m's map */
+    std::vector<ll_localize_fit> fit;             /* per lane: the last step's fit record (zeros unless the lane localised and optimised) */
     int *d_fidx = nullptr;                        /* [S]: the frame counter, mirrored on the device */
     int *d_ck_bad = nullptr;                      /* [1]: ll_drives_save's pack launch found a less-flat table that disagrees with its header */
     float4 *d_reg = nullptr;                      /* [S][CS] registered clouds (keep_registered) */
@@ -180,7 +187,15 @@ extern "C" int ll_drives_create(ll_ctx *ctx, const ll_drives_params *p, ll_drive
     ll_drives *d = new ll_drives();
     d->ctx = ctx; d->cms = cms; d->S = S; d->base = p->base; d->n_outer = p->n_outer; d->keep_registered = p->keep_registered;
     d->ran_prev.assign(S, 0); d->fidx.assign(S, 0); d->reg_n.assign(S, 0); d->feat.assign(S, DrvFeat());
-    bool ok = drv_alloc(d, d->d_odom, (size_t)S * 7) && drv_alloc(d, d->d_m2o, (size_t)S * 7) && drv_alloc(d, d->d_fidx, (size_t)S) && drv_alloc(d, d->d_ck_bad, 1);
+    d->map_of.assign(S, -1); d->fit.assign(S, ll_localize_fit());
+    bool ok = drv_alloc(d, d->d_odom, (size_t)S * 7) && drv_alloc(d, d->d_m2o, (size_t)S * 7) && drv_alloc(d, d->d_fidx, (size_t)S) && drv_alloc(d, d->d_ck_bad, 1) &&
+              drv_alloc(d, d->d_start, (size_t)S * 7);
+    if (ok) {
+        std::vector<double> ident((size_t)S * 7, 0.0);
+        for (int q = 0; q < S; ++q) ident[(size_t)q * 7 + 3] = 1.0;
+        ok = hipMemcpy(d->d_start, ident.data(), ident.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+        if (!ok) d->err = "upload of the start poses failed";
+    }
     if (ok && d->keep_registered) ok = drv_alloc(d, d->d_reg, (size_t)S * (size_t)ctx->V.CS);
     if (!ok) { ctx->err = d->err; ll_drives_destroy(d); return LL_ERR_HIP; }
     *out = d;
@@ -236,17 +251,26 @@ static int drv_run(ll_drives *d, const int *cmd, const std::vector<double> &p0, 
     }
     double *d_map_pose = llcms_dev_pose(d->cms);
     const unsigned nb = (unsigned)((S + 63) / 64);
-    hipLaunchKernelGGL(k_drives_associate, dim3(nb), dim3(64), 0, st, ctx->V.pose, first, S, d_cmd, d_p0, d->d_odom, d->d_m2o, d->d_fidx, d_map_pose);
+    hipLaunchKernelGGL(k_drives_associate, dim3(nb), dim3(64), 0, st, ctx->V.pose, first, S, d_cmd, d_p0, (const double *)d->d_start, d->d_odom, d->d_m2o, d->d_fidx, d_map_pose);
     DRV_HIP(hipGetLastError());
-    std::vector<int> slots(S, -1);
+    std::vector<int> slots(S, -1), loc_slots(S, -1);                                    /* the mapping lanes' frame, the localising lanes' */
+    int n_map = 0, n_loc = 0;
     for (int q = 0; q < S; ++q) {
         if (cmd[q] == LL_DRIVE_IDLE) continue;
-        slots[q] = first + q;
+        if (d->map_of[q] >= 0) { loc_slots[q] = first + q; ++n_loc; continue; }         /* START resets no map */
+        slots[q] = first + q; ++n_map;
         if (cmd[q] == LL_DRIVE_START) { rc = ll_cubemaps_reset(d->cms, q); if (rc) { d->err = drv_lane_msg(llcms_err(d->cms)); return rc; } }
     }
     std::vector<ScanHdr> hdr(S);
-    rc = llcms_process_slots_dev(d->cms, slots.data(), mapped.data(), ran.data(), d->d_odom, odom.data(), (size_t)S * 7 * sizeof(double), hdr.data());
-    if (rc) { d->err = "mapping: " + drv_lane_msg(llcms_err(d->cms)); return rc; }
+    if (n_map > 0) {
+        rc = llcms_process_slots_dev(d->cms, slots.data(), mapped.data(), ran.data(), d->d_odom, odom.data(), (size_t)S * 7 * sizeof(double), hdr.data());
+        if (rc) { d->err = "mapping: " + drv_lane_msg(llcms_err(d->cms)); return rc; }
+    }
+    if (n_loc > 0) {                                                                    /* the step's guard: no map read here was written above */
+        rc = llcms_localize_slots_dev(d->cms, loc_slots.data(), d->map_of.data(), mapped.data(), ran.data(), d->fit.data(), d->d_odom, odom.data(),
+                                      (size_t)S * 7 * sizeof(double), hdr.data());
+        if (rc) { d->err = "localising: " + drv_lane_msg(llcms_err(d->cms)); return rc; }
+    }
     hipLaunchKernelGGL(k_drives_update, dim3(nb), dim3(64), 0, st, S, d_cmd, d->d_odom, d->d_m2o, (const double *)d_map_pose);
     DRV_HIP(hipGetLastError());
     for (int q = 0; q < S; ++q) {                                                       /* what a checkpoint of the lane will hold of this slot */
@@ -291,6 +315,15 @@ extern "C" int ll_drives_step(ll_drives *d, const int *cmd, const double *pose0,
                 if (!std::isfinite(pose0[(size_t)q * 7 + k])) { d->err = "lane " + std::to_string(q) + ": non-finite pose0"; return LL_ERR_ARG; }
         n_run += c != LL_DRIVE_IDLE;
     }
+    for (int q = 0; q < S; ++q) {                                                       /* no step writes a map that a running lane reads */
+        const int m = d->map_of[q];
+        if (cmd[q] == LL_DRIVE_IDLE || m < 0 || m == q) continue;
+        if (d->map_of[m] < 0 && cmd[m] != LL_DRIVE_IDLE) {
+            d->err = "lane " + std::to_string(q) + " localises against the map of lane " + std::to_string(m) + ", which this step would map into: one of the two must be IDLE";
+            return LL_ERR_ARG;
+        }
+    }
+    std::fill(d->fit.begin(), d->fit.end(), ll_localize_fit());
     const double nan = std::nan("");
     std::vector<double> odom((size_t)S * 7, nan), mapped((size_t)S * 7, nan), p0((size_t)S * 7, 0.0);
     std::vector<int> r(S, 0);
@@ -308,6 +341,7 @@ extern "C" int ll_drives_step(ll_drives *d, const int *cmd, const double *pose0,
         d->row ^= 1;
         if (rc) {                                                                       /* the step is lost: its lanes are stopped */
             for (int q = 0; q < S; ++q) { d->ran_prev[q] = 0; if (cmd[q] != LL_DRIVE_IDLE) d->reg_n[q] = 0; }
+            std::fill(d->fit.begin(), d->fit.end(), ll_localize_fit());
             return rc;
         }
         ++d->frames;
@@ -325,6 +359,36 @@ extern "C" int ll_drives_step(ll_drives *d, const int *cmd, const double *pose0,
     if (odom_w7) std::memcpy(odom_w7, odom.data(), odom.size() * sizeof(double));
     if (mapped_w7) std::memcpy(mapped_w7, mapped.data(), mapped.size() * sizeof(double));
     if (ran) std::memcpy(ran, r.data(), r.size() * sizeof(int));
+    return LL_OK;
+}
+
+extern "C" int ll_drives_set_localize(ll_drives *d, const int *map_of, const double *start_w7)
+{
+    if (!d) return LL_ERR_ARG;
+    if (!map_of) { d->err = "no map_of"; return LL_ERR_ARG; }
+    const int S = d->S;
+    std::vector<double> start((size_t)S * 7, 0.0);
+    for (int q = 0; q < S; ++q) {
+        if (map_of[q] < -1 || map_of[q] >= S) { d->err = "lane " + std::to_string(q) + ": map_of = " + std::to_string(map_of[q]) + " is neither -1 nor a lane"; return LL_ERR_ARG; }
+        start[(size_t)q * 7 + 3] = 1.0;
+        if (map_of[q] < 0 || !start_w7) continue;                                       /* a mapping lane starts at the identity, as ever */
+        for (int k = 0; k < 7; ++k) {
+            if (!std::isfinite(start_w7[(size_t)q * 7 + k])) { d->err = "lane " + std::to_string(q) + ": non-finite start pose"; return LL_ERR_ARG; }
+            start[(size_t)q * 7 + k] = start_w7[(size_t)q * 7 + k];
+        }
+    }
+    DRV_HIP(hipSetDevice(d->ctx->device));
+    DRV_HIP(hipMemcpyAsync(d->d_start, start.data(), start.size() * sizeof(double), hipMemcpyHostToDevice, d->ctx->stream));
+    DRV_HIP(hipStreamSynchronize(d->ctx->stream));                                      /* `start` goes away */
+    d->map_of.assign(map_of, map_of + S);
+    return LL_OK;
+}
+
+extern "C" int ll_drives_fit(ll_drives *d, ll_localize_fit *fit)
+{
+    if (!d) return LL_ERR_ARG;
+    if (!fit) { d->err = "no fit array"; return LL_ERR_ARG; }
+    std::memcpy(fit, d->fit.data(), d->fit.size() * sizeof(ll_localize_fit));
     return LL_OK;
 }
 

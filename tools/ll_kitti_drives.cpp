@@ -4,8 +4,8 @@
 // A lane starts the next directory of the queue when its drive ends.  Directory i's mapped trajectory goes to <result_dir>/<i>.txt
 // in the reference's trajectory-file format (laserMapping.cpp:2284-2325), byte for byte what ll_odometry_kitti writes for it.
 //
-//   ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] <result_dir> <scan_line> <first-guess tx>
-//                   <max_ring_points> <lanes> <dir>...
+//   ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose "qx qy qz qw x y z"]]
+//                   <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...
 //
 // --checkpoint FILE --checkpoint-at N: after step N (N >= 1 steps done) the lanes that ran on it are saved (ll_drives_save) to FILE
 // together with the tool's own queue state -- per lane the drive it runs, its next frame and the first pose of its trajectory
@@ -18,14 +18,24 @@
 // also written, as <result_dir>/<i>_map.bin in the layout of the scans (float32 x, y, z, intensity: read_lidar_data reads it back).
 // Lanes whose drives end on the same step are read in one export.  Without --maps the output is what it was.
 //
+// --localize-in BLOB: localise the drives in a saved map instead of mapping them.  BLOB is a file --checkpoint wrote (or a bare
+// ll_drives_save blob); its R records are restored into lanes 0 .. R-1, which stay idle and keep their maps frozen; the drives run
+// on the remaining lanes (lanes > R), each localising against record 0's map (ll_drives_set_localize): no map is written, any
+// number of drives read the one map.  A drive begins at --start-pose in that map (seven numbers in one argument: quaternion x y z
+// w, then x y z; identity when absent).  The trajectories are written as ever -- poses in the map's frame -- and beside each,
+// <result_dir>/<i>_fit.txt with one line per frame: ran n_edge n_plane cost sq_edge sq_plane (ll_localize_fit), the answer to
+// "am I still on the map?".  Not together with --checkpoint, --resume or --maps.
+//
 // Build:  g++ -O2 -std=c++14 -I include tools/ll_kitti_drives.cpp -L light-loam_amd -llightloam_hip -o ll_kitti_drives
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <dirent.h>
+#include <fstream>
 #include <iostream>
 #include <memory>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -78,7 +88,7 @@ static void read_checkpoint(const std::string &path, long long &steps, int &next
 int main(int argc, char **argv)
 {
     bool maps = false;
-    std::string ck_path, resume_path;
+    std::string ck_path, resume_path, loc_path, start_text;
     long long ck_at = -1;
     while (argc > 1 && std::strncmp(argv[1], "--", 2) == 0) {
         const std::string opt = argv[1];
@@ -87,11 +97,21 @@ int main(int argc, char **argv)
         if (opt == "--checkpoint") ck_path = argv[2];
         else if (opt == "--checkpoint-at") ck_at = std::atoll(argv[2]);
         else if (opt == "--resume") resume_path = argv[2];
+        else if (opt == "--localize-in") loc_path = argv[2];
+        else if (opt == "--start-pose") start_text = argv[2];
         else { std::cerr << "unknown option " << opt << "\n"; return 2; }
         argc -= 2; argv += 2;
     }
     if (ck_path.empty() != (ck_at < 1)) { std::cerr << "--checkpoint FILE and --checkpoint-at N (>= 1) go together\n"; return 2; }
-    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
+    if (!loc_path.empty() && (maps || !ck_path.empty() || !resume_path.empty())) { std::cerr << "--localize-in does not go with --maps, --checkpoint or --resume\n"; return 2; }
+    double start7[7] = {0, 0, 0, 1, 0, 0, 0};
+    if (!start_text.empty()) {
+        std::istringstream in(start_text);
+        int got = 0;
+        while (got < 7 && (in >> start7[got])) ++got;
+        if (got != 7 || loc_path.empty()) { std::cerr << "--start-pose takes seven numbers in one argument and needs --localize-in\n"; return 2; }
+    }
+    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose \"qx qy qz qw x y z\"]] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
     const std::string result_dir = argv[1];
     const int scan_line = std::atoi(argv[2]);
     const double tx0 = std::atof(argv[3]);
@@ -130,9 +150,36 @@ int main(int argc, char **argv)
             }
             d.restore(blob, into);
         }
+        int first_lane = 0;                                                                /* --localize-in: the lanes below hold the frozen maps */
+        std::vector<std::unique_ptr<std::ofstream>> fit_out(drives.size());
+        if (!loc_path.empty()) {
+            std::vector<unsigned char> blob;
+            try {                                                                          /* a file --checkpoint wrote ... */
+                std::vector<LaneState> st; long long s0 = 0; int nxt = 0;
+                read_checkpoint(loc_path, s0, nxt, st, blob);
+            } catch (const Error &) {                                                      /* ... or a bare ll_drives_save blob */
+                const std::vector<float> raw = read_lidar_data(loc_path);
+                blob.assign((const unsigned char *)raw.data(), (const unsigned char *)raw.data() + raw.size() * sizeof(float));
+            }
+            ll_checkpoint_info info;
+            std::memset(&info, 0, sizeof(info));
+            if (ll_checkpoint_describe(blob.data(), (long long)blob.size(), &info) != LL_OK || info.n_records < 1) throw Error(LL_ERR_ARG, loc_path + " holds no checkpoint");
+            if (info.n_records >= lanes) throw Error(LL_ERR_ARG, "--localize-in: " + std::to_string(info.n_records) + " records need more than " + std::to_string(info.n_records) + " lanes");
+            first_lane = info.n_records;
+            std::vector<int> into((size_t)first_lane);
+            for (int r = 0; r < first_lane; ++r) into[(size_t)r] = r;
+            d.restore(blob, into);
+            std::vector<int> map_of(lanes, -1);
+            std::vector<double> start((size_t)7 * lanes, 0.0);
+            for (int q = 0; q < lanes; ++q) {
+                std::copy(start7, start7 + 7, &start[(size_t)7 * q]);
+                if (q >= first_lane) map_of[q] = 0;
+            }
+            d.set_localize(map_of, start.data());
+        }
         for (;;) {
             std::vector<int> cmd(lanes, LL_DRIVE_IDLE);
-            for (int q = 0; q < lanes; ++q) {
+            for (int q = first_lane; q < lanes; ++q) {
                 if (drive_of[q] >= 0 && frame[q] < (int)drives[drive_of[q]].size()) { cmd[q] = LL_DRIVE_RUN; continue; }
                 drive_of[q] = -1;
                 if (next < drives.size()) {                                                 /* the lane takes the next drive of the queue */
@@ -140,6 +187,7 @@ int main(int argc, char **argv)
                     const std::string path = result_dir + "/" + std::to_string(drive_of[q]) + ".txt";
                     std::remove(path.c_str());
                     out[drive_of[q]].reset(new TrajectoryWriter(path));
+                    if (!loc_path.empty()) fit_out[drive_of[q]].reset(new std::ofstream(result_dir + "/" + std::to_string(drive_of[q]) + "_fit.txt", std::ios::trunc));
                 }
             }
             if (std::all_of(cmd.begin(), cmd.end(), [](int c) { return c == LL_DRIVE_IDLE; })) break;
@@ -151,9 +199,16 @@ int main(int argc, char **argv)
             }
             d.step(cmd, pose0.data());
             ++steps;
+            const std::vector<ll_localize_fit> fit = loc_path.empty() ? std::vector<ll_localize_fit>() : d.fit();
             for (int q = 0; q < lanes; ++q) {
                 if (cmd[q] == LL_DRIVE_IDLE) continue;
                 out[drive_of[q]]->append(d.mapped_pose(q));
+                if (!loc_path.empty()) {
+                    char line[160];
+                    std::snprintf(line, sizeof(line), "%d %d %d %.9e %.9e %.9e\n", d.ran[(size_t)q], fit[(size_t)q].n_edge, fit[(size_t)q].n_plane, fit[(size_t)q].cost,
+                                  fit[(size_t)q].sq_edge, fit[(size_t)q].sq_plane);
+                    *fit_out[drive_of[q]] << line << std::flush;
+                }
                 ++frame[q];
             }
             if (steps == ck_at) {                                                           /* the lanes that ran on this step, and the queue */
