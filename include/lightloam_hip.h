@@ -476,6 +476,44 @@ int  ll_cubemaps_import(ll_cubemaps *cms, const int *sel /* [S] */, const ll_poi
 int  ll_cubemap_layout(ll_cubemap *cm, int *cen3, int *counts, int *valid, int *n_valid);
 int  ll_cubemap_import(ll_cubemap *cm, const ll_point *points, long long n, const int *cen3, const int *counts, const int *valid, int n_valid);
 
+/* ---------------------------------------------------------------- map merge: cube maps combined under a rigid transform
+ * One merge op (dst, src, T): dst and src are two different maps of one ll_cubemaps; T (pose_w7 layout: qx, qy, qz, qw, tx, ty,
+ * tz) takes src's world frame into dst's and is used as given -- pointAssociateToMap never normalises (laserMapping.cpp:125-134).
+ * Per cloud type (0 corner, 1 surf), independently:
+ *   order      src's points in the order ll_cubemaps_export(.., LL_MAP_ALL) lists that type: cube 0 .. 4850, inside a cube its own
+ *              point order;
+ *   transform  pointAssociateToMap (:125-134) in f64, the translation added last, rounded to float once per coordinate; the
+ *              fourth float is carried over.  With the identity T every coordinate keeps its bits;
+ *   binning    the cube arithmetic of :2108-2125 with dst's centre, the negative-side decrement included; a point whose cube lies
+ *              outside 0..20 x 0..20 x 0..10 is dropped and counted;
+ *   touched    a dst cube that receives at least one point becomes its old cloud followed by the new points in that order, passed
+ *              through the library's VoxelGrid (:2151-2165) with the type's leaf (line_res / plane_res).  EVERY touched cube is
+ *              filtered, not only those of dst's valid list: a merge has no current frame.
+ * A cube that receives nothing is unchanged byte for byte; dst's centre, valid list and four per-frame clouds
+ * (ll_cubemaps_download_cloud) are unchanged; src is unchanged whole.  added[i][w]: the points of op i, type w that entered a
+ * cube (before the filter); dropped[i][w]: those that fell outside the array.  Either may be NULL.
+ * Nothing passes through the host: the points are read where they lie in src's pool, ordered by destination cube by a counting
+ * sort that is stable and gives the same bytes on every run, gathered behind the touched cubes' old clouds, filtered in one
+ * VoxelGrid call per type over all ops, and copied into dst's pool in one launch.  The workspace grows to the need of the call
+ * and is freed with the object.  Host synchronisations per successful call, whatever n_ops is: THREE (the per-cube counts, the
+ * filtered sizes, the commit), plus one per cloud type whose filter call is above 65 536 points with a cube above 8 192 points (or
+ * one cube only) -- the voxel filter's documented read-back; all are added to ll_cubemaps_stats' syncs.  frames does not rise.
+ * The handle from ll_drives_cubemaps(d) is accepted between any two ll_drives_step calls; a lane that localises against dst
+ * (ll_drives_set_localize) sees the merged map from its next step.
+ * Errors: LL_ERR_ARG, decided before anything is enqueued: NULL handle or ops, n_ops < 1, a map index out of range, dst == src, a
+ * map that is dst of two ops, a map that is dst of one op and src of another (a map may be src of several ops), a non-finite T.
+ * LL_ERR_STATE, also before anything is enqueued: a dst or src map that is unusable (last_error names it).  LL_ERR_CAPACITY,
+ * decided for every op and both types from the per-cube counts, before any pair table changes: a dst pool cannot hold what the map
+ * holds of one type plus that type's added points (last_error names the op and the type) -- no cube of any map has changed and the
+ * call can be repeated on an object with a larger pool_points.  LL_ERR_HIP: the workspace cannot be allocated (the object
+ * stays usable) or a runtime call failed.
+ * ll_cubemaps_merge_timing: the last merge's device time per stage in ms (assign, sort + gather, filter, commit; events) and its
+ * counts (source points, touched cubes, points written to the pools); either pointer may be NULL.                            */
+typedef struct { int dst, src; double T_w7[7]; } ll_merge_op;
+int  ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops,
+                       long long *added /* [n_ops][2], may be NULL */, long long *dropped /* [n_ops][2], may be NULL */);
+int  ll_cubemaps_merge_timing(const ll_cubemaps *cms, double *ms /* assign, sort+gather, filter, commit */, long long *counts /* points in, touched cubes, points out */);
+
 /* ---------------------------------------------------------------- whole drives side by side
  * S lanes; each runs one drive at a time through registration (ll_extract_batch), odometry (ll_odometry_sequences, one
  * row) and mapping (ll_cubemaps), the single-drive chain of ll_odometry_kitti with mapping = 1 for every lane at once.

@@ -451,6 +451,18 @@ public:
         const int rc = import_into(cms_, S, points.data(), offset.data(), layouts);
         if (rc != LL_OK) check(rc);
     }
+    /* ll_cubemaps_merge: op i takes map ops[i].src through pointAssociateToMap with ops[i].T_w7 into map ops[i].dst and filters every
+     * cube that received a point.  added / dropped [n_ops][2] (corner, surf) when given.  Everything on the device */
+    void merge_maps(const std::vector<ll_merge_op> &ops, std::vector<long long> *added = nullptr, std::vector<long long> *dropped = nullptr) {
+        const int rc = merge_into(cms_, ops, added, dropped);
+        if (rc != LL_OK) check(rc);
+    }
+    /* the same on a borrowed handle (Drives::cubemaps(), between two steps); returns the status */
+    static int merge_into(ll_cubemaps *cms, const std::vector<ll_merge_op> &ops, std::vector<long long> *added = nullptr, std::vector<long long> *dropped = nullptr) {
+        if (added) added->assign(2 * ops.size(), 0);
+        if (dropped) dropped->assign(2 * ops.size(), 0);
+        return ll_cubemaps_merge(cms, ops.data(), (int)ops.size(), added ? added->data() : nullptr, dropped ? dropped->data() : nullptr);
+    }
     static int import_into(ll_cubemaps *cms, int n_seq, const PointXYZI *points, const long long *offset, const std::vector<const MapLayout *> &layouts) {
         const size_t S_ = (size_t)n_seq;
         std::vector<int> sel(S_, 0), cen(3 * S_, 0), counts(S_ * MapLayout::N_COUNTS, 0), valid(S_ * 125, 0), nv(S_, 0);

@@ -41,6 +41,7 @@ EXPORTS = [
     "ll_cubemaps_layout", "ll_cubemaps_import", "ll_cubemap_layout", "ll_cubemap_import",
     "ll_drives_save_size", "ll_drives_save", "ll_drives_restore", "ll_checkpoint_describe",
     "ll_cubemaps_localize_slots", "ll_drives_set_localize", "ll_drives_fit",
+    "ll_cubemaps_merge", "ll_cubemaps_merge_timing",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -75,6 +76,11 @@ class PairInfo(C.Structure):
 class LocalizeFit(C.Structure):
     """ll_localize_fit: how a localised pose fits the frozen map (residual blocks, Huber cost, sums of squared residuals)"""
     _fields_ = [("n_edge", C.c_int), ("n_plane", C.c_int), ("cost", C.c_double), ("sq_edge", C.c_double), ("sq_plane", C.c_double)]
+
+
+class MergeOp(C.Structure):
+    """ll_merge_op: map src goes into map dst under the pose T_w7 (qx, qy, qz, qw, tx, ty, tz)"""
+    _fields_ = [("dst", C.c_int), ("src", C.c_int), ("T_w7", C.c_double * 7)]
 
 
 class SeqLayout(C.Structure):
@@ -129,6 +135,10 @@ def load_library():
         _lib.ll_drives_set_localize.argtypes = [C.c_void_p] * 3
         _lib.ll_drives_fit.argtypes = [C.c_void_p] * 2
         _lib.ll_checkpoint_describe.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
+        _lib.ll_cubemaps_last_error.restype = C.c_char_p             # a borrowed CubeMaps (Drives.cubemaps) runs no CubeMaps.__init__
+        _lib.ll_cubemaps_last_error.argtypes = [C.c_void_p]
+        _lib.ll_cubemaps_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ll_cubemaps_merge_timing.argtypes = [C.c_void_p] * 3
     return _lib
 
 
@@ -925,6 +935,27 @@ class CubeMaps:
             ptr = int(device_ptr)
         self._ck(self.lib.ll_cubemaps_import(self.h, sel.ctypes.data, ptr, off.ctypes.data, cen.ctypes.data, counts.ctypes.data,
                                              valid.ctypes.data, nv.ctypes.data))
+
+    def merge(self, ops):
+        """ops: a list of (dst, src, pose_w7) -- map src, taken through pointAssociateToMap with the pose, is binned into map dst and
+        every cube that received a point is voxel-filtered -> (added [n_ops, 2], dropped [n_ops, 2]) int64: per op and cloud type
+        the points that entered a cube (before the filter) and those that fell outside the cube array.  Everything on the device;
+        three synchronisations whatever len(ops) is, plus the voxel filter's read-back above 65 536 points"""
+        rec = (MergeOp * max(len(ops), 1))()
+        for i, (dst, src, pose) in enumerate(ops):
+            p = np.ascontiguousarray(pose, np.float64).reshape(7)
+            rec[i].dst = int(dst); rec[i].src = int(src)
+            for k in range(7):
+                rec[i].T_w7[k] = p[k]
+        added = np.zeros((len(ops), 2), np.int64); dropped = np.zeros((len(ops), 2), np.int64)
+        self._ck(self.lib.ll_cubemaps_merge(self.h, C.addressof(rec), len(ops), added.ctypes.data, dropped.ctypes.data))
+        return added, dropped
+
+    def merge_timing(self):
+        """the last merge: ((assign ms, sort + gather ms, filter ms, commit ms), (points in, touched cubes, points out))"""
+        ms = np.zeros(4); cnt = np.zeros(3, np.int64)
+        self._ck(self.lib.ll_cubemaps_merge_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
+        return tuple(ms), tuple(int(c) for c in cnt)
 
     def stats(self):
         """(host synchronisations, frames) since create"""

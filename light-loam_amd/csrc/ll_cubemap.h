@@ -36,6 +36,16 @@ struct LLMapExport {
     long long points = 0, segments = 0, tiles = 0;
 };
 
+/* map merge (ll_map_merge.hip): what a merging object keeps between calls -- two device buffers grown to the need (0: the by-cube
+ * order of the source points, 1: the filters' input, output and workspace), the events around the stages, the last call's figures */
+#define LL_MM_EVENTS 8
+struct LLMapMerge {
+    unsigned char *d_mem[2] = {nullptr, nullptr}; size_t cap_mem[2] = {0, 0};
+    hipEvent_t ev[LL_MM_EVENTS] = {}; bool have_ev = false;
+    double ms[4] = {0.0, 0.0, 0.0, 0.0};          /* the last merge: assign, sort + gather, filter, commit (events) */
+    long long counts[3] = {0, 0, 0};              /* points in, touched cubes, points out */
+};
+
 struct ll_cubemap {
     ll_ctx *ctx = nullptr;
     ll_map *map = nullptr;
@@ -142,6 +152,14 @@ LL_HIDDEN ll_cubemap *llcms_map(ll_cubemaps *cms, int q);
 LL_HIDDEN LLMapExport &llcms_export_state(ll_cubemaps *cms);
 LL_HIDDEN void *llcms_stage_to(ll_cubemaps *cms, const void *src, size_t bytes, void *dst);
 LL_HIDDEN int llcms_sync(ll_cubemaps *cms);
+/* for the map merge (ll_map_merge.hip): the number of maps, the two leaf sizes, the merge's buffers, last_error set and rc handed
+ * back, one more counted synchronisation (the voxel filter's read-back) */
+LL_HIDDEN int llcms_size(const ll_cubemaps *cms);
+LL_HIDDEN const float *llcms_leaf(const ll_cubemaps *cms);
+LL_HIDDEN LLMapMerge &llcms_merge_state(ll_cubemaps *cms);
+LL_HIDDEN int llcms_fail(ll_cubemaps *cms, int rc, const std::string &msg);
+LL_HIDDEN void llcms_count_sync(ll_cubemaps *cms);
+LL_HIDDEN void llmm_free(LLMapMerge &G);
 LL_HIDDEN int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran, const void *extra_dev, void *extra_host,
                                       size_t extra_bytes, ScanHdr *hdr_out);
 /* the same for ll_cubemaps_localize_slots (map_of [S], read for the running sequences; fit [S], rows of the running sequences) */

@@ -234,6 +234,7 @@ struct ll_cubemaps {
     LLVoxWork W[2], WS;                           /* per cloud type: prepare's and update's filters; WS: the by-cube sort */
     CmsArena ar[2]; int par = 0;
     LLMapExport X;                                /* ll_cubemaps_export's staging buffer and events */
+    LLMapMerge G;                                 /* ll_cubemaps_merge's workspace and events */
     std::vector<void *> allocs, host_allocs;
     long long syncs = 0, frames = 0;
     std::string err;
@@ -318,6 +319,7 @@ extern "C" void ll_cubemaps_destroy(ll_cubemaps *cms)
     for (void *p : cms->allocs) (void)hipFree(p);
     for (void *p : cms->host_allocs) (void)hipHostFree(p);
     llx_free(cms->X);
+    llmm_free(cms->G);
     delete cms;
 }
 
@@ -1050,6 +1052,11 @@ ll_cubemap *llcms_map(ll_cubemaps *cms, int q) { return cms->cm[q]; }
 LLMapExport &llcms_export_state(ll_cubemaps *cms) { return cms->X; }
 void *llcms_stage_to(ll_cubemaps *cms, const void *src, size_t bytes, void *dst) { return cms_stage(cms, src, bytes, dst); }
 int llcms_sync(ll_cubemaps *cms) { return cms_sync(cms); }
+int llcms_size(const ll_cubemaps *cms) { return cms->S; }
+const float *llcms_leaf(const ll_cubemaps *cms) { return cms->leaf; }
+LLMapMerge &llcms_merge_state(ll_cubemaps *cms) { return cms->G; }
+int llcms_fail(ll_cubemaps *cms, int rc, const std::string &msg) { cms->err = msg; return rc; }
+void llcms_count_sync(ll_cubemaps *cms) { ++cms->syncs; }
 
 /* ll_cubemaps_process_slots (map_of == nullptr) or ll_cubemaps_localize_slots with the guesses already in d_pose (rows of the
  * running sequences; llcms_begin called): they come to the host with the slot headers, in the same synchronisation, together

@@ -1,0 +1,471 @@
+/*
+ * ll_map_merge.hip -- cube maps of one ll_cubemaps combined on the device: op (dst, src, T) takes every point of map src through
+ * pointAssociateToMap (laserMapping.cpp:125-134) with the pose T, bins it with dst's centre (:2108-2125) and appends it to the cube
+ * it falls into; every cube that received a point is then down-sized by the library's VoxelGrid (:2151-2165), as a mapping frame
+ * does with its valid cubes.  The update path of ll_cubemaps.hip is sized for one scan (max_scan_*, cap_work); a merge moves whole
+ * maps from a pool to a pool, so it has its own kernels and its own workspace, grown to the need of the call.
+ *
+ * One record per (op, cloud type).  The points of a record are numbered in the order an LL_MAP_ALL export lists that type: cube
+ * 0 .. 4850 of src, inside a cube its own order; the records lie back to back in one flat index space.
+ *   k_mm_assign   a workgroup takes one tile of one source cloud where it lies in src's pool (a segment table and a binary search
+ *                 over the segments' first tiles, as k_map_export): transformed point and cube key per point, and the points per
+ *                 (record, cube) with one add per wave and cube -- nearly all points of a source cube land in at most eight
+ *                 destination cubes.  Key 4851 = outside the array (dropped, counted in the same table).
+ *   k_mm_cstart   per record the exclusive scan of the 4852 counts: where each cube's new points begin in the by-cube order.
+ *   k_mm_hist     a counting sort over the 4852 bins, stable and the same from run to run: the record's points in chunks of 2048,
+ *                 one LDS histogram per chunk;
+ *   k_mm_colscan  per (record, cube) the running sum over the record's chunks, from the cube's beginning;
+ *   k_mm_place    one wave per chunk walks it in order: a point's place is its chunk's start for its cube plus the points of the
+ *                 same cube before it in the chunk (ballots inside the wave, a counter per cube in LDS).  No rank comes from the
+ *                 order in which an atomic is served.
+ *   k_mm_gather   copies over a table in fixed tiles (k_map_export's shape), optionally through an index: the filter input --
+ *                 per touched cube its old cloud, then its new points in order -- and, after the filters, the commit copy.
+ * The host synchronises three times per call whatever the number of ops: the per-cube counts, the filtered sizes, the commit;
+ * plus the voxel filter's read-back when a filter call is above 65 536 points and cannot sort inside its workgroups.
+ */
+#include "ll_cubemap.h"
+#include <chrono>
+#include <cmath>
+
+#define MM_BINS (CM_N + 1)               /* 4851 cubes + "outside the array" */
+#define MM_CHUNK 2048                    /* points per histogram row of the counting sort */
+#define MM_TILE 1024                     /* points per workgroup of k_mm_assign / k_mm_gather: 256 lanes x 4 */
+
+struct MmRec { double T[7]; int cen[3]; int first, n, chunk0, nchunk, pad; };      /* first: its first point in the flat order */
+struct MmSeg { const float4 *src; int dst, cnt; unsigned tile0; int rec; };        /* one source cloud; dst: flat index of its first point */
+struct MmChunk { int first, cnt, rec, pad; };
+struct MmCopy { const float4 *src; const int *index; float4 *dst; int cnt; unsigned tile0; };   /* dst[i] = index ? src[index[i]] : src[i] */
+
+/* ------------------------------------------------------------------ kernels */
+template <typename S>
+__device__ __forceinline__ int mm_find(const S *seg, int nseg, unsigned t)
+{
+    int lo = 0, hi = nseg;                                        /* the last segment whose first tile is <= t */
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned)__builtin_amdgcn_readfirstlane((int)seg[mid].tile0) <= t) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_mm_assign(const MmSeg *seg, int nseg, const MmRec *recs, float4 *tp, int *keys, int *addcnt)
+{
+    const MmSeg s = seg[mm_find(seg, nseg, blockIdx.x)];
+    const MmRec &R = recs[s.rec];
+    const int first = (int)(blockIdx.x - s.tile0) * MM_TILE, n = min(MM_TILE, s.cnt - first);
+    const double ux = R.T[0], uy = R.T[1], uz = R.T[2], w = R.T[3], tx = R.T[4], ty = R.T[5], tz = R.T[6];
+    const int cenx = R.cen[0], ceny = R.cen[1], cenz = R.cen[2];
+    int *cnt = addcnt + (size_t)s.rec * MM_BINS;
+    float4 po[MM_TILE / 256];
+#pragma unroll
+    for (int k = 0; k < MM_TILE / 256; ++k) po[k] = s.src[first + min(k * 256 + (int)threadIdx.x, n - 1)];   /* every load before the first store */
+#pragma unroll
+    for (int k = 0; k < MM_TILE / 256; ++k) {
+        const int i = k * 256 + (int)threadIdx.x;
+        int cube = -1;                                            /* -1: no point */
+        if (i < n) {
+            /* pointAssociateToMap (:125-134) in k_cm_assign's operation order; the pose is used as given, never normalised */
+            const double v[3] = {(double)po[k].x, (double)po[k].y, (double)po[k].z};
+            double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
+            uvx += uvx; uvy += uvy; uvz += uvz;
+            const float sx = (float)(((v[0] + w * uvx) + (uy * uvz - uz * uvy)) + tx);
+            const float sy = (float)(((v[1] + w * uvy) + (uz * uvx - ux * uvz)) + ty);
+            const float sz = (float)(((v[2] + w * uvz) + (ux * uvy - uy * uvx)) + tz);
+            tp[s.dst + first + i] = make_float4(sx, sy, sz, po[k].w);
+            int ci = (int)(((double)sx + 25.0) / 50.0) + cenx, cj = (int)(((double)sy + 25.0) / 50.0) + ceny, ck = (int)(((double)sz + 25.0) / 50.0) + cenz;   /* :2108-2125 */
+            if ((double)sx + 25.0 < 0) ci--;
+            if ((double)sy + 25.0 < 0) cj--;
+            if ((double)sz + 25.0 < 0) ck--;
+            cube = (ci >= 0 && ci < CM_W && cj >= 0 && cj < CM_H && ck >= 0 && ck < CM_D) ? ci + CM_W * cj + CM_W * CM_H * ck : CM_N;
+            keys[s.dst + first + i] = cube;
+        }
+        unsigned long long todo = __ballot(cube >= 0);            /* one add per wave and cube */
+        while (todo) {
+            const int c0 = __shfl(cube, __ffsll((long long)todo) - 1);
+            const unsigned long long same = __ballot(cube == c0);
+            if ((threadIdx.x & 63) == __ffsll((long long)same) - 1) atomicAdd(&cnt[c0], __popcll(same));
+            todo &= ~same;
+        }
+    }
+}
+
+/* cstart[r][b] = addcnt[r][0] + .. + addcnt[r][b - 1]: one workgroup per record */
+__global__ __launch_bounds__(256) void k_mm_cstart(const int *addcnt, int *cstart)
+{
+    __shared__ int sc[4];
+    const int *a = addcnt + (size_t)blockIdx.x * MM_BINS;
+    int *c = cstart + (size_t)blockIdx.x * MM_BINS;
+    int base = 0;
+    for (int b0 = 0; b0 < MM_BINS; b0 += 256) {
+        const int b = b0 + (int)threadIdx.x;
+        int total;
+        const int pos = base + ll_block_exscan_n<4>(b < MM_BINS ? a[b] : 0, sc, total);
+        if (b < MM_BINS) c[b] = pos;
+        base += total;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mm_hist(const MmChunk *chunks, const int *keys, int *H)
+{
+    __shared__ int h[MM_BINS];
+    const MmChunk c = chunks[blockIdx.x];
+    for (int b = threadIdx.x; b < MM_BINS; b += 256) h[b] = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < c.cnt; i += 256) atomicAdd(&h[keys[c.first + i]], 1);
+    __syncthreads();
+    int *row = H + (size_t)blockIdx.x * MM_BINS;
+    for (int b = threadIdx.x; b < MM_BINS; b += 256) row[b] = h[b];
+}
+
+/* H[chunk][b]: the count of cube b in the chunk -> the place of the chunk's first point of cube b in the record's by-cube order */
+__global__ __launch_bounds__(256) void k_mm_colscan(const MmRec *recs, const int *cstart, int *H)
+{
+    const int b = blockIdx.x * 256 + (int)threadIdx.x;
+    if (b >= MM_BINS) return;
+    const MmRec &R = recs[blockIdx.y];
+    int run = cstart[(size_t)blockIdx.y * MM_BINS + b];
+    int *col = H + (size_t)R.chunk0 * MM_BINS + b;
+    for (int k0 = 0; k0 < R.nchunk; k0 += 8) {
+        int v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = k0 + j < R.nchunk ? col[(size_t)(k0 + j) * MM_BINS] : 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) if (k0 + j < R.nchunk) { col[(size_t)(k0 + j) * MM_BINS] = run; run += v[j]; }
+    }
+}
+
+/* one wave per chunk, in order: perm[record's first + place] = flat index of the point */
+__global__ __launch_bounds__(64) void k_mm_place(const MmChunk *chunks, const MmRec *recs, const int *keys, const int *H, int *perm)
+{
+    __shared__ int pos[MM_BINS];
+    const MmChunk c = chunks[blockIdx.x];
+    const int lane = threadIdx.x, rec_first = recs[c.rec].first;
+    const int *row = H + (size_t)blockIdx.x * MM_BINS;
+    for (int b = lane; b < MM_BINS; b += 64) pos[b] = row[b];
+    __syncthreads();
+    for (int i0 = 0; i0 < c.cnt; i0 += 64) {
+        const int i = i0 + lane;
+        const int key = i < c.cnt ? keys[c.first + i] : -1;
+        int place = 0;
+        unsigned long long todo = __ballot(key >= 0);
+        while (todo) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const int k0 = __shfl(key, leader);
+            const unsigned long long same = __ballot(key == k0);
+            int base = 0;
+            if (lane == leader) { base = pos[k0]; pos[k0] = base + __popcll(same); }
+            base = __shfl(base, leader);
+            if (key == k0) place = base + __popcll(same & ((1ull << lane) - 1ull));
+            todo &= ~same;
+        }
+        if (key >= 0) perm[rec_first + place] = c.first + i;
+        __syncthreads();                                          /* one wave: the counters of this step before the next step reads them */
+    }
+}
+
+typedef float mm_f4 __attribute__((ext_vector_type(4)));
+typedef mm_f4 __attribute__((address_space(1))) mm_gf4;          /* the pointers come out of a table: said to be global, not flat */
+__global__ __launch_bounds__(256) void k_mm_gather(const MmCopy *ops, int nops)
+{
+    const MmCopy o = ops[mm_find(ops, nops, blockIdx.x)];
+    const int first = (int)(blockIdx.x - o.tile0) * MM_TILE, n = min(MM_TILE, o.cnt - first);
+    const mm_gf4 *src = (const mm_gf4 *)o.src;
+    mm_gf4 *dst = (mm_gf4 *)o.dst + first;
+    mm_f4 v[MM_TILE / 256];
+    if (o.index) {
+        int idx[MM_TILE / 256];
+#pragma unroll
+        for (int k = 0; k < MM_TILE / 256; ++k) idx[k] = o.index[first + min(k * 256 + (int)threadIdx.x, n - 1)];
+#pragma unroll
+        for (int k = 0; k < MM_TILE / 256; ++k) v[k] = src[idx[k]];
+    } else {
+#pragma unroll
+        for (int k = 0; k < MM_TILE / 256; ++k) v[k] = src[first + min(k * 256 + (int)threadIdx.x, n - 1)];
+    }
+#pragma unroll
+    for (int k = 0; k < MM_TILE / 256; ++k) { const int i = k * 256 + (int)threadIdx.x; if (i < n) dst[i] = v[k]; }
+}
+
+/* ------------------------------------------------------------------ host side */
+void llmm_free(LLMapMerge &G)
+{
+    for (int k = 0; k < 2; ++k) if (G.d_mem[k]) (void)hipFree(G.d_mem[k]);
+    if (G.have_ev) for (int k = 0; k < LL_MM_EVENTS; ++k) (void)hipEventDestroy(G.ev[k]);
+    G = LLMapMerge();
+}
+
+/* buffer k (0: the by-cube order, sized from the source maps; 1: the filters, sized from what they receive) grown to `bytes`; the
+ * old buffer is kept when the new one cannot be had */
+static unsigned char *mm_reserve(LLMapMerge &G, int k, size_t bytes, std::string &err)
+{
+    if (bytes > G.cap_mem[k]) {
+        void *p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            err = "map merge: hipMalloc failed for the workspace (" + std::to_string(bytes) + " bytes)"; return nullptr;
+        }
+        if (G.d_mem[k]) (void)hipFree(G.d_mem[k]);                  /* hipFree waits for the work that may still read it */
+        G.d_mem[k] = (unsigned char *)p; G.cap_mem[k] = bytes;
+    }
+    return G.d_mem[k];
+}
+
+struct MmCarve {
+    unsigned char *p; size_t at = 0;
+    template <typename T> T *take(size_t count) { T *r = p ? (T *)(p + at) : nullptr; at += (count * sizeof(T) + 255) / 256 * 256; return r; }
+};
+
+static const char *mm_type(int w) { return w ? "surf" : "corner"; }
+
+#define MM_HIP(call)                                                                         \
+    do {                                                                                     \
+        hipError_t e_ = (call);                                                              \
+        if (e_ != hipSuccess) return llcms_fail(cms, LL_ERR_HIP, std::string("map merge: " #call ": ") + hipGetErrorString(e_)); \
+    } while (0)
+
+static int mm_gather(ll_cubemaps *cms, std::vector<MmCopy> &ops, hipStream_t st)
+{
+    unsigned long long tile = 0;
+    for (MmCopy &o : ops) { o.tile0 = (unsigned)tile; tile += (unsigned long long)((o.cnt + MM_TILE - 1) / MM_TILE); }
+    if (ops.empty()) return LL_OK;
+    if (tile > 0x7fffffffull) return llcms_fail(cms, LL_ERR_CAPACITY, "map merge: too many tiles for one launch");
+    const MmCopy *d = (const MmCopy *)llcms_stage(cms, ops.data(), ops.size() * sizeof(MmCopy));
+    if (!d) return LL_ERR_HIP;
+    hipLaunchKernelGGL(k_mm_gather, dim3((unsigned)tile), dim3(256), 0, st, d, (int)ops.size());
+    return LL_OK;
+}
+
+extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops, long long *added, long long *dropped)
+{
+    if (!cms) return LL_ERR_ARG;
+    if (!ops || n_ops < 1) return llcms_fail(cms, LL_ERR_ARG, "map merge: ops is NULL or n_ops < 1");
+    const int S = llcms_size(cms);
+    /* ---- every refusal that needs no look at a point: before anything is enqueued */
+    std::vector<int> role(S, 0);                                  /* 1: src of some op, 2: dst of one */
+    for (int i = 0; i < n_ops; ++i) {
+        const ll_merge_op &o = ops[i];
+        const std::string who = "map merge: op " + std::to_string(i) + ": ";
+        if (o.dst < 0 || o.dst >= S || o.src < 0 || o.src >= S) return llcms_fail(cms, LL_ERR_ARG, who + "dst or src is no map");
+        if (o.dst == o.src) return llcms_fail(cms, LL_ERR_ARG, who + "dst and src are the same map");
+        for (int k = 0; k < 7; ++k) if (!std::isfinite(o.T_w7[k])) return llcms_fail(cms, LL_ERR_ARG, who + "T is not finite");
+        if (role[o.dst] == 2) return llcms_fail(cms, LL_ERR_ARG, who + "map " + std::to_string(o.dst) + " is dst of two ops");
+        if (role[o.dst] == 1 || role[o.src] == 2) return llcms_fail(cms, LL_ERR_ARG, who + "a map is dst of one op and src of another");
+        role[o.dst] = 2; role[o.src] = 1;
+    }
+    for (int i = 0; i < n_ops; ++i)
+        for (const int q : {ops[i].dst, ops[i].src})
+            if (llcms_map(cms, q)->broken) return llcms_fail(cms, LL_ERR_STATE, "map merge: op " + std::to_string(i) + ": map " + std::to_string(q) + " is unusable, an earlier update failed half-way");
+    LLMapMerge &G = llcms_merge_state(cms);
+    ll_ctx *ctx = llcms_map(cms, 0)->ctx;
+    hipStream_t st = ctx->stream;
+    const int nrec = 2 * n_ops;
+    /* ---- the records, the source clouds where they lie, the chunks of the counting sort */
+    std::vector<MmRec> recs(nrec);
+    std::vector<MmSeg> segs;
+    std::vector<MmChunk> chunks;
+    unsigned long long tile = 0;
+    long long N = 0;
+    for (int i = 0; i < n_ops; ++i) {
+        const ll_cubemap *src = llcms_map(cms, ops[i].src), *dst = llcms_map(cms, ops[i].dst);
+        for (int w = 0; w < 2; ++w) {
+            MmRec &R = recs[2 * i + w];
+            for (int k = 0; k < 7; ++k) R.T[k] = ops[i].T_w7[k];
+            for (int k = 0; k < 3; ++k) R.cen[k] = dst->cen[k];
+            R.first = (int)N; R.pad = 0;
+            long long n = 0;
+            for (int c = 0; c < CM_N; ++c) {
+                const int cnt = src->cnt[w][c];
+                if (cnt <= 0) continue;
+                if (N + n + cnt > (1ll << 30)) return llcms_fail(cms, LL_ERR_CAPACITY, "map merge: more than 2^30 source points in one call");
+                segs.push_back({src->pool[w][src->cur[w]] + src->off[w][c], (int)(N + n), cnt, (unsigned)tile, 2 * i + w});
+                tile += (unsigned long long)((cnt + MM_TILE - 1) / MM_TILE);
+                n += cnt;
+            }
+            R.n = (int)n; R.chunk0 = (int)chunks.size(); R.nchunk = (int)((n + MM_CHUNK - 1) / MM_CHUNK);
+            for (int k = 0; k < R.nchunk; ++k) chunks.push_back({(int)(N + (long long)k * MM_CHUNK), (int)std::min<long long>(MM_CHUNK, n - (long long)k * MM_CHUNK), 2 * i + w, 0});
+            N += n;
+        }
+    }
+    G.ms[0] = G.ms[1] = G.ms[2] = G.ms[3] = 0.0; G.counts[0] = N; G.counts[1] = G.counts[2] = 0;
+    if (added) std::fill(added, added + nrec, 0ll);
+    if (dropped) std::fill(dropped, dropped + nrec, 0ll);
+    if (N == 0) return LL_OK;                                     /* empty sources: nothing to move */
+    MM_HIP(hipSetDevice(ctx->device));
+    if (!G.have_ev) {
+        for (int k = 0; k < LL_MM_EVENTS; ++k)
+            if (hipEventCreate(&G.ev[k]) != hipSuccess) { for (int j = 0; j < k; ++j) (void)hipEventDestroy(G.ev[j]); return llcms_fail(cms, LL_ERR_HIP, "map merge: hipEventCreate failed"); }
+        G.have_ev = true;
+    }
+    MmCarve A{nullptr};                                           /* first the size, then the pointers */
+    A.take<float4>((size_t)N); A.take<int>((size_t)N); A.take<int>((size_t)N);
+    A.take<int>((size_t)nrec * MM_BINS); A.take<int>((size_t)nrec * MM_BINS); A.take<int>(chunks.size() * MM_BINS);
+    {
+        std::string why;
+        A.p = mm_reserve(G, 0, A.at, why);
+        if (!A.p) return llcms_fail(cms, LL_ERR_HIP, why);
+    }
+    A.at = 0;
+    float4 *d_tp = A.take<float4>((size_t)N);
+    int *d_keys = A.take<int>((size_t)N), *d_perm = A.take<int>((size_t)N);
+    int *d_addcnt = A.take<int>((size_t)nrec * MM_BINS), *d_cstart = A.take<int>((size_t)nrec * MM_BINS), *d_H = A.take<int>(chunks.size() * MM_BINS);
+    llcms_begin(cms);
+    const MmRec *d_recs = (const MmRec *)llcms_stage(cms, recs.data(), recs.size() * sizeof(MmRec));
+    const MmSeg *d_segs = (const MmSeg *)llcms_stage(cms, segs.data(), segs.size() * sizeof(MmSeg));
+    const MmChunk *d_chunks = (const MmChunk *)llcms_stage(cms, chunks.data(), chunks.size() * sizeof(MmChunk));
+    if (!d_recs || !d_segs || !d_chunks) return LL_ERR_HIP;
+    /* ---- stage A: points -> cubes, by-cube order; host: the cubes' new-point counts of every record */
+    MM_HIP(hipMemsetAsync(d_addcnt, 0, (size_t)nrec * MM_BINS * sizeof(int), st));
+    MM_HIP(hipEventRecord(G.ev[0], st));
+    hipLaunchKernelGGL(k_mm_assign, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt);
+    MM_HIP(hipEventRecord(G.ev[1], st));
+    hipLaunchKernelGGL(k_mm_cstart, dim3(nrec), dim3(256), 0, st, (const int *)d_addcnt, d_cstart);
+    hipLaunchKernelGGL(k_mm_hist, dim3((unsigned)chunks.size()), dim3(256), 0, st, d_chunks, (const int *)d_keys, d_H);
+    hipLaunchKernelGGL(k_mm_colscan, dim3((MM_BINS + 255) / 256, nrec), dim3(256), 0, st, d_recs, (const int *)d_cstart, d_H);
+    hipLaunchKernelGGL(k_mm_place, dim3((unsigned)chunks.size()), dim3(64), 0, st, d_chunks, d_recs, (const int *)d_keys, (const int *)d_H, d_perm);
+    MM_HIP(hipEventRecord(G.ev[2], st));
+    MM_HIP(hipGetLastError());
+    std::vector<int> addcnt((size_t)nrec * MM_BINS);
+    {
+        int *pin = (int *)ll_pinned_scratch(addcnt.size() * sizeof(int));
+        if (!pin) return llcms_fail(cms, LL_ERR_HIP, "map merge: no page-locked scratch");
+        MM_HIP(hipMemcpyAsync(pin, d_addcnt, addcnt.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+        const int rc = llcms_sync(cms); if (rc) return rc;
+        std::memcpy(addcnt.data(), pin, addcnt.size() * sizeof(int));
+    }
+    /* ---- will it fit?  Every op and both types, before any pair table changes: a dst pool must hold what the map holds of the
+     * type plus the added points, so that the commit below cannot fail whatever the filters leave */
+    std::vector<long long> n_add(nrec, 0);
+    for (int r = 0; r < nrec; ++r) {
+        const int *a = addcnt.data() + (size_t)r * MM_BINS;
+        const ll_cubemap *dst = llcms_map(cms, ops[r / 2].dst);
+        const int w = r & 1;
+        long long live = 0;
+        for (int c = 0; c < CM_N; ++c) { n_add[r] += a[c]; live += dst->cnt[w][c]; }
+        if (added) added[r] = n_add[r];
+        if (dropped) dropped[r] = a[CM_N];
+        if (live + n_add[r] > (long long)dst->cap_pool)
+            return llcms_fail(cms, LL_ERR_CAPACITY, "map merge: op " + std::to_string(r / 2) + " (map " + std::to_string(ops[r / 2].dst) + " <- map " + std::to_string(ops[r / 2].src) + "): " +
+                              std::to_string(live) + " " + mm_type(w) + " points + " + std::to_string(n_add[r]) + " added, pool_points is " + std::to_string(dst->cap_pool));
+    }
+    /* ---- stage B: one voxel-grid segment per touched cube of every op -- its cloud, then its new points in order */
+    std::vector<int> seg_off[2] = {std::vector<int>(1, 0), std::vector<int>(1, 0)}, seg_cube[2], seg0(nrec, 0), seg1(nrec, 0);
+    long long F[2] = {0, 0};
+    for (int w = 0; w < 2; ++w) {
+        for (int i = 0; i < n_ops; ++i) {
+            const int r = 2 * i + w;
+            const int *a = addcnt.data() + (size_t)r * MM_BINS;
+            const ll_cubemap *dst = llcms_map(cms, ops[i].dst);
+            seg0[r] = (int)seg_cube[w].size();
+            for (int c = 0; c < CM_N; ++c)
+                if (a[c] > 0) { F[w] += (long long)dst->cnt[w][c] + a[c]; seg_cube[w].push_back(c); seg_off[w].push_back((int)F[w]); }
+            seg1[r] = (int)seg_cube[w].size();
+        }
+        if (F[w] > (long long)(INT_MAX / 2)) return llcms_fail(cms, LL_ERR_CAPACITY, std::string("map merge: the touched ") + mm_type(w) + " cubes hold more points than one filter call takes");
+    }
+    G.counts[1] = (long long)(seg_cube[0].size() + seg_cube[1].size());
+    float4 *d_work[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
+    int *d_nout = nullptr;
+    LLVoxWork W[2];
+    {
+        MmCarve B{nullptr};
+        unsigned char *vox[2] = {nullptr, nullptr};
+        for (int pass = 0; pass < 2; ++pass) {
+            B.at = 0;
+            d_nout = B.take<int>(4);
+            for (int w = 0; w < 2; ++w) {
+                d_work[w] = B.take<float4>((size_t)F[w]); d_out[w] = B.take<float4>((size_t)F[w]);
+                vox[w] = B.take<unsigned char>(ll_vox_work_bytes((int)F[w], (int)seg_cube[w].size() + 1));
+            }
+            if (pass == 0) {
+                std::string why;
+                B.p = mm_reserve(G, 1, B.at, why);
+                if (!B.p) return llcms_fail(cms, LL_ERR_HIP, why);
+            }
+        }
+        for (int w = 0; w < 2; ++w) ll_vox_work_carve(vox[w], (int)F[w], (int)seg_cube[w].size() + 1, &W[w]);
+    }
+    std::vector<MmCopy> cp;
+    for (int w = 0; w < 2; ++w)
+        for (int i = 0; i < n_ops; ++i) {
+            const int r = 2 * i + w;
+            const int *a = addcnt.data() + (size_t)r * MM_BINS;
+            const ll_cubemap *dst = llcms_map(cms, ops[i].dst);
+            int g = 0;                                            /* the new points of cube c in the record's by-cube order */
+            for (int c = 0, s = seg0[r]; c < CM_N; ++c) {
+                if (a[c] <= 0) continue;
+                float4 *at = d_work[w] + seg_off[w][s++];
+                if (dst->cnt[w][c] > 0) cp.push_back({dst->pool[w][dst->cur[w]] + dst->off[w][c], nullptr, at, dst->cnt[w][c], 0});
+                cp.push_back({d_tp, d_perm + recs[r].first + g, at + dst->cnt[w][c], a[c], 0});
+                g += a[c];
+            }
+        }
+    MM_HIP(hipEventRecord(G.ev[3], st));
+    int rc = mm_gather(cms, cp, st); if (rc) return rc;
+    MM_HIP(hipEventRecord(G.ev[4], st));
+    for (int w = 0; w < 2; ++w) {
+        if (F[w] <= 0) continue;
+        const int nseg = (int)seg_cube[w].size();
+        int max_seg = 0;
+        for (int s = 0; s < nseg; ++s) max_seg = std::max(max_seg, seg_off[w][(size_t)s + 1] - seg_off[w][(size_t)s]);
+        if (!llcms_stage_to(cms, seg_off[w].data(), seg_off[w].size() * sizeof(int), W[w].seg_off)) return LL_ERR_HIP;
+        /* the voxel filter's sort reads back once when it cannot stay inside the workgroups (ll_voxel.hip): counted with the syncs */
+        if (!(nseg > 1 && max_seg <= 8192) && F[w] > 65536) llcms_count_sync(cms);
+        if (ll_voxel_grid_segments(d_work[w], (int)F[w], nseg, llcms_leaf(cms)[w], W[w], d_out[w], d_nout + w, st, nseg > 1 ? max_seg : 0))
+            return llcms_fail(cms, LL_ERR_HIP, "map merge: voxel filter: read-back failed");
+    }
+    MM_HIP(hipEventRecord(G.ev[5], st));
+    MM_HIP(hipGetLastError());
+    std::vector<int> seg_count[2];
+    {
+        const size_t n0 = seg_cube[0].size(), n1 = seg_cube[1].size();
+        int *pin = (int *)ll_pinned_scratch((n0 + n1 + 2) * sizeof(int));
+        if (!pin) return llcms_fail(cms, LL_ERR_HIP, "map merge: no page-locked scratch");
+        if (n0) MM_HIP(hipMemcpyAsync(pin, W[0].seg_count, n0 * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (n1) MM_HIP(hipMemcpyAsync(pin + n0, W[1].seg_count, n1 * sizeof(int), hipMemcpyDeviceToHost, st));
+        rc = llcms_sync(cms); if (rc) return rc;
+        seg_count[0].assign(pin, pin + n0); seg_count[1].assign(pin + n0, pin + n0 + n1);
+    }
+    /* ---- commit: from here on a failure leaves the pair tables half-updated (the dst maps are marked unusable).  The capacity
+     * decision above covers it: the filtered clouds are never larger than what went into the filters */
+    for (int i = 0; i < n_ops; ++i) llcms_map(cms, ops[i].dst)->broken = true;
+    cp.clear();
+    long long n_out_all = 0;
+    for (int w = 0; w < 2; ++w) {
+        size_t out_at = 0;
+        for (int i = 0; i < n_ops; ++i) {
+            const int r = 2 * i + w, s0 = seg0[r], s1 = seg1[r];
+            if (s1 == s0) continue;
+            ll_cubemap *dst = llcms_map(cms, ops[i].dst);
+            size_t n = 0;
+            for (int s = s0; s < s1; ++s) { n += (size_t)seg_count[w][s]; dst->cnt[w][seg_cube[w][s]] = 0; }   /* the touched cubes' old clouds are dead: not carried through a compaction */
+            rc = cm_reserve(dst, w, n);
+            if (rc) return llcms_fail(cms, rc, "map merge: op " + std::to_string(i) + ": " + dst->err);
+            float4 *pool = dst->pool[w][dst->cur[w]];
+            if (n > 0) cp.push_back({d_out[w] + out_at, nullptr, pool + dst->top[w], (int)n, 0});
+            size_t at = dst->top[w];
+            for (int s = s0; s < s1; ++s) { const int c = seg_cube[w][s]; dst->off[w][c] = (int)at; dst->cnt[w][c] = seg_count[w][s]; at += (size_t)seg_count[w][s]; }
+            dst->top[w] = at;
+            out_at += n; n_out_all += (long long)n;
+        }
+    }
+    MM_HIP(hipEventRecord(G.ev[6], st));
+    rc = mm_gather(cms, cp, st); if (rc) return rc;              /* after every compaction above: stream order */
+    MM_HIP(hipEventRecord(G.ev[7], st));
+    MM_HIP(hipGetLastError());
+    rc = llcms_sync(cms); if (rc) return rc;                      /* the copy has landed: the maps are whole again, the events can be read */
+    for (int i = 0; i < n_ops; ++i) llcms_map(cms, ops[i].dst)->broken = false;
+    auto span = [&](int a, int b) { float ms = 0.0f; return hipEventElapsedTime(&ms, G.ev[a], G.ev[b]) == hipSuccess ? (double)ms : 0.0; };
+    G.ms[0] = span(0, 1); G.ms[1] = span(1, 2) + span(3, 4); G.ms[2] = span(4, 5); G.ms[3] = span(6, 7);
+    G.counts[2] = n_out_all;
+    return LL_OK;
+}
+
+/* the last ll_cubemaps_merge: ms4 = assign, sort + gather, filter, commit (device events); counts3 = points in, touched cubes, points out */
+extern "C" int ll_cubemaps_merge_timing(const ll_cubemaps *cms, double *ms4, long long *counts3)
+{
+    if (!cms) return LL_ERR_ARG;
+    const LLMapMerge &G = llcms_merge_state(const_cast<ll_cubemaps *>(cms));
+    if (ms4) for (int k = 0; k < 4; ++k) ms4[k] = G.ms[k];
+    if (counts3) for (int k = 0; k < 3; ++k) counts3[k] = G.counts[k];
+    return LL_OK;
+}
