@@ -655,6 +655,43 @@ int  ll_cubemaps_localize_slots(ll_cubemaps *cms, const int *slots /* [S] */, co
 int  ll_drives_set_localize(ll_drives *d, const int *map_of /* [S] */, const double *start_w7 /* [S][7], may be NULL */);
 int  ll_drives_fit(ll_drives *d, ll_localize_fit *fit /* [S] */);
 
+/* ---------------------------------------------------------------- one cube map registered to another
+ * ll_cubemaps_align: op i = (dst, src, T0_w7), in ll_merge_op's layout, estimates the rigid transform that takes map src's world
+ * frame into map dst's: the T a following ll_cubemaps_merge needs.  It is laserMapping's scan-to-map optimisation (:1822-2095)
+ * over the WHOLE of both maps, started at T0 (used as given, never normalised) -- local registration from a guess inside the
+ * basin of the 1 m association radius, not global relocalisation.  Per cloud type w (0 corner, 1 surf) MAP_w = dst's points of the
+ * type in the order an LL_MAP_ALL export lists them (cube index ascending, own order inside a cube) and STK_w = src's in the same
+ * order; the result is what ll_map_optimize gives for the search clouds MAP_0, MAP_1, the scan STK_0, STK_1 (no voxel filter of
+ * the stacks: a map's cubes are filtered at the stacks' leaf sizes already), the pose T0 and the same n_outer and opt:
+ *   gate     :1822 (more than 10 corner and more than 50 surf points in dst); shut: ran[i] = 0, T comes back as given, fit all zero;
+ *   n_outer x { pointAssociateToMap of every stack point; its exact five nearest in MAP_w by (distance, index in MAP_w); the
+ *              nb == 5 && bd[4] < 1 acceptance; line / plane fit; ceres::Solve with `opt` (NULL: ll_lm_default_options) }
+ *   fit      != NULL: the residual blocks once more at the final T and ll_localize_fit's five figures with the meaning they have
+ *              there; NULL: that pass is not launched, the poses are the same bits.
+ * n_outer = 0 is allowed: no solve, T comes back as given, ran reports the gate, the record describes the blocks at T0 -- how a
+ * caller scores a transform it already has.
+ * Read-only: no pool, pair table, centre, valid list, per-frame cloud or counter of any map changes (ll_cubemaps_stats' syncs
+ * rises); a map may be dst and src of any number of ops.  Each op's T, ran and fit are the same bits whether it runs alone or among
+ * others, and from call to call.
+ * Nothing passes through the host.  Per distinct dst map and type the call builds a search structure over the whole map: occupied
+ * cube -> slot, per slot 40^3 + 1 ints over world-anchored cells of 1.25 m (256 KB per occupied cube and type), the points in (cube,
+ * cell) order; the normal equations are summed over (op, chunk of 1024 blocks) workgroups and one small workgroup per op takes the
+ * Levenberg-Marquardt steps, n_outer x (1 + max_num_iterations) launch pairs enqueued back to back.  The search is exact for maps
+ * whose points lie in the cubes the library's own arithmetic gives them (every frame, merge, and import of an export).  The
+ * workspace grows to the need of the call and is freed with the object.
+ * Host synchronisations per call in which an op passes the gate, whatever n_ops, n_outer, the maps' sizes and fit are: ONE (poses,
+ * records and block counts in one copy); none otherwise.  Added to ll_cubemaps_stats' syncs; frames does not rise.
+ * The handle from ll_drives_cubemaps(d) is accepted between any two ll_drives_step calls.
+ * Errors, decided before anything is enqueued, last_error names the op: LL_ERR_ARG for a NULL handle, n_ops < 0, n_outer < 0, ops or
+ * T_w7 NULL with n_ops > 0, a map index out of range, dst == src; LL_ERR_STATE for an unusable map or a NaN in T0; LL_ERR_CAPACITY
+ * above 2^30 map or stack points.  LL_ERR_STATE also when a solve returns a NaN pose (cms_optimize's rule; the other ops' results are
+ * delivered).  LL_ERR_HIP: the workspace cannot be allocated (the object stays usable) or a runtime call failed.
+ * ll_cubemaps_align_timing: the last call's device time per stage in ms (build, search + fit, evaluate + solve, fit record; events)
+ * and its counts (stack points, map points, residual blocks at the end, summed over the ops that ran); either may be NULL.        */
+int  ll_cubemaps_align(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops, int n_outer, const ll_lm_options *opt /* NULL: defaults */,
+                       double *T_w7 /* [n_ops][7] out */, int *ran /* [n_ops], may be NULL */, ll_localize_fit *fit /* [n_ops], may be NULL */);
+int  ll_cubemaps_align_timing(const ll_cubemaps *cms, double *ms /* build, search+fit, evaluate+solve, fit */, long long *counts /* stack points, map points, residual blocks */);
+
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),
  * everything device-resident, no host synchronisation inside.  `vote_enable` as above.                   */

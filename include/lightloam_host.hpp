@@ -463,6 +463,23 @@ public:
         if (dropped) dropped->assign(2 * ops.size(), 0);
         return ll_cubemaps_merge(cms, ops.data(), (int)ops.size(), added ? added->data() : nullptr, dropped ? dropped->data() : nullptr);
     }
+    /* ll_cubemaps_align: op i estimates the transform that takes map ops[i].src's world frame into map ops[i].dst's, starting at
+     * ops[i].T_w7 -- laserMapping's optimisation over the whole of both maps, read-only.  T [n_ops][7]; ran [n_ops] and fit [n_ops]
+     * when given (fit == nullptr: the extra pass at the final poses is not launched).  Follow it with merge_maps under T */
+    void align_maps(const std::vector<ll_merge_op> &ops, int n_outer, std::vector<double> *T, std::vector<int> *ran = nullptr,
+                    std::vector<ll_localize_fit> *fit = nullptr, const ll_lm_options *opt = nullptr) {
+        const int rc = align_into(cms_, ops, n_outer, T, ran, fit, opt);
+        if (rc != LL_OK) check(rc);
+    }
+    /* the same on a borrowed handle (Drives::cubemaps(), between two steps); returns the status */
+    static int align_into(ll_cubemaps *cms, const std::vector<ll_merge_op> &ops, int n_outer, std::vector<double> *T, std::vector<int> *ran = nullptr,
+                          std::vector<ll_localize_fit> *fit = nullptr, const ll_lm_options *opt = nullptr) {
+        if (!T) return LL_ERR_ARG;
+        T->assign(7 * ops.size(), 0.0);
+        if (ran) ran->assign(ops.size(), 0);
+        if (fit) fit->assign(ops.size(), ll_localize_fit());
+        return ll_cubemaps_align(cms, ops.data(), (int)ops.size(), n_outer, opt, T->data(), ran ? ran->data() : nullptr, fit ? fit->data() : nullptr);
+    }
     static int import_into(ll_cubemaps *cms, int n_seq, const PointXYZI *points, const long long *offset, const std::vector<const MapLayout *> &layouts) {
         const size_t S_ = (size_t)n_seq;
         std::vector<int> sel(S_, 0), cen(3 * S_, 0), counts(S_ * MapLayout::N_COUNTS, 0), valid(S_ * 125, 0), nv(S_, 0);

@@ -42,6 +42,7 @@ EXPORTS = [
     "ll_drives_save_size", "ll_drives_save", "ll_drives_restore", "ll_checkpoint_describe",
     "ll_cubemaps_localize_slots", "ll_drives_set_localize", "ll_drives_fit",
     "ll_cubemaps_merge", "ll_cubemaps_merge_timing",
+    "ll_cubemaps_align", "ll_cubemaps_align_timing",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -139,6 +140,8 @@ def load_library():
         _lib.ll_cubemaps_last_error.argtypes = [C.c_void_p]
         _lib.ll_cubemaps_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ll_cubemaps_merge_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_cubemaps_align.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ll_cubemaps_align_timing.argtypes = [C.c_void_p] * 3
     return _lib
 
 
@@ -955,6 +958,30 @@ class CubeMaps:
         """the last merge: ((assign ms, sort + gather ms, filter ms, commit ms), (points in, touched cubes, points out))"""
         ms = np.zeros(4); cnt = np.zeros(3, np.int64)
         self._ck(self.lib.ll_cubemaps_merge_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
+        return tuple(ms), tuple(int(c) for c in cnt)
+
+    def align(self, ops, n_outer=2, opt=None, fit=True):
+        """ops: a list of (dst, src, guess_w7) -- the rigid transform that takes map src's world frame into map dst's, by
+        laserMapping's scan-to-map optimisation over the whole of both maps from the guess (local registration: the guess must lie
+        inside the basin of the 1 m association radius) -> (T [n_ops, 7], ran [n_ops] bool, fit: a LocalizeFit array [n_ops], or
+        None with fit=False -- then the extra pass at the final poses is not launched).  n_outer = 0 scores the guess.  No map
+        changes; everything on the device; one synchronisation whatever len(ops) and n_outer are"""
+        rec = (MergeOp * max(len(ops), 1))()
+        for i, (dst, src, pose) in enumerate(ops):
+            p = np.ascontiguousarray(pose, np.float64).reshape(7)
+            rec[i].dst = int(dst); rec[i].src = int(src)
+            for k in range(7):
+                rec[i].T_w7[k] = p[k]
+        T = np.zeros((len(ops), 7)); ran = np.zeros(len(ops), np.int32)
+        out = (LocalizeFit * max(len(ops), 1))() if fit else None
+        self._ck(self.lib.ll_cubemaps_align(self.h, C.addressof(rec), len(ops), int(n_outer), None if opt is None else C.addressof(opt),
+                                            T.ctypes.data, ran.ctypes.data, C.addressof(out) if fit else None))
+        return T, ran.astype(bool), out
+
+    def align_timing(self):
+        """the last align: ((build ms, search + fit ms, evaluate + solve ms, fit record ms), (stack points, map points, residual blocks))"""
+        ms = np.zeros(4); cnt = np.zeros(3, np.int64)
+        self._ck(self.lib.ll_cubemaps_align_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
         return tuple(ms), tuple(int(c) for c in cnt)
 
     def stats(self):

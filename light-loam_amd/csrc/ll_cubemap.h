@@ -46,6 +46,16 @@ struct LLMapMerge {
     long long counts[3] = {0, 0, 0};              /* points in, touched cubes, points out */
 };
 
+/* map alignment (ll_map_align.hip): what an aligning object keeps between calls -- one device buffer grown to the need (search
+ * tables, cell-ordered dst points, flat src stacks, per-op fit results, residual blocks and partial sums), the events around the
+ * stages (two more per outer iteration), the last call's figures */
+struct LLMapAlign {
+    unsigned char *d_mem = nullptr; size_t cap_mem = 0;
+    std::vector<hipEvent_t> ev;
+    double ms[4] = {0.0, 0.0, 0.0, 0.0};          /* the last align: build, search + fit, evaluate + solve, fit record (events) */
+    long long counts[3] = {0, 0, 0};              /* stack points, map points, residual blocks at the end */
+};
+
 struct ll_cubemap {
     ll_ctx *ctx = nullptr;
     ll_map *map = nullptr;
@@ -160,6 +170,9 @@ LL_HIDDEN LLMapMerge &llcms_merge_state(ll_cubemaps *cms);
 LL_HIDDEN int llcms_fail(ll_cubemaps *cms, int rc, const std::string &msg);
 LL_HIDDEN void llcms_count_sync(ll_cubemaps *cms);
 LL_HIDDEN void llmm_free(LLMapMerge &G);
+/* for the map alignment (ll_map_align.hip): its buffers */
+LL_HIDDEN LLMapAlign &llcms_align_state(ll_cubemaps *cms);
+LL_HIDDEN void llal_free(LLMapAlign &A);
 LL_HIDDEN int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran, const void *extra_dev, void *extra_host,
                                       size_t extra_bytes, ScanHdr *hdr_out);
 /* the same for ll_cubemaps_localize_slots (map_of [S], read for the running sequences; fit [S], rows of the running sequences) */

@@ -235,6 +235,7 @@ struct ll_cubemaps {
     CmsArena ar[2]; int par = 0;
     LLMapExport X;                                /* ll_cubemaps_export's staging buffer and events */
     LLMapMerge G;                                 /* ll_cubemaps_merge's workspace and events */
+    LLMapAlign A;                                 /* ll_cubemaps_align's workspace and events */
     std::vector<void *> allocs, host_allocs;
     long long syncs = 0, frames = 0;
     std::string err;
@@ -320,6 +321,7 @@ extern "C" void ll_cubemaps_destroy(ll_cubemaps *cms)
     for (void *p : cms->host_allocs) (void)hipHostFree(p);
     llx_free(cms->X);
     llmm_free(cms->G);
+    llal_free(cms->A);
     delete cms;
 }
 
@@ -1055,6 +1057,7 @@ int llcms_sync(ll_cubemaps *cms) { return cms_sync(cms); }
 int llcms_size(const ll_cubemaps *cms) { return cms->S; }
 const float *llcms_leaf(const ll_cubemaps *cms) { return cms->leaf; }
 LLMapMerge &llcms_merge_state(ll_cubemaps *cms) { return cms->G; }
+LLMapAlign &llcms_align_state(ll_cubemaps *cms) { return cms->A; }
 int llcms_fail(ll_cubemaps *cms, int rc, const std::string &msg) { cms->err = msg; return rc; }
 void llcms_count_sync(ll_cubemaps *cms) { ++cms->syncs; }
 
