@@ -52,7 +52,7 @@ extern __shared__ __attribute__((aligned(16))) unsigned char ll_gsm[];
  * array; = index for a contiguous cloud): place order = index order, and every consumer of the grid only compares.
  * For an extracted slot this kernel is also where the scan's totals become known: the workgroup of the less-flat cloud scans the
  * per-ring counts into lf_pre and writes the four totals of the header (no ring of k_ring_features waited for another to learn them). */
-#define LL_GB 1024      /* threads: the kernel is a chain of latency-bound sweeps and LDS (68 KB) allows two workgroups per CU */
+#define LL_GB 1024      /* threads: one workgroup per CU (below); LDS (68 KB) would allow two */
 /* Workgroups per CU.  Two 1024-thread workgroups are 8 waves per SIMD, and the hardware admits the eighth wave only below 81 SGPRs
  * (MI355X_MICROARCH.md, residency: floor(800 / (ceil(sgpr / 16) * 16 + 16)) waves per SIMD; the occupancy query says 8 up to 96):
  * rounds 1-4 compiled this kernel to 82 SGPRs, so ONE workgroup per CU was resident whatever the occupancy report said.  Round 5
@@ -199,20 +199,32 @@ __global__ __launch_bounds__(LL_GB, LL_GRID_WAVES) void k_build_grid(LLView V, i
             if (lane == 63 || lane == nv - 1 || r != rnext) atomicMax(&leq[r], place);
         }
     };
-    if (cw0 < cw1) {
+    /* Both sweeps walk the wave's chunks in BATCHES of UN (load UN chunks, wait, process them), and they SHARE the wave's last two
+     * batches: the histogram sweep loads them last, into A and B, and leaves them there; the scatter sweep starts with them and reads
+     * only the batches in front of them again.  A cloud of at most 2 UN chunks per wave (every less-sharp cloud) is read once, the
+     * headline's less-flat cloud (33 chunks per wave) 1.52 times instead of twice -- the kernel is held by its traffic.  The batches
+     * end-align with the wave's block, so the one short batch is the FIRST and the two that stay are full. */
+    const int nb = (cw1 - cw0 + UN - 1) / UN;            /* batches of this wave; batch j = chunks c0 + j UN ..., those >= cw0 */
+    const int c0 = cw1 - nb * UN, crest = cw1 - 2 * UN;  /* the batches in front of the last two start at c0, c0 + UN, ... < crest */
+    float4 pA[UN], pB[UN]; int plA[UN], nvA[UN], plB[UN], nvB[UN];
+    /* the cursor first, for all UN chunks, THEN the loads back to back: with the cursor's loop between two loads the compiler
+     * waits for the first (s_waitcnt vmcnt(0) at the loop's head) before it issues the second -- one load in flight, not UN */
+    auto load_batch = [&](Cursor &cu, int c, float4 (&p)[UN], int (&pl)[UN], int (&nv)[UN]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < UN; ++u) { pl[u] = 0; nv[u] = 0; if (c + u >= cw0) take(cu, pl[u], nv[u]); }
+#pragma unroll
+        for (int u = 0; u < UN; ++u) if (lane < nv[u]) p[u] = pts[pl[u] + lane];
+    };
+    auto count_batch = [&](float4 (&p)[UN], int (&pl)[UN], int (&nv)[UN]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < UN; ++u) count_chunk(lane < nv[u] ? ll_grid_key(p[u]) : 0u, pl[u], nv[u]);
+    };
+    if (nb > 0) {
         Cursor cu = cursor_at(cw0);
-        for (int c = cw0; c < cw1; c += UN) {
-            float4 p[UN]; int pl[UN], nv[UN];
-            /* the cursor first, for all UN chunks, THEN the loads back to back: with the cursor's loop between two loads the compiler
-             * waits for the first (s_waitcnt vmcnt(0) at the loop's head) before it issues the second -- one load in flight, not UN */
-#pragma unroll
-            for (int u = 0; u < UN; ++u) { pl[u] = 0; nv[u] = 0; if (c + u < cw1) take(cu, pl[u], nv[u]); }
-#pragma unroll
-            for (int u = 0; u < UN; ++u) if (lane < nv[u]) p[u] = pts[pl[u] + lane];
-            LL_LOADS_LANDED();
-#pragma unroll
-            for (int u = 0; u < UN; ++u) count_chunk(lane < nv[u] ? ll_grid_key(p[u]) : 0u, pl[u], nv[u]);
-        }
+        int c = c0;
+        for (; c < crest; c += UN) { load_batch(cu, c, pA, plA, nvA); LL_LOADS_LANDED(); count_batch(pA, plA, nvA); }
+        if (nb >= 2) { load_batch(cu, c, pB, plB, nvB); LL_LOADS_LANDED(); count_batch(pB, plB, nvB); c += UN; }     /* the two that stay */
+        load_batch(cu, c, pA, plA, nvA); LL_LOADS_LANDED(); count_batch(pA, plA, nvA);
     }
     if (bad) okflag = 0;
     __syncthreads();
@@ -226,25 +238,24 @@ __global__ __launch_bounds__(LL_GB, LL_GRID_WAVES) void k_build_grid(LLView V, i
     if (tid == LL_GB - 1) gstart[LL_GRID_NC] = total;
     __syncthreads();
     LL_GPHASE(9);
-    if (cw0 < cw1) {
+    auto scatter_batch = [&](float4 (&p)[UN], int (&pl)[UN], int (&nv)[UN]) __attribute__((always_inline)) {
+        int pos[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u)
+            if (lane < nv[u]) { const int cc = ll_cell_coord(p[u].y) * LL_GRID_G + ll_cell_coord(p[u].x); pos[u] = atomicAdd(&hist[LL_HI(cc)], 1); }
+#pragma unroll
+        for (int u = 0; u < UN; ++u)
+            if (lane < nv[u]) {
+                const int r = (int)p[u].w;                                   /* int(intensity): the walk's scan id */
+                gpts[pos[u]] = make_float4(p[u].x, p[u].y, p[u].z, __int_as_float(((pl[u] + lane) << 8) | (r & 0xFF)));   /* place < 2^24 */
+            }
+    };
+    if (nb > 0) {
+        /* what the histogram sweep left in registers first, then the batches in front of it, read again */
+        if (nb >= 2) scatter_batch(pB, plB, nvB);
+        scatter_batch(pA, plA, nvA);
         Cursor cu = cursor_at(cw0);
-        for (int c = cw0; c < cw1; c += UN) {
-            float4 p[UN]; int pl[UN], nv[UN], pos[UN];
-#pragma unroll
-            for (int u = 0; u < UN; ++u) { pl[u] = 0; nv[u] = 0; if (c + u < cw1) take(cu, pl[u], nv[u]); }
-#pragma unroll
-            for (int u = 0; u < UN; ++u) if (lane < nv[u]) p[u] = pts[pl[u] + lane];
-            LL_LOADS_LANDED();
-#pragma unroll
-            for (int u = 0; u < UN; ++u)
-                if (lane < nv[u]) { const int cc = ll_cell_coord(p[u].y) * LL_GRID_G + ll_cell_coord(p[u].x); pos[u] = atomicAdd(&hist[LL_HI(cc)], 1); }
-#pragma unroll
-            for (int u = 0; u < UN; ++u)
-                if (lane < nv[u]) {
-                    const int r = (int)p[u].w;                                   /* int(intensity): the walk's scan id */
-                    gpts[pos[u]] = make_float4(p[u].x, p[u].y, p[u].z, __int_as_float(((pl[u] + lane) << 8) | (r & 0xFF)));   /* place < 2^24 */
-                }
-        }
+        for (int c = c0; c < crest; c += UN) { load_batch(cu, c, pA, plA, nvA); LL_LOADS_LANDED(); scatter_batch(pA, plA, nvA); }
     }
 #undef LL_HI
 #undef LL_LOADS_LANDED
