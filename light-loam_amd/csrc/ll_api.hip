@@ -177,7 +177,7 @@ extern "C" int ll_create(int device, const ll_params *p, ll_ctx **out)
     ok = ok && dev_alloc(ctx, V.hdr, B) && dev_alloc(ctx, V.ring_off, (size_t)B * (R + 1));
     V.ring_cap = p->max_ring_points < NP ? p->max_ring_points : NP; V.CS = R * V.ring_cap;
     ok = ok && dev_alloc(ctx, V.cloud, (size_t)B * V.CS, false) && dev_alloc(ctx, ctx->cloud_flat, NP, false);
-    ok = ok && dev_alloc(ctx, V.label, BN) && dev_alloc(ctx, V.curv, p->write_curvature ? BN : 1);
+    ok = ok && dev_alloc(ctx, V.label, NP) && dev_alloc(ctx, V.curv, p->write_curvature ? BN : 1);
     ok = ok && dev_alloc(ctx, V.ring_rec, (size_t)B * R * LL_REC_U16) && dev_alloc(ctx, V.ring_cnt, (size_t)B * R);
     ok = ok && dev_alloc(ctx, V.ring_nlf, (size_t)B * R) && dev_alloc(ctx, V.lf_pre, (size_t)B * (R + 1));
     if (p->max_ring_points > 2304) ok = ok && dev_alloc(ctx, V.tier_cnt, 4) && dev_alloc(ctx, V.tier_list, (size_t)3 * B * R, false);   /* else both stay null: no tiers */
@@ -1474,7 +1474,11 @@ extern "C" int ll_download_labels(ll_ctx *ctx, int slot, int8_t *label, float *c
     if (h.status != 0 && h.status != LL_ERR_EMPTY) { ctx->err = "the slot's scan was refused (status " + std::to_string(h.status) + "): nothing to download"; return h.status; }
     if (cap < h.n) { ctx->err = "label capacity too small"; return LL_ERR_CAPACITY; }
     if (curvature && !V.write_curv) { ctx->err = "curvature requested but write_curvature = 0"; return LL_ERR_STATE; }
-    rc = dl(ctx, label, V.label + (size_t)slot * V.NP, (size_t)h.n); if (rc) return rc;
+    if (label && h.n > 0) {
+        ll_launch_labels(V, slot, V.label, ctx->stream);                         /* no kernel reads labels: they are built from the pick's lists here */
+        LL_HIP(hipGetLastError());
+        rc = dl(ctx, label, V.label, (size_t)h.n); if (rc) return rc;
+    }
     rc = dl(ctx, curvature, V.curv + (size_t)slot * V.NP, (size_t)h.n * 4); if (rc) return rc;
     LL_HIP(hipStreamSynchronize(ctx->stream));
     return LL_OK;

@@ -52,7 +52,7 @@ extern __shared__ __attribute__((aligned(16))) unsigned char ll_gsm[];
  * array; = index for a contiguous cloud): place order = index order, and every consumer of the grid only compares.
  * For an extracted slot this kernel is also where the scan's totals become known: the workgroup of the less-flat cloud scans the
  * per-ring counts into lf_pre and writes the four totals of the header (no ring of k_ring_features waited for another to learn them). */
-#define LL_GB 1024      /* threads: one workgroup per CU (below); LDS (68 KB) would allow two */
+#define LL_GB 1024      /* threads: one workgroup per CU (below), which is why the LDS beside the 68 KB histogram is free for the waves' stashes */
 /* Workgroups per CU.  Two 1024-thread workgroups are 8 waves per SIMD, and the hardware admits the eighth wave only below 81 SGPRs
  * (MI355X_MICROARCH.md, residency: floor(800 / (ceil(sgpr / 16) * 16 + 16)) waves per SIMD; the occupancy query says 8 up to 96):
  * rounds 1-4 compiled this kernel to 82 SGPRs, so ONE workgroup per CU was resident whatever the occupancy report said.  Round 5
@@ -63,8 +63,16 @@ extern __shared__ __attribute__((aligned(16))) unsigned char ll_gsm[];
 #ifndef LL_GRID_WAVES
 #define LL_GRID_WAVES 4
 #endif
-static size_t ll_grid_lds_bytes(const LLView &) { return (LL_GRID_NC + LL_GRID_NC / 16) * sizeof(int); }
-__global__ __launch_bounds__(LL_GB, LL_GRID_WAVES) void k_build_grid(LLView V, int first, int count, int carry)
+#ifndef LL_GRID_UN
+#define LL_GRID_UN 8          /* chunks per batch = independent loads in flight per lane */
+#endif
+#ifndef LL_GRID_KEEP
+#define LL_GRID_KEEP 3        /* batches a wave keeps in registers between the two sweeps */
+#endif
+#define LL_GRID_HIST_BYTES ((LL_GRID_NC + LL_GRID_NC / 16) * sizeof(int))
+/* dynamic LDS: the histogram, then the waves' stashes -- `stash` chunks of 64 whole points (1 KB) for each of the LL_GB / 64 waves */
+static size_t ll_grid_lds_bytes(int stash) { return LL_GRID_HIST_BYTES + (size_t)(LL_GB / 64) * stash * 64 * sizeof(float4); }
+__global__ __launch_bounds__(LL_GB, LL_GRID_WAVES) void k_build_grid(LLView V, int first, int count, int carry, int stash)
 {
     const int which = blockIdx.x & 1, sl = blockIdx.x >> 1;
     if (sl >= count) return;
@@ -172,9 +180,6 @@ __global__ __launch_bounds__(LL_GB, LL_GRID_WAVES) void k_build_grid(LLView V, i
             }
         } else { place0 = cu.k * 64; nv = m - cu.k * 64; ++cu.k; }
     };
-#ifndef LL_GRID_UN
-#define LL_GRID_UN 8
-#endif
     constexpr int UN = LL_GRID_UN;                   /* independent loads in flight per lane */
 /* One UNCONDITIONAL wait behind a batch of predicated loads.  Left to itself the compiler waits inside each `if (lane < nv)` block that
  * uses a point; on the path around the block nothing was waited for, so at the join the destination registers still count as "in
@@ -199,32 +204,67 @@ __global__ __launch_bounds__(LL_GB, LL_GRID_WAVES) void k_build_grid(LLView V, i
             if (lane == 63 || lane == nv - 1 || r != rnext) atomicMax(&leq[r], place);
         }
     };
-    /* Both sweeps walk the wave's chunks in BATCHES of UN (load UN chunks, wait, process them), and they SHARE the wave's last two
-     * batches: the histogram sweep loads them last, into A and B, and leaves them there; the scatter sweep starts with them and reads
-     * only the batches in front of them again.  A cloud of at most 2 UN chunks per wave (every less-sharp cloud) is read once, the
-     * headline's less-flat cloud (33 chunks per wave) 1.52 times instead of twice -- the kernel is held by its traffic.  The batches
-     * end-align with the wave's block, so the one short batch is the FIRST and the two that stay are full. */
+    /* Both sweeps walk the wave's chunks in BATCHES of UN (load UN chunks, wait, process them), and what the histogram sweep has read
+     * of the END of the wave's block the scatter sweep does not read again -- the kernel is held by its traffic:
+     *   - the last LL_GRID_KEEP batches stay in registers, narrowed to what the scatter sweep wants of a point: x, y, z and the low byte
+     *     of int(w) (four chunks' bytes to a register), their places and counts packed into one scalar per chunk.  The histogram
+     *     sweep takes its ring key from the full w first (ll_grid_key): the tables and the out-of-range flag never see the byte;
+     *   - the `stash` chunks in front of them wait in the wave's private piece of the LDS the workgroup leaves free (whole points);
+     *   - only what lies in front of the stash is fetched again.
+     * A cloud of at most LL_GRID_KEEP UN + stash chunks per wave is read once (every less-sharp cloud; with 5 stashed chunks the
+     * headline's less-flat cloud, 33 per wave, 1.12 times; round 7 kept two whole batches: 1.52).  The batches end-align with the
+     * wave's block, so the one short batch is the FIRST and those that stay are full. */
+    constexpr int KB = LL_GRID_KEEP, KC = KB * UN;
+    static_assert(UN % 4 == 0 && KB >= 1 && KB <= 3, "four ring bytes to a register; one to three kept batches");
     const int nb = (cw1 - cw0 + UN - 1) / UN;            /* batches of this wave; batch j = chunks c0 + j UN ..., those >= cw0 */
-    const int c0 = cw1 - nb * UN, crest = cw1 - 2 * UN;  /* the batches in front of the last two start at c0, c0 + UN, ... < crest */
-    float4 pA[UN], pB[UN]; int plA[UN], nvA[UN], plB[UN], nvB[UN];
+    const int c0 = cw1 - nb * UN;
+    const int ckeep = cw1 - min(nb, KB) * UN;            /* the kept batches start here (below cw0: the short batch is one of them) */
+    const int cst = max(cw0, ckeep - stash);             /* the stash holds chunks [cst, ckeep); [cw0, cst) is read twice */
+    float4 *const stw = (float4 *)(ll_gsm + LL_GRID_HIST_BYTES) + (size_t)wave * stash * 64;
+    float4 p[UN]; int pl[UN], nv[UN];
+    float kx[KC], ky[KC], kz[KC]; unsigned kr[KC / 4]; int kpn[KC];     /* kpn: place << 7 | points (<= 64); place < 2^24 */
     /* the cursor first, for all UN chunks, THEN the loads back to back: with the cursor's loop between two loads the compiler
      * waits for the first (s_waitcnt vmcnt(0) at the loop's head) before it issues the second -- one load in flight, not UN */
-    auto load_batch = [&](Cursor &cu, int c, float4 (&p)[UN], int (&pl)[UN], int (&nv)[UN]) __attribute__((always_inline)) {
+    auto load_batch = [&](Cursor &cu, int c) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < UN; ++u) { pl[u] = 0; nv[u] = 0; if (c + u >= cw0) take(cu, pl[u], nv[u]); }
 #pragma unroll
         for (int u = 0; u < UN; ++u) if (lane < nv[u]) p[u] = pts[pl[u] + lane];
     };
-    auto count_batch = [&](float4 (&p)[UN], int (&pl)[UN], int (&nv)[UN]) __attribute__((always_inline)) {
+    auto count_batch = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < UN; ++u) count_chunk(lane < nv[u] ? ll_grid_key(p[u]) : 0u, pl[u], nv[u]);
     };
+    auto keep_batch = [&](auto J) __attribute__((always_inline)) {     /* the batch just counted -> kept batch J */
+        constexpr int j = decltype(J)::value;
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            kx[j * UN + u] = p[u].x; ky[j * UN + u] = p[u].y; kz[j * UN + u] = p[u].z;
+            kpn[j * UN + u] = (pl[u] << 7) | min(nv[u], 64);
+        }
+#pragma unroll
+        for (int g = 0; g < UN / 4; ++g) {
+            unsigned w = 0u;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) w |= (unsigned)((int)p[g * 4 + b].w & 0xFF) << (8 * b);
+            kr[j * UN / 4 + g] = w;
+        }
+    };
+    /* the head's speculative loads of the rings' counts are waited for only where an extracted slot uses them: on the other path
+     * their registers would count as "in flight" all through the sweep, and wherever the allocator reuses one -- for a load's
+     * address, say -- every load of a batch would wait for the one before it */
+    LL_LOADS_LANDED();
     if (nb > 0) {
         Cursor cu = cursor_at(cw0);
         int c = c0;
-        for (; c < crest; c += UN) { load_batch(cu, c, pA, plA, nvA); LL_LOADS_LANDED(); count_batch(pA, plA, nvA); }
-        if (nb >= 2) { load_batch(cu, c, pB, plB, nvB); LL_LOADS_LANDED(); count_batch(pB, plB, nvB); c += UN; }     /* the two that stay */
-        load_batch(cu, c, pA, plA, nvA); LL_LOADS_LANDED(); count_batch(pA, plA, nvA);
+        for (; c < ckeep; c += UN) {
+            load_batch(cu, c); LL_LOADS_LANDED(); count_batch();
+#pragma unroll
+            for (int u = 0; u < UN; ++u) if (c + u >= cst) stw[(c + u - cst) * 64 + lane] = p[u];
+        }
+        if constexpr (KB >= 3) if (nb >= 3) { load_batch(cu, c); LL_LOADS_LANDED(); count_batch(); keep_batch(std::integral_constant<int, KB - 3>{}); c += UN; }
+        if constexpr (KB >= 2) if (nb >= 2) { load_batch(cu, c); LL_LOADS_LANDED(); count_batch(); keep_batch(std::integral_constant<int, KB - 2>{}); c += UN; }
+        load_batch(cu, c); LL_LOADS_LANDED(); count_batch(); keep_batch(std::integral_constant<int, KB - 1>{});
     }
     if (bad) okflag = 0;
     __syncthreads();
@@ -238,24 +278,50 @@ __global__ __launch_bounds__(LL_GB, LL_GRID_WAVES) void k_build_grid(LLView V, i
     if (tid == LL_GB - 1) gstart[LL_GRID_NC] = total;
     __syncthreads();
     LL_GPHASE(9);
-    auto scatter_batch = [&](float4 (&p)[UN], int (&pl)[UN], int (&nv)[UN]) __attribute__((always_inline)) {
+    /* a batch of UN chunks into cell order; rb: int(intensity) & 0xFF, the walk's scan id */
+    auto scatter_batch = [&](const float (&x)[UN], const float (&y)[UN], const float (&z)[UN], const int (&rb)[UN], const int (&bpl)[UN], const int (&bnv)[UN])
+                         __attribute__((always_inline)) {
         int pos[UN];
 #pragma unroll
         for (int u = 0; u < UN; ++u)
-            if (lane < nv[u]) { const int cc = ll_cell_coord(p[u].y) * LL_GRID_G + ll_cell_coord(p[u].x); pos[u] = atomicAdd(&hist[LL_HI(cc)], 1); }
+            if (lane < bnv[u]) { const int cc = ll_cell_coord(y[u]) * LL_GRID_G + ll_cell_coord(x[u]); pos[u] = atomicAdd(&hist[LL_HI(cc)], 1); }
 #pragma unroll
         for (int u = 0; u < UN; ++u)
-            if (lane < nv[u]) {
-                const int r = (int)p[u].w;                                   /* int(intensity): the walk's scan id */
-                gpts[pos[u]] = make_float4(p[u].x, p[u].y, p[u].z, __int_as_float(((pl[u] + lane) << 8) | (r & 0xFF)));   /* place < 2^24 */
-            }
+            if (lane < bnv[u]) gpts[pos[u]] = make_float4(x[u], y[u], z[u], __int_as_float(((bpl[u] + lane) << 8) | rb[u]));   /* place < 2^24 */
+    };
+    auto scatter_loaded = [&]() __attribute__((always_inline)) {        /* the batch in p */
+        float x[UN], y[UN], z[UN]; int rb[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) { x[u] = p[u].x; y[u] = p[u].y; z[u] = p[u].z; rb[u] = (int)p[u].w & 0xFF; }
+        scatter_batch(x, y, z, rb, pl, nv);
+    };
+    auto scatter_kept = [&](auto J) __attribute__((always_inline)) {
+        constexpr int j = decltype(J)::value;
+        float x[UN], y[UN], z[UN]; int rb[UN], bpl[UN], bnv[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            x[u] = kx[j * UN + u]; y[u] = ky[j * UN + u]; z[u] = kz[j * UN + u];
+            rb[u] = (int)((kr[(j * UN + u) / 4] >> (8 * (u & 3))) & 0xFFu);
+            bpl[u] = kpn[j * UN + u] >> 7; bnv[u] = kpn[j * UN + u] & 127;
+        }
+        scatter_batch(x, y, z, rb, bpl, bnv);
     };
     if (nb > 0) {
-        /* what the histogram sweep left in registers first, then the batches in front of it, read again */
-        if (nb >= 2) scatter_batch(pB, plB, nvB);
-        scatter_batch(pA, plA, nvA);
-        Cursor cu = cursor_at(cw0);
-        for (int c = c0; c < crest; c += UN) { load_batch(cu, c, pA, plA, nvA); LL_LOADS_LANDED(); scatter_batch(pA, plA, nvA); }
+        /* what the histogram sweep left in registers first, then the batches in front of the stash, read again, then the stash */
+        scatter_kept(std::integral_constant<int, KB - 1>{});
+        if constexpr (KB >= 2) if (nb >= 2) scatter_kept(std::integral_constant<int, KB - 2>{});
+        if constexpr (KB >= 3) if (nb >= 3) scatter_kept(std::integral_constant<int, KB - 3>{});
+        if (ckeep > cw0) {
+            Cursor cu = cursor_at(cw0);
+            const int nbf = (cst - cw0 + UN - 1) / UN;                   /* end-aligned with the stash's first chunk */
+            for (int c = cst - nbf * UN; c < cst; c += UN) { load_batch(cu, c); LL_LOADS_LANDED(); scatter_loaded(); }
+            const int ns = ckeep - cst;                                  /* <= stash <= UN: one batch, from LDS; the cursor stands at cst */
+#pragma unroll
+            for (int u = 0; u < UN; ++u) { pl[u] = 0; nv[u] = 0; if (u < ns) take(cu, pl[u], nv[u]); }
+#pragma unroll
+            for (int u = 0; u < UN; ++u) if (lane < nv[u]) p[u] = stw[u * 64 + lane];
+            if (ns > 0) scatter_loaded();
+        }
     }
 #undef LL_HI
 #undef LL_LOADS_LANDED
@@ -355,13 +421,36 @@ __global__ __launch_bounds__(LL_BLOCK, LL_ASSOC_WAVES) void k_associate(LLView V
     }
 }
 
+/* chunks per wave of k_build_grid's stash: what the device's LDS limit for a workgroup leaves beside the histogram and the kernel's
+ * static arrays, in whole chunks per wave, at most one batch (MI355X: 160 KB - 68 KB - 4.2 KB -> 5) */
+static int ll_grid_stash_chunks()
+{
+    static int cache[LL_MAX_DEVICES] = {0};         /* stash + 1; 0: not asked yet */
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= LL_MAX_DEVICES) dev = 0;
+    if (cache[dev] == 0) {
+        int per_block = 0, per_cu = 0;
+        hipFuncAttributes fa;
+        if (hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) per_block = 0;
+        if (hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess) per_cu = 0;
+        long long room = -1;
+        if (hipFuncGetAttributes(&fa, (const void *)k_build_grid) == hipSuccess)
+            room = (long long)(per_block > per_cu ? per_block : per_cu) - (long long)fa.sharedSizeBytes - (long long)LL_GRID_HIST_BYTES;
+        (void)hipGetLastError();
+        const long long per_wave = room / (long long)((LL_GB / 64) * 64 * sizeof(float4));
+        cache[dev] = 1 + (int)(per_wave < 0 ? 0 : per_wave > LL_GRID_UN ? LL_GRID_UN : per_wave);
+    }
+    return cache[dev] - 1;
+}
+
 void ll_launch_build_grid(const LLView &V, int first, int count, int carry, hipStream_t st, LLProfiler *prof)
 {
-    static size_t attr_bytes[LL_MAX_DEVICES] = {0};   /* 68 KiB histogram + the chunk table + static LDS exceed the default dynamic-LDS limit */
-    const size_t lds = ll_grid_lds_bytes(V);
+    static size_t attr_bytes[LL_MAX_DEVICES] = {0};   /* 68 KiB histogram + the stashes + static LDS exceed the default dynamic-LDS limit */
+    const int stash = ll_grid_stash_chunks();
+    const size_t lds = ll_grid_lds_bytes(stash);
     ll_ensure_dynamic_lds(k_build_grid, lds, attr_bytes);
     ll_prof_mark(prof, LL_K_GRID, st);
-    hipLaunchKernelGGL(k_build_grid, dim3(2 * (carry ? 1 : count)), dim3(LL_GB), lds, st, V, first, carry ? 1 : count, carry);
+    hipLaunchKernelGGL(k_build_grid, dim3(2 * (carry ? 1 : count)), dim3(LL_GB), lds, st, V, first, carry ? 1 : count, carry, stash);
     ll_prof_mark(prof, LL_K_END, st);
 }
 

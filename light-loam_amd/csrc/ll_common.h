@@ -6,8 +6,9 @@
  *   hdr        ScanHdr[B]          startOri / endOri / halfPassed index / sizes / status
  *   ring_off   int    [B][R+1]     ring r is laserCloud[ring_off[r], ring_off[r+1]) (labels, curvature, C ABI)
  *   cloud      float4 [B][R][ring_cap]  laserCloud (x, y, z, intensity), every ring at a fixed stride (ring_cap = max_ring_points)
- *   label      int8   [B][NP]      cloudLabel   curv float [B][NP] (optional)
- *   ring_rec, ring_cnt             k_ring_pick's lists per ring (local indices) and its three counts
+ *   curv       float  [B][NP]      cloudCurvature (optional)
+ *   ring_rec, ring_cnt             k_ring_pick's lists per ring (local indices) and its three counts; cloudLabel is not stored:
+ *                                  ll_download_labels rebuilds one slot's from these lists into label, int8 [NP] (k_labels)
  *   sharp / less_sharp / flat      float4 [B][R*12 / R*120 / R*24], contiguous, in the reference's publication order (ring, segment, pick)
  *   carry_*    target clouds for the first slot of a batch (previous batch's last scan).
  *   corr / vote / neq / pose arrays for the odometry stages.
@@ -114,7 +115,7 @@ struct LLView {
     int *tile_hist; int *tile_base; int *tile_first_p; int *tile_first_kept; int *tile_last_kept;
     ScanHdr *hdr; int *ring_off;
     float4 *cloud; int ring_cap, CS;   /* laserCloud, ring r of slot s at cloud[s * CS + r * ring_cap]; CS = R * ring_cap */
-    int8_t *label; float *curv;
+    int8_t *label; float *curv;    /* label: [NP], ONE slot's cloudLabel, filled by ll_download_labels (k_labels); curv: [B][NP] */
     /* features */
     unsigned short *ring_rec;      /* [B][R][LL_REC_U16] k_ring_pick's lists of one ring */
     unsigned *ring_cnt;            /* [B][R] n_sharp | n_less_sharp << 8 | n_flat << 16 | 1 << 31 (the ring has segments): k_ring_pick -> k_ring_features, k_build_grid */
@@ -366,6 +367,7 @@ void ll_prof_mark(LLProfiler *p, int kernel_id, hipStream_t st);
 /* launchers implemented in the per-stage .hip files */
 void ll_launch_organize(const LLView &V, int first, int count, hipStream_t st, LLProfiler *prof);
 void ll_launch_cloud_flatten(const LLView &V, int slot, float4 *dst, hipStream_t st);
+void ll_launch_labels(const LLView &V, int slot, int8_t *dst, hipStream_t st);          /* the slot's cloudLabel, rebuilt from k_ring_pick's lists (dst: >= NP bytes) */
 void ll_launch_lflat_flatten(const LLView &V, int slot, float4 *dst, hipStream_t st);   /* the slot's less-flat cloud, contiguous (dst: >= NP points) */
 void ll_launch_features(const LLView &V, int first, int count, size_t lds_bytes, hipStream_t st, LLProfiler *prof, int what = 3);   /* what: 1 = the pick kernel, 2 = the voxel kernel */
 void ll_launch_pick(const LLView &V, int first, int count, hipStream_t st);

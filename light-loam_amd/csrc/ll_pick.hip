@@ -15,8 +15,8 @@
  *     get) are ten bits of the ballot words picked out with v_alignbit,
  *   - the pick itself is the sort-free arg-max loop of rounds 1-3 (lane-local max, DPP wave max, ballot; see k_ring_features'
  *     history in DESIGN.md), with the earlier segments' forward marks imported eagerly -- they are complete, the wave made them,
- *   - labels, the picked points' local indices (sharp / less-sharp / flat, per segment) and the ring's counts go to HBM; the
- *     next kernel turns indices into published clouds.
+ *   - the picked points' local indices (sharp / less-sharp / flat, per segment) and the ring's counts go to HBM; the next kernel
+ *     turns indices into published clouds, and cloudLabel is rebuilt from them when somebody asks (k_labels below).
  * No __syncthreads, no cross-wave traffic: a workgroup is LL_PK_WAVES independent rings, 8 waves per SIMD.
  */
 #include "ll_common.h"
@@ -49,7 +49,6 @@ struct PickLds {
                                                                          * next segment's first tile): curvature bits; local index | extents << 16 */
     };
     unsigned picked[(SR * 64 * 6 + 16 + 31) / 32 + 2];   /* cloudNeighborPicked over the ring's local indices */
-    unsigned lab2[(SR * 64 * 6 + 16 + 15) / 16 + 2];     /* cloudLabel, two bits per local index: 0, 1, 2, 3 = -1 */
 #ifdef LL_PK_LDS_PAD
     unsigned char pad[LL_PK_LDS_PAD];           /* timing builds: fewer waves per SIMD */
 #endif
@@ -91,7 +90,6 @@ __device__ __forceinline__ void ll_ring_pick_ring(const LLView &V, int s, int r,
     PickLds<SR> &L = lds_all[wave];
     unsigned short *rec_g = V.ring_rec + ((size_t)s * V.R + r) * LL_REC_U16;
     unsigned *rcnt = V.ring_cnt + (size_t)s * V.R + r;
-    int8_t *label = V.label + (size_t)s * V.NP + off;
     const int S = off + 5, E = off + nr - 6;                          /* scanStartInd / scanEndInd (:218-220) */
     const bool active = (nr > 0) && (E - S >= 6);                     /* :248 */
     const int Lseg = active ? (E - S) : 0;
@@ -129,8 +127,7 @@ __device__ __forceinline__ void ll_ring_pick_ring(const LLView &V, int s, int r,
             V.curv[(size_t)s * V.NP + g] = dX * dX + dY * dY + dZ * dZ;
         }
     }
-    if (!active) {                                                    /* no segments: every label 0, no features (also nr <= 0) */
-        for (int i = lane; i < nr; i += 64) label[i] = 0;
+    if (!active) {                                                    /* no segments: no features (also nr <= 0) */
         if (lane < 3 * LL_SEGS) rec_g[156 + lane] = 0;
         if (lane == 0) *rcnt = 0u;
         return;
@@ -138,7 +135,6 @@ __device__ __forceinline__ void ll_ring_pick_ring(const LLView &V, int s, int r,
     {
         const int nwords = (nr + 31) / 32 + 1;
         for (int i = lane; i < nwords; i += 64) L.picked[i] = 0;
-        for (int i = lane; i < 2 * nwords; i += 64) L.lab2[i] = 0;   /* the points outside the segments keep label 0 */
     }
     unsigned short *rec = L.rec;
 
@@ -456,18 +452,16 @@ __device__ __forceinline__ void ll_ring_pick_ring(const LLView &V, int s, int r,
             } else if (ncr <= 1) { if (nc > 0 && !sorted_walk()) pick_loop(integral_constant<int, 1>{}, true_type{}, true_type{}, ck, cli); }
             else if (ncr <= 2) pick_loop(integral_constant<int, 2>{}, true_type{}, true_type{}, ck, cli);
             else pick_loop(integral_constant<int, LL_PK_CROWS>{}, true_type{}, true_type{}, ck, cli);
-            /* the picked records, lane-parallel: labels, list entries, marks */
+            /* the picked records, lane-parallel: list entries, marks */
             const int nr_ = pass == 0 ? min(npick, LL_LSHARP_PER_SEG) : npick;
             nrec[pass] = nr_;
             if (lane < nr_) {
                 const int sel = (int)(myrec & 0xffffu), e = (int)(myrec >> 16);
-                unsigned code;                                        /* cloudLabel (:271, :276, :323) */
+                /* cloudLabel (:271, :276, :323) is what the lists say: ll_download_labels rebuilds it from them (k_labels) */
                 if (pass == 0) {
-                    if (lane < LL_SHARP_PER_SEG) { code = 2u; rec[j * LL_SHARP_PER_SEG + lane] = (unsigned short)sel; }
-                    else code = 1u;
+                    if (lane < LL_SHARP_PER_SEG) rec[j * LL_SHARP_PER_SEG + lane] = (unsigned short)sel;
                     rec[12 + j * LL_LSHARP_PER_SEG + lane] = (unsigned short)sel;
-                } else { code = 3u; rec[132 + j * LL_FLAT_PER_SEG + lane] = (unsigned short)sel; }
-                atomicOr(&L.lab2[sel >> 4], code << ((sel & 15) * 2));
+                } else rec[132 + j * LL_FLAT_PER_SEG + lane] = (unsigned short)sel;
                 /* marks into the bitmap: a corner pick's whole range from this segment's first index on (the flat pass reads it
                  * back), a flat pick's only beyond this segment (inside it the flat pass keeps them in registers) */
                 const int shi = sel + (e >> 4), f0 = max(sel - (e & 15), pass == 0 ? sp + 5 : ep + 6);
@@ -481,12 +475,8 @@ __device__ __forceinline__ void ll_ring_pick_ring(const LLView &V, int s, int r,
         if (lane < 3) rec[156 + j * 3 + lane] = (unsigned short)(lane == 0 ? min(nrec[0], LL_SHARP_PER_SEG) : lane == 1 ? nrec[0] : nrec[1]);
         segc += (unsigned)min(nrec[0], LL_SHARP_PER_SEG) | ((unsigned)nrec[0] << 8) | ((unsigned)nrec[1] << 16);
     }
-    /* the ring is done: labels, lists, counts */
+    /* the ring is done: lists, counts */
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    for (int li = lane; li < nr; li += 64) {
-        const unsigned c = (L.lab2[li >> 4] >> ((li & 15) * 2)) & 3u;
-        label[li] = (int8_t)(c == 3u ? -1 : (int)c);
-    }
     if (lane < LL_REC_U16 / 2) ((unsigned *)rec_g)[lane] = ((const unsigned *)L.rec)[lane];
     if (lane + 64 < LL_REC_U16 / 2) ((unsigned *)rec_g)[lane + 64] = ((const unsigned *)L.rec)[lane + 64];
     if (lane == 0) *rcnt = segc | 0x80000000u;                        /* the ring's counts */
@@ -564,4 +554,33 @@ void ll_launch_pick(const LLView &V, int first, int count, hipStream_t st)
     if (cap > 2304) ll_launch_ring_pick_tier(k_ring_pick8, V, count, 2304, cap < 3072 ? cap : 3072, 1, 6, st);
     const int groups = (V.R + LL_PK_WAVES - 1) / LL_PK_WAVES;
     hipLaunchKernelGGL(k_ring_pick6, dim3(8 * groups * ((count + 7) / 8)), dim3(64 * LL_PK_WAVES), 0, st, V, first, count, INT_MIN, cap < 2304 ? cap : 2304);
+}
+
+/* cloudLabel of one slot (:271, :276, :323), rebuilt from what k_ring_pick left -- no kernel reads labels, so none is written on the
+ * hot path: 0 everywhere; per segment the first n_sharp entries of the less-sharp list 2, its other entries 1, the flat entries -1.
+ * A ring without segments, and one whose counts no pick kernel wrote (ring_cnt's bit 31 clear), keeps 0.  One wave per ring; the
+ * zero fill and the lists touch different bytes only through the barrier. */
+__global__ __launch_bounds__(1024) void k_labels(LLView V, int slot, int8_t *dst)
+{
+    const int n = V.hdr[slot].n;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = 0;
+    __syncthreads();
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63, nwaves = (int)blockDim.x >> 6;
+    const int *ro = V.ring_off + (size_t)slot * (V.R + 1);
+    for (int r = wave; r < V.R; r += nwaves) {
+        if (!(V.ring_cnt[(size_t)slot * V.R + r] & 0x80000000u)) continue;
+        const int off = ro[r], nr = ro[r + 1] - off;
+        const unsigned short *rec = V.ring_rec + ((size_t)slot * V.R + r) * LL_REC_U16;
+        for (int j = 0; j < LL_SEGS; ++j) {
+            const int n_sharp = min((int)rec[156 + j * 3], LL_SHARP_PER_SEG), n_ls = min((int)rec[156 + j * 3 + 1], LL_LSHARP_PER_SEG);
+            const int n_flat = min((int)rec[156 + j * 3 + 2], LL_FLAT_PER_SEG);
+            if (lane < n_ls) { const int li = rec[12 + j * LL_LSHARP_PER_SEG + lane]; if (li < nr && off + li < n) dst[off + li] = lane < n_sharp ? 2 : 1; }
+            if (lane < n_flat) { const int li = rec[132 + j * LL_FLAT_PER_SEG + lane]; if (li < nr && off + li < n) dst[off + li] = -1; }
+        }
+    }
+}
+
+void ll_launch_labels(const LLView &V, int slot, int8_t *dst, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_labels, dim3(1), dim3(1024), 0, st, V, slot, dst);
 }

@@ -26,16 +26,24 @@ ORDER = ["k_organize", "k_ring_pick", "k_ring_features", "k_build_grid", "k_asso
 HOLDS = {"k_organize": "bytes: all of its traffic is algorithmic, at 0.85 of the copy rate of these strides (5.6 TB/s)",
          "k_ring_pick": "the greedy pick's dependent chains; vector and scalar issue both half busy",
          "k_ring_features": "no single unit: 0.78 of the read-stream rate on the bytes it moves, the gather re-reads the ring",
-         "k_build_grid": "fabric traffic (clouds read 1.5 times + scatter + start tables): 15 % fewer bytes, 19 % less time in round 7; no CU unit busy",
+         "k_build_grid": "fabric traffic (the less-flat cloud read 1.12 times + scatter + start tables): time follows bytes in rounds 7 and 8; no CU unit busy",
          "k_associate": "latency of ~5 dependent rounds per query + vector issue; 8 lanes per query in lockstep",
          "k_vote": "vector issue + LDS reads", "k_normal_equations": "latency (one workgroup per scan, f64 chains)"}
 # a later round that re-measured the headline only (profiles/r07_bench.json: k_build_grid changed, nothing else): its row comes from there
 r7 = last("r07_bench.json")["roofline"] if os.path.exists(os.path.join(P, "r07_bench.json")) and TAG == "r06" else None
+# ... and round 8 (profiles/r08_bench.json: k_build_grid and k_ring_pick changed): those two rows come from there
+r8 = last("r08_bench.json")["roofline"] if os.path.exists(os.path.join(P, "r08_bench.json")) and TAG == "r06" else None
 rows = []
 for k in ORDER:
     t = pt["kernels"].get(k, {})
-    src = r7 if (r7 and k == "k_build_grid") else r
+    src = r8 if (r8 and k in ("k_build_grid", "k_ring_pick")) else r7 if (r7 and k == "k_build_grid") else r
     ms, g, i = src["kernel_ms_per_step"][k], src["kernel_algorithmic_GBps"][k], src["issue"].get(k, {})
+    if not i and os.path.exists(os.path.join(P, "sq_issue.json")):      # a bench line taken before its counter pass: bench.py's issue model on the pass's counts
+        import bench
+        q = json.load(open(os.path.join(P, "sq_issue.json")))["kernels"].get(k)
+        if q:
+            i = {"valu_busy": q["valu"] / (bench.N_SIMD * bench.CLOCK_GHZ * 1e9 / bench.VALU_CYCLES * ms * 1e-3),
+                 "salu_busy": q["salu"] / (bench.N_SIMD / 4 * bench.CLOCK_GHZ * 1e9 * ms * 1e-3)}
     traffic = t.get("hbm_read_bytes_per_launch", 0.0) + t.get("hbm_write_bytes_per_launch", 0.0)
     alg = g * 1e9 * ms * 1e-3
     rows.append("| `%s` | %.2f | %.0f (%.3f) | %.2f | %.0f %% / %.0f %% | %s |" % (k, ms, g, g / 8000.0, traffic / alg if alg else 0.0,
