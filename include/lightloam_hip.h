@@ -728,6 +728,23 @@ int ll_debug_launch_stage(ll_ctx *ctx, int stage, int first, int count);
  *   op 6  ring id (int) by evaluating the reference's formula chain directly on the device (:139-168)
  * Test surface (tests/test_gpu_a1_edges.py compares with glibc on the GPU box); not used by the pipeline. */
 int ll_debug_exact_math(ll_ctx *ctx, int op, const float *a, const float *b, const float *c, int n, void *out);
+/* The primitives under every map operation (the whole-cloud voxel filter, the sort by cube, merge, export, import), each on its own over
+ * host arrays; every call allocates and frees its own workspace and synchronises once.  Test surface (tests/test_gpu_sort_scan.py,
+ * tests/test_gpu_voxel.py); not used by the pipeline.
+ *   ll_debug_sort_pairs      the stable sort of (u64 key, i32 value) pairs by key, in place.  seg_off == NULL: all n pairs in one sort (one
+ *                            LDS workgroup up to 8192 pairs, eight LDS chunks and a merge up to 65536, device-wide radix passes above).
+ *                            Else nseg + 1 host offsets: every segment [seg_off[s], seg_off[s + 1]) sorted on its own by one workgroup;
+ *                            LL_ERR_ARG unless the offsets ascend from 0 to n, nseg is 1 .. 65535 and no segment exceeds 8192 pairs.
+ *   ll_debug_exscan          the in-place exclusive prefix sum of n ints; LL_ERR_ARG for n < 0 or n > 4096 * 4096.
+ *   ll_debug_voxel_segments  pcl::VoxelGrid of nseg clouds that lie back to back in `in` (offsets as above), as the cube-map stages call it:
+ *                            the filtered clouds back to back in `out`, their sizes in seg_count[nseg], the total in *n_out.  max_seg_len is
+ *                            handed on as those stages do: 1 .. 8192 (a bound on every segment, else LL_ERR_ARG) selects the sort per
+ *                            segment when nseg > 1; 0, or more than 8192, the sort over all n.  LL_ERR_ARG for leaf <= 0 or bad offsets;
+ *                            LL_ERR_CAPACITY, with *n_out set, when more than cap points result. */
+int ll_debug_sort_pairs(ll_ctx *ctx, unsigned long long *keys, int *vals, int n, const int *seg_off, int nseg);
+int ll_debug_exscan(ll_ctx *ctx, int *data, int n);
+int ll_debug_voxel_segments(ll_ctx *ctx, const ll_point *in, int n, const int *seg_off, int nseg, float leaf, int max_seg_len,
+                            ll_point *out, int cap, int *seg_count, int *n_out);
 
 /* Algorithmic HBM bytes of the last ll_hot_path_batch / stage calls, summed over the slots they covered,
  * by SURVEY.md section 8d's formula (B_ext, B_assoc, B_vote, B_rj).                                      */

@@ -43,6 +43,7 @@ EXPORTS = [
     "ll_cubemaps_localize_slots", "ll_drives_set_localize", "ll_drives_fit",
     "ll_cubemaps_merge", "ll_cubemaps_merge_timing",
     "ll_cubemaps_align", "ll_cubemaps_align_timing",
+    "ll_debug_sort_pairs", "ll_debug_exscan", "ll_debug_voxel_segments",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -483,6 +484,36 @@ class Context:
         out = np.zeros(len(a), np.int32 if op >= 5 else np.float32)
         self._ck(self.lib.ll_debug_exact_math(self.h, int(op), _ptr(a), _ptr(b), _ptr(c), len(a), _ptr(out)))
         return out
+
+    def debug_sort_pairs(self, keys, vals, seg_off=None):
+        """the stable (u64 key, i32 value) pair sort on its own (ll_debug_sort_pairs): over all pairs, or over every
+        segment [seg_off[s], seg_off[s + 1]) separately -> (sorted keys, values carried along)"""
+        k = np.array(keys, np.uint64).ravel(); v = np.array(vals, np.int32).ravel()       # copies: the call sorts in place
+        assert len(k) == len(v)
+        so = None if seg_off is None else np.ascontiguousarray(seg_off, np.int32)
+        self._ck(self.lib.ll_debug_sort_pairs(self.h, _ptr(k), _ptr(v), len(k), _ptr(so), 0 if so is None else len(so) - 1))
+        return k, v
+
+    def debug_exscan(self, data):
+        """the device's exclusive prefix sum of an int32 array (ll_debug_exscan)"""
+        d = np.array(data, np.int32).ravel()
+        self._ck(self.lib.ll_debug_exscan(self.h, _ptr(d), len(d)))
+        return d
+
+    def debug_voxel_segments(self, points, seg_off, leaf, max_seg_len=0, cap=None):
+        """pcl::VoxelGrid of the clouds [seg_off[s], seg_off[s + 1]) of `points` in one call (ll_debug_voxel_segments) ->
+        (filtered clouds back to back, points per filtered cloud).  On LL_ERR_CAPACITY the error carries n_out."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        so = np.ascontiguousarray(seg_off, np.int32)
+        cap = len(pts) if cap is None else int(cap)
+        out = np.zeros((max(cap, 1), 4), np.float32); cnt = np.zeros(max(len(so) - 1, 1), np.int32); n = C.c_int(0)
+        rc = self.lib.ll_debug_voxel_segments(self.h, _ptr(pts), len(pts), _ptr(so), len(so) - 1, C.c_float(leaf), int(max_seg_len),
+                                              _ptr(out), cap, _ptr(cnt), C.byref(n))
+        if rc != LL_OK:
+            err = LightLoamError(rc, self.lib.ll_last_error(self.h).decode())
+            err.n_out = n.value
+            raise err
+        return out[:n.value].copy(), cnt[:len(so) - 1].copy()
 
     def algorithmic_bytes(self, first=0, count=1):
         b = [C.c_double(0) for _ in range(4)]

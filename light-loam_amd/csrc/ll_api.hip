@@ -1693,6 +1693,115 @@ extern "C" int ll_debug_exact_math(ll_ctx *ctx, int op, const float *a, const fl
     return LL_OK;
 }
 
+/* ---- test surface: the sort, the scan and the segmented voxel filter of ll_voxel.hip / ll_mapping.hip on their own ---- */
+int ll_sort_pairs(unsigned long long *keys, int *vals, unsigned long long *tmp_keys, int *tmp_vals, int n, int *hist, int *tile_sum,
+                  unsigned long long *or_and_dev, hipStream_t st);
+void ll_sort_pairs_segments(unsigned long long *keys, int *vals, const int *seg_off_dev, int nseg, hipStream_t st);
+
+/* nseg + 1 offsets ascending from 0 to n, no segment longer than max_len (0: any length) */
+static bool ll_debug_offsets_ok(const int *seg_off, int nseg, int n, int max_len)
+{
+    if (!seg_off || nseg < 1 || nseg > 65535 || seg_off[0] != 0 || seg_off[nseg] != n) return false;
+    for (int s = 0; s < nseg; ++s) {
+        const int len = seg_off[s + 1] - seg_off[s];
+        if (len < 0 || (max_len > 0 && len > max_len)) return false;
+    }
+    return true;
+}
+
+extern "C" int ll_debug_sort_pairs(ll_ctx *ctx, unsigned long long *keys, int *vals, int n, const int *seg_off, int nseg)
+{
+    int rc = ll_enter(ctx); if (rc) return rc;
+    if (n < 0 || (n > 0 && (!keys || !vals)) || (seg_off && !ll_debug_offsets_ok(seg_off, nseg, n, 8192))) {
+        ctx->err = "bad ll_debug_sort_pairs arguments"; return LL_ERR_ARG;
+    }
+    if (n == 0) return LL_OK;
+    const int ms = seg_off ? nseg : 1;
+    hipStream_t st = ctx->stream;
+    void *work = nullptr;
+    LL_HIP(hipMalloc(&work, ll_vox_work_bytes(n, ms)));
+    LLVoxWork W;
+    ll_vox_work_carve(work, n, ms, &W);
+    int srt = 0;
+    hipError_t e = hipMemcpyAsync(W.keys, keys, (size_t)n * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(W.vals, vals, (size_t)n * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && seg_off) e = hipMemcpyAsync(W.seg_off, seg_off, (size_t)(nseg + 1) * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        if (seg_off) ll_sort_pairs_segments(W.keys, W.vals, W.seg_off, nseg, st);
+        else srt = ll_sort_pairs(W.keys, W.vals, W.tmp_keys, W.tmp_vals, n, W.hist, W.tile_sum, W.or_and, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(keys, W.keys, (size_t)n * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(vals, W.vals, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipGetLastError();
+    (void)hipFree(work);
+    if (e != hipSuccess) { ctx->err = std::string("ll_debug_sort_pairs: ") + hipGetErrorString(e); return LL_ERR_HIP; }
+    if (srt) { ctx->err = "ll_debug_sort_pairs: read-back failed"; return LL_ERR_HIP; }
+    return LL_OK;
+}
+
+extern "C" int ll_debug_exscan(ll_ctx *ctx, int *data, int n)
+{
+    int rc = ll_enter(ctx); if (rc) return rc;
+    if (n < 0 || n > 4096 * 4096 || (n > 0 && !data)) { ctx->err = "bad ll_debug_exscan arguments"; return LL_ERR_ARG; }
+    if (n == 0) return LL_OK;
+    hipStream_t st = ctx->stream;
+    int *d = nullptr;                                             /* the data, then ceil(n / 4096) tile totals */
+    const size_t nt = ((size_t)n + 4095) / 4096;
+    LL_HIP(hipMalloc((void **)&d, ((size_t)n + nt) * sizeof(int)));
+    hipError_t e = hipMemcpyAsync(d, data, (size_t)n * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) { ll_device_exscan(d, n, d + n, st); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(data, d, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipGetLastError();
+    (void)hipFree(d);
+    if (e != hipSuccess) { ctx->err = std::string("ll_debug_exscan: ") + hipGetErrorString(e); return LL_ERR_HIP; }
+    return LL_OK;
+}
+
+extern "C" int ll_debug_voxel_segments(ll_ctx *ctx, const ll_point *in, int n, const int *seg_off, int nseg, float leaf, int max_seg_len,
+                                       ll_point *out, int cap, int *seg_count, int *n_out)
+{
+    int rc = ll_enter(ctx); if (rc) return rc;
+    /* a max_seg_len of 1 .. 8192 selects the one-workgroup-per-segment sort: it must then bound every segment */
+    if (!n_out || !seg_count || n < 0 || cap < 0 || (n > 0 && !in) || (cap > 0 && !out) || !(leaf > 0.0f) || max_seg_len < 0 ||
+        !ll_debug_offsets_ok(seg_off, nseg, n, max_seg_len <= 8192 ? max_seg_len : 0)) {
+        ctx->err = "bad ll_debug_voxel_segments arguments"; return LL_ERR_ARG;
+    }
+    *n_out = 0;
+    hipStream_t st = ctx->stream;
+    const int na = n > 0 ? n : 1, ncopy = n < cap ? n : cap;
+    void *work = nullptr; float4 *d_in = nullptr, *d_out = nullptr; int *d_n = nullptr;
+    hipError_t e = hipMalloc(&work, ll_vox_work_bytes(na, nseg));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_in, (size_t)na * 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_out, (size_t)na * 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_n, sizeof(int));
+    LLVoxWork W;
+    int vrc = 0, m = 0;
+    if (e == hipSuccess) {
+        ll_vox_work_carve(work, na, nseg, &W);
+        if (n > 0) e = hipMemcpyAsync(d_in, in, (size_t)n * 16, hipMemcpyHostToDevice, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(W.seg_off, seg_off, (size_t)(nseg + 1) * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        vrc = ll_voxel_grid_segments(d_in, n, nseg, leaf, W, d_out, d_n, st, max_seg_len);
+        e = hipGetLastError();
+    }
+    /* the whole input's worth of output slots (what fits into out): the count is known only after the one synchronisation */
+    if (e == hipSuccess) e = hipMemcpyAsync(&m, d_n, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(seg_count, W.seg_count, (size_t)nseg * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && ncopy > 0) e = hipMemcpyAsync(out, d_out, (size_t)ncopy * 16, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipGetLastError();
+    (void)hipFree(d_n); (void)hipFree(d_out); (void)hipFree(d_in); (void)hipFree(work);
+    if (e != hipSuccess) { ctx->err = std::string("ll_debug_voxel_segments: ") + hipGetErrorString(e); return LL_ERR_HIP; }
+    if (vrc) { ctx->err = "ll_debug_voxel_segments: read-back failed"; return LL_ERR_HIP; }
+    *n_out = m;
+    if (m > cap) { ctx->err = "voxel grid output capacity too small"; return LL_ERR_CAPACITY; }
+    return LL_OK;
+}
+
 extern "C" int ll_debug_counters(ll_ctx *ctx, unsigned long long *out16, int reset)
 {
     if (!ctx || !out16) return LL_ERR_ARG;
