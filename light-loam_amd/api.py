@@ -380,6 +380,16 @@ class Context:
         self._ck(self.lib.ll_download_vote(self.h, slot, _ptr(cnt), _ptr(sel), _ptr(w), len(cnt)))
         return cnt[:n], sel[:n].astype(bool), w[:n]
 
+    def vote_points(self, src, tgt, corner_case=False):
+        """graph_based_correspondence_vote_simple on caller-supplied correspondences (ll_vote_host): src / tgt (n, 4) float32,
+        5 regions for the corner case, else 10 -> (count int32[n], selected bool[n], weight float32[n])"""
+        s = np.ascontiguousarray(src, np.float32).reshape(-1, 4); t = np.ascontiguousarray(tgt, np.float32).reshape(-1, 4)
+        assert len(s) == len(t)
+        n = len(s)
+        cnt = np.zeros(max(n, 1), np.int32); sel = np.zeros(max(n, 1), np.uint8); w = np.zeros(max(n, 1), np.float32)
+        self._ck(self.lib.ll_vote_host(self.h, _ptr(s), _ptr(t), n, int(bool(corner_case)), _ptr(cnt), _ptr(sel), _ptr(w)))
+        return cnt[:n], sel[:n].astype(bool), w[:n]
+
     def normal_equations(self, first=0, count=1, pose=None):
         p = self._poses(pose, count)
         self._ck(self.lib.ll_normal_equations_batch(self.h, first, count, _ptr(p)))
