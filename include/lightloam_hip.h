@@ -224,6 +224,40 @@ int ll_lm_solve_batch(ll_ctx *ctx, int first, int count, const ll_lm_options *op
  * The slots must have been extracted (ll_extract_batch).                                                             */
 int ll_odometry_frames(ll_ctx *ctx, int first, int count, const double *host_pose0, int n_outer, int first_frame_index,
                        const ll_lm_options *opt, double *host_poses_out);
+/* ---------------------------------------------------------------- TransformToEnd: the other half of motion compensation
+ * With ll_params.distortion = 1 every point carries its interpolation ratio s, and TransformToStart slerps per point.  The reference's
+ * TransformToEnd (laserOdometry.cpp:99-114) re-projects the clouds of the frame just solved to the END of its sweep -- the start of the
+ * next one -- so that they can serve as the next frame's target and as laserMapping's input (:860-918); the reference calls it under
+ * `if (0)` (:861) because KITTI arrives deskewed.  Per point p, with q = q_last_curr, t = t_last_curr as the solve left them (never
+ * normalised):  un = Identity.slerp(s, q) * p + s * t  in f64, stored to f32 (the bits the association computes);
+ * end = q.inverse() * (un - t)  in f64, stored to f32;  intensity = int(intensity).  Everything is rewritten IN PLACE:
+ *   mode 1   the slot's less-sharp and less-flat clouds (what ll_set_target_from_slot, ll_associate_batch, the mapping frames and
+ *            ll_download_features read afterwards);
+ *   mode 2   also laserCloud (what ll_download_cloud and ll_drives_registered read).
+ * A slot whose extraction was refused (status != 0) is left alone and is no error.
+ *
+ * ll_set_deskew switches it on for the frame loops (0 = off, the default: nothing the library computes changes by a bit).  With a
+ * mode set, ll_odometry_frames deskews slot k with its solved pose after frame k's last outer iteration and rebuilds the slot's
+ * search grids before frame k + 1 is associated; ll_odometry_sequences does the same per row for the row's running sequences (one
+ * deskew and one grid launch more per row; a sequence that sits out keeps every byte of its clouds); ll_drives inherits it: the mapping
+ * or localising frame of a step reads the deskewed clouds, and a lane's LL_DRIVE_START frame, which has no solve, is not deskewed.
+ * The loops deskew only slots they solve -- the first target is whatever the caller set -- on the context's stream, without a host
+ * synchronisation.  A non-finite solved pose makes non-finite clouds.  Checkpoints do not record the mode (as with
+ * ll_drives_set_localize: set it again before ll_drives_restore); a saved carry holds the clouds as they are, and a restore into a
+ * context whose mode is on marks the slots it fills as deskewed.  ll_hot_path_batch, ll_hot_path_chain and ll_associate_batch are NOT
+ * affected: their pairs are independent by construction (every slot is solved from its own guess against a target nobody re-projects).
+ * LL_ERR_ARG: mode outside 0..2; LL_ERR_STATE: the context has distortion = 0 -- there s = 1 and TransformToEnd is the identity up to
+ * rounding: refused, not rounded.
+ *
+ * ll_deskew_slots is the stage on its own: slots [first, first + count) with host_pose7 ([count][7]; NULL = the poses the slots hold on
+ * the device), mode 1 or 2, then their search grids anew.  No host synchronisation beyond the pose upload's.
+ *
+ * A slot is deskewed at most ONCE per extraction / upload -- a second application would transform again.  ll_extract_batch, the hot
+ * path, ll_upload_scan* and ll_upload_features clear the mark of the slots they fill; ll_deskew_slots, and a loop asked to solve
+ * such a slot while a mode is set, return LL_ERR_STATE before anything is enqueued, and ll_last_error names the slot.             */
+int ll_set_deskew(ll_ctx *ctx, int mode);   /* 0 off (default); 1: less-sharp + less-flat; 2: also laserCloud */
+int ll_deskew_slots(ll_ctx *ctx, int first, int count, const double *host_pose7 /* [count][7], NULL: the slots' device poses */, int mode /* 1 or 2 */);
+
 /* The same frame loop for S independent sequences side by side: frame k of every sequence advances in one set of launches.
  * The frames live in a ring of rows, one row = S contiguous slots; frame row r of sequence q sits in slot
  *     base + (r mod ring_rows) * S + q,

@@ -71,6 +71,13 @@ public:
     ll_ctx *get() const { return ctx_; }
     const ll_params &params() const { return p_; }
     void check(int rc) const { if (rc != LL_OK) throw Error(rc, ll_last_error(ctx_)); }
+    /* TransformToEnd (laserOdometry.cpp:99-114; the reference's call sits under `if (0)`, :861) in the frame loops -- odometry_frames,
+     * Drives --: 0 off (default), 1 the solved frames' less-sharp / less-flat clouds are re-projected to the end of their sweep in place,
+     * 2 also laserCloud.  Needs distortion = 1 (Error LL_ERR_STATE otherwise). */
+    void set_deskew(int mode) { check(ll_set_deskew(ctx_, mode)); }
+    /* the stage on its own: slots [first, first + count) with pose7 ([count][7]; nullptr = the poses the slots hold on the device), then
+     * their search grids anew.  A slot takes it once per extraction / upload (Error LL_ERR_STATE for a second one). */
+    void deskew_slots(int first, int count, const double *pose7 = nullptr, int mode = 1) { check(ll_deskew_slots(ctx_, first, count, pose7, mode)); }
 private:
     ll_params p_;
     ll_ctx *ctx_ = nullptr;

@@ -44,6 +44,7 @@ EXPORTS = [
     "ll_cubemaps_merge", "ll_cubemaps_merge_timing",
     "ll_cubemaps_align", "ll_cubemaps_align_timing",
     "ll_debug_sort_pairs", "ll_debug_exscan", "ll_debug_voxel_segments",
+    "ll_set_deskew", "ll_deskew_slots",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -143,6 +144,8 @@ def load_library():
         _lib.ll_cubemaps_merge_timing.argtypes = [C.c_void_p] * 3
         _lib.ll_cubemaps_align.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ll_cubemaps_align_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_set_deskew.argtypes = [C.c_void_p, C.c_int]
+        _lib.ll_deskew_slots.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     return _lib
 
 
@@ -439,6 +442,17 @@ class Context:
         self._ck(self.lib.ll_odometry_sequences(self.h, C.byref(L), int(row0), int(n_rows), _ptr(rows), _ptr(fidx), _ptr(p0), int(n_outer),
                                                 None if opt is None else C.byref(opt), _ptr(out)))
         return out
+
+    def set_deskew(self, mode):
+        """TransformToEnd in the frame loops (ll_set_deskew): 0 off, 1 the solved slots' less-sharp / less-flat clouds are re-projected
+        to the end of their sweep in place, 2 also laserCloud.  Needs Params.distortion = 1 (LL_ERR_STATE otherwise)."""
+        self._ck(self.lib.ll_set_deskew(self.h, int(mode)))
+
+    def deskew_slots(self, first, count, poses=None, mode=1):
+        """the stage on its own (ll_deskew_slots): slots [first, first + count) with `poses` ((count, 7) or one pose; None = the poses
+        the slots hold on the device), then their search grids anew.  A slot takes it once per extraction / upload."""
+        p = self._poses(poses, count)
+        self._ck(self.lib.ll_deskew_slots(self.h, int(first), int(count), _ptr(p), int(mode)))
 
     def hot_path(self, first=0, count=1, pose=None, vote=True):
         p = self._poses(pose, count)

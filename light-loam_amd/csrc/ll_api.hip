@@ -225,6 +225,7 @@ extern "C" int ll_create(int device, const ll_params *p, ll_ctx **out)
     ctx->h_stage_pts = NP;
     if (hipHostMalloc((void **)&ctx->h_stage, (size_t)NP * sizeof(float4), hipHostMallocDefault) != hipSuccess) { g_create_err = "hipHostMalloc failed"; ll_destroy(ctx); return LL_ERR_HIP; }
     ctx->n_in_host.assign(B, 0);
+    ctx->deskewed.assign(B, 0);
     if (const char *e = std::getenv("LIGHTLOAM_TWO_STREAM")) ctx->two_stream = (std::atoi(e) != 0) ? 1 : 0;
     ctx->ts_pieces = LL_TWO_STREAM_PIECES;
     if (const char *e = std::getenv("LIGHTLOAM_TS_PIECES")) { const int v = std::atoi(e); if (v >= 2 && v <= LL_TWO_STREAM_MAX_PIECES) ctx->ts_pieces = v; }   /* A/B runs */
@@ -273,6 +274,7 @@ extern "C" int ll_upload_scan(ll_ctx *ctx, int slot, const float *xyz, int strid
         LL_HIP(hipMemcpyAsync(dst, ctx->h_stage, (size_t)n * rs * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     ctx->n_in_host[slot] = n;
+    ctx->deskewed[slot] = 0;
     LL_HIP(hipMemcpyAsync(const_cast<int *>(V.n_in) + slot, &ctx->n_in_host[slot], sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     LL_HIP(hipStreamSynchronize(ctx->stream));
     return LL_OK;
@@ -327,6 +329,7 @@ extern "C" int ll_upload_scan_async(ll_ctx *ctx, int slot, const float *xyz4, in
     LLView &V = ctx->V;
     if (n > 0) LL_HIP(hipMemcpyAsync(const_cast<float4 *>(V.raw) + (size_t)slot * V.NP, xyz4, (size_t)n * V.raw_stride * 4, hipMemcpyHostToDevice, ctx->copy_stream));
     ctx->n_in_host[slot] = n;
+    ctx->deskewed[slot] = 0;
     enqueue_counts(ctx, slot, &n, 1);
     LL_HIP(hipGetLastError());
     return LL_OK;
@@ -355,6 +358,7 @@ extern "C" int ll_upload_scans_async_strided(ll_ctx *ctx, int first, int count, 
         nmax = n[i] > nmax ? n[i] : nmax;
         ctx->n_in_host[first + i] = n[i];
     }
+    std::fill(ctx->deskewed.begin() + first, ctx->deskewed.begin() + first + count, 0);
     LLView &V = ctx->V;
     if (nmax > 0)
         LL_HIP(hipMemcpy2DAsync(const_cast<float4 *>(V.raw) + (size_t)first * V.NP, (size_t)V.NP * 16, base, stride_bytes, (size_t)nmax * pt, (size_t)count,
@@ -399,6 +403,7 @@ extern "C" int ll_synchronize_copy(ll_ctx *ctx)
 extern "C" int ll_extract_batch(ll_ctx *ctx, int first, int count)
 {
     int rc = check_range(ctx, first, count); if (rc) return rc;
+    std::fill(ctx->deskewed.begin() + first, ctx->deskewed.begin() + first + count, 0);      /* fresh clouds: not deskewed */
     ll_launch_organize(ctx->V, first, count, ctx->stream, &ctx->prof);
     ll_launch_features(ctx->V, first, count, ctx->feat_lds, ctx->stream, &ctx->prof);
     ll_launch_build_grid(ctx->V, first, count, 0, ctx->stream, &ctx->prof);
@@ -460,6 +465,7 @@ extern "C" int ll_upload_features(ll_ctx *ctx, int slot, const ll_point *sharp, 
     LL_HIP(hipGetLastError());
     LL_HIP(hipStreamSynchronize(ctx->stream));              /* the host arrays and h may go away */
     if ((size_t)slot < ctx->n_in_host.size()) ctx->n_in_host[slot] = 0;
+    ctx->deskewed[slot] = 0;
     return LL_OK;
 }
 
@@ -599,6 +605,52 @@ extern "C" int ll_lm_solve_batch(ll_ctx *ctx, int first, int count, const ll_lm_
     return LL_OK;
 }
 
+/* ---- TransformToEnd (ll_deskew.hip): the stage on its own, and the switch of the frame loops ----
+ * A slot is deskewed at most once per extraction / upload: deskewed[] is set when a deskew is enqueued and cleared by whatever fills the
+ * slot anew.  Asked for a flagged slot, ll_deskew_slots and the loops refuse (LL_ERR_STATE, the slot named) before enqueuing anything. */
+static int deskew_refuse_flagged(ll_ctx *ctx, int first, int count)
+{
+    for (int s = first; s < first + count; ++s)
+        if (ctx->deskewed[s]) { ctx->err = "slot " + std::to_string(s) + " is already deskewed: a second TransformToEnd would transform it again (extract or upload it anew)"; return LL_ERR_STATE; }
+    return LL_OK;
+}
+/* the deskew of slots [first, first + count) (rows: those with row_mode bit 0; the caller flags exactly the slots that run) and the
+ * search grids of the range over the rewritten clouds -- k_build_grid is idempotent on a slot it has seen: counts, lf_pre, header stay */
+static int enqueue_deskew(ll_ctx *ctx, int first, int count, const double *pose, int pose_base, int mode, int rows)
+{
+    if (ll_launch_deskew(ctx->V, first, count, pose, pose_base, mode, rows, ctx->stream)) { ctx->err = "deskew: the slot range needs more workgroups than one launch holds"; return LL_ERR_CAPACITY; }
+    ll_launch_build_grid(ctx->V, first, count, 0, ctx->stream, nullptr);
+    if (!rows) std::fill(ctx->deskewed.begin() + first, ctx->deskewed.begin() + first + count, 1);
+    return LL_OK;
+}
+
+extern "C" int ll_set_deskew(ll_ctx *ctx, int mode)
+{
+    if (!ctx) return LL_ERR_ARG;
+    if (mode < 0 || mode > 2) { ctx->err = "deskew mode must be 0 (off), 1 (less-sharp + less-flat) or 2 (also laserCloud)"; return LL_ERR_ARG; }
+    if (!ctx->p.distortion) { ctx->err = "deskew needs ll_params.distortion = 1: with s = 1 TransformToEnd is the identity up to rounding"; return LL_ERR_STATE; }
+    ctx->deskew_mode = mode;
+    return LL_OK;
+}
+
+extern "C" int ll_deskew_slots(ll_ctx *ctx, int first, int count, const double *host_pose7, int mode)
+{
+    int rc = check_range(ctx, first, count); if (rc) return rc;
+    if (mode != 1 && mode != 2) { ctx->err = "deskew mode must be 1 (less-sharp + less-flat) or 2 (also laserCloud)"; return LL_ERR_ARG; }
+    if (!ctx->p.distortion) { ctx->err = "deskew needs ll_params.distortion = 1: with s = 1 TransformToEnd is the identity up to rounding"; return LL_ERR_STATE; }
+    rc = deskew_refuse_flagged(ctx, first, count); if (rc) return rc;
+    const double *pose = ctx->V.pose; int pose_base = 0;
+    if (host_pose7) {
+        if (!ctx->d_deskew_pose && !dev_alloc(ctx, ctx->d_deskew_pose, (size_t)ctx->p.batch * 7, false)) { ctx->err = "hipMalloc failed (deskew poses)"; return LL_ERR_HIP; }
+        LL_HIP(hipMemcpyAsync(ctx->d_deskew_pose, host_pose7, (size_t)count * 7 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        LL_HIP(hipStreamSynchronize(ctx->stream));    /* host buffer may be reused by the caller */
+        pose = ctx->d_deskew_pose; pose_base = first;
+    }
+    rc = enqueue_deskew(ctx, first, count, pose, pose_base, mode, 0); if (rc) return rc;
+    LL_HIP(hipGetLastError());
+    return LL_OK;
+}
+
 struct LLPose7 { double v[7]; };
 __global__ void k_set_pose7(double *dst, LLPose7 p) { if (threadIdx.x < 7) dst[threadIdx.x] = p.v[threadIdx.x]; }
 
@@ -607,6 +659,8 @@ extern "C" int ll_odometry_frames(ll_ctx *ctx, int first, int count, const doubl
 {
     int rc = check_range(ctx, first, count); if (rc) return rc;
     if (n_outer < 1 || n_outer > 16) { ctx->err = "n_outer out of range"; return LL_ERR_ARG; }
+    const int dmode = ctx->deskew_mode;
+    if (dmode) { rc = deskew_refuse_flagged(ctx, first, count); if (rc) return rc; }          /* before anything is enqueued */
     const LLLmOpt o = ll_to_dev_opt(opt);
     LLPose7 p0 = {{0, 0, 0, 1, 0, 0, 0}};
     if (host_pose0) std::memcpy(p0.v, host_pose0, sizeof(p0.v));
@@ -621,6 +675,7 @@ extern "C" int ll_odometry_frames(ll_ctx *ctx, int first, int count, const doubl
             ll_launch_vote(ctx->V, k, 1, vote, ctx->stream, &ctx->prof);
             enqueue_lm(ctx, k, 1, o);
         }
+        if (dmode) { rc = enqueue_deskew(ctx, k, 1, ctx->V.pose, 0, dmode, 0); if (rc) return rc; }   /* TransformToEnd (:860-896): slot k is frame k + 1's target */
     }
     LL_HIP(hipGetLastError());
     if (host_poses_out) {
@@ -675,6 +730,11 @@ extern "C" int ll_odometry_sequences(ll_ctx *ctx, const ll_seq_layout *L, int ro
     if (n_outer < 1 || n_outer > 16) { ctx->err = "n_outer out of range"; return LL_ERR_ARG; }
     const LLLmOpt o = ll_to_dev_opt(opt);
     if (o.max_num_iterations < 0 || o.max_num_iterations > 64) { ctx->err = "max_num_iterations out of range"; return LL_ERR_ARG; }
+    const int dmode = ctx->deskew_mode;
+    if (dmode)                                                               /* before anything is enqueued: no slot that would run is deskewed already */
+        for (int ri = 0; ri < max_rows; ++ri)
+            for (int q = 0; q < S; ++q)
+                if (ri < (seq_rows ? seq_rows[q] : n_rows)) { rc = deskew_refuse_flagged(ctx, base + ll_ring_row((long long)row0 + ri, RR) * S + q, 1); if (rc) return rc; }
     LLView &V = ctx->V;
     if (!V.row_pred) {
         void *a = nullptr, *b = nullptr;
@@ -704,6 +764,14 @@ extern "C" int ll_odometry_sequences(ll_ctx *ctx, const ll_seq_layout *L, int ro
             for (int outer = 0; outer < n_outer; ++outer) {                  /* :439 */
                 ll_launch_associate_rows(V, first, S, ctx->stream, &ctx->prof);
                 ll_launch_vote_lm_rows(V, first, S, outer == n_outer - 1 ? succ : -1, o, ctx->stream, &ctx->prof);
+            }
+            if (dmode) {
+                /* TransformToEnd for the row's running sequences: one deskew launch (row_mode picks the slots) and one grid launch over the span
+                 * from the first to the last of them -- a sequence in between that sits out has its grids rebuilt from unchanged clouds */
+                int qa = S, qb = -1;
+                for (int q = 0; q < S; ++q)
+                    if (ri < (seq_rows ? seq_rows[q] : n_rows)) { qa = std::min(qa, q); qb = q; ctx->deskewed[first + q] = 1; }
+                if (qb >= qa) { rc = enqueue_deskew(ctx, first + qa, qb - qa + 1, V.pose, 0, dmode, 1); if (rc) return rc; }
             }
         }
         LL_HIP(hipGetLastError());
@@ -786,6 +854,7 @@ static int hot_path(ll_ctx *ctx, int first, int count, const double *host_pose_g
     if (!host_pose_guess)
         LL_HIP(hipMemcpyAsync(ctx->V.pose + (size_t)first * 7, ctx->V.pose_guess + (size_t)first * 7, (size_t)count * 7 * sizeof(double),
                               hipMemcpyDeviceToDevice, ctx->stream));
+    std::fill(ctx->deskewed.begin() + first, ctx->deskewed.begin() + first + count, 0);      /* extracted anew below */
     if (!chain) ctx->V.carry_slot = first;                      /* chain: the carry belongs to the slot that opened the batch */
     /* chunks keep a chunk's intermediates (ori/ring, laserCloud, feature slots) inside the Infinity Cache between
      * the producing and the consuming kernel; the target of a chunk's first slot is the previous chunk's last slot */

@@ -379,6 +379,9 @@ void ll_launch_associate_rows(const LLView &V, int first, int count, hipStream_t
 /* vote + LM solve per active slot of a row in one launch; succ_first >= 0: also leave the solved pose in slot succ_first + i when that
  * slot is active (the warm start of the next row) */
 void ll_launch_vote_lm_rows(const LLView &V, int first, int count, int succ_first, const LLLmOpt &o, hipStream_t st, LLProfiler *prof);
+/* TransformToEnd in place on the less-sharp / less-flat (mode 2: and full-resolution) clouds of slots [first, first + count) (ll_deskew.hip); the pose of
+ * slot s is pose[(s - pose_base) * 7 ..]; rows != 0: only the slots whose row_mode bit 0 is set.  0, or -1: too many workgroups for one launch */
+int ll_launch_deskew(const LLView &V, int first, int count, const double *pose, int pose_base, int mode, int rows, hipStream_t st);
 void ll_launch_vote_points(const float4 *src, const float4 *tgt, int n, int regions, int *vc, uint8_t *vs, float *vw, hipStream_t st);
 void ll_launch_normal_equations(const LLView &V, int first, int count, int do_step, hipStream_t st, LLProfiler *prof);
 void ll_launch_gn_step(const LLView &V, int first, int count, hipStream_t st, LLProfiler *prof);

@@ -724,6 +724,7 @@ extern "C" int ll_drives_restore(ll_drives *d, const int *into, const void *blob
         for (int k = 0; k < 4; ++k) d->feat[q].n[k] = R.n_feat[k];
         d->feat[q].strided = 0;
         if ((size_t)(prev + q) < ctx->n_in_host.size()) ctx->n_in_host[prev + q] = 0;
+        ctx->deskewed[prev + q] = ctx->deskew_mode != 0;                                 /* a saved carry holds the clouds as they were, and the slot is only ever a target */
     }
     return LL_OK;
 }

@@ -35,6 +35,11 @@ struct ll_ctx {
     double *d_tmp_pose = nullptr, *d_rows = nullptr;
     size_t rows_cap = 0;
     std::vector<int> n_in_host;
+    /* TransformToEnd (ll_set_deskew / ll_deskew_slots): the switch of the frame loops, and per slot whether a deskew has been enqueued since
+     * the slot was last filled (ll_extract_batch, the hot path, ll_upload_scan*, ll_upload_features clear it): a second one would transform again */
+    int deskew_mode = 0;
+    std::vector<char> deskewed;
+    double *d_deskew_pose = nullptr;    /* [batch][7] the host poses of an ll_deskew_slots call (allocated by the first such call) */
     hipEvent_t ev[16];
     bool ev_ok = false;
     /* caller-supplied residual blocks (ll_factor_blocks_set / _evaluate) */

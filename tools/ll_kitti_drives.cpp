@@ -5,7 +5,7 @@
 // in the reference's trajectory-file format (laserMapping.cpp:2284-2325), byte for byte what ll_odometry_kitti writes for it.
 //
 //   ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose "qx qy qz qw x y z"]]
-//                   <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...
+//                   [--distortion {0,1}] [--deskew {0,1,2}] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...
 //
 // --checkpoint FILE --checkpoint-at N: after step N (N >= 1 steps done) the lanes that ran on it are saved (ll_drives_save) to FILE
 // together with the tool's own queue state -- per lane the drive it runs, its next frame and the first pose of its trajectory
@@ -25,6 +25,11 @@
 // w, then x y z; identity when absent).  The trajectories are written as ever -- poses in the map's frame -- and beside each,
 // <result_dir>/<i>_fit.txt with one line per frame: ran n_edge n_plane cost sq_edge sq_plane (ll_localize_fit), the answer to
 // "am I still on the map?".  Not together with --checkpoint, --resume or --maps.
+//
+// --distortion 1: the reference's DISTORTION 1 path (ll_params.distortion) for a lidar whose scans are NOT motion-compensated (KITTI's
+// are: leave it at 0).  --deskew 1 | 2 (needs --distortion 1, refused otherwise): TransformToEnd after every solved frame
+// (ll_set_deskew) -- 1: the feature clouds the next frame and the mapper read, 2: also the full-resolution cloud.  A run resumed
+// from a checkpoint takes the same two options again: the blob does not record the deskew mode.
 //
 // Build:  g++ -O2 -std=c++14 -I include tools/ll_kitti_drives.cpp -L light-loam_amd -llightloam_hip -o ll_kitti_drives
 #include <algorithm>
@@ -90,6 +95,7 @@ int main(int argc, char **argv)
     bool maps = false;
     std::string ck_path, resume_path, loc_path, start_text;
     long long ck_at = -1;
+    int distortion = 0, deskew = 0;
     while (argc > 1 && std::strncmp(argv[1], "--", 2) == 0) {
         const std::string opt = argv[1];
         if (opt == "--maps") { maps = true; --argc; ++argv; continue; }
@@ -99,11 +105,15 @@ int main(int argc, char **argv)
         else if (opt == "--resume") resume_path = argv[2];
         else if (opt == "--localize-in") loc_path = argv[2];
         else if (opt == "--start-pose") start_text = argv[2];
+        else if (opt == "--distortion") distortion = std::atoi(argv[2]);
+        else if (opt == "--deskew") deskew = std::atoi(argv[2]);
         else { std::cerr << "unknown option " << opt << "\n"; return 2; }
         argc -= 2; argv += 2;
     }
     if (ck_path.empty() != (ck_at < 1)) { std::cerr << "--checkpoint FILE and --checkpoint-at N (>= 1) go together\n"; return 2; }
     if (!loc_path.empty() && (maps || !ck_path.empty() || !resume_path.empty())) { std::cerr << "--localize-in does not go with --maps, --checkpoint or --resume\n"; return 2; }
+    if (distortion < 0 || distortion > 1 || deskew < 0 || deskew > 2) { std::cerr << "--distortion takes 0 or 1, --deskew 0, 1 or 2\n"; return 2; }
+    if (deskew != 0 && distortion == 0) { std::cerr << "--deskew " << deskew << " needs --distortion 1: without per-point interpolation ratios there is nothing to compensate\n"; return 2; }
     double start7[7] = {0, 0, 0, 1, 0, 0, 0};
     if (!start_text.empty()) {
         std::istringstream in(start_text);
@@ -111,7 +121,7 @@ int main(int argc, char **argv)
         while (got < 7 && (in >> start7[got])) ++got;
         if (got != 7 || loc_path.empty()) { std::cerr << "--start-pose takes seven numbers in one argument and needs --localize-in\n"; return 2; }
     }
-    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose \"qx qy qz qw x y z\"]] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
+    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose \"qx qy qz qw x y z\"]] [--distortion {0,1}] [--deskew {0,1,2}] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
     const std::string result_dir = argv[1];
     const int scan_line = std::atoi(argv[2]);
     const double tx0 = std::atof(argv[3]);
@@ -124,7 +134,8 @@ int main(int argc, char **argv)
     }
     try {
         using namespace lightloam;
-        Context ctx(scan_line, 2 * lanes, 0, -1.0, -24.9f, 2.0f, 0, max_ring_points, 3);   /* as ll_odometry_kitti: x, y, z resident */
+        Context ctx(scan_line, 2 * lanes, 0, -1.0, -24.9f, 2.0f, distortion, max_ring_points, 3);   /* as ll_odometry_kitti: x, y, z resident */
+        if (deskew != 0) ctx.set_deskew(deskew);                                           /* before any restore: it marks the slots it fills */
         Drives d(ctx, lanes, scan_line * 120 + 64, 400000, 1 << 22);                      /* ll_odometry_kitti's mapping capacities */
         const double p0[7] = {0, 0, 0, 1, tx0, 0, 0};
         std::vector<double> pose0((size_t)7 * lanes);
