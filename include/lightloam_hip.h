@@ -364,6 +364,33 @@ int ll_map_solve_dev(ll_map *m, const ll_lm_options *opt);
  * all blocks.  ll_map_solve / ll_map_optimize refuse while a row shard is set.                                        */
 int ll_map_set_row_shard(ll_map *m, int rank, int world);
 
+/* ---------------------------------------------------------------- the graph-based correspondence vote in the mapping stage
+ * Light-LOAM's vote, which the library has had in the odometry (a8, ll_vote_batch), on laserMapping's plane blocks.  The reference's
+ * mapping stage is written for it -- laserMapping.cpp:1843-1850, :1993-2003, :2026 collect a Corre_Match per plane block that passed
+ * the fit (src = the raw stack point, tgt = the float centroid of its five neighbours: float sums in K-NN order, :1960-1962, each
+ * / 5 in float, :1969-1971), :836-1030 is mapping's own graph_based_correspondence_vote_simple, :2057-2072 feed the selected blocks
+ * to the problem -- but the call is commented out.  It is opt-in here, off by default, and off changes nothing by a bit.
+ *   The vote (:836-1030): 20 regions of n / 20 correspondences in stack order, the last one takes the remainder (n < 20: everything
+ *   is in the last); every unordered pair of a region is incompatible, and counts for both, when
+ *   (double)expf(-gap * gap) < 0.95 with gap = | |src_i - src_j| - |tgt_i - tgt_j| | on f32 square roots (0.95 is a double literal;
+ *   bit-exact thresholds in csrc/ll_exact_math.h); an entry of a region of m is selected iff (float)count < 0.75f * (float)m
+ *   (strict; corner_case = true at :2059).  The weight is 1: LidarPlaneNormFactor takes none.  Edge blocks are never voted.
+ * Two decisions: (1) with the vote on, the plane blocks of the solve are the selected ones INSTEAD of all of them -- the intent of
+ * the commented gate at :2027-2032; the literal text would add the selected blocks a second time on top of :2033.  (2) The selected
+ * blocks keep stack order, as the odometry vote keeps correspondence order; the reference's order only permutes residual blocks.
+ * What is not shown: no accuracy claim is made -- the synthetic drives have no outlier structure that would show one.
+ * ll_map_set_vote(m, 1): ll_map_associate (at a host pose or, with NULL, at the device pose) and ll_map_optimize vote after the
+ * compaction -- two launches more per association, no synchronisation; ll_map_get_counts, ll_map_download_planes and everything that
+ * reads the blocks (normal equations, rows, solves) then see the selected blocks.  LL_ERR_STATE together with a row shard or a tile
+ * shard (those modes stay un-voted; they in turn refuse while the vote is on); LL_ERR_ARG when a region of max_scan_surf / 20 + 19
+ * candidates at 28 B each does not fit the 160 KiB of LDS.
+ * ll_map_download_vote: the candidates of the last voted association, in stack order: stack index, count of incompatible pairs,
+ * selected flag, tgt (3 floats each); any of the four may be NULL; *n = their number (cap < *n: LL_ERR_CAPACITY).
+ * ll_map_vote_host: the same vote on caller-supplied correspondences through the same kernel (ll_vote_host's counterpart).          */
+int ll_map_set_vote(ll_map *m, int on);
+int ll_map_download_vote(ll_map *m, int *src, int *count, uint8_t *selected, float *tgt3, int cap, int *n);
+int ll_map_vote_host(ll_ctx *ctx, const ll_point *src, const ll_point *tgt, int n, int *count, uint8_t *selected);
+
 /* pcl::VoxelGrid<PointType>::filter on a whole cloud of any size (downSizeFilterCorner / downSizeFilterSurf,
  * laserMapping.cpp:1813-1821, :2151-2165): centroids (x, y, z, intensity) per voxel, in voxel-index order.       */
 int ll_voxel_grid(ll_ctx *ctx, const ll_point *host_in, int n, float leaf_size, ll_point *host_out, int cap, int *n_out);
@@ -412,6 +439,7 @@ int ll_cubemap_process_slot(ll_cubemap *cm, double *pose_w7, int slot, int *ran)
  * The union of the ranks' cubes is the unsplit cube map, cube by cube and bit for bit.                               */
 int ll_cubemap_set_shard(ll_cubemap *cm, int rank, int world);
 ll_map *ll_cubemap_map(ll_cubemap *cm);                       /* the inner ll_map (owned by the cube map) */
+int ll_cubemap_set_vote(ll_cubemap *cm, int on);               /* ll_map_set_vote of the inner map: ll_cubemap_optimize / _process* then vote */
 /* cen3: laserCloudCenWidth / Height / Depth; counts4: corner / surf from map, corner / surf stack */
 int ll_cubemap_info(ll_cubemap *cm, int *cen3, int *counts4);
 /* which: 0 laserCloudCornerFromMap, 1 laserCloudSurfFromMap, 2 laserCloudCornerStack, 3 laserCloudSurfStack */
@@ -445,6 +473,10 @@ int  ll_cubemaps_info(ll_cubemaps *cms, int q, int *cen3, int *counts4);
 int  ll_cubemaps_download_cloud(ll_cubemaps *cms, int q, int which, ll_point *out, int cap, int *n);
 int  ll_cubemaps_download_cube(ll_cubemaps *cms, int q, int surf, int cube_index, ll_point *out, int cap, int *n);
 int  ll_cubemaps_stats(const ll_cubemaps *cms, long long *syncs, long long *frames);
+/* The mapping vote (ll_map_set_vote) per sequence: on[q] = 1 votes sequence q's plane blocks in ll_cubemaps_process* from now on, until
+ * changed -- two launches more per outer iteration of a frame in which any sequence votes, no synchronisation more.
+ * ll_cubemaps_localize_slots never votes: its fit record keeps its meaning.                                          */
+int  ll_cubemaps_set_vote(ll_cubemaps *cms, const int *on /* [n_seq] */);
 /* sequence q back to what ll_cubemaps_create gave it (centre, counts, pool cursors, pair tables); the others are untouched */
 int  ll_cubemaps_reset(ll_cubemaps *cms, int q);
 
@@ -593,6 +625,11 @@ int  ll_drives_step(ll_drives *d, const int *cmd, const double *pose0, double *o
 int  ll_drives_registered(ll_drives *d, int lane, ll_point *out, int cap, int *n);   /* the last step's cloud of that lane (n = 0: it did not run) */
 int  ll_drives_stats(const ll_drives *d, long long *syncs, long long *frames);
 ll_cubemaps *ll_drives_cubemaps(ll_drives *d);    /* borrowed: info / cloud / cube of each lane's map */
+/* The mapping vote (ll_map_set_vote) in the lanes that map: a lane votes in the frames whose per-lane frame index (0 at START) is
+ * > from_frame -- the reference's gate is 20 (:2057) -- negative = off, the default.  Localising lanes never vote.  The setting is not
+ * part of a checkpoint (the blob format is unchanged): set it again after ll_drives_restore.  While it is >= 0 every step sets the
+ * lanes' switches itself; with it off they are left as ll_cubemaps_set_vote on ll_drives_cubemaps(d) put them.                     */
+int ll_drives_set_map_vote(ll_drives *d, int from_frame);
 
 /* ---------------------------------------------------------------- lane checkpoints
  * A lane's state between two steps is its cube map (ll_cubemaps_layout + the LL_MAP_ALL cloud), its world-odometry and

@@ -141,6 +141,20 @@ inline void graph_based_correspondence_vote_simple(Context &c, std::vector<Corre
     }
 }
 
+/* ---- laserMapping.cpp:836-1030 (mapping's own vote: 20 regions, (double)expf(-gap^2) < 0.95, selected iff count < 0.75f * m) on
+ * caller-supplied correspondences (ll_map_vote_host): count / selected per correspondence, in the caller's order */
+inline void map_vote_host(Context &c, const std::vector<Corre_Match> &correspondences, std::vector<int> &count, std::vector<unsigned char> &selected)
+{
+    const int n = (int)correspondences.size();
+    std::vector<ll_point> src(n), tgt(n);
+    for (int i = 0; i < n; ++i) {
+        src[i] = {correspondences[i].src.x, correspondences[i].src.y, correspondences[i].src.z, correspondences[i].src.intensity};
+        tgt[i] = {correspondences[i].tgt.x, correspondences[i].tgt.y, correspondences[i].tgt.z, correspondences[i].tgt.intensity};
+    }
+    count.assign((size_t)n, 0); selected.assign((size_t)n, 0);
+    c.check(ll_map_vote_host(c.get(), src.data(), tgt.data(), n, count.data(), selected.data()));
+}
+
 /* ---- the per-frame body of laserOdometry.cpp:439-832, one outer iteration at a time.
  * slot_curr holds the current scan's features (after laserCloudHandler), the target is what set_last() stored
  * (laserCloudCornerLast / laserCloudSurfLast, :882-896).  q = para_q (x,y,z,w), t = para_t (:61-62). */
@@ -203,6 +217,22 @@ public:
         return ran != 0;
     }
     void counts(int &corner_num, int &surf_num) { check(ll_map_get_counts(m_, &corner_num, &surf_num)); }
+    /* the graph-based vote on the plane blocks (ll_map_set_vote; laserMapping.cpp:836-1030, :2057-2072): the data association then
+     * keeps the selected blocks only, in stack order.  Off by default */
+    void set_vote(bool on) { check(ll_map_set_vote(m_, on ? 1 : 0)); }
+    /* the candidates of the last voted association, in stack order: stack index, incompatible pairs, selected flag, tgt (3 floats each) */
+    void download_vote(std::vector<int> &src, std::vector<int> &count, std::vector<unsigned char> &selected, std::vector<float> &tgt3) {
+        int n = 0;
+        size_t cap = 1024;
+        for (;;) {
+            src.assign(cap, 0); count.assign(cap, 0); selected.assign(cap, 0); tgt3.assign(cap * 3, 0.0f);
+            const int rc = ll_map_download_vote(m_, src.data(), count.data(), selected.data(), tgt3.data(), (int)cap, &n);
+            if (rc == LL_ERR_CAPACITY && cap < ((size_t)1 << 24)) { cap *= 4; continue; }
+            check(rc);
+            break;
+        }
+        src.resize((size_t)n); count.resize((size_t)n); selected.resize((size_t)n); tgt3.resize((size_t)n * 3);
+    }
     ll_map *get() const { return m_; }
 private:
     void check(int rc) { if (rc != LL_OK) throw Error(rc, ll_map_last_error(m_)); }
@@ -255,6 +285,8 @@ public:
      * owns.  all_gather(send, recv, bytes): `bytes` from every rank into recv, rank-major (ncclAllGather / MPI_Allgather;
      * the buffers handed over are host memory).  Every rank passes the same scan and ends with the same parameters[]. */
     void set_shard(int rank, int world) { check(ll_cubemap_set_shard(cm_, rank, world)); world_ = world; }
+    /* vote the plane blocks in process / process_slot (ll_cubemap_set_vote); not together with a shard */
+    void set_vote(bool on) { check(ll_cubemap_set_vote(cm_, on ? 1 : 0)); }
     /* Failure discipline: nothing here throws between two collectives.  A rank whose library call failed remembers it, skips its
      * remaining library calls of the frame but still takes part in every all_gather of the sequence; the ranks exchange a status
      * word with the counts and once per outer iteration, so that ALL of them leave the frame at the same point -- each with an
@@ -409,6 +441,11 @@ public:
     void process_slots(const std::vector<int> &slots) {
         if ((int)slots.size() != S) throw Error(LL_ERR_ARG, "one slot per sequence");
         check(ll_cubemaps_process_slots(cms_, slots.data(), parameters.data(), ran.data()));
+    }
+    /* on[q] != 0: sequence q votes its plane blocks in process_slots / process from now on (ll_cubemaps_set_vote); localize_slots never votes */
+    void set_vote(const std::vector<int> &on) {
+        if ((int)on.size() != S) throw Error(LL_ERR_ARG, "one flag per sequence");
+        check(ll_cubemaps_set_vote(cms_, on.data()));
     }
     /* a READ-ONLY frame (ll_cubemaps_localize_slots): sequence q with slots[q] >= 0 localises that extracted slot against map
      * map_of[q] (an empty map_of: its own map) from the guess in its parameters row; no map changes, several sequences may read
@@ -645,6 +682,9 @@ public:
         if ((int)map_of.size() != S) throw Error(LL_ERR_ARG, "one map per lane");
         check(ll_drives_set_localize(d_, map_of.data(), start));
     }
+    /* the mapping lanes vote their plane blocks in frames whose per-lane index is > from_frame (the reference's gate: 20); negative: off.
+     * Not part of a checkpoint: set it again after restore */
+    void set_map_vote(int from_frame) { check(ll_drives_set_map_vote(d_, from_frame)); }
     /* the last step's fit records [S]: zeros for lanes that mapped, sat out or did not optimise */
     std::vector<ll_localize_fit> fit() {
         std::vector<ll_localize_fit> f((size_t)S);

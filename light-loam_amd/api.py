@@ -45,6 +45,7 @@ EXPORTS = [
     "ll_cubemaps_align", "ll_cubemaps_align_timing",
     "ll_debug_sort_pairs", "ll_debug_exscan", "ll_debug_voxel_segments",
     "ll_set_deskew", "ll_deskew_slots",
+    "ll_map_set_vote", "ll_map_download_vote", "ll_map_vote_host", "ll_cubemap_set_vote", "ll_cubemaps_set_vote", "ll_drives_set_map_vote",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -146,6 +147,12 @@ def load_library():
         _lib.ll_cubemaps_align_timing.argtypes = [C.c_void_p] * 3
         _lib.ll_set_deskew.argtypes = [C.c_void_p, C.c_int]
         _lib.ll_deskew_slots.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        _lib.ll_map_set_vote.argtypes = [C.c_void_p, C.c_int]
+        _lib.ll_map_download_vote.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_map_vote_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ll_cubemap_set_vote.argtypes = [C.c_void_p, C.c_int]
+        _lib.ll_cubemaps_set_vote.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.ll_drives_set_map_vote.argtypes = [C.c_void_p, C.c_int]
     return _lib
 
 
@@ -635,6 +642,26 @@ class Map:
         self._ck(self.lib.ll_map_residual_jacobian(self.h, _ptr(p), _ptr(r), _ptr(Jq), _ptr(Jt), len(r)))
         return r[:rows], Jq[:rows], Jt[:rows]
 
+    def set_vote(self, on):
+        """the graph-based correspondence vote on the plane blocks (ll_map_set_vote, laserMapping.cpp:836-1030): associate / optimize
+        then keep the selected blocks only, in stack order; off (the default) changes nothing by a bit"""
+        self._ck(self.lib.ll_map_set_vote(self.h, int(bool(on))))
+
+    def download_vote(self):
+        """the candidates of the last voted association, in stack order (ll_map_download_vote) ->
+        (stack index int32[n], count int32[n], selected bool[n], tgt float32[n, 3])"""
+        n = C.c_int(0)
+        cap = max(getattr(self, "_n_stack", (0, 0))[1], 1)
+        while True:
+            src = np.zeros(cap, np.int32); cnt = np.zeros(cap, np.int32); sel = np.zeros(cap, np.uint8); tgt = np.zeros((cap, 3), np.float32)
+            rc = self.lib.ll_map_download_vote(self.h, _ptr(src), _ptr(cnt), _ptr(sel), _ptr(tgt), cap, C.byref(n))
+            if rc == -4 and cap < (1 << 24):
+                cap *= 4
+                continue
+            self._ck(rc)
+            k = n.value
+            return src[:k], cnt[:k], sel[:k].astype(bool), tgt[:k]
+
     def optimize(self, pose_w, n_outer=2, opt=None):
         p = np.ascontiguousarray(pose_w, np.float64).copy()
         ran = C.c_int(0)
@@ -722,6 +749,17 @@ class Map:
         self._ck(self.lib.ll_map_solve_dev(self.h, None if opt is None else C.byref(opt)))
 
 
+def map_vote_host(ctx, src, tgt):
+    """laserMapping's graph_based_correspondence_vote_simple (:836-1030) on caller-supplied correspondences through k_map_vote
+    (ll_map_vote_host): src / tgt (n, 4) float32 -> (count int32[n], selected bool[n])"""
+    s = np.ascontiguousarray(src, np.float32).reshape(-1, 4); t = np.ascontiguousarray(tgt, np.float32).reshape(-1, 4)
+    assert len(s) == len(t)
+    n = len(s)
+    cnt = np.zeros(max(n, 1), np.int32); sel = np.zeros(max(n, 1), np.uint8)
+    ctx._ck(ctx.lib.ll_map_vote_host(ctx.h, _ptr(s), _ptr(t), n, _ptr(cnt), _ptr(sel)))
+    return cnt[:n], sel[:n].astype(bool)
+
+
 class CubeMap:
     """One ll_cubemap: laserMapping's cube map + per-frame body (laserMapping.cpp:1584-2165) on the device of `ctx`."""
 
@@ -755,6 +793,10 @@ class CubeMap:
     def set_shard(self, rank, world):
         """Keep only the cubes of `rank` out of `world` (tile-parallel mapping); before the first scan."""
         self._ck(self.lib.ll_cubemap_set_shard(self.h, int(rank), int(world)))
+
+    def set_vote(self, on):
+        """vote the plane blocks in optimize / process* (ll_cubemap_set_vote: the inner map's Map.set_vote)"""
+        self._ck(self.lib.ll_cubemap_set_vote(self.h, int(bool(on))))
 
     def map(self):
         """The inner Map (borrowed): knn_partial / associate_merged / solve / edges / planes on the gathered clouds."""
@@ -1045,6 +1087,14 @@ class CubeMaps:
         self._ck(self.lib.ll_cubemaps_stats(self.h, C.byref(s), C.byref(f)))
         return s.value, f.value
 
+    def set_vote(self, on):
+        """on [S] of 0 / 1: the sequences whose plane blocks are voted in process / process_slots from now on (ll_cubemaps_set_vote);
+        localize_slots never votes"""
+        o = np.ascontiguousarray(on).astype(np.int32)
+        if o.shape != (self.n_seq,):
+            raise ValueError("on must have one entry per sequence")
+        self._ck(self.lib.ll_cubemaps_set_vote(self.h, o.ctypes.data))
+
     def reset(self, q):
         """sequence q back to a freshly created cube map; the others are untouched"""
         self._ck(self.lib.ll_cubemaps_reset(self.h, int(q)))
@@ -1130,6 +1180,11 @@ class Drives:
             raise ValueError("map_of must have one entry per lane")
         st = None if start is None else np.ascontiguousarray(start, np.float64).reshape(self.n_lanes, 7)
         self._ck(self.lib.ll_drives_set_localize(self.h, m.ctypes.data, None if st is None else st.ctypes.data))
+
+    def set_map_vote(self, from_frame):
+        """the mapping lanes vote their plane blocks in frames whose per-lane index is > from_frame (the reference's gate: 20); negative:
+        off, the default (ll_drives_set_map_vote).  Not part of a checkpoint: set it again after restore"""
+        self._ck(self.lib.ll_drives_set_map_vote(self.h, int(from_frame)))
 
     def fit(self):
         """the last step's LocalizeFit records [S]: zeros for lanes that mapped, sat out or did not optimise"""

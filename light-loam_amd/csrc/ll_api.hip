@@ -1080,12 +1080,119 @@ static int map_set_pose(ll_map *m, const double *pose_w7)
     return LL_OK;
 }
 
+/* ---- the mapping vote (ll_map_vote.hip): laserMapping.cpp:836-1030 on the plane blocks of an association ---- */
+/* after the compaction of an association: vote, then compact to the selected blocks (two launches; nothing when the vote is off) */
+static void map_vote(ll_map *m)
+{
+    if (m->M.ctr) ll_map_launch_vote(m->d_view, 1, m->M.n_stk[1], m->ctx->stream);
+}
+
+extern "C" int ll_map_set_vote(ll_map *m, int on)
+{
+    if (!m) return LL_ERR_ARG;
+    if (on != 0 && on != 1) { m->err = "ll_map_set_vote: on must be 0 or 1"; return LL_ERR_ARG; }
+    if (!on) { m->M.ctr = nullptr; return LL_OK; }                 /* the buffers stay; nothing reads or writes them */
+    if (m->M.row_world > 1) { m->err = "the map sums a row shard: the vote is not built for it"; return LL_ERR_STATE; }
+    if (m->M.gid[0]) { m->err = "the map holds a tile shard (merged association): the vote is not built for it"; return LL_ERR_STATE; }
+    if (ll_map_vote_lds_bytes(m->cap_stk[1]) > LL_MAP_VOTE_LDS_MAX) {
+        m->err = "ll_map_set_vote: a region of max_scan_surf / 20 + 19 candidates at 28 B each does not fit the 160 KiB of LDS"; return LL_ERR_ARG;
+    }
+    const bool first = !m->d_view;
+    if (first) {                                                   /* the first switch-on allocates and uploads; every later one only flips M.ctr */
+        LLM_HIP(hipSetDevice(m->ctx->device));
+        const size_t n = (size_t)m->cap_stk[1];
+        LLMapView *dv = nullptr;
+        if (!map_alloc(m, m->d_ctr, n * 3) || !map_alloc(m, m->d_vsrc, n) || !map_alloc(m, m->d_vcount, n) || !map_alloc(m, m->d_vsel, n) ||
+            !map_alloc(m, m->d_vn, 1) || !map_alloc(m, dv, 1)) return LL_ERR_HIP;
+        m->M.v_src = m->d_vsrc; m->M.v_count = m->d_vcount; m->M.v_sel = m->d_vsel; m->M.v_n = m->d_vn;
+        /* the table of one: the vote kernels read ctr, v_*, src[1], stk[1], fn, fd and counts -- pointers that never change */
+        LLMapView V = m->M;
+        V.ctr = m->d_ctr;
+        LLM_HIP(hipMemcpy(dv, &V, sizeof(LLMapView), hipMemcpyHostToDevice));
+        m->d_view = dv;
+    }
+    m->M.ctr = m->d_ctr;
+    return LL_OK;
+}
+
+extern "C" int ll_map_download_vote(ll_map *m, int *src, int *count, uint8_t *selected, float *tgt3, int cap, int *n)
+{
+    if (!m || !n) return LL_ERR_ARG;
+    *n = 0;
+    if (!m->d_view) { m->err = "ll_map_download_vote: the vote was never switched on"; return LL_ERR_STATE; }
+    LLM_HIP(hipSetDevice(m->ctx->device));
+    hipStream_t st = m->ctx->stream;
+    int nc = 0;
+    if (ll_read_back(&nc, m->d_vn, sizeof(int), st)) { m->err = "read-back failed"; return LL_ERR_HIP; }
+    if (nc < 0 || nc > m->cap_stk[1]) { m->err = "ll_map_download_vote: no voted association yet"; return LL_ERR_STATE; }
+    if (cap < nc) { m->err = "vote capacity too small"; return LL_ERR_CAPACITY; }
+    *n = nc;
+    if (nc == 0) return LL_OK;
+    std::vector<int> hs((size_t)nc);
+    std::vector<float> hc;
+    LLM_HIP(hipMemcpyAsync(hs.data(), m->d_vsrc, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (count) LLM_HIP(hipMemcpyAsync(count, m->d_vcount, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (selected) LLM_HIP(hipMemcpyAsync(selected, m->d_vsel, (size_t)nc, hipMemcpyDeviceToHost, st));
+    if (tgt3) { hc.resize((size_t)m->cap_stk[1] * 3); LLM_HIP(hipMemcpyAsync(hc.data(), m->d_ctr, hc.size() * sizeof(float), hipMemcpyDeviceToHost, st)); }
+    LLM_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < nc; ++i) {
+        const int k = hs[(size_t)i];
+        if (k < 0 || k >= m->cap_stk[1]) { m->err = "ll_map_download_vote: a candidate's stack index is out of range"; return LL_ERR_STATE; }
+        if (src) src[i] = k;
+        if (tgt3) for (int c = 0; c < 3; ++c) tgt3[(size_t)i * 3 + c] = hc[(size_t)k * 3 + c];
+    }
+    return LL_OK;
+}
+
+/* mapping's graph_based_correspondence_vote_simple on caller-supplied correspondences, through k_map_vote: the counterpart of ll_vote_host */
+extern "C" int ll_map_vote_host(ll_ctx *ctx, const ll_point *src, const ll_point *tgt, int n, int *count, uint8_t *selected)
+{
+    if (!ctx || n < 0 || (n > 0 && (!src || !tgt))) return LL_ERR_ARG;
+    if (n == 0) return LL_OK;
+    LL_HIP(hipSetDevice(ctx->device));
+    if (ll_map_vote_lds_bytes(n) > LL_MAP_VOTE_LDS_MAX) { ctx->err = "ll_map_vote_host: a region of n / 20 + 19 correspondences does not fit one workgroup's LDS"; return LL_ERR_CAPACITY; }
+    /* scratch: the view, src (float4), tgt (3 floats), identity indices, count (int), counts[2], selected (u8) */
+    const size_t view_bytes = (sizeof(LLMapView) + 15) & ~(size_t)15;
+    const size_t bytes = view_bytes + (size_t)n * (16 + 12 + 4 + 4 + 1) + 64;
+    std::vector<float> t3((size_t)n * 3);
+    std::vector<int> ident((size_t)n);
+    for (int i = 0; i < n; ++i) { t3[(size_t)i * 3] = tgt[i].x; t3[(size_t)i * 3 + 1] = tgt[i].y; t3[(size_t)i * 3 + 2] = tgt[i].z; ident[(size_t)i] = i; }
+    void *d = nullptr;
+    LL_HIP(hipMallocAsync(&d, bytes, ctx->stream));
+    LLMapView *dview = (LLMapView *)d;
+    float4 *dsrc = (float4 *)((unsigned char *)d + view_bytes);
+    float *dtgt = (float *)(dsrc + n);
+    int *didx = (int *)(dtgt + (size_t)n * 3), *dcnt = didx + n, *dcounts = dcnt + n;
+    uint8_t *dsel = (uint8_t *)(dcounts + 2);
+    LLMapView V;
+    std::memset(&V, 0, sizeof(V));
+    V.stk[1] = dsrc; V.n_stk[1] = n; V.src[1] = didx; V.ctr = dtgt; V.counts = dcounts; V.v_count = dcnt; V.v_sel = dsel;
+    const int counts[2] = {0, n};
+    int rc = LL_OK;
+    do {
+        if (hipMemcpyAsync(dview, &V, sizeof(V), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(dsrc, src, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(dtgt, t3.data(), (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(didx, ident.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(dcounts, counts, sizeof(counts), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { rc = LL_ERR_HIP; break; }
+        ll_map_launch_vote_only(dview, 1, n, ctx->stream);
+        if (hipGetLastError() != hipSuccess) { rc = LL_ERR_HIP; break; }
+        if (count && hipMemcpyAsync(count, dcnt, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { rc = LL_ERR_HIP; break; }
+        if (selected && hipMemcpyAsync(selected, dsel, (size_t)n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { rc = LL_ERR_HIP; break; }
+    } while (0);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = LL_ERR_HIP;        /* the host tables above are read by the copies until here */
+    (void)hipFreeAsync(d, ctx->stream);
+    if (rc != LL_OK) ctx->err = "ll_map_vote_host: HIP runtime call failed";
+    return rc;
+}
+
 extern "C" int ll_map_associate(ll_map *m, const double *pose_w7)
 {
     if (!m) return LL_ERR_ARG;
     LLM_HIP(hipSetDevice(m->ctx->device));
     int rc = map_set_pose(m, pose_w7); if (rc) return rc;
     ll_map_launch_associate(m->M, m->ctx->stream);
+    map_vote(m);
     LLM_HIP(hipGetLastError());
     return LL_OK;
 }
@@ -1172,6 +1279,7 @@ extern "C" int ll_map_set_map_ids(ll_map *m, const int *corner_gid, const int *s
     LLM_HIP(hipSetDevice(m->ctx->device));
     if (!corner_gid && !surf_gid) return ll_map_use_ids(m, false);
     if (!corner_gid || !surf_gid) { m->err = "give the ids of both clouds or of neither"; return LL_ERR_ARG; }
+    if (m->M.ctr) { m->err = "the map votes its plane blocks (ll_map_set_vote): the merged association stays un-voted, switch the vote off first"; return LL_ERR_STATE; }
     int rc = ll_map_use_ids(m, true); if (rc) return rc;
     const int *src[2] = {corner_gid, surf_gid};
     for (int w = 0; w < 2; ++w)
@@ -1256,6 +1364,7 @@ extern "C" int ll_map_set_row_shard(ll_map *m, int rank, int world)
 {
     if (!m) return LL_ERR_ARG;
     if (world < 1 || world > 64 || rank < 0 || rank >= world) { m->err = "bad row shard"; return LL_ERR_ARG; }
+    if (world > 1 && m->M.ctr) { m->err = "the map votes its plane blocks (ll_map_set_vote): a row shard stays un-voted, switch the vote off first"; return LL_ERR_STATE; }
     m->M.row_rank = rank; m->M.row_world = world;
     return LL_OK;
 }
@@ -1290,6 +1399,7 @@ extern "C" int ll_map_optimize(ll_map *m, double *pose_w7, int n_outer, const ll
     if (m->M.gid[0]) { m->err = "the map holds a tile shard: search with ll_map_knn_partial / ll_map_associate_merged"; return LL_ERR_STATE; }
     for (int it = 0; it < n_outer; ++it) {                                     /* :1832 */
         ll_map_launch_associate(m->M, st);
+        map_vote(m);
         map_lm_solve(m, o);
     }
     LLM_HIP(hipGetLastError());

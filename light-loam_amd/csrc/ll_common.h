@@ -313,8 +313,21 @@ struct LLMapView {
     double *neq_part; unsigned *neq_ticket;      /* k_map_normal_eq: per-workgroup partial sums [LL_NEQ_NB][28], arrival counter */
     unsigned *lm_go;                             /* k_map_lm_solve: the round workgroup 0 has released */
     unsigned long long *cpub[2]; int cpub_tag;   /* k_map_compact: launch tag << 32 | valid blocks of workgroup b, per cloud type */
+    /* the mapping vote (ll_map_vote.hip); ctr == nullptr: off, nothing below is touched */
+    float *ctr;                                  /* per surf stack point [n][3]: the float centroid of its five neighbours (Corre_Match.tgt) */
+    int *v_src, *v_count; unsigned char *v_sel;  /* per candidate plane block, in stack order: stack index, incompatible pairs, selected */
+    int *v_n;                                    /* [1] the candidates of the last association */
 };
 #define LL_NEQ_NB 16                             /* workgroups of k_map_normal_eq */
+#define LL_MAP_VOTE_REGIONS 20                   /* laserMapping.cpp:841 */
+/* the longest region of n candidates (n / 20 each, the last one takes the remainder) and the LDS it needs: src + tgt triples + a count */
+static inline int ll_map_vote_region_max(int n) { return n / LL_MAP_VOTE_REGIONS + (LL_MAP_VOTE_REGIONS - 1); }
+static inline size_t ll_map_vote_lds_bytes(int n) { return (size_t)ll_map_vote_region_max(n) * 28; }
+#define LL_MAP_VOTE_LDS_MAX (160 * 1024)
+/* ll_map_vote.hip: the vote + the compaction to the selected blocks for the views whose ctr is set (two launches); max_stk: the largest
+ * surf stack among them.  ll_map_launch_vote_only: the vote alone (ll_map_vote_host) */
+void ll_map_launch_vote(const LLMapView *d_views, int n_views, int max_stk, hipStream_t st);
+void ll_map_launch_vote_only(const LLMapView *d_views, int n_views, int max_stk, hipStream_t st);
 /* device-to-device copy / small constant fill as kernel launches: on this stack an asynchronous copy costs the host ~26 us,
  * a launch ~8 us, and the mapping stage issues dozens of them per frame */
 void *ll_pinned_scratch(size_t bytes);                                               /* per host thread, page-locked, >= bytes (NULL on failure) */

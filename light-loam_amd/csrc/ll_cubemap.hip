@@ -242,6 +242,7 @@ extern "C" int ll_cubemap_set_shard(ll_cubemap *cm, int rank, int world)
     if (!cm) return LL_ERR_ARG;
     if (world < 1 || world > 64 || rank < 0 || rank >= world) { cm->err = "bad shard"; return LL_ERR_ARG; }
     for (int w = 0; w < 2; ++w) if (cm->top[w] != 0) { cm->err = "the cube map already holds points"; return LL_ERR_STATE; }
+    if (world > 1 && cm->map->M.ctr) { cm->err = "the cube map votes its plane blocks (ll_cubemap_set_vote): a tile shard stays un-voted, switch the vote off first"; return LL_ERR_STATE; }
     CM_HIP(hipSetDevice(cm->ctx->device));
     const int rc = ll_map_use_ids(cm->map, world > 1);
     if (rc) { cm->err = cm->map->err; return rc; }
@@ -250,6 +251,15 @@ extern "C" int ll_cubemap_set_shard(ll_cubemap *cm, int rank, int world)
 }
 
 extern "C" ll_map *ll_cubemap_map(ll_cubemap *cm) { return cm ? cm->map : nullptr; }
+
+/* the mapping vote (ll_map_vote.hip) in ll_cubemap_optimize / ll_cubemap_process*: the map's own switch */
+extern "C" int ll_cubemap_set_vote(ll_cubemap *cm, int on)
+{
+    if (!cm) return LL_ERR_ARG;
+    const int rc = ll_map_set_vote(cm->map, on);
+    if (rc) cm->err = cm->map->err;
+    return rc;
+}
 
 extern "C" int ll_cubemap_prepare(ll_cubemap *cm, const double *t_w3, const ll_point *corner_last, int n_corner, const ll_point *surf_last, int n_surf)
 {

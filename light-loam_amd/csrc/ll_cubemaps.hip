@@ -490,7 +490,7 @@ static int cms_prepare_finish(ll_cubemaps *cms, const std::vector<int> &run, con
 /* optimize (:1822-2100) for the prepared sequences: the :1822 gate, 2 x {knn, compact, LM}, all poses back in ONE synchronisation.
  * fit != nullptr: the residual blocks once more at the final poses and k_cms_fit (ll_localize.hip); the records come back in the
  * poses' copy -- rows of the running sequences, zeros where the gate was shut */
-static int cms_optimize(ll_cubemaps *cms, const std::vector<int> &run, double *pose_w7, int *ran, ll_localize_fit *fit)
+static int cms_optimize(ll_cubemaps *cms, const std::vector<int> &run, double *pose_w7, int *ran, ll_localize_fit *fit, bool may_vote)
 {
     hipStream_t st = cms->ctx->stream;
     const int R = (int)run.size();
@@ -506,9 +506,12 @@ static int cms_optimize(ll_cubemaps *cms, const std::vector<int> &run, double *p
     if (O > 0) {
         std::vector<LLMapView> views;
         std::vector<int4> blk;
+        int n_vote = 0, max_vote_stk = 0;                                           /* the sequences that vote their plane blocks */
         for (int k = 0; k < O; ++k) {
             LLMapView V = cms->cm[run[opt_r[k]]]->map->M;
             V.pose = cms->d_pose + 7 * run[opt_r[k]];
+            if (!may_vote) V.ctr = nullptr;                                         /* a read-only frame never votes (ll_map_vote.hip) */
+            if (V.ctr) { ++n_vote; max_vote_stk = std::max(max_vote_stk, V.n_stk[1]); }
             views.push_back(V);
             for (int w = 0; w < 2; ++w) for (int f = 0; f < V.n_stk[w]; f += LL_KNNB) blk.push_back(make_int4(k, w, f, 0));
         }
@@ -519,6 +522,7 @@ static int cms_optimize(ll_cubemaps *cms, const std::vector<int> &run, double *p
         for (int it = 0; it < 2; ++it) {                                           /* :1832 */
             if (!blk.empty()) hipLaunchKernelGGL(k_cms_knn, dim3((unsigned)blk.size()), dim3(LL_KNNB), 0, st, d_views, d_blk);
             hipLaunchKernelGGL(k_cms_compact, dim3(2 * O), dim3(256), 0, st, d_views);
+            if (n_vote > 0) ll_map_launch_vote(d_views, O, max_vote_stk, st);      /* the views without ctr return at once */
             hipLaunchKernelGGL(k_cms_lm, dim3(O), dim3(256), 0, st, d_views, o);
         }
         if (fit) {                                                                 /* the blocks at the final pose, reduced */
@@ -578,7 +582,7 @@ static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::v
     rc = cms_prepare_finish(cms, run, src, n_in, flat_slot, ops, n_from); if (rc) return rc;
 
     /* ---------------- optimize (:1822-2100) */
-    rc = cms_optimize(cms, run, pose_w7, ran, nullptr); if (rc) return rc;
+    rc = cms_optimize(cms, run, pose_w7, ran, nullptr, true); if (rc) return rc;
 
     /* ---------------- update (:2103-2165) */
     CMS_HIP(hipMemsetAsync(cms->d_addcnt, 0, (size_t)R * 2 * (CM_N + 1) * sizeof(int), st));
@@ -817,7 +821,7 @@ static int cms_localize(ll_cubemaps *cms, const std::vector<int> &run, const int
         n_from[0][r] = nf[0]; n_from[1][r] = nf[1];
     }
     rc = cms_prepare_finish(cms, run, src, n_in, flat_slot, ops, n_from); if (rc) return rc;
-    return cms_optimize(cms, run, pose_w7, ran, fit);
+    return cms_optimize(cms, run, pose_w7, ran, fit, false);
 }
 
 /* the maps the running sequences read: inside 0..S-1 and usable */
@@ -903,6 +907,23 @@ extern "C" int ll_cubemaps_download_cube(ll_cubemaps *cms, int q, int surf, int 
     rc = ll_cubemap_download_cube(cms->cm[q], surf, cube_index, out, cap, n);
     if (rc) cms->err = cms->cm[q]->err;
     return rc;
+}
+
+/* the mapping vote (ll_map_vote.hip) per sequence: on[q] != 0 votes sequence q's plane blocks in ll_cubemaps_process* from now on (the switch
+ * of its own ll_map; it persists until changed).  ll_cubemaps_localize_slots never votes.  Refusals come before any switch changes. */
+extern "C" int ll_cubemaps_set_vote(ll_cubemaps *cms, const int *on)
+{
+    if (!cms) return LL_ERR_ARG;
+    if (!on) { cms->err = "ll_cubemaps_set_vote: on is NULL"; return LL_ERR_ARG; }
+    for (int q = 0; q < cms->S; ++q)
+        if (on[q] != 0 && on[q] != 1) { cms->err = "sequence " + std::to_string(q) + ": on must be 0 or 1"; return LL_ERR_ARG; }
+    for (int q = 0; q < cms->S; ++q) {
+        ll_map *m = cms->cm[q]->map;
+        if ((m->M.ctr != nullptr) == (on[q] != 0)) continue;
+        const int rc = ll_map_set_vote(m, on[q]);
+        if (rc) { cms->err = "sequence " + std::to_string(q) + ": " + m->err; return rc; }
+    }
+    return LL_OK;
 }
 
 /* host synchronisations and frames since create (a frame = one process call that ran at least one sequence) */

@@ -127,6 +127,7 @@ struct ll_drives {
     ll_ctx *ctx = nullptr;
     ll_cubemaps *cms = nullptr;
     int S = 0, base = 0, n_outer = 3, keep_registered = 0;
+    int map_vote_from = -1;                       /* ll_drives_set_map_vote: a mapping lane votes its plane blocks in frames with index > this; < 0: never */
     int row = 0;                                  /* the row the next step reads */
     std::vector<int> ran_prev, fidx, reg_n;       /* per lane: ran on the last step, frame index of its last frame, registered points */
     std::vector<DrvFeat> feat;                    /* per lane: the feature counts of its previous-row slot (from the step's header read-back, or a restore) */
@@ -226,6 +227,30 @@ static std::string drv_lane_msg(const std::string &m)
     return m.compare(0, pre.size(), pre) == 0 ? "lane " + m.substr(pre.size()) : m;
 }
 
+/* the mapping vote of the lanes that map: frames whose per-lane index (0 at START) is > from_frame vote; from_frame < 0 switches it off for
+ * every lane.  Localising lanes never vote.  Not part of a checkpoint: set it again after ll_drives_restore. */
+extern "C" int ll_drives_set_map_vote(ll_drives *d, int from_frame)
+{
+    if (!d) return LL_ERR_ARG;
+    if (from_frame < 0) {
+        std::vector<int> off(d->S, 0);
+        const int rc = ll_cubemaps_set_vote(d->cms, off.data());
+        if (rc) { d->err = "mapping vote: " + drv_lane_msg(llcms_err(d->cms)); return rc; }
+        d->map_vote_from = -1;
+        return LL_OK;
+    }
+    /* the first switch-on of a map allocates and may refuse: now, not in the middle of a drive -- a step then only flips the switches */
+    for (int q = 0; q < d->S; ++q) {
+        ll_map *m = llcms_map(d->cms, q)->map;
+        if (m->M.ctr) continue;
+        const int rc = ll_map_set_vote(m, 1);
+        if (rc) { d->err = "mapping vote: lane " + std::to_string(q) + ": " + m->err; return rc; }
+        (void)ll_map_set_vote(m, 0);
+    }
+    d->map_vote_from = from_frame;
+    return LL_OK;
+}
+
 /* everything after the argument checks: a failure loses the step for every lane in run */
 static int drv_run(ll_drives *d, const int *cmd, const std::vector<double> &p0, std::vector<double> &odom, std::vector<double> &mapped, std::vector<int> &ran)
 {
@@ -262,6 +287,13 @@ static int drv_run(ll_drives *d, const int *cmd, const std::vector<double> &p0, 
         if (cmd[q] == LL_DRIVE_START) { rc = ll_cubemaps_reset(d->cms, q); if (rc) { d->err = drv_lane_msg(llcms_err(d->cms)); return rc; } }
     }
     std::vector<ScanHdr> hdr(S);
+    if (n_map > 0 && d->map_vote_from >= 0) {                                           /* the reference's gate, now_frame > 20 (:2057) */
+        std::vector<int> on(S, 0);
+        for (int q = 0; q < S; ++q)
+            if (slots[q] >= 0) on[q] = (cmd[q] == LL_DRIVE_START ? 0 : d->fidx[q] + 1) > d->map_vote_from;
+        rc = ll_cubemaps_set_vote(d->cms, on.data());
+        if (rc) { d->err = "mapping vote: " + drv_lane_msg(llcms_err(d->cms)); return rc; }
+    }
     if (n_map > 0) {
         rc = llcms_process_slots_dev(d->cms, slots.data(), mapped.data(), ran.data(), d->d_odom, odom.data(), (size_t)S * 7 * sizeof(double), hdr.data());
         if (rc) { d->err = "mapping: " + drv_lane_msg(llcms_err(d->cms)); return rc; }

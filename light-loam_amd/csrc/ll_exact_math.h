@@ -262,3 +262,12 @@ LL_HD bool ll_vote_incompatible(float gap2) { return ll_f2u(gap2) >= LL_VOTE_GAP
  * whose square rounds to at least the threshold above (tests/test_exact_math.py: every non-negative float) */
 #define LL_VOTE_GAP_BITS 0x3e4ee4cdu
 LL_HD bool ll_vote_incompatible_gap(float gap) { return ll_f2u(gap) >= LL_VOTE_GAP_BITS && !(gap != gap); }
+
+/* the mapping stage's vote predicate: std::exp(-(gap*gap)/(1*1)) < 0.95 (laserMapping.cpp:932-937).  0.95 is a double literal there,
+ * so the float score is widened: (double)expf(-gap2) < 0.95, which with glibc's expf is exactly gap2 >= 0x3d5218e6 (the 0.95f
+ * reading would start at 0x3d5218f7); on the gap itself, 0x3e67ea6c is the smallest float whose square rounds to at least that
+ * (tests/test_map_vote_cases.py: every non-negative float, both statements, against the host libm) */
+#define LL_MAP_VOTE_GAP2_BITS 0x3d5218e6u
+LL_HD bool ll_map_vote_incompatible(float gap2) { return ll_f2u(gap2) >= LL_MAP_VOTE_GAP2_BITS && !(gap2 != gap2); }
+#define LL_MAP_VOTE_GAP_BITS 0x3e67ea6cu
+LL_HD bool ll_map_vote_incompatible_gap(float gap) { return ll_f2u(gap) >= LL_MAP_VOTE_GAP_BITS && !(gap != gap); }

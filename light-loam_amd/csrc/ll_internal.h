@@ -79,6 +79,11 @@ struct ll_map {
     int *d_gid[2] = {nullptr, nullptr};
     float4 *d_all_pt[2] = {nullptr, nullptr}; int *d_all_id[2] = {nullptr, nullptr};
     int cap_parts = 0;
+    /* the mapping vote (ll_map_set_vote): the buffers behind M.ctr / M.v_* and the device copy of M (with ctr set) that the single-map path
+     * hands to the vote kernels as a table of one -- they read its pointers and counts[1] only.  Allocated and uploaded by the first
+     * switch-on (d_view != nullptr says so), kept; every later switch only sets or clears M.ctr on the host */
+    float *d_ctr = nullptr; int *d_vsrc = nullptr, *d_vcount = nullptr, *d_vn = nullptr; unsigned char *d_vsel = nullptr;
+    LLMapView *d_view = nullptr;
     std::vector<void *> allocs;
     std::string err;
 };

@@ -234,6 +234,12 @@ __device__ __forceinline__ void ll_map_fit(const LLMapView &M, int i, const doub
             ok = 1;
             for (int k = 0; k < 3; ++k) M.qn[(size_t)i * 3 + k] = nrm[k];
             M.qd[i] = nd;
+            if (M.ctr) {                                                                               /* the vote's Corre_Match.tgt (:1949, :1960-1962, :1969-1971) */
+                float c[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int j = 0; j < 5; ++j) for (int k = 0; k < 3; ++k) c[k] += (float)P5[j][k];      /* P5 holds floats: the conversion back is exact */
+                for (int k = 0; k < 3; ++k) M.ctr[(size_t)i * 3 + k] = c[k] / 5.0f;
+            }
         }
     }
     M.ok[which][i] = ok;

@@ -5,7 +5,7 @@
 // in the reference's trajectory-file format (laserMapping.cpp:2284-2325), byte for byte what ll_odometry_kitti writes for it.
 //
 //   ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose "qx qy qz qw x y z"]]
-//                   [--distortion {0,1}] [--deskew {0,1,2}] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...
+//                   [--distortion {0,1}] [--deskew {0,1,2}] [--map-vote N] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...
 //
 // --checkpoint FILE --checkpoint-at N: after step N (N >= 1 steps done) the lanes that ran on it are saved (ll_drives_save) to FILE
 // together with the tool's own queue state -- per lane the drive it runs, its next frame and the first pose of its trajectory
@@ -30,6 +30,11 @@
 // are: leave it at 0).  --deskew 1 | 2 (needs --distortion 1, refused otherwise): TransformToEnd after every solved frame
 // (ll_set_deskew) -- 1: the feature clouds the next frame and the mapper read, 2: also the full-resolution cloud.  A run resumed
 // from a checkpoint takes the same two options again: the blob does not record the deskew mode.
+//
+// --map-vote N: the graph-based correspondence vote on the mapping stage's plane blocks (ll_drives_set_map_vote; laserMapping.cpp:836-1030,
+// commented out in the reference) in every frame of a drive whose index is > N -- the reference's own gate is 20; the selected blocks
+// replace the full list and keep stack order.  The surf capacity of the maps is then 116 000 points instead of 400 000: a twentieth of
+// it must fit a workgroup's LDS.  Not recorded in a checkpoint: a resumed run takes the option again.  Localising lanes never vote.
 //
 // Build:  g++ -O2 -std=c++14 -I include tools/ll_kitti_drives.cpp -L light-loam_amd -llightloam_hip -o ll_kitti_drives
 #include <algorithm>
@@ -95,7 +100,7 @@ int main(int argc, char **argv)
     bool maps = false;
     std::string ck_path, resume_path, loc_path, start_text;
     long long ck_at = -1;
-    int distortion = 0, deskew = 0;
+    int distortion = 0, deskew = 0, map_vote = -1;
     while (argc > 1 && std::strncmp(argv[1], "--", 2) == 0) {
         const std::string opt = argv[1];
         if (opt == "--maps") { maps = true; --argc; ++argv; continue; }
@@ -107,6 +112,7 @@ int main(int argc, char **argv)
         else if (opt == "--start-pose") start_text = argv[2];
         else if (opt == "--distortion") distortion = std::atoi(argv[2]);
         else if (opt == "--deskew") deskew = std::atoi(argv[2]);
+        else if (opt == "--map-vote") { map_vote = std::atoi(argv[2]); if (map_vote < 0) { std::cerr << "--map-vote takes a frame index >= 0\n"; return 2; } }
         else { std::cerr << "unknown option " << opt << "\n"; return 2; }
         argc -= 2; argv += 2;
     }
@@ -121,7 +127,7 @@ int main(int argc, char **argv)
         while (got < 7 && (in >> start7[got])) ++got;
         if (got != 7 || loc_path.empty()) { std::cerr << "--start-pose takes seven numbers in one argument and needs --localize-in\n"; return 2; }
     }
-    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose \"qx qy qz qw x y z\"]] [--distortion {0,1}] [--deskew {0,1,2}] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
+    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose \"qx qy qz qw x y z\"]] [--distortion {0,1}] [--deskew {0,1,2}] [--map-vote N] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
     const std::string result_dir = argv[1];
     const int scan_line = std::atoi(argv[2]);
     const double tx0 = std::atof(argv[3]);
@@ -136,7 +142,8 @@ int main(int argc, char **argv)
         using namespace lightloam;
         Context ctx(scan_line, 2 * lanes, 0, -1.0, -24.9f, 2.0f, distortion, max_ring_points, 3);   /* as ll_odometry_kitti: x, y, z resident */
         if (deskew != 0) ctx.set_deskew(deskew);                                           /* before any restore: it marks the slots it fills */
-        Drives d(ctx, lanes, scan_line * 120 + 64, 400000, 1 << 22);                      /* ll_odometry_kitti's mapping capacities */
+        Drives d(ctx, lanes, scan_line * 120 + 64, map_vote >= 0 ? 116000 : 400000, 1 << 22);   /* ll_odometry_kitti's mapping capacities; voting: a region must fit the LDS */
+        if (map_vote >= 0) d.set_map_vote(map_vote);
         const double p0[7] = {0, 0, 0, 1, tx0, 0, 0};
         std::vector<double> pose0((size_t)7 * lanes);
         for (int q = 0; q < lanes; ++q) std::copy(p0, p0 + 7, &pose0[(size_t)7 * q]);
