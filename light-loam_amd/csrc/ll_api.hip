@@ -588,6 +588,14 @@ LLLmOpt ll_to_dev_opt(const ll_lm_options *opt)
     return o;
 }
 
+/* the same, refused (err set) when max_num_iterations is not in 0 .. 64 */
+static bool ll_checked_opt(const ll_lm_options *opt, LLLmOpt *o, std::string &err)
+{
+    *o = ll_to_dev_opt(opt);
+    if (o->max_num_iterations < 0 || o->max_num_iterations > 64) { err = "max_num_iterations out of range"; return false; }
+    return true;
+}
+
 /* enqueue one LM solve for a slot range (carry_slot must already be set by the caller) */
 static void enqueue_lm(ll_ctx *ctx, int first, int count, const LLLmOpt &o)
 {
@@ -597,8 +605,8 @@ static void enqueue_lm(ll_ctx *ctx, int first, int count, const LLLmOpt &o)
 extern "C" int ll_lm_solve_batch(ll_ctx *ctx, int first, int count, const ll_lm_options *opt)
 {
     int rc = check_range(ctx, first, count); if (rc) return rc;
-    const LLLmOpt o = ll_to_dev_opt(opt);
-    if (o.max_num_iterations < 0 || o.max_num_iterations > 64) { ctx->err = "max_num_iterations out of range"; return LL_ERR_ARG; }
+    LLLmOpt o;
+    if (!ll_checked_opt(opt, &o, ctx->err)) return LL_ERR_ARG;
     ctx->V.carry_slot = first;
     enqueue_lm(ctx, first, count, o);
     LL_HIP(hipGetLastError());
@@ -728,8 +736,8 @@ extern "C" int ll_odometry_sequences(ll_ctx *ctx, const ll_seq_layout *L, int ro
         }
     }
     if (n_outer < 1 || n_outer > 16) { ctx->err = "n_outer out of range"; return LL_ERR_ARG; }
-    const LLLmOpt o = ll_to_dev_opt(opt);
-    if (o.max_num_iterations < 0 || o.max_num_iterations > 64) { ctx->err = "max_num_iterations out of range"; return LL_ERR_ARG; }
+    LLLmOpt o;
+    if (!ll_checked_opt(opt, &o, ctx->err)) return LL_ERR_ARG;
     const int dmode = ctx->deskew_mode;
     if (dmode)                                                               /* before anything is enqueued: no slot that would run is deskewed already */
         for (int ri = 0; ri < max_rows; ++ri)
@@ -1372,8 +1380,8 @@ extern "C" int ll_map_set_row_shard(ll_map *m, int rank, int world)
 extern "C" int ll_map_solve(ll_map *m, double *pose_w7, const ll_lm_options *opt)
 {
     if (!m || !pose_w7) return LL_ERR_ARG;
-    const LLLmOpt o = ll_to_dev_opt(opt);
-    if (o.max_num_iterations < 0 || o.max_num_iterations > 64) { m->err = "max_num_iterations out of range"; return LL_ERR_ARG; }
+    LLLmOpt o;
+    if (!ll_checked_opt(opt, &o, m->err)) return LL_ERR_ARG;
     if (m->M.row_world > 1) { m->err = "the map sums a row shard: step with ll_map_evaluate + all-reduce + ll_map_lm_*"; return LL_ERR_STATE; }
     LLM_HIP(hipSetDevice(m->ctx->device));
     int rc = map_set_pose(m, pose_w7); if (rc) return rc;
@@ -1388,8 +1396,8 @@ extern "C" int ll_map_optimize(ll_map *m, double *pose_w7, int n_outer, const ll
 {
     if (!m || !pose_w7) return LL_ERR_ARG;
     if (n_outer < 1 || n_outer > 16) { m->err = "n_outer out of range"; return LL_ERR_ARG; }
-    const LLLmOpt o = ll_to_dev_opt(opt);
-    if (o.max_num_iterations < 0 || o.max_num_iterations > 64) { m->err = "max_num_iterations out of range"; return LL_ERR_ARG; }
+    LLLmOpt o;
+    if (!ll_checked_opt(opt, &o, m->err)) return LL_ERR_ARG;
     LLM_HIP(hipSetDevice(m->ctx->device));
     if (ran) *ran = 0;
     if (!(m->M.n_map[0] > 10 && m->M.n_map[1] > 50)) return LL_OK;           /* :1822 */
@@ -1459,28 +1467,31 @@ extern "C" int ll_map_evaluate(ll_map *m, double *neq44)
     return LL_OK;
 }
 
-static int map_lm_stage(ll_map *m, int stage, const double *neq44_sum, const ll_lm_options *opt)
+/* one step of the launch-per-step solve on the map's slot: 0 begin, 1 propose, 2 accept; neq44_sum: the (all-reduced) normal
+ * equations, host memory -- then the call synchronises, the caller may reuse it -- or, on_device, device memory: enqueued only */
+static int map_lm_stage(ll_map *m, int stage, const double *neq44_sum, const ll_lm_options *opt, bool on_device)
 {
     if (!m || (stage != 1 && !neq44_sum)) return LL_ERR_ARG;
-    LLLmOpt o = ll_to_dev_opt(opt);
+    LLLmOpt o;
+    if (!ll_checked_opt(opt, &o, m->err)) return LL_ERR_ARG;     /* as ll_map_optimize */
     o.nan_poisons_pose = 1;                                     /* a failing rank's NaN record must reach every rank's pose (lightloam_rccl.hpp) */
-    if (o.max_num_iterations < 0 || o.max_num_iterations > 64) { m->err = "max_num_iterations out of range"; return LL_ERR_ARG; }   /* as ll_map_optimize */
     LLM_HIP(hipSetDevice(m->ctx->device));
     hipStream_t st = m->ctx->stream;
-    if (neq44_sum) LLM_HIP(hipMemcpyAsync(m->M.neq, neq44_sum, LL_NEQ_STRIDE * sizeof(double), hipMemcpyHostToDevice, st));
+    if (neq44_sum && on_device) ll_copy_d2d(m->M.neq, neq44_sum, LL_NEQ_STRIDE * sizeof(double), st);
+    else if (neq44_sum) LLM_HIP(hipMemcpyAsync(m->M.neq, neq44_sum, LL_NEQ_STRIDE * sizeof(double), hipMemcpyHostToDevice, st));
     LLView Vm = m->ctx->V;
     Vm.pose = m->M.pose; Vm.neq = m->M.neq; Vm.lm = m->M.lm;
     if (stage == 0) ll_launch_lm_begin(Vm, 0, 1, o, st);
     else if (stage == 1) ll_launch_lm_propose(Vm, 0, 1, o, st);
     else ll_launch_lm_accept(Vm, 0, 1, o, st);
     LLM_HIP(hipGetLastError());
-    LLM_HIP(hipStreamSynchronize(st));                          /* neq44_sum may be reused by the caller */
+    if (!on_device) LLM_HIP(hipStreamSynchronize(st));
     return LL_OK;
 }
 
-extern "C" int ll_map_lm_begin(ll_map *m, const double *neq44_sum, const ll_lm_options *opt) { return map_lm_stage(m, 0, neq44_sum, opt); }
-extern "C" int ll_map_lm_propose(ll_map *m, const ll_lm_options *opt) { return map_lm_stage(m, 1, nullptr, opt); }
-extern "C" int ll_map_lm_accept(ll_map *m, const double *neq44_sum, const ll_lm_options *opt) { return map_lm_stage(m, 2, neq44_sum, opt); }
+extern "C" int ll_map_lm_begin(ll_map *m, const double *neq44_sum, const ll_lm_options *opt) { return map_lm_stage(m, 0, neq44_sum, opt, false); }
+extern "C" int ll_map_lm_propose(ll_map *m, const ll_lm_options *opt) { return map_lm_stage(m, 1, nullptr, opt, false); }
+extern "C" int ll_map_lm_accept(ll_map *m, const double *neq44_sum, const ll_lm_options *opt) { return map_lm_stage(m, 2, neq44_sum, opt, false); }
 
 /* ---- device-resident variants for the collectives of SURVEY 8e: every pointer is a DEVICE pointer on the context's GPU, every
  * call only enqueues on ll_stream(ctx) and returns (no host hop, no stream synchronisation).  The caller runs its collective
@@ -1496,26 +1507,9 @@ extern "C" int ll_map_evaluate_dev(ll_map *m, double *neq44_dev)
     return LL_OK;
 }
 
-static int map_lm_stage_dev(ll_map *m, int stage, const double *neq44_sum_dev, const ll_lm_options *opt)
-{
-    if (!m || (stage != 1 && !neq44_sum_dev)) return LL_ERR_ARG;
-    LLLmOpt o = ll_to_dev_opt(opt);
-    o.nan_poisons_pose = 1;
-    if (o.max_num_iterations < 0 || o.max_num_iterations > 64) { m->err = "max_num_iterations out of range"; return LL_ERR_ARG; }   /* as ll_map_optimize */
-    LLM_HIP(hipSetDevice(m->ctx->device));
-    hipStream_t st = m->ctx->stream;
-    if (neq44_sum_dev) ll_copy_d2d(m->M.neq, neq44_sum_dev, LL_NEQ_STRIDE * sizeof(double), st);
-    LLView Vm = m->ctx->V;
-    Vm.pose = m->M.pose; Vm.neq = m->M.neq; Vm.lm = m->M.lm;
-    if (stage == 0) ll_launch_lm_begin(Vm, 0, 1, o, st);
-    else if (stage == 1) ll_launch_lm_propose(Vm, 0, 1, o, st);
-    else ll_launch_lm_accept(Vm, 0, 1, o, st);
-    LLM_HIP(hipGetLastError());
-    return LL_OK;
-}
-extern "C" int ll_map_lm_begin_dev(ll_map *m, const double *neq44_sum_dev, const ll_lm_options *opt) { return map_lm_stage_dev(m, 0, neq44_sum_dev, opt); }
-extern "C" int ll_map_lm_propose_dev(ll_map *m, const ll_lm_options *opt) { return map_lm_stage_dev(m, 1, nullptr, opt); }
-extern "C" int ll_map_lm_accept_dev(ll_map *m, const double *neq44_sum_dev, const ll_lm_options *opt) { return map_lm_stage_dev(m, 2, neq44_sum_dev, opt); }
+extern "C" int ll_map_lm_begin_dev(ll_map *m, const double *neq44_sum_dev, const ll_lm_options *opt) { return map_lm_stage(m, 0, neq44_sum_dev, opt, true); }
+extern "C" int ll_map_lm_propose_dev(ll_map *m, const ll_lm_options *opt) { return map_lm_stage(m, 1, nullptr, opt, true); }
+extern "C" int ll_map_lm_accept_dev(ll_map *m, const double *neq44_sum_dev, const ll_lm_options *opt) { return map_lm_stage(m, 2, neq44_sum_dev, opt, true); }
 
 extern "C" int ll_map_knn_partial_dev(ll_map *m, float *corner_nn_dev, int *corner_id_dev, float *surf_nn_dev, int *surf_id_dev)
 {
@@ -1551,8 +1545,8 @@ extern "C" int ll_map_associate_merged_dev(ll_map *m, int n_parts, const float *
 extern "C" int ll_map_solve_dev(ll_map *m, const ll_lm_options *opt)
 {
     if (!m) return LL_ERR_ARG;
-    const LLLmOpt o = ll_to_dev_opt(opt);
-    if (o.max_num_iterations < 0 || o.max_num_iterations > 64) { m->err = "max_num_iterations out of range"; return LL_ERR_ARG; }
+    LLLmOpt o;
+    if (!ll_checked_opt(opt, &o, m->err)) return LL_ERR_ARG;
     if (m->M.row_world > 1) { m->err = "the map sums a row shard: step with ll_map_evaluate_dev + all-reduce + ll_map_lm_*_dev"; return LL_ERR_STATE; }
     LLM_HIP(hipSetDevice(m->ctx->device));
     /* no read-back here to notice a timed-out predecessor by: the hand-over words are zeroed on the stream before every solve */
@@ -1873,10 +1867,6 @@ extern "C" int ll_debug_exact_math(ll_ctx *ctx, int op, const float *a, const fl
 }
 
 /* ---- test surface: the sort, the scan and the segmented voxel filter of ll_voxel.hip / ll_mapping.hip on their own ---- */
-int ll_sort_pairs(unsigned long long *keys, int *vals, unsigned long long *tmp_keys, int *tmp_vals, int n, int *hist, int *tile_sum,
-                  unsigned long long *or_and_dev, hipStream_t st);
-void ll_sort_pairs_segments(unsigned long long *keys, int *vals, const int *seg_off_dev, int nseg, hipStream_t st);
-
 /* nseg + 1 offsets ascending from 0 to n, no segment longer than max_len (0: any length) */
 static bool ll_debug_offsets_ok(const int *seg_off, int nseg, int n, int max_len)
 {

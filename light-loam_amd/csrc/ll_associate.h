@@ -55,17 +55,6 @@ __device__ __forceinline__ TargetRef ll_target_row(const LLView &V, int t, int w
     return T;
 }
 
-__device__ __forceinline__ void ll_rotate(const double q[4], const double v[3], double out[3])
-{
-    /* Eigen _transformVector: uv = u x v; uv += uv; v + w*uv + u x uv */
-    const double ux = q[0], uy = q[1], uz = q[2], w = q[3];
-    double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
-    uvx += uvx; uvy += uvy; uvz += uvz;
-    out[0] = (v[0] + w * uvx) + (uy * uvz - uz * uvy);
-    out[1] = (v[1] + w * uvy) + (uz * uvx - ux * uvz);
-    out[2] = (v[2] + w * uvz) + (ux * uvy - uy * uvx);
-}
-
 struct Best { float d; int ord; int j; };
 
 __device__ __forceinline__ void ll_best_take(Best &b, float d, int ord, int j, float dmax)

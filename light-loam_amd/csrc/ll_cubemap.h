@@ -4,6 +4,7 @@
  */
 #pragma once
 #include "ll_internal.h"
+#include "ll_map_search.h"
 #include <algorithm>
 
 #define CM_W 21
@@ -20,6 +21,50 @@ __host__ __device__ __forceinline__ int cm_owner(int wi, int wj, int wk, int wor
 {
     const int h = (wi + 3 * wj + 5 * wk) % world;            /* any distance from the origin: the remainder is folded to 0 .. world - 1 */
     return h < 0 ? h + world : h;
+}
+
+/* the cube a world point falls into (:2108-2125) in the array centred at cen: its three indices, and the cube index or -1 outside */
+__device__ __forceinline__ int cm_cube_of(float sx, float sy, float sz, const int cen[3], int *ci, int *cj, int *ck)
+{
+    int i = (int)(((double)sx + 25.0) / 50.0) + cen[0], j = (int)(((double)sy + 25.0) / 50.0) + cen[1], k = (int)(((double)sz + 25.0) / 50.0) + cen[2];
+    if ((double)sx + 25.0 < 0) i--;
+    if ((double)sy + 25.0 < 0) j--;
+    if ((double)sz + 25.0 < 0) k--;
+    *ci = i; *cj = j; *ck = k;
+    return (i >= 0 && i < CM_W && j >= 0 && j < CM_H && k >= 0 && k < CM_D) ? i + CM_W * j + CM_W * CM_H * k : -1;
+}
+
+/* addcnt[cube] += the lanes of this wave with that cube (cube < 0: not counted).  The points of a scan fall into a handful of
+ * cubes: one add per wave and cube, not one per point on the same address.  Every lane of the wave has to call it */
+__device__ __forceinline__ void cm_wave_count(int cube, int *addcnt)
+{
+    unsigned long long todo = __ballot(cube >= 0);
+    while (todo) {
+        const int c0 = __shfl(cube, __ffsll((long long)todo) - 1);
+        const unsigned long long same = __ballot(cube == c0);
+        if ((threadIdx.x & 63) == __ffsll((long long)same) - 1) atomicAdd(&addcnt[c0], __popcll(same));
+        todo &= ~same;
+    }
+}
+
+/* stack point i of one cube map's update: pointAssociateToMap (:125-134) into tp, its cube as the sort key (CM_N: outside the
+ * array, or -- world > 1 -- another rank's cube: not kept here), vals = i, and the per-cube counts.  Called by whole waves */
+__device__ __forceinline__ void cm_assign_one(const float4 *stk, int n, const double *pose, const int cen[3], int rank, int world,
+                                              float4 *tp, unsigned long long *keys, int *vals, int *addcnt, int i)
+{
+    int cube = -1;                                            /* -1: no point / not counted */
+    if (i < n) {
+        const float4 po = stk[i];
+        float sx, sy, sz;
+        ll_map_to_world(pose, po, sx, sy, sz);
+        tp[i] = make_float4(sx, sy, sz, po.w);
+        int ci, cj, ck;
+        cube = cm_cube_of(sx, sy, sz, cen, &ci, &cj, &ck);
+        if (cube >= 0 && world != 1 && cm_owner(ci - cen[0], cj - cen[1], ck - cen[2], world) != rank) cube = -1;
+        keys[i] = (unsigned long long)(cube >= 0 ? cube : CM_N);
+        vals[i] = i;
+    }
+    cm_wave_count(cube, addcnt);
 }
 #define CM_GID_SHIFT 20                  /* global id = position in the valid list << 20 | position in the cube */
 

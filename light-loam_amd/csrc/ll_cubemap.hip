@@ -33,44 +33,13 @@ __global__ __launch_bounds__(256) void k_cm_copy(const float4 *pool, const float
     }
 }
 
-/* pointAssociateToMap (:125-134) + the cube of the result (:2108-2125).  key = cube index, or CM_N when outside the map */
+/* cm_assign_one (ll_cubemap.h) for stack point blockIdx.x * 256 + threadIdx.x */
 __global__ __launch_bounds__(256) void k_cm_assign(const float4 *stack, int n, const double *pose, int cenx, int ceny, int cenz, int rank, int world,
                                                    float4 *tp, unsigned long long *keys, int *vals, int *addcnt)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    int cube = -1;                                            /* -1: no point / not counted */
-    if (i < n) {
-    const float4 po = stack[i];
-    const double ux = pose[0], uy = pose[1], uz = pose[2], w = pose[3];
-    const double v[3] = {(double)po.x, (double)po.y, (double)po.z};
-    double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
-    uvx += uvx; uvy += uvy; uvz += uvz;
-    const float sx = (float)(((v[0] + w * uvx) + (uy * uvz - uz * uvy)) + pose[4]);
-    const float sy = (float)(((v[1] + w * uvy) + (uz * uvx - ux * uvz)) + pose[5]);
-    const float sz = (float)(((v[2] + w * uvz) + (ux * uvy - uy * uvx)) + pose[6]);
-    tp[i] = make_float4(sx, sy, sz, po.w);
-    int ci = (int)(((double)sx + 25.0) / 50.0) + cenx, cj = (int)(((double)sy + 25.0) / 50.0) + ceny, ck = (int)(((double)sz + 25.0) / 50.0) + cenz;
-    if ((double)sx + 25.0 < 0) ci--;
-    if ((double)sy + 25.0 < 0) cj--;
-    if ((double)sz + 25.0 < 0) ck--;
-    if (ci >= 0 && ci < CM_W && cj >= 0 && cj < CM_H && ck >= 0 && ck < CM_D &&
-        (world == 1 || cm_owner(ci - cenx, cj - ceny, ck - cenz, world) == rank))            /* another rank's cube: not kept here */
-        cube = ci + CM_W * cj + CM_W * CM_H * ck;
-    keys[i] = (unsigned long long)(cube >= 0 ? cube : CM_N);
-    vals[i] = i;
-    }
-    /* the points of a scan fall into a handful of cubes: one add per wave and cube, not one per point on the same address */
-    unsigned long long todo = __ballot(cube >= 0);
-    while (todo) {
-        const int c0 = __shfl(cube, __ffsll((long long)todo) - 1);
-        const unsigned long long same = __ballot(cube == c0);
-        if ((threadIdx.x & 63) == __ffsll((long long)same) - 1) atomicAdd(&addcnt[c0], __popcll(same));
-        todo &= ~same;
-    }
+    const int cen[3] = {cenx, ceny, cenz};
+    cm_assign_one(stack, n, pose, cen, rank, world, tp, keys, vals, addcnt, blockIdx.x * 256 + threadIdx.x);
 }
-
-int ll_sort_pairs(unsigned long long *keys, int *vals, unsigned long long *tmp_keys, int *tmp_vals, int n, int *hist, int *tile_sum,
-                  unsigned long long *or_and_dev, hipStream_t st);
 
 /* ------------------------------------------------------------------ host side */
 template <typename T>

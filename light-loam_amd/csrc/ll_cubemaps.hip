@@ -9,13 +9,13 @@
  *              search cloud; then the boxes and the stack sizes of all sequences come back together
  *   optimize   :1822 gate per sequence; 2 x {k_cms_knn (ll_map_knn_one per stack point over a block table of (sequence, cloud
  *              type, first point)), k_cms_compact (one workgroup per sequence and type), k_cms_lm (one workgroup per sequence
- *              for the whole ceres::Solve)}; all poses come back once
- *   update     k_cms_assign (k_cm_assign's body over a block table), a stable sort by cube per sequence, then the per-cube
+ *              for the whole ceres::Solve, the arithmetic of ll_map_neq.h)}; all poses come back once
+ *   update     k_cms_assign (cm_assign_one, ll_cubemap.h, over a block table), a stable sort by cube per sequence, then the per-cube
  *              counts of all sequences; one ll_voxel_grid_segments call per type over every valid cube of every sequence,
  *              then the filtered sizes; the capacity decision for all sequences, the commit, one k_cms_copy for all clouds.
  * No kernel here waits on another workgroup.  k_cms_lm runs k_map_lm_solve's LL_NEQ_NB x 256-thread partition of the blocks as
- * LL_NEQ_NB passes of one 256-thread workgroup, with the same per-partial reduction tree and the same order of the partials:
- * the normal equations, and so the poses, are bit for bit those of ll_cubemap_process_slot.  The grids of the search clouds
+ * LL_NEQ_NB passes of one 256-thread workgroup; block sums, reduction tree and the order of the partials are the same functions
+ * of ll_map_neq.h in both: the normal equations, and so the poses, are bit for bit those of ll_cubemap_process_slot.  The grids of the search clouds
  * are still built per sequence (ll_map_rebuild_finish: a handful of launches each, no synchronisation).
  * ll_cubemaps_localize_slots is the same frame read-only: slots, prepare without the shift loops (the map may be another
  * sequence's and shared: cms_localize), optimize, no update -- three synchronisations; with a fit record, one more knn + compact
@@ -23,19 +23,16 @@
  */
 #include "ll_cubemap.h"
 #include "ll_factor_math.h"
-#include "ll_lm_step.h"
+#include "ll_map_neq.h"
 #include "ll_map_search.h"
 #include <chrono>
 #include <cmath>
-
-int ll_sort_pairs(unsigned long long *keys, int *vals, unsigned long long *tmp_keys, int *tmp_vals, int n, int *hist, int *tile_sum,
-                  unsigned long long *or_and_dev, hipStream_t st);
 
 /* dst[i] = index ? src[index[i]] : src[i], i < cnt */
 struct CmsCopy { const float4 *src; const int *index; float4 *dst; int cnt, pad; };
 /* one bounding box: 6 ordered ints (min xyz, max xyz) of pts[0, n) */
 struct CmsBox { const float4 *pts; int *out; int n, pad; };
-/* k_cm_assign's arguments for one (sequence, cloud type) */
+/* cm_assign_one's arguments for one (sequence, cloud type) */
 struct CmsAssign { const float4 *stk; const double *pose; float4 *tp; unsigned long long *keys; int *vals; int *addcnt; int n, cen[3]; };
 
 /* ------------------------------------------------------------------ kernels */
@@ -90,11 +87,7 @@ __global__ __launch_bounds__(256) void k_cms_compact(const LLMapView *views)
         const bool ok = i < n && M.ok[which][i];
         int total;
         const int pos = base + ll_block_exscan_n<4>(ok ? 1 : 0, sc, total);
-        if (ok) {
-            M.src[which][pos] = i;
-            if (which == 0) for (int k = 0; k < 3; ++k) { M.fa[(size_t)pos * 3 + k] = M.qa[(size_t)i * 3 + k]; M.fb[(size_t)pos * 3 + k] = M.qb[(size_t)i * 3 + k]; }
-            else { for (int k = 0; k < 3; ++k) M.fn[(size_t)pos * 3 + k] = M.qn[(size_t)i * 3 + k]; M.fd[pos] = M.qd[i]; }
-        }
+        if (ok) ll_map_place(M, which, pos, i);
         base += total;
     }
     if (tid == 0) M.counts[which] = base;
@@ -105,8 +98,7 @@ __global__ __launch_bounds__(256) void k_cms_compact(const LLMapView *views)
 __global__ __launch_bounds__(256) void k_cms_lm(const LLMapView *views, LLLmOpt o)
 {
     const LLMapView &M = views[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int gsz = LL_NEQ_NB * 256;
+    const int tid = threadIdx.x, gsz = LL_NEQ_NB * 256;
     const int n_e = M.counts[0], n_p = M.counts[1];
     __shared__ double red[4][LL_NACC];
     __shared__ double sp[7], sneq[LL_NEQ_STRIDE], sL[LL_LM_STRIDE], stot[LL_NACC], spart[LL_NEQ_NB * LL_NACC];
@@ -114,59 +106,21 @@ __global__ __launch_bounds__(256) void k_cms_lm(const LLMapView *views, LLLmOpt 
     if (tid < 7) sp[tid] = M.pose[tid];
     __syncthreads();
     for (int round = 0; round <= o.max_num_iterations; ++round) {
-        Pose P;
-        for (int k = 0; k < 4; ++k) P.q[k] = sp[k];
-        for (int k = 0; k < 3; ++k) P.t[k] = sp[4 + k];
+        const Pose P = ll_pose_load(sp);
         for (int wg = 0; wg < LL_NEQ_NB; ++wg) {
-            const int gtid = wg * 256 + tid;
             double acc[LL_NACC];
 #pragma unroll
             for (int k = 0; k < LL_NACC; ++k) acc[k] = 0.0;
-            for (int i = gtid; i < n_e; i += gsz) {
-                double r[3], Jq[3][4], Jt[3][3];
-                ll_edge_d(P, M.stk[0][M.src[0][i]], &M.fa[(size_t)i * 3], &M.fb[(size_t)i * 3], r, Jq, Jt);
-                const double sc = ll_huber_scale(r[0] * r[0] + r[1] * r[1] + r[2] * r[2], M.huber, acc[27]);
-                for (int row = 0; row < 3; ++row) {
-                    double J[6];
-                    ll_to_local(P, Jq[row], J);
-                    J[3] = Jt[row][0]; J[4] = Jt[row][1]; J[5] = Jt[row][2];
-                    for (int k = 0; k < 6; ++k) J[k] *= sc;
-                    ll_acc_row(acc, J, r[row] * sc);
-                }
-            }
-            for (int i = gtid; i < n_p; i += gsz) {
-                double r, Jq[4], Jt[3], J[6];
-                ll_plane_norm(P, M.stk[1][M.src[1][i]], &M.fn[(size_t)i * 3], M.fd[i], r, Jq, Jt);
-                const double sc = ll_huber_scale(r * r, M.huber, acc[27]);
-                ll_to_local(P, Jq, J);
-                J[3] = Jt[0]; J[4] = Jt[1]; J[5] = Jt[2];
-                for (int k = 0; k < 6; ++k) J[k] *= sc;
-                ll_acc_row(acc, J, r * sc);
-            }
-#pragma unroll
-            for (int k = 0; k < LL_NACC; ++k) {
-                double v = acc[k];
-                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-                if (lane == 0) red[wave][k] = v;
-            }
-            __syncthreads();
-            if (tid < LL_NACC) spart[wg * LL_NACC + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+            ll_map_acc_blocks(M, P, wg * 256 + tid, gsz, acc);
+            ll_wg_sum<LL_NACC>(acc, red);
+            if (tid < LL_NACC) spart[wg * LL_NACC + tid] = ll_wg_total(red, tid);
             __syncthreads();
         }
-        if (tid < LL_NACC) {
-            double v = 0.0;
-            for (int b = 0; b < LL_NEQ_NB; ++b) v += spart[b * LL_NACC + tid];
-            stot[tid] = v;
-        }
+        if (tid < LL_NACC) stot[tid] = ll_partials_sum(spart, LL_NEQ_NB, tid);
         __syncthreads();
         if (tid == 0) {
-            int k = 0;
-            for (int a = 0; a < 6; ++a) for (int b = a; b < 6; ++b) { sneq[a * 6 + b] = stot[k]; sneq[b * 6 + a] = stot[k]; ++k; }
-            for (int a = 0; a < 6; ++a) sneq[36 + a] = stot[21 + a];
-            sneq[42] = stot[27];
-            sneq[43] = (double)(3 * n_e + n_p);
-            if (round == 0) ll_lm_begin_one(sL, sneq, sp, o); else ll_lm_accept_one(sL, sneq, sp, o);
-            if (round < o.max_num_iterations) ll_lm_propose_one(sL, sp, o);
+            ll_neq_unpack(stot, 3 * n_e + n_p, sneq);
+            ll_lm_round(sL, sneq, sp, o, round);
         }
         __syncthreads();
     }
@@ -175,39 +129,12 @@ __global__ __launch_bounds__(256) void k_cms_lm(const LLMapView *views, LLLmOpt 
     for (int k = tid; k < LL_LM_STRIDE; k += 256) M.lm[k] = sL[k];
 }
 
-/* k_cm_assign (one cube map, no tile shard) for the 256 stack points from blk[b].y of record blk[b].x */
+/* cm_assign_one (ll_cubemap.h; one cube map each, no tile shard) for the 256 stack points from blk[b].y of record blk[b].x */
 __global__ __launch_bounds__(256) void k_cms_assign(const CmsAssign *recs, const int2 *blk)
 {
     const int2 b = blk[blockIdx.x];
     const CmsAssign &A = recs[b.x];
-    const int i = b.y + threadIdx.x;
-    int cube = -1;
-    if (i < A.n) {
-        const float4 po = A.stk[i];
-        const double *pose = A.pose;
-        const double ux = pose[0], uy = pose[1], uz = pose[2], w = pose[3];
-        const double v[3] = {(double)po.x, (double)po.y, (double)po.z};
-        double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
-        uvx += uvx; uvy += uvy; uvz += uvz;
-        const float sx = (float)(((v[0] + w * uvx) + (uy * uvz - uz * uvy)) + pose[4]);
-        const float sy = (float)(((v[1] + w * uvy) + (uz * uvx - ux * uvz)) + pose[5]);
-        const float sz = (float)(((v[2] + w * uvz) + (ux * uvy - uy * uvx)) + pose[6]);
-        A.tp[i] = make_float4(sx, sy, sz, po.w);
-        int ci = (int)(((double)sx + 25.0) / 50.0) + A.cen[0], cj = (int)(((double)sy + 25.0) / 50.0) + A.cen[1], ck = (int)(((double)sz + 25.0) / 50.0) + A.cen[2];
-        if ((double)sx + 25.0 < 0) ci--;
-        if ((double)sy + 25.0 < 0) cj--;
-        if ((double)sz + 25.0 < 0) ck--;
-        if (ci >= 0 && ci < CM_W && cj >= 0 && cj < CM_H && ck >= 0 && ck < CM_D) cube = ci + CM_W * cj + CM_W * CM_H * ck;
-        A.keys[i] = (unsigned long long)(cube >= 0 ? cube : CM_N);
-        A.vals[i] = i;
-    }
-    unsigned long long todo = __ballot(cube >= 0);
-    while (todo) {
-        const int c0 = __shfl(cube, __ffsll((long long)todo) - 1);
-        const unsigned long long same = __ballot(cube == c0);
-        if ((threadIdx.x & 63) == __ffsll((long long)same) - 1) atomicAdd(&A.addcnt[c0], __popcll(same));
-        todo &= ~same;
-    }
+    cm_assign_one(A.stk, A.n, A.pose, A.cen, 0, 1, A.tp, A.keys, A.vals, A.addcnt, b.y + threadIdx.x);
 }
 
 /* ------------------------------------------------------------------ host side */

@@ -7,24 +7,16 @@
  *   transformAssociateToMap, laserMapping.cpp:113-117, straight into the cube maps' pose array), the cube-map frame from those
  *   guesses (ll_cubemaps.hip: they come to the host with the slot headers it reads back anyway), k_drives_update
  *   (transformUpdate, :119-123) and, with keep_registered, k_drives_register (pointAssociateToMap of laserCloud, :125-133).
- * The pose arithmetic restates lightloam::WorldPose::compose and LaserMapping::qmul / qrot (lightloam_host.hpp) in their
- * operation order, in double; the library is built with -ffp-contract=off, so it is bit for bit the host's.  No fma(), no
+ * The pose arithmetic restates lightloam::WorldPose::compose and LaserMapping::qmul / qrot (lightloam_host.hpp;
+ * qrot is ll_rotate of ll_factor_math.h) in their operation order, in double; the library is built with -ffp-contract=off, so it is bit for bit the host's.  No fma(), no
  * reassociation here.
  * A lane may instead localise against another lane's frozen map (ll_drives_set_localize): the same chain with the read-only frame
  * of ll_cubemaps_localize_slots in place of the mapping frame; a step runs the mapping lanes' frame, then the localising lanes',
  * and refuses beforehand any command set in which one would write what the other reads.
  */
 #include "ll_cubemap.h"
+#include "ll_factor_math.h"
 #include <cmath>
-
-/* q (x, y, z, w) * v, LaserMapping::qrot */
-__device__ __forceinline__ void drv_qrot(const double *q, const double *v, double *o)
-{
-    const double ux = q[0], uy = q[1], uz = q[2], w = q[3];
-    double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
-    uvx += uvx; uvy += uvy; uvz += uvz;
-    o[0] = v[0] + w * uvx + (uy * uvz - uz * uvy); o[1] = v[1] + w * uvy + (uz * uvx - ux * uvz); o[2] = v[2] + w * uvz + (ux * uvy - uy * uvx);
-}
 
 /* a * b, LaserMapping::qmul */
 __device__ __forceinline__ void drv_qmul(const double *a, const double *b, double *o)
@@ -48,7 +40,7 @@ __global__ __launch_bounds__(64) void k_drives_associate(double *vpose, int firs
         for (int k = 0; k < 7; ++k) { W[k] = k == 3 ? 1.0 : 0.0; M[k] = start[(size_t)q * 7 + k]; }   /* identity for a mapping lane; where a localising lane's drive begins in the map */
         for (int k = 0; k < 7; ++k) slot_pose[k] = pose0[(size_t)q * 7 + k];     /* the warm start of frame 1 (:61-65) */
         fidx[q] = 0;
-    } else {                                                                      /* WorldPose::compose (:830-831) */
+    } else {                                                                      /* WorldPose::compose (:830-831), kept as the host spells it: W is updated in place, t before q */
         const double ql[4] = {slot_pose[0], slot_pose[1], slot_pose[2], slot_pose[3]}, tl[3] = {slot_pose[4], slot_pose[5], slot_pose[6]};
         const double ux = W[0], uy = W[1], uz = W[2], w = W[3];
         double uv[3] = {uy * tl[2] - uz * tl[1], uz * tl[0] - ux * tl[2], ux * tl[1] - uy * tl[0]};
@@ -65,7 +57,7 @@ __global__ __launch_bounds__(64) void k_drives_associate(double *vpose, int firs
     }
     double P[7], r[3];                                                            /* transformAssociateToMap (:113-117) */
     drv_qmul(M, W, P);
-    drv_qrot(M, W + 4, r);
+    ll_rotate(M, W + 4, r);
     for (int k = 0; k < 3; ++k) P[4 + k] = r[k] + M[4 + k];
     for (int k = 0; k < 7; ++k) map_pose[(size_t)q * 7 + k] = P[k];
 }
@@ -81,7 +73,7 @@ __global__ __launch_bounds__(64) void k_drives_update(int S, const int *cmd, con
     const double inv[4] = {-qc[0] / n2, -qc[1] / n2, -qc[2] / n2, qc[3] / n2};
     double qm[4], r[3];
     drv_qmul(P, inv, qm);
-    drv_qrot(qm, tc, r);
+    ll_rotate(qm, tc, r);
     for (int k = 0; k < 4; ++k) M[k] = qm[k];
     for (int k = 0; k < 3; ++k) M[4 + k] = P[4 + k] - r[k];
 }
@@ -98,14 +90,8 @@ __global__ __launch_bounds__(256) void k_drives_register(LLView V, const DrvReg 
     const int off = ring_off[r], n = min(ring_off[r + 1] - off, V.ring_cap);
     if (i >= n || off + i >= V.CS || off < 0) return;
     const float4 p = V.cloud[(size_t)L.slot * V.CS + (size_t)r * V.ring_cap + i];
-    const double *pose = map_pose + (size_t)L.lane * 7;
-    const double ux = pose[0], uy = pose[1], uz = pose[2], w = pose[3];
-    const double v[3] = {(double)p.x, (double)p.y, (double)p.z};
-    double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
-    uvx += uvx; uvy += uvy; uvz += uvz;
-    const float sx = (float)(((v[0] + w * uvx) + (uy * uvz - uz * uvy)) + pose[4]);
-    const float sy = (float)(((v[1] + w * uvy) + (uz * uvx - ux * uvz)) + pose[5]);
-    const float sz = (float)(((v[2] + w * uvz) + (ux * uvy - uy * uvx)) + pose[6]);
+    float sx, sy, sz;
+    ll_map_to_world(map_pose + (size_t)L.lane * 7, p, sx, sy, sz);
     out[(size_t)L.lane * V.CS + off + i] = make_float4(sx, sy, sz, p.w);
 }
 

@@ -9,6 +9,18 @@
 
 struct Pose { double q[4], t[3]; };
 
+/* q (x, y, z, w) * v: Eigen's _transformVector, uv = u x v; uv += uv; v + w*uv + u x uv (LaserMapping::qrot on the host) */
+__device__ __forceinline__ void ll_rotate(const double q[4], const double v[3], double out[3])
+{
+    const double ux = q[0], uy = q[1], uz = q[2], w = q[3];
+    double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
+    uvx += uvx; uvy += uvy; uvz += uvz;
+    out[0] = (v[0] + w * uvx) + (uy * uvz - uz * uvy);
+    out[1] = (v[1] + w * uvy) + (uz * uvx - ux * uvz);
+    out[2] = (v[2] + w * uvz) + (ux * uvy - uy * uvx);
+}
+
+/* spells ll_rotate out once more: the Jacobian reuses uv (d lp / d w) */
 __device__ __forceinline__ void ll_lp_and_jac(const Pose &P, const double v[3], double lp[3], double Jq[3][4])
 {
     const double ux = P.q[0], uy = P.q[1], uz = P.q[2], w = P.q[3];

@@ -5,49 +5,24 @@
  * plain sums of squares of the edge and the plane residuals.  Nothing here changes a pose or a map.
  */
 #include "ll_cubemap.h"
-#include "ll_factor_math.h"
+#include "ll_map_neq.h"
 
-#define LL_FIT_NACC 3     /* cost, sq_edge, sq_plane */
-
-/* one workgroup per view: the rows of k_map_normal_eq without the Jacobians' products, summed in f64 -- per thread, then over the
- * wave, then over the four waves through LDS in wave order.  The record of view v goes to fit[(views[v].pose - pose0) / 7], the
- * sequence the view's pose row belongs to, with plain stores by thread 0. */
+/* one workgroup per view: the blocks of k_map_normal_eq without the Jacobians' products (ll_map_fit_edge / _plane, ll_map_neq.h),
+ * summed in f64 -- per thread, then over the wave, then over the four waves through LDS in wave order.  The record of view v goes
+ * to fit[(views[v].pose - pose0) / 7], the sequence the view's pose row belongs to, with plain stores by thread 0. */
 __global__ __launch_bounds__(256) void k_cms_fit(const LLMapView *views, const double *pose0, ll_localize_fit *fit)
 {
     const LLMapView &M = views[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n_e = M.counts[0], n_p = M.counts[1];
-    Pose P;
-    for (int k = 0; k < 4; ++k) P.q[k] = M.pose[k];
-    for (int k = 0; k < 3; ++k) P.t[k] = M.pose[4 + k];
-    double acc[LL_FIT_NACC] = {0.0, 0.0, 0.0};
-    for (int i = tid; i < n_e; i += 256) {
-        double r[3], Jq[3][4], Jt[3][3];
-        ll_edge_d(P, M.stk[0][M.src[0][i]], &M.fa[(size_t)i * 3], &M.fb[(size_t)i * 3], r, Jq, Jt);
-        const double sq = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-        (void)ll_huber_scale(sq, M.huber, acc[0]);
-        acc[1] += sq;
-    }
-    for (int i = tid; i < n_p; i += 256) {
-        double r, Jq[4], Jt[3];
-        ll_plane_norm(P, M.stk[1][M.src[1][i]], &M.fn[(size_t)i * 3], M.fd[i], r, Jq, Jt);
-        (void)ll_huber_scale(r * r, M.huber, acc[0]);
-        acc[2] += r * r;
-    }
+    const int tid = threadIdx.x;
+    const Pose P = ll_pose_load(M.pose);
+    double acc[LL_FIT_NACC] = {0.0, 0.0, 0.0};                    /* cost, sq_edge, sq_plane */
+    ll_map_acc_blocks(M, P, tid, 256, acc);
     __shared__ double red[4][LL_FIT_NACC];
-#pragma unroll
-    for (int k = 0; k < LL_FIT_NACC; ++k) {
-        double v = acc[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
+    ll_wg_sum<LL_FIT_NACC>(acc, red);
     if (tid == 0) {
         ll_localize_fit F;
-        F.n_edge = n_e; F.n_plane = n_p;
-        F.cost = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        F.sq_edge = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-        F.sq_plane = ((red[0][2] + red[1][2]) + red[2][2]) + red[3][2];
+        F.n_edge = M.counts[0]; F.n_plane = M.counts[1];
+        F.cost = ll_wg_total(red, 0); F.sq_edge = ll_wg_total(red, 1); F.sq_plane = ll_wg_total(red, 2);
         fit[(M.pose - pose0) / 7] = F;
     }
 }

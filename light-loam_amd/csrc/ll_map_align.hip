@@ -36,7 +36,7 @@
  */
 #include "ll_cubemap.h"
 #include "ll_factor_math.h"
-#include "ll_lm_step.h"
+#include "ll_map_neq.h"
 #include "ll_map_search.h"
 #include <cmath>
 
@@ -262,9 +262,7 @@ __global__ __launch_bounds__(LL_KNNB) void k_al_place(const LLMapView *views, co
     const unsigned long long m = __ballot(ok);
     if (!ok) return;
     const int pos = blkbase[blockIdx.x] + __popcll(m & ((1ull << threadIdx.x) - 1ull));
-    M.src[which][pos] = i;
-    if (which == 0) for (int k = 0; k < 3; ++k) { M.fa[(size_t)pos * 3 + k] = M.qa[(size_t)i * 3 + k]; M.fb[(size_t)pos * 3 + k] = M.qb[(size_t)i * 3 + k]; }
-    else { for (int k = 0; k < 3; ++k) M.fn[(size_t)pos * 3 + k] = M.qn[(size_t)i * 3 + k]; M.fd[pos] = M.qd[i]; }
+    ll_map_place(M, which, pos, i);
 }
 
 /* workgroup b: chunk chunks[b].y of op chunks[b].x -- blocks j0 .. j0 + AL_CHUNK - 1 of the op's edges-then-planes order, block
@@ -276,56 +274,21 @@ __global__ __launch_bounds__(256) void k_al_eval(const LLMapView *views, const i
 {
     const int2 c = chunks[blockIdx.x];
     const LLMapView &M = views[c.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tid = threadIdx.x;
     const int n_e = M.counts[0], n_p = M.counts[1], j0 = c.y * AL_CHUNK;
     if (j0 >= n_e + n_p) return;
-    Pose P;
-    for (int k = 0; k < 4; ++k) P.q[k] = M.pose[k];
-    for (int k = 0; k < 3; ++k) P.t[k] = M.pose[4 + k];
+    const Pose P = ll_pose_load(M.pose);
     double acc[LL_NACC];
 #pragma unroll
     for (int k = 0; k < LL_NACC; ++k) acc[k] = 0.0;
     for (int u = 0; u < AL_CHUNK / 256; ++u) {
         const int j = j0 + u * 256 + tid;
-        if (j < n_e) {
-            double r[3], Jq[3][4], Jt[3][3];
-            ll_edge_d(P, M.stk[0][M.src[0][j]], &M.fa[(size_t)j * 3], &M.fb[(size_t)j * 3], r, Jq, Jt);
-            const double sq = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-            if (FIT) { (void)ll_huber_scale(sq, M.huber, acc[0]); acc[1] += sq; }
-            else {
-                const double sc = ll_huber_scale(sq, M.huber, acc[27]);
-                for (int row = 0; row < 3; ++row) {
-                    double J[6];
-                    ll_to_local(P, Jq[row], J);
-                    J[3] = Jt[row][0]; J[4] = Jt[row][1]; J[5] = Jt[row][2];
-                    for (int k = 0; k < 6; ++k) J[k] *= sc;
-                    ll_acc_row(acc, J, r[row] * sc);
-                }
-            }
-        } else if (j < n_e + n_p) {
-            const int i = j - n_e;
-            double r, Jq[4], Jt[3], J[6];
-            ll_plane_norm(P, M.stk[1][M.src[1][i]], &M.fn[(size_t)i * 3], M.fd[i], r, Jq, Jt);
-            if (FIT) { (void)ll_huber_scale(r * r, M.huber, acc[0]); acc[2] += r * r; }
-            else {
-                const double sc = ll_huber_scale(r * r, M.huber, acc[27]);
-                ll_to_local(P, Jq, J);
-                J[3] = Jt[0]; J[4] = Jt[1]; J[5] = Jt[2];
-                for (int k = 0; k < 6; ++k) J[k] *= sc;
-                ll_acc_row(acc, J, r * sc);
-            }
-        }
+        if (j < n_e) { if (FIT) ll_map_fit_edge(M, P, j, acc); else ll_map_acc_edge(M, P, j, acc); }
+        else if (j < n_e + n_p) { if (FIT) ll_map_fit_plane(M, P, j - n_e, acc); else ll_map_acc_plane(M, P, j - n_e, acc); }
     }
     __shared__ double red[4][LL_NACC];
-#pragma unroll
-    for (int k = 0; k < LL_NACC; ++k) {
-        if (FIT && k >= 3) break;
-        double v = acc[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
-    if (tid < (FIT ? 3 : LL_NACC)) part[(size_t)blockIdx.x * LL_NACC + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    ll_wg_sum<(FIT ? LL_FIT_NACC : LL_NACC)>(acc, red);
+    if (tid < (FIT ? LL_FIT_NACC : LL_NACC)) part[(size_t)blockIdx.x * LL_NACC + tid] = ll_wg_total(red, tid);
 }
 
 /* one wave per op: round `round` of k_cms_lm's loop on the partials of the evaluation at the op's pose, summed in chunk order */
@@ -335,23 +298,13 @@ __global__ __launch_bounds__(64) void k_al_solve(const LLMapView *views, const A
     const int tid = threadIdx.x, n_e = M.counts[0], n_p = M.counts[1];
     const int used = (n_e + n_p + AL_CHUNK - 1) / AL_CHUNK;
     __shared__ double stot[LL_NACC], sneq[LL_NEQ_STRIDE], sL[LL_LM_STRIDE], sp[7];
-    if (tid < LL_NACC) {
-        const double *p = part + (size_t)ops[blockIdx.x].chunk0 * LL_NACC + tid;
-        double v = 0.0;
-        for (int c = 0; c < used; ++c) v += p[(size_t)c * LL_NACC];
-        stot[tid] = v;
-    }
+    if (tid < LL_NACC) stot[tid] = ll_partials_sum(part + (size_t)ops[blockIdx.x].chunk0 * LL_NACC, used, tid);
     for (int k = tid; k < LL_LM_STRIDE; k += 64) sL[k] = round == 0 ? 0.0 : M.lm[k];
     if (tid < 7) sp[tid] = M.pose[tid];
     __syncthreads();
     if (tid == 0) {
-        int k = 0;
-        for (int a = 0; a < 6; ++a) for (int b = a; b < 6; ++b) { sneq[a * 6 + b] = stot[k]; sneq[b * 6 + a] = stot[k]; ++k; }
-        for (int a = 0; a < 6; ++a) sneq[36 + a] = stot[21 + a];
-        sneq[42] = stot[27];
-        sneq[43] = (double)(3 * n_e + n_p);
-        if (round == 0) ll_lm_begin_one(sL, sneq, sp, o); else ll_lm_accept_one(sL, sneq, sp, o);
-        if (round < o.max_num_iterations) ll_lm_propose_one(sL, sp, o);
+        ll_neq_unpack(stot, 3 * n_e + n_p, sneq);
+        ll_lm_round(sL, sneq, sp, o, round);
     }
     __syncthreads();
     if (tid < 7) M.pose[tid] = sp[tid];
@@ -364,13 +317,8 @@ __global__ __launch_bounds__(64) void k_al_fitsum(const LLMapView *views, const 
     const LLMapView &M = views[blockIdx.x];
     const int tid = threadIdx.x, n_e = M.counts[0], n_p = M.counts[1];
     const int used = (n_e + n_p + AL_CHUNK - 1) / AL_CHUNK;
-    __shared__ double stot[3];
-    if (tid < 3) {
-        const double *p = part + (size_t)ops[blockIdx.x].chunk0 * LL_NACC + tid;
-        double v = 0.0;
-        for (int c = 0; c < used; ++c) v += p[(size_t)c * LL_NACC];
-        stot[tid] = v;
-    }
+    __shared__ double stot[LL_FIT_NACC];
+    if (tid < LL_FIT_NACC) stot[tid] = ll_partials_sum(part + (size_t)ops[blockIdx.x].chunk0 * LL_NACC, used, tid);
     __syncthreads();
     if (tid == 0) {
         ll_localize_fit F;

@@ -53,8 +53,9 @@ __global__ __launch_bounds__(256) void k_mm_assign(const MmSeg *seg, int nseg, c
     const MmSeg s = seg[mm_find(seg, nseg, blockIdx.x)];
     const MmRec &R = recs[s.rec];
     const int first = (int)(blockIdx.x - s.tile0) * MM_TILE, n = min(MM_TILE, s.cnt - first);
-    const double ux = R.T[0], uy = R.T[1], uz = R.T[2], w = R.T[3], tx = R.T[4], ty = R.T[5], tz = R.T[6];
-    const int cenx = R.cen[0], ceny = R.cen[1], cenz = R.cen[2];
+    double T[7]; int cen[3];                                      /* like the points: every load before the first store */
+    for (int k = 0; k < 7; ++k) T[k] = R.T[k];
+    for (int k = 0; k < 3; ++k) cen[k] = R.cen[k];
     int *cnt = addcnt + (size_t)s.rec * MM_BINS;
     float4 po[MM_TILE / 256];
 #pragma unroll
@@ -64,28 +65,17 @@ __global__ __launch_bounds__(256) void k_mm_assign(const MmSeg *seg, int nseg, c
         const int i = k * 256 + (int)threadIdx.x;
         int cube = -1;                                            /* -1: no point */
         if (i < n) {
-            /* pointAssociateToMap (:125-134) in k_cm_assign's operation order; the pose is used as given, never normalised */
-            const double v[3] = {(double)po[k].x, (double)po[k].y, (double)po[k].z};
-            double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
-            uvx += uvx; uvy += uvy; uvz += uvz;
-            const float sx = (float)(((v[0] + w * uvx) + (uy * uvz - uz * uvy)) + tx);
-            const float sy = (float)(((v[1] + w * uvy) + (uz * uvx - ux * uvz)) + ty);
-            const float sz = (float)(((v[2] + w * uvz) + (ux * uvy - uy * uvx)) + tz);
+            /* pointAssociateToMap (:125-134) and the cube (:2108-2125) as a frame's update has them (ll_map_to_world, cm_cube_of); the
+             * pose is used as given, never normalised */
+            float sx, sy, sz;
+            ll_map_to_world(T, po[k], sx, sy, sz);
             tp[s.dst + first + i] = make_float4(sx, sy, sz, po[k].w);
-            int ci = (int)(((double)sx + 25.0) / 50.0) + cenx, cj = (int)(((double)sy + 25.0) / 50.0) + ceny, ck = (int)(((double)sz + 25.0) / 50.0) + cenz;   /* :2108-2125 */
-            if ((double)sx + 25.0 < 0) ci--;
-            if ((double)sy + 25.0 < 0) cj--;
-            if ((double)sz + 25.0 < 0) ck--;
-            cube = (ci >= 0 && ci < CM_W && cj >= 0 && cj < CM_H && ck >= 0 && ck < CM_D) ? ci + CM_W * cj + CM_W * CM_H * ck : CM_N;
+            int ci, cj, ck;
+            cube = cm_cube_of(sx, sy, sz, cen, &ci, &cj, &ck);
+            if (cube < 0) cube = CM_N;                            /* outside the array: a bin of its own */
             keys[s.dst + first + i] = cube;
         }
-        unsigned long long todo = __ballot(cube >= 0);            /* one add per wave and cube */
-        while (todo) {
-            const int c0 = __shfl(cube, __ffsll((long long)todo) - 1);
-            const unsigned long long same = __ballot(cube == c0);
-            if ((threadIdx.x & 63) == __ffsll((long long)same) - 1) atomicAdd(&cnt[c0], __popcll(same));
-            todo &= ~same;
-        }
+        cm_wave_count(cube, cnt);                                 /* one add per wave and cube */
     }
 }
 

@@ -124,6 +124,14 @@ __device__ __forceinline__ void ll_map_to_world(const double *pose, const float4
     sz = (float)(((v[2] + w * uvz) + (ux * uvy - uy * uvx)) + pose[6]);
 }
 
+/* residual block `pos` of cloud type `which` <- the fit of stack point i (ll_map_fit leaves it in q*, the solves read f*) */
+__device__ __forceinline__ void ll_map_place(const LLMapView &M, int which, int pos, int i)
+{
+    M.src[which][pos] = i;
+    if (which == 0) for (int k = 0; k < 3; ++k) { M.fa[(size_t)pos * 3 + k] = M.qa[(size_t)i * 3 + k]; M.fb[(size_t)pos * 3 + k] = M.qb[(size_t)i * 3 + k]; }
+    else { for (int k = 0; k < 3; ++k) M.fn[(size_t)pos * 3 + k] = M.qn[(size_t)i * 3 + k]; M.fd[pos] = M.qd[i]; }
+}
+
 /* insertion of (d, j[, p]) into five slots kept ascending by (distance, index) */
 template <bool WITH_PT>
 __device__ __forceinline__ void ll_five_insert(float bd[5], int bi[5], float4 bp[5], int &nb, float d, int j, const float4 &p)

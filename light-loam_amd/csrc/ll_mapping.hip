@@ -17,12 +17,13 @@
  *                           are within 0.2 of the plane.
  *   k_map_compact       residual blocks in stack order (the order AddResidualBlock sees them).
  *   k_map_normal_eq     LidarEdgeFactor + LidarPlaneNormFactor rows (lidarFactor.hpp:9-52, :253-285), HuberLoss(0.1),
- *                       EigenQuaternionManifold, 28 f64 accumulators per thread -> shuffle tree -> LDS.
+ *                       EigenQuaternionManifold, 28 f64 accumulators per thread -> shuffle tree -> LDS: the arithmetic is
+ *                       ll_map_neq.h's, shared with every other solve of this problem.
  * The LM iterations reuse k_lm_begin / k_lm_propose / k_lm_accept of ll_factors.hip on a one-slot view.
  * Everything after the f32 distances is f64; parity with the oracle is to rounding (1e-9), the selected blocks exact.
  */
 #include "ll_factor_math.h"
-#include "ll_lm_step.h"
+#include "ll_map_neq.h"
 #include "ll_map_search.h"
 #include <limits.h>
 #include <string.h>
@@ -226,51 +227,20 @@ __global__ __launch_bounds__(LL_CMPB) void k_map_compact(LLMapView M, int blocks
 
 __global__ __launch_bounds__(256) void k_map_normal_eq(LLMapView M)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tid = threadIdx.x;
     const int gtid = blockIdx.x * 256 + tid, gsz = LL_NEQ_NB * 256;
-    Pose P;
-    for (int k = 0; k < 4; ++k) P.q[k] = M.pose[k];
-    for (int k = 0; k < 3; ++k) P.t[k] = M.pose[4 + k];
+    const Pose P = ll_pose_load(M.pose);
     const int n_e = M.counts[0], n_p = M.counts[1];
     double acc[LL_NACC];
 #pragma unroll
     for (int k = 0; k < LL_NACC; ++k) acc[k] = 0.0;
     const int rw = M.row_world > 1 ? M.row_world : 1, rr = M.row_world > 1 ? M.row_rank : 0;   /* this rank's share of the blocks */
-    for (int i = rr + rw * gtid; i < n_e; i += gsz * rw) {
-        double r[3], Jq[3][4], Jt[3][3];
-        ll_edge_d(P, M.stk[0][M.src[0][i]], &M.fa[(size_t)i * 3], &M.fb[(size_t)i * 3], r, Jq, Jt);
-        const double sc = ll_huber_scale(r[0] * r[0] + r[1] * r[1] + r[2] * r[2], M.huber, acc[27]);
-        for (int row = 0; row < 3; ++row) {
-            double J[6];
-            ll_to_local(P, Jq[row], J);
-            J[3] = Jt[row][0]; J[4] = Jt[row][1]; J[5] = Jt[row][2];
-            for (int k = 0; k < 6; ++k) J[k] *= sc;
-            ll_acc_row(acc, J, r[row] * sc);
-        }
-    }
-    for (int i = rr + rw * gtid; i < n_p; i += gsz * rw) {
-        double r, Jq[4], Jt[3], J[6];
-        ll_plane_norm(P, M.stk[1][M.src[1][i]], &M.fn[(size_t)i * 3], M.fd[i], r, Jq, Jt);
-        const double sc = ll_huber_scale(r * r, M.huber, acc[27]);
-        ll_to_local(P, Jq, J);
-        J[3] = Jt[0]; J[4] = Jt[1]; J[5] = Jt[2];
-        for (int k = 0; k < 6; ++k) J[k] *= sc;
-        ll_acc_row(acc, J, r * sc);
-    }
+    ll_map_acc_blocks(M, P, rr + rw * gtid, gsz * rw, acc);
     __shared__ double red[4][LL_NACC];
     __shared__ double tot[LL_NACC];
     __shared__ int s_last;
-#pragma unroll
-    for (int k = 0; k < LL_NACC; ++k) {
-        double v = acc[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
-    if (tid < LL_NACC) {
-        const double v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-        __hip_atomic_store(&M.neq_part[blockIdx.x * LL_NACC + tid], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    ll_wg_sum<LL_NACC>(acc, red);
+    if (tid < LL_NACC) __hip_atomic_store(&M.neq_part[blockIdx.x * LL_NACC + tid], ll_wg_total(red, tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __threadfence();
     __syncthreads();
     if (tid == 0) s_last = (__hip_atomic_fetch_add(M.neq_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == LL_NEQ_NB - 1);
@@ -280,26 +250,17 @@ __global__ __launch_bounds__(256) void k_map_normal_eq(LLMapView M)
     for (int e = tid; e < LL_NEQ_NB * LL_NACC; e += 256)
         spart[e] = __hip_atomic_load(&M.neq_part[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    if (tid < LL_NACC) {
-        double v = 0.0;
-        for (int b = 0; b < LL_NEQ_NB; ++b) v += spart[b * LL_NACC + tid];
-        tot[tid] = v;
-    }
+    if (tid < LL_NACC) tot[tid] = ll_partials_sum(spart, LL_NEQ_NB, tid);
     __syncthreads();
     if (tid == 0) {
-        double *out = M.neq;
-        int k = 0;
-        for (int a = 0; a < 6; ++a) for (int b = a; b < 6; ++b) { out[a * 6 + b] = tot[k]; out[b * 6 + a] = tot[k]; ++k; }
-        for (int a = 0; a < 6; ++a) out[36 + a] = tot[21 + a];
-        out[42] = tot[27];
-        out[43] = (double)(3 * ((n_e - rr + rw - 1) / rw) + (n_p - rr + rw - 1) / rw);   /* rows summed here */
+        ll_neq_unpack(tot, 3 * ((n_e - rr + rw - 1) / rw) + (n_p - rr + rw - 1) / rw, M.neq);   /* the rows summed here */
         __hip_atomic_store(M.neq_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   /* for the next launch */
     }
 }
 
 /* One ceres::Solve (:2072-2082) in ONE launch: evaluate, begin, n x (propose, evaluate, accept) on the LL_NEQ_NB workgroups of
  * k_map_normal_eq, which stay resident for the whole solve.  Every round all workgroups sum their rows at the current pose
- * (the same partition and the same fixed order of the partial sums as k_map_normal_eq: bit-identical normal equations);
+ * (ll_map_neq.h: the block sums, the partition and the order of the partial sums that k_map_normal_eq uses -- bit-identical normal equations);
  * workgroup 0 waits for the LL_NEQ_NB partial sums, takes the single-thread trust-region step (ll_lm_step.h, state in its LDS),
  * publishes the next pose and releases the others.  Partial sums, pose, arrival counter and round counter cross the
  * workgroups (and the XCDs) as agent-scope atomics; every wait is bounded and a time-out leaves a NaN pose (fails loudly).
@@ -307,7 +268,7 @@ __global__ __launch_bounds__(256) void k_map_normal_eq(LLMapView M)
  * stay for the row-parallel mode, where an all-reduce sits between evaluate and accept). */
 __global__ __launch_bounds__(256) void k_map_lm_solve(LLMapView M, LLLmOpt o)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tid = threadIdx.x;
     const int wg = blockIdx.x;
     const int gtid = wg * 256 + tid, gsz = LL_NEQ_NB * 256;
     const int n_e = M.counts[0], n_p = M.counts[1];
@@ -330,44 +291,13 @@ __global__ __launch_bounds__(256) void k_map_lm_solve(LLMapView M, LLLmOpt o)
             if (tid < 7) sp[tid] = __hip_atomic_load(&M.pose[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __syncthreads();
-        Pose P;
-        for (int k = 0; k < 4; ++k) P.q[k] = sp[k];
-        for (int k = 0; k < 3; ++k) P.t[k] = sp[4 + k];
+        const Pose P = ll_pose_load(sp);
         double acc[LL_NACC];
 #pragma unroll
         for (int k = 0; k < LL_NACC; ++k) acc[k] = 0.0;
-        for (int i = gtid; i < n_e; i += gsz) {
-            double r[3], Jq[3][4], Jt[3][3];
-            ll_edge_d(P, M.stk[0][M.src[0][i]], &M.fa[(size_t)i * 3], &M.fb[(size_t)i * 3], r, Jq, Jt);
-            const double sc = ll_huber_scale(r[0] * r[0] + r[1] * r[1] + r[2] * r[2], M.huber, acc[27]);
-            for (int row = 0; row < 3; ++row) {
-                double J[6];
-                ll_to_local(P, Jq[row], J);
-                J[3] = Jt[row][0]; J[4] = Jt[row][1]; J[5] = Jt[row][2];
-                for (int k = 0; k < 6; ++k) J[k] *= sc;
-                ll_acc_row(acc, J, r[row] * sc);
-            }
-        }
-        for (int i = gtid; i < n_p; i += gsz) {
-            double r, Jq[4], Jt[3], J[6];
-            ll_plane_norm(P, M.stk[1][M.src[1][i]], &M.fn[(size_t)i * 3], M.fd[i], r, Jq, Jt);
-            const double sc = ll_huber_scale(r * r, M.huber, acc[27]);
-            ll_to_local(P, Jq, J);
-            J[3] = Jt[0]; J[4] = Jt[1]; J[5] = Jt[2];
-            for (int k = 0; k < 6; ++k) J[k] *= sc;
-            ll_acc_row(acc, J, r * sc);
-        }
-#pragma unroll
-        for (int k = 0; k < LL_NACC; ++k) {
-            double v = acc[k];
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-            if (lane == 0) red[wave][k] = v;
-        }
-        __syncthreads();
-        if (tid < LL_NACC) {
-            const double v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-            __hip_atomic_store(&M.neq_part[wg * LL_NACC + tid], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        ll_map_acc_blocks(M, P, gtid, gsz, acc);
+        ll_wg_sum<LL_NACC>(acc, red);
+        if (tid < LL_NACC) __hip_atomic_store(&M.neq_part[wg * LL_NACC + tid], ll_wg_total(red, tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __threadfence();
         __syncthreads();
         if (tid == 0) __hip_atomic_fetch_add(M.neq_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
@@ -383,21 +313,12 @@ __global__ __launch_bounds__(256) void k_map_lm_solve(LLMapView M, LLLmOpt o)
         for (int e = tid; e < LL_NEQ_NB * LL_NACC; e += 256)      /* all loads in flight at once, the sums in workgroup order */
             spart[e] = __hip_atomic_load(&M.neq_part[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
-        if (tid < LL_NACC) {
-            double v = 0.0;
-            for (int b = 0; b < LL_NEQ_NB; ++b) v += spart[b * LL_NACC + tid];
-            stot[tid] = v;
-        }
+        if (tid < LL_NACC) stot[tid] = ll_partials_sum(spart, LL_NEQ_NB, tid);
         __syncthreads();
         if (tid == 0) {
-            int k = 0;
-            for (int a = 0; a < 6; ++a) for (int b = a; b < 6; ++b) { sneq[a * 6 + b] = stot[k]; sneq[b * 6 + a] = stot[k]; ++k; }
-            for (int a = 0; a < 6; ++a) sneq[36 + a] = stot[21 + a];
-            sneq[42] = stot[27];
-            sneq[43] = (double)(3 * n_e + n_p);
-            if (round == 0) ll_lm_begin_one(sL, sneq, sp, o); else ll_lm_accept_one(sL, sneq, sp, o);
-            if (round < o.max_num_iterations) {
-                ll_lm_propose_one(sL, sp, o);
+            ll_neq_unpack(stot, 3 * n_e + n_p, sneq);
+            ll_lm_round(sL, sneq, sp, o, round);
+            if (round < o.max_num_iterations) {                   /* the next pose, then the others' release */
                 for (int q = 0; q < 7; ++q) __hip_atomic_store(&M.pose[q], sp[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(M.lm_go, (unsigned)(round + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -420,9 +341,7 @@ __global__ __launch_bounds__(256) void k_map_lm_solve(LLMapView M, LLLmOpt o)
 /* what ceres::CostFunction::Evaluate returns for the blocks (loss not applied): edges first (3 rows each), then planes */
 __global__ __launch_bounds__(LL_MAPB) void k_map_rows(LLMapView M, double *r_out, double *Jq_out, double *Jt_out)
 {
-    Pose P;
-    for (int k = 0; k < 4; ++k) P.q[k] = M.pose[k];
-    for (int k = 0; k < 3; ++k) P.t[k] = M.pose[4 + k];
+    const Pose P = ll_pose_load(M.pose);
     const int n_e = M.counts[0], n_p = M.counts[1];
     const int gtid = blockIdx.x * LL_MAPB + threadIdx.x, gsz = gridDim.x * LL_MAPB;
     for (int i = gtid; i < n_e; i += gsz) {
