@@ -1,16 +1,13 @@
 /*
- * ll_cubemap.h -- what ll_cubemap.hip (one cube map) and ll_cubemaps.hip (S cube maps side by side) share: the cube array's
- * dimensions, the copy descriptor, the state behind an ll_cubemap handle and the host-side bookkeeping of the pair tables.
+ * ll_cubemap.h -- what ll_cubemap.hip (one cube map) and ll_cubemaps.hip (S cube maps side by side) share: the device-side cube
+ * arithmetic, the copy descriptor and the state behind an ll_cubemap handle.  The cube array's dimensions and the host-side
+ * bookkeeping of the pair tables are ll_cubemap_tables.h.
  */
 #pragma once
 #include "ll_internal.h"
 #include "ll_map_search.h"
-#include <algorithm>
+#include "ll_cubemap_tables.h"
 
-#define CM_W 21
-#define CM_H 21
-#define CM_D 11
-#define CM_N (CM_W * CM_H * CM_D)     /* 4851 (:53) */
 #define CM_MAX_OPS 16384
 
 struct CmOp { int kind, src, cnt, dst, tag; };   /* kind 0: pool[src + i]; kind 1: points[index[src + i]]; tag + i: global id */
@@ -101,17 +98,12 @@ struct LLMapAlign {
     long long counts[3] = {0, 0, 0};              /* stack points, map points, residual blocks at the end */
 };
 
-struct ll_cubemap {
+struct ll_cubemap : CmTables {                   /* the pair tables (ll_cubemap_tables.h) and the device memory they describe */
     ll_ctx *ctx = nullptr;
     ll_map *map = nullptr;
     float leaf[2] = {0.4f, 0.8f};
-    int cen[3] = {10, 10, 5};
     int cap_last[2] = {0, 0};
-    size_t cap_pool = 0, top[2] = {0, 0};
     float4 *pool[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    int cur[2] = {0, 0};
-    std::vector<int> off[2], cnt[2];
-    int valid[125]; int n_valid = 0;
     int rank = 0, world = 1;                      /* tile shard: this map keeps the cubes with cm_owner() == rank */
     float4 *d_last = nullptr;
     /* ll_cubemap_update runs both cloud types through every stage before it synchronises: one set of buffers per type */
@@ -135,28 +127,8 @@ struct ll_cubemap {
         if (e_ != hipSuccess) { cm->err = std::string(#call) + ": " + hipGetErrorString(e_); return LL_ERR_HIP; } \
     } while (0)
 
-/* one step of a shift loop (:1598-1778) on the pair tables */
-static void cm_shift(ll_cubemap *cm, int axis, int dir)
-{
-    const int dim[3] = {CM_W, CM_H, CM_D}, stride[3] = {1, CM_W, CM_W * CM_H};
-    const int a1 = (axis + 1) % 3, a2 = (axis + 2) % 3;
-    for (int w = 0; w < 2; ++w)
-        for (int u = 0; u < dim[a1]; ++u) for (int v = 0; v < dim[a2]; ++v) {
-            const int base = u * stride[a1] + v * stride[a2];
-            std::vector<int> &off = cm->off[w], &cnt = cm->cnt[w];
-            if (dir > 0) {
-                for (int i = dim[axis] - 1; i >= 1; --i) { off[base + i * stride[axis]] = off[base + (i - 1) * stride[axis]]; cnt[base + i * stride[axis]] = cnt[base + (i - 1) * stride[axis]]; }
-                cnt[base] = 0; off[base] = 0;
-            } else {
-                for (int i = 0; i < dim[axis] - 1; ++i) { off[base + i * stride[axis]] = off[base + (i + 1) * stride[axis]]; cnt[base + i * stride[axis]] = cnt[base + (i + 1) * stride[axis]]; }
-                cnt[base + (dim[axis] - 1) * stride[axis]] = 0; off[base + (dim[axis] - 1) * stride[axis]] = 0;
-            }
-        }
-}
-
-/* ll_cubemap.hip: live clouds of type w -> the other pool, back to back; room for `need` more points (compacting when 3/4 full) */
-int cm_compact(ll_cubemap *cm, int w);
-int cm_reserve(ll_cubemap *cm, int w, size_t need);
+/* ll_cubemap.hip: a compaction's copies (cm_commit's moves) of type w, out of the pool that was current into the one that is */
+void cm_run_moves(ll_cubemap *cm, int w, const std::vector<CmPiece> &moves);
 
 #define LL_HIDDEN __attribute__((visibility("hidden")))
 /* ll_map_export.hip: the tile size of this call; the segments of one map in output order (returns its points; segs == nullptr:

@@ -85,10 +85,7 @@ extern "C" int ll_cubemap_create(ll_ctx *ctx, float line_res, float plane_res, i
     if (cap_from_map < mx_last) { ctx->err = "pool_points must be at least the scan capacity"; ll_cubemap_destroy(cm); return LL_ERR_ARG; }
     cm->cap_work = cap_from_map;
     bool ok = true;
-    for (int w = 0; w < 2 && ok; ++w) {
-        ok = ok && cm_alloc(cm, cm->pool[w][0], cm->cap_pool) && cm_alloc(cm, cm->pool[w][1], cm->cap_pool);
-        cm->off[w].assign(CM_N, 0); cm->cnt[w].assign(CM_N, 0);
-    }
+    for (int w = 0; w < 2 && ok; ++w) ok = ok && cm_alloc(cm, cm->pool[w][0], cm->cap_pool) && cm_alloc(cm, cm->pool[w][1], cm->cap_pool);
     ok = ok && cm_alloc(cm, cm->d_last, (size_t)mx_last);
     for (int w = 0; w < 2; ++w) {
         ok = ok && cm_alloc(cm, cm->d_tp[w], (size_t)mx_last) && cm_alloc(cm, cm->d_work[w], (size_t)cm->cap_work) && cm_alloc(cm, cm->d_out[w], (size_t)cm->cap_work);
@@ -109,7 +106,7 @@ extern "C" int ll_cubemap_create(ll_ctx *ctx, float line_res, float plane_res, i
     return LL_OK;
 }
 
-static int cm_run_ops(ll_cubemap *cm, const std::vector<CmOp> &ops, const float4 *pool, const float4 *points, const int *index, float4 *dst, int *gid = nullptr)
+static void cm_run_ops(ll_cubemap *cm, const std::vector<CmOp> &ops, const float4 *pool, const float4 *points, const int *index, float4 *dst, int *gid = nullptr)
 {
     hipStream_t st = cm->ctx->stream;
     for (size_t o0 = 0; o0 < ops.size(); o0 += CM_PACK) {
@@ -119,30 +116,20 @@ static int cm_run_ops(ll_cubemap *cm, const std::vector<CmOp> &ops, const float4
         for (int i = 0; i < n; ++i) { pk.op[i] = ops[o0 + i]; mx = std::max(mx, ops[o0 + i].cnt); }
         hipLaunchKernelGGL(k_cm_copy, dim3(std::min(64, (mx + 255) / 256), n), dim3(256), 0, st, pool, points, index, pk, n, dst, gid);
     }
-    return LL_OK;
 }
 
-/* live clouds -> the other pool, back to back */
-int cm_compact(ll_cubemap *cm, int w)
+/* the pieces of a plan or a commit (ll_cubemap_tables.h) as copies: a cube's cloud out of a pool, then its new points through the index */
+static std::vector<CmOp> cm_ops(const std::vector<CmPiece> &pieces)
 {
     std::vector<CmOp> ops;
-    size_t top = 0;
-    for (int c = 0; c < CM_N; ++c)
-        if (cm->cnt[w][c] > 0) { ops.push_back({0, cm->off[w][c], cm->cnt[w][c], (int)top, 0}); top += (size_t)cm->cnt[w][c]; }
-    const int other = cm->cur[w] ^ 1;
-    int rc = cm_run_ops(cm, ops, cm->pool[w][cm->cur[w]], nullptr, nullptr, cm->pool[w][other]); if (rc) return rc;
-    size_t k = 0;
-    for (int c = 0; c < CM_N; ++c) if (cm->cnt[w][c] > 0) cm->off[w][c] = ops[k++].dst;
-    cm->cur[w] = other; cm->top[w] = top;
-    return LL_OK;
+    for (const CmPiece &e : pieces) {
+        if (e.old_cnt > 0) ops.push_back({0, e.old_off, e.old_cnt, e.dst, 0});
+        if (e.new_cnt > 0) ops.push_back({1, e.new_first, e.new_cnt, e.dst + e.old_cnt, 0});
+    }
+    return ops;
 }
 
-int cm_reserve(ll_cubemap *cm, int w, size_t need)
-{
-    if (cm->top[w] + need > cm->cap_pool * 3 / 4) { int rc = cm_compact(cm, w); if (rc) return rc; }
-    if (cm->top[w] + need > cm->cap_pool) { cm->err = "cube map pool exhausted (pool_points too small)"; return LL_ERR_CAPACITY; }
-    return LL_OK;
-}
+void cm_run_moves(ll_cubemap *cm, int w, const std::vector<CmPiece> &moves) { cm_run_ops(cm, cm_ops(moves), cm->pool[w][cm->cur[w] ^ 1], nullptr, nullptr, cm->pool[w][cm->cur[w]]); }
 
 static int cm_prepare(ll_cubemap *cm, const double *t_w3, const ll_point *corner_last, int n_corner, const ll_point *surf_last, int n_surf, bool on_device)
 {
@@ -152,19 +139,7 @@ static int cm_prepare(ll_cubemap *cm, const double *t_w3, const ll_point *corner
     if (cm->broken) { cm->err = "the cube map is unusable: an earlier ll_cubemap_update failed half-way"; return LL_ERR_STATE; }
     CM_HIP(hipSetDevice(cm->ctx->device));
     hipStream_t st = cm->ctx->stream;
-    const int dim[3] = {CM_W, CM_H, CM_D};
-    int cc[3];
-    for (int k = 0; k < 3; ++k) {
-        cc[k] = (int)((t_w3[k] + 25.0) / 50.0) + cm->cen[k];                       /* :1584-1586 */
-        if (t_w3[k] + 25.0 < 0) cc[k]--;                                           /* :1588-1593 */
-    }
-    for (int k = 0; k < 3; ++k) {
-        while (cc[k] < 3) { cm_shift(cm, k, +1); cc[k]++; cm->cen[k]++; }          /* :1595-1625 and the J, K twins */
-        while (cc[k] >= dim[k] - 3) { cm_shift(cm, k, -1); cc[k]--; cm->cen[k]--; }
-    }
-    cm->n_valid = 0;
-    for (int i = cc[0] - 2; i <= cc[0] + 2; i++) for (int j = cc[1] - 2; j <= cc[1] + 2; j++) for (int k = cc[2] - 1; k <= cc[2] + 1; k++)   /* :1783-1801 */
-        if (i >= 0 && i < CM_W && j >= 0 && j < CM_H && k >= 0 && k < CM_D) cm->valid[cm->n_valid++] = i + CM_W * j + CM_W * CM_H * k;
+    cm_follow(*cm, t_w3);                                                          /* centre cube, shift loops, valid cubes (:1584-1801) */
     /* laserCloudCornerFromMap / SurfFromMap (:1803-1808) */
     int n_from[2];
     for (int w = 0; w < 2; ++w) {
@@ -175,7 +150,7 @@ static int cm_prepare(ll_cubemap *cm, const double *t_w3, const ll_point *corner
             if (cm->cnt[w][c] > 0) { ops.push_back({0, cm->off[w][c], cm->cnt[w][c], (int)tot, v << CM_GID_SHIFT}); tot += (size_t)cm->cnt[w][c]; }
         }
         if (tot > (size_t)cm->map->cap_map[w]) { cm->err = "the valid cubes hold more points than the search cloud capacity"; return LL_ERR_CAPACITY; }
-        int rc = cm_run_ops(cm, ops, cm->pool[w][cm->cur[w]], nullptr, nullptr, cm->map->d_map[w], cm->world > 1 ? cm->map->d_gid[w] : nullptr); if (rc) return rc;
+        cm_run_ops(cm, ops, cm->pool[w][cm->cur[w]], nullptr, nullptr, cm->map->d_map[w], cm->world > 1 ? cm->map->d_gid[w] : nullptr);
         n_from[w] = (int)tot;
     }
     ll_map_rebuild_begin(cm->map, n_from[0], n_from[1]);                           /* the clouds' bounding boxes: enqueued, read below */
@@ -294,28 +269,15 @@ extern "C" int ll_cubemap_update(ll_cubemap *cm, const double *pose_w7)
     std::vector<int> addcnt_all(2 * (CM_N + 1));
     if (ll_read_back(addcnt_all.data(), cm->d_addcnt, addcnt_all.size() * sizeof(int), st)) { cm->err = "read-back failed"; return LL_ERR_HIP; }
     /* Stage B: one voxel-grid segment per valid cube -- its cloud, then its new points (:2119-2125 push_back, :2151-2165 filter) */
-    std::vector<int> goff[2], seg_off[2]; std::vector<char> is_valid(CM_N, 0);
-    size_t tot[2] = {0, 0};
-    for (int v = 0; v < cm->n_valid; ++v) is_valid[cm->valid[v]] = 1;
+    CmPlan plan[2]; int tot[2];
     for (int w = 0; w < 2; ++w) {
-        const int *addcnt = addcnt_all.data() + w * (CM_N + 1);
-        goff[w].assign(CM_N + 2, 0);
-        for (int c = 0; c < CM_N; ++c) goff[w][c + 1] = goff[w][c] + addcnt[c];        /* the new points of cube c in the sorted order */
-        std::vector<CmOp> ops; seg_off[w].assign(cm->n_valid + 1, 0);
-        for (int v = 0; v < cm->n_valid; ++v) {
-            const int c = cm->valid[v];
-            seg_off[w][v] = (int)tot[w];
-            if (cm->cnt[w][c] > 0) { ops.push_back({0, cm->off[w][c], cm->cnt[w][c], (int)tot[w], 0}); tot[w] += (size_t)cm->cnt[w][c]; }
-            if (addcnt[c] > 0) { ops.push_back({1, goff[w][c], addcnt[c], (int)tot[w], 0}); tot[w] += (size_t)addcnt[c]; }
-        }
-        seg_off[w][cm->n_valid] = (int)tot[w];
-        if (tot[w] > (size_t)cm->cap_work) { cm->err = "the valid cubes hold more points than the filter workspace"; return LL_ERR_CAPACITY; }
-        int rc = cm_run_ops(cm, ops, cm->pool[w][cm->cur[w]], cm->d_tp[w], cm->d_vals[w], cm->d_work[w]); if (rc) return rc;
+        const CmPlan &P = plan[w] = cm_plan(*cm, w, cm->valid, cm->n_valid, addcnt_all.data() + w * (CM_N + 1));
+        tot[w] = P.seg_off.back();
+        if (tot[w] > cm->cap_work) { cm->err = "the valid cubes hold more points than the filter workspace"; return LL_ERR_CAPACITY; }
+        cm_run_ops(cm, cm_ops(P.pieces), cm->pool[w][cm->cur[w]], cm->d_tp[w], cm->d_vals[w], cm->d_work[w]);
         if (tot[w] > 0) {
-            CM_HIP(hipMemcpyAsync(VW[w]->seg_off, seg_off[w].data(), seg_off[w].size() * sizeof(int), hipMemcpyHostToDevice, st));   /* the vector lives until the synchronisation below */
-            int max_seg = 0;
-            for (int v = 0; v < cm->n_valid; ++v) max_seg = std::max(max_seg, seg_off[w][(size_t)v + 1] - seg_off[w][(size_t)v]);
-            if (ll_voxel_grid_segments(cm->d_work[w], (int)tot[w], cm->n_valid, cm->leaf[w], *VW[w], cm->d_out[w], cm->d_nout + 2 + w, st, max_seg)) { cm->err = "voxel filter: read-back failed"; return LL_ERR_HIP; }
+            CM_HIP(hipMemcpyAsync(VW[w]->seg_off, P.seg_off.data(), P.seg_off.size() * sizeof(int), hipMemcpyHostToDevice, st));   /* the plan lives until the synchronisation below */
+            if (ll_voxel_grid_segments(cm->d_work[w], tot[w], cm->n_valid, cm->leaf[w], *VW[w], cm->d_out[w], cm->d_nout + 2 + w, st, cm_max_segment(P.seg_off))) { cm->err = "voxel filter: read-back failed"; return LL_ERR_HIP; }
         }
     }
     /* Host: both filtered sizes and both sets of per-cube counts in one page-locked read-back */
@@ -338,39 +300,17 @@ extern "C" int ll_cubemap_update(ll_cubemap *cm, const double *pose_w7)
     /* Stage C: the pair tables.  Will it fit?  Decided for BOTH cloud types BEFORE any table changes (a compaction keeps the clouds
      * of the cubes outside the valid set only): a pool that is too small for either type leaves the whole cube map as it was, with
      * nothing of this stage enqueued, and the call can be repeated with a larger pool_points. */
-    size_t need_w[2] = {0, 0};
+    size_t need[2] = {0, 0};
+    for (int w = 0; w < 2; ++w)
+        if (!cm_fit(*cm, w, plan[w], cm->valid, cm->n_valid, addcnt_all.data() + w * (CM_N + 1), seg_count[w].data(), &need[w], &cm->err)) return LL_ERR_CAPACITY;
     for (int w = 0; w < 2; ++w) {
-        const int *addcnt = addcnt_all.data() + w * (CM_N + 1);
-        /* pool space: the filtered valid cubes + the grown clouds of the other cubes that received points */
-        size_t need = (size_t)n_out[w];
-        for (int c = 0; c < CM_N; ++c) if (!is_valid[c] && addcnt[c] > 0) need += (size_t)cm->cnt[w][c] + (size_t)addcnt[c];
-        need_w[w] = need;
-        if (cm->top[w] + need > cm->cap_pool * 3 / 4) {
-            size_t live = 0;
-            for (int c = 0; c < CM_N; ++c) if (!is_valid[c]) live += (size_t)cm->cnt[w][c];
-            if (live + need > cm->cap_pool) { cm->err = "cube map pool exhausted (pool_points too small)"; return LL_ERR_CAPACITY; }
-        }
-    }
-    for (int w = 0; w < 2; ++w) {
-        const int *addcnt = addcnt_all.data() + w * (CM_N + 1);
-        const size_t need = need_w[w];
         /* ---- commit: the valid cubes' old clouds are dead from here on (not carried through a compaction) ---- */
         guard.armed = true;
-        for (int v = 0; v < cm->n_valid; ++v) cm->cnt[w][cm->valid[v]] = 0;
-        int rc = cm_reserve(cm, w, need); if (rc) return rc;
+        const CmCommit K = cm_commit(*cm, w, plan[w], cm->valid, cm->n_valid, addcnt_all.data() + w * (CM_N + 1), seg_count[w].data(), need[w]);
+        cm_run_moves(cm, w, K.moves);
         float4 *pool = cm->pool[w][cm->cur[w]];
-        if (n_out[w] > 0) ll_copy_d2d(pool + cm->top[w], cm->d_out[w], (size_t)n_out[w] * sizeof(float4), st);
-        size_t at = cm->top[w];
-        for (int v = 0; v < cm->n_valid; ++v) { const int c = cm->valid[v]; cm->off[w][c] = (int)at; cm->cnt[w][c] = seg_count[w][v]; at += (size_t)seg_count[w][v]; }
-        std::vector<CmOp> grow;
-        for (int c = 0; c < CM_N; ++c)
-            if (!is_valid[c] && addcnt[c] > 0) {
-                if (cm->cnt[w][c] > 0) grow.push_back({0, cm->off[w][c], cm->cnt[w][c], (int)at, 0});
-                grow.push_back({1, goff[w][c], addcnt[c], (int)(at + (size_t)cm->cnt[w][c]), 0});
-                cm->off[w][c] = (int)at; cm->cnt[w][c] += addcnt[c]; at += (size_t)cm->cnt[w][c];
-            }
-        rc = cm_run_ops(cm, grow, pool, cm->d_tp[w], cm->d_vals[w], pool); if (rc) return rc;
-        cm->top[w] = at;
+        if (n_out[w] > 0) ll_copy_d2d(pool + K.at, cm->d_out[w], (size_t)n_out[w] * sizeof(float4), st);
+        cm_run_ops(cm, cm_ops(K.grow), pool, cm->d_tp[w], cm->d_vals[w], pool);
     }
     CM_HIP(hipStreamSynchronize(st));
     guard.armed = false;                                             /* both cloud types are consistent again */

@@ -27,6 +27,7 @@
 #include "ll_map_search.h"
 #include <chrono>
 #include <cmath>
+#include <numeric>
 
 /* dst[i] = index ? src[index[i]] : src[i], i < cnt */
 struct CmsCopy { const float4 *src; const int *index; float4 *dst; int cnt, pad; };
@@ -230,12 +231,10 @@ static int cms_copy(ll_cubemaps *cms, const std::vector<CmsCopy> &ops)
 /* the voxel filter's sort reads back once when it cannot stay inside the workgroups (ll_voxel.hip): counted with the syncs */
 static int cms_voxel(ll_cubemaps *cms, int w, const float4 *pts, const std::vector<int> &seg_off, float4 *out, int *n_out_dev)
 {
-    const int nseg = (int)seg_off.size() - 1, n = seg_off.back();
-    int max_seg = 0;
-    for (int s = 0; s < nseg; ++s) max_seg = std::max(max_seg, seg_off[(size_t)s + 1] - seg_off[(size_t)s]);
+    const int nseg = (int)seg_off.size() - 1, n = seg_off.back(), max_seg = nseg > 1 ? cm_max_segment(seg_off) : 0;
     if (!cms_stage(cms, seg_off.data(), seg_off.size() * sizeof(int), cms->W[w].seg_off)) return LL_ERR_HIP;
-    if (!(nseg > 1 && max_seg <= 8192) && n > 65536) ++cms->syncs;
-    if (ll_voxel_grid_segments(pts, n, nseg, cms->leaf[w], cms->W[w], out, n_out_dev, cms->ctx->stream, nseg > 1 ? max_seg : 0)) { cms->err = "voxel filter: read-back failed"; return LL_ERR_HIP; }
+    if (ll_voxel_grid_segments_reads_back(n, nseg, max_seg)) ++cms->syncs;
+    if (ll_voxel_grid_segments(pts, n, nseg, cms->leaf[w], cms->W[w], out, n_out_dev, cms->ctx->stream, max_seg)) { cms->err = "voxel filter: read-back failed"; return LL_ERR_HIP; }
     return LL_OK;
 }
 
@@ -299,33 +298,12 @@ extern "C" int ll_cubemaps_create(ll_ctx *ctx, int n_seq, float line_res, float 
         cm->leaf[0] = line_res; cm->leaf[1] = plane_res;
         cm->cap_last[0] = max_scan_corner; cm->cap_last[1] = max_scan_surf;
         cm->cap_pool = cms->cap_pool; cm->cap_work = cap_from_map;
-        for (int w = 0; w < 2; ++w) {
-            for (int b = 0; b < 2; ++b) cm->pool[w][b] = cms->pool_mem[w][b] + (size_t)q * cms->cap_pool;
-            cm->off[w].assign(CM_N, 0); cm->cnt[w].assign(CM_N, 0);
-        }
+        for (int w = 0; w < 2; ++w) for (int b = 0; b < 2; ++b) cm->pool[w][b] = cms->pool_mem[w][b] + (size_t)q * cms->cap_pool;
         if (ll_map_create(ctx, cap_from_map, cap_from_map, max_scan_corner, max_scan_surf, &cm->map) != LL_OK) { cms->err = ctx->err; ok = false; }
     }
     if (!ok) { ctx->err = cms->err; ll_cubemaps_destroy(cms); return LL_ERR_HIP; }
     *out = cms;
     return LL_OK;
-}
-
-/* the cube the guess's translation falls into, in the indices of map cm (:1584-1593) */
-static void cms_centre(const ll_cubemap *cm, const double *t_w3, int cc[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        cc[k] = (int)((t_w3[k] + 25.0) / 50.0) + cm->cen[k];                       /* :1584-1586 */
-        if (t_w3[k] + 25.0 < 0) cc[k]--;                                           /* :1588-1593 */
-    }
-}
-
-/* the cubes around cc that lie inside the array, in laserMapping's loop order (:1783-1801) */
-static int cms_valid_cubes(const int cc[3], int *valid)
-{
-    int n = 0;
-    for (int i = cc[0] - 2; i <= cc[0] + 2; i++) for (int j = cc[1] - 2; j <= cc[1] + 2; j++) for (int k = cc[2] - 1; k <= cc[2] + 1; k++)
-        if (i >= 0 && i < CM_W && j >= 0 && j < CM_H && k >= 0 && k < CM_D) valid[n++] = i + CM_W * j + CM_W * CM_H * k;
-    return n;
 }
 
 /* the copies that gather those cubes of map cm into the search clouds of sequence q's own ll_map (:1803-1808); n_from[w]: their sizes */
@@ -495,14 +473,8 @@ static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::v
     std::vector<int> n_from[2] = {std::vector<int>(R), std::vector<int>(R)};
     for (int r = 0; r < R; ++r) {
         ll_cubemap *cm = cms->cm[run[r]];
-        const int dim[3] = {CM_W, CM_H, CM_D};
-        int cc[3], nf[2];
-        cms_centre(cm, pose_w7 + 7 * run[r] + 4, cc);
-        for (int k = 0; k < 3; ++k) {
-            while (cc[k] < 3) { cm_shift(cm, k, +1); cc[k]++; cm->cen[k]++; }      /* :1595-1625 and the J, K twins */
-            while (cc[k] >= dim[k] - 3) { cm_shift(cm, k, -1); cc[k]--; cm->cen[k]--; }
-        }
-        cm->n_valid = cms_valid_cubes(cc, cm->valid);
+        int nf[2];
+        cm_follow(*cm, pose_w7 + 7 * run[r] + 4);                                  /* centre cube, shift loops, valid cubes (:1584-1801) */
         rc = cms_gather(cms, run[r], cm, cm->valid, cm->n_valid, ops, nf); if (rc) return rc;
         n_from[0][r] = nf[0]; n_from[1][r] = nf[1];
     }
@@ -536,7 +508,7 @@ static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::v
         if (!d_recs || !d_ablk) return LL_ERR_HIP;
         hipLaunchKernelGGL(k_cms_assign, dim3((unsigned)ablk.size()), dim3(256), 0, st, d_recs, d_ablk);
         for (const CmsAssign &A : recs) {                                          /* by cube, stack order kept */
-            if (A.n > 65536) ++cms->syncs;
+            if (ll_sort_pairs_reads_back(A.n)) ++cms->syncs;
             if (ll_sort_pairs(A.keys, A.vals, cms->WS.keys, cms->WS.vals, A.n, cms->WS.hist, cms->WS.tile_sum, cms->WS.or_and, st)) { cms->err = "sort by cube: read-back failed"; return LL_ERR_HIP; }
         }
     }
@@ -549,29 +521,28 @@ static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::v
         std::memcpy(addcnt_all.data(), pin, addcnt_all.size() * sizeof(int));
     }
     /* one voxel-grid segment per valid cube of every sequence: its cloud, then its new points (:2119-2125, :2151-2165) */
-    std::vector<std::vector<int>> goff(2 * R);
-    std::vector<int> useg[2], seg0[2] = {std::vector<int>(R + 1, 0), std::vector<int>(R + 1, 0)};
+    std::vector<CmPlan> plan(2 * R);
+    std::vector<int> useg[2], seg0[2] = {std::vector<int>(R, 0), std::vector<int>(R, 0)};
     ops.clear();
+    auto new_points = [&](int r, int w) { return addcnt_all.data() + ((size_t)r * 2 + w) * (CM_N + 1); };
+    /* the pieces of a plan or a commit of sequence r, type w as copies: a cube's cloud out of `from`, then its new points in by-cube order */
+    auto copies = [&](const std::vector<CmPiece> &pieces, int r, int w, const float4 *from, float4 *to) {
+        for (const CmPiece &e : pieces) {
+            if (e.old_cnt > 0) ops.push_back({from + e.old_off, nullptr, to + e.dst, e.old_cnt, 0});
+            if (e.new_cnt > 0) ops.push_back({cms->d_tp[w] + toff[w][r], cms->d_vals[w] + toff[w][r] + e.new_first, to + e.dst + e.old_cnt, e.new_cnt, 0});
+        }
+    };
     for (int w = 0; w < 2; ++w) {
         useg[w].assign(1, 0);
         for (int r = 0; r < R; ++r) {
-            ll_cubemap *cm = cms->cm[run[r]];
-            const int *addcnt = addcnt_all.data() + ((size_t)r * 2 + w) * (CM_N + 1);
-            std::vector<int> &g = goff[2 * r + w];
-            g.assign(CM_N + 2, 0);
-            for (int c = 0; c < CM_N; ++c) g[c + 1] = g[c] + addcnt[c];
-            const size_t start = (size_t)useg[w].back();
-            size_t tot = start;
+            const ll_cubemap *cm = cms->cm[run[r]];
+            const CmPlan &P = plan[2 * r + w] = cm_plan(*cm, w, cm->valid, cm->n_valid, new_points(r, w));
+            if (P.seg_off.back() > cms->cap_work) { cms->err = "sequence " + std::to_string(run[r]) + ": the valid cubes hold more points than the filter workspace"; return LL_ERR_CAPACITY; }
+            const int start = useg[w].back();
             seg0[w][r] = (int)useg[w].size() - 1;
-            for (int v = 0; v < cm->n_valid; ++v) {
-                const int c = cm->valid[v];
-                if (cm->cnt[w][c] > 0) { ops.push_back({cm->pool[w][cm->cur[w]] + cm->off[w][c], nullptr, cms->d_work[w] + tot, cm->cnt[w][c], 0}); tot += (size_t)cm->cnt[w][c]; }
-                if (addcnt[c] > 0) { ops.push_back({cms->d_tp[w] + toff[w][r], cms->d_vals[w] + toff[w][r] + g[c], cms->d_work[w] + tot, addcnt[c], 0}); tot += (size_t)addcnt[c]; }
-                useg[w].push_back((int)tot);
-            }
-            if (tot - start > (size_t)cms->cap_work) { cms->err = "sequence " + std::to_string(run[r]) + ": the valid cubes hold more points than the filter workspace"; return LL_ERR_CAPACITY; }
+            copies(P.pieces, r, w, cm->pool[w][cm->cur[w]], cms->d_work[w] + start);
+            for (int v = 1; v <= cm->n_valid; ++v) useg[w].push_back(start + P.seg_off[v]);
         }
-        seg0[w][R] = (int)useg[w].size() - 1;
     }
     rc = cms_copy(cms, ops); if (rc) return rc;
     for (int w = 0; w < 2; ++w)
@@ -588,60 +559,30 @@ static int cms_frame(ll_cubemaps *cms, const std::vector<int> &run, const std::v
         if (useg[0].back() > 0) std::memcpy(seg_count[0].data(), pin, n0 * sizeof(int));
         if (useg[1].back() > 0) std::memcpy(seg_count[1].data(), pin + n0, n1 * sizeof(int));
     }
-    /* Will it fit?  Decided for every sequence and both cloud types before any pair table changes (ll_cubemap_update's rule) */
-    std::vector<size_t> need((size_t)R * 2), nout((size_t)R * 2), out_at((size_t)R * 2);
-    std::vector<char> is_valid(CM_N, 0);
-    for (int w = 0; w < 2; ++w) {
-        size_t at = 0;
+    /* Will it fit?  Decided for every sequence and both cloud types before any pair table changes */
+    std::vector<size_t> need((size_t)R * 2);
+    for (int w = 0; w < 2; ++w)
         for (int r = 0; r < R; ++r) {
-            ll_cubemap *cm = cms->cm[run[r]];
-            const int *addcnt = addcnt_all.data() + ((size_t)r * 2 + w) * (CM_N + 1);
-            size_t n = 0;
-            for (int v = 0; v < cm->n_valid; ++v) n += (size_t)seg_count[w][(size_t)seg0[w][r] + v];
-            out_at[(size_t)2 * r + w] = at; nout[(size_t)2 * r + w] = n; at += n;
-            for (int v = 0; v < cm->n_valid; ++v) is_valid[cm->valid[v]] = 1;
-            size_t nd = n;
-            for (int c = 0; c < CM_N; ++c) if (!is_valid[c] && addcnt[c] > 0) nd += (size_t)cm->cnt[w][c] + (size_t)addcnt[c];
-            need[(size_t)2 * r + w] = nd;
-            bool full = false;
-            if (cm->top[w] + nd > cm->cap_pool * 3 / 4) {
-                size_t live = 0;
-                for (int c = 0; c < CM_N; ++c) if (!is_valid[c]) live += (size_t)cm->cnt[w][c];
-                full = live + nd > cm->cap_pool;
-            }
-            for (int v = 0; v < cm->n_valid; ++v) is_valid[cm->valid[v]] = 0;
-            if (full) { cms->err = "sequence " + std::to_string(run[r]) + ": cube map pool exhausted (pool_points too small)"; return LL_ERR_CAPACITY; }
+            const ll_cubemap *cm = cms->cm[run[r]];
+            std::string why;
+            if (!cm_fit(*cm, w, plan[2 * r + w], cm->valid, cm->n_valid, new_points(r, w), seg_count[w].data() + seg0[w][r], &need[(size_t)2 * r + w], &why)) { cms->err = "sequence " + std::to_string(run[r]) + ": " + why; return LL_ERR_CAPACITY; }
         }
-    }
     /* ---- commit: from here on a failure leaves the pair tables half-updated (the sequences are marked unusable) ---- */
     for (int r = 0; r < R; ++r) cms->cm[run[r]]->broken = true;
     ops.clear();
+    size_t out_at[2] = {0, 0};                                                     /* the filter output of a type: the sequences back to back */
     for (int r = 0; r < R; ++r) {
         ll_cubemap *cm = cms->cm[run[r]];
-        for (int v = 0; v < cm->n_valid; ++v) is_valid[cm->valid[v]] = 1;
         for (int w = 0; w < 2; ++w) {
-            const int *addcnt = addcnt_all.data() + ((size_t)r * 2 + w) * (CM_N + 1);
-            const std::vector<int> &g = goff[2 * r + w];
-            for (int v = 0; v < cm->n_valid; ++v) cm->cnt[w][cm->valid[v]] = 0;
-            rc = cm_reserve(cm, w, need[(size_t)2 * r + w]);
-            if (rc) { cms->err = "sequence " + std::to_string(run[r]) + ": " + cm->err; return rc; }
+            const int *sc = seg_count[w].data() + seg0[w][r];
+            const CmCommit K = cm_commit(*cm, w, plan[2 * r + w], cm->valid, cm->n_valid, new_points(r, w), sc, need[(size_t)2 * r + w]);
+            const size_t n = std::accumulate(sc, sc + cm->n_valid, (size_t)0);
+            cm_run_moves(cm, w, K.moves);                                          /* a compaction: launched at once, the copies below follow it */
             float4 *pool = cm->pool[w][cm->cur[w]];
-            const size_t n = nout[(size_t)2 * r + w];
-            if (n > 0) ops.push_back({cms->d_out[w] + out_at[(size_t)2 * r + w], nullptr, pool + cm->top[w], (int)n, 0});
-            size_t at = cm->top[w];
-            for (int v = 0; v < cm->n_valid; ++v) {
-                const int c = cm->valid[v], k = seg_count[w][(size_t)seg0[w][r] + v];
-                cm->off[w][c] = (int)at; cm->cnt[w][c] = k; at += (size_t)k;
-            }
-            for (int c = 0; c < CM_N; ++c)
-                if (!is_valid[c] && addcnt[c] > 0) {
-                    if (cm->cnt[w][c] > 0) ops.push_back({pool + cm->off[w][c], nullptr, pool + at, cm->cnt[w][c], 0});
-                    ops.push_back({cms->d_tp[w] + toff[w][r], cms->d_vals[w] + toff[w][r] + g[c], pool + at + (size_t)cm->cnt[w][c], addcnt[c], 0});
-                    cm->off[w][c] = (int)at; cm->cnt[w][c] += addcnt[c]; at += (size_t)cm->cnt[w][c];
-                }
-            cm->top[w] = at;
+            if (n > 0) ops.push_back({cms->d_out[w] + out_at[w], nullptr, pool + K.at, (int)n, 0});
+            out_at[w] += n;
+            copies(K.grow, r, w, pool, pool);
         }
-        for (int v = 0; v < cm->n_valid; ++v) is_valid[cm->valid[v]] = 0;
     }
     rc = cms_copy(cms, ops); if (rc) return rc;                                   /* after every compaction above: stream order */
     CMS_HIP(hipGetLastError());
@@ -729,7 +670,7 @@ extern "C" int ll_cubemaps_process(ll_cubemaps *cms, const ll_point *const *corn
 }
 
 /* one READ-ONLY frame: sequence run[r] localises against map map_of[run[r]].  No shift loops: the centre cube in the indices the
- * map has, the cubes around it that lie inside the array (cms_valid_cubes skips the others: they hold nothing), the shared
+ * map has, the cubes around it that lie inside the array (cm_valid_cubes skips the others: they hold nothing), the shared
  * prepare and optimize, no update.  Nothing of any ll_cubemap is written: the valid list is a local, the workspace is the
  * reader's ll_map.  Every refusal comes before the first launch. */
 static int cms_localize(ll_cubemaps *cms, const std::vector<int> &run, const int *map_of, const std::vector<const float4 *> src[2],
@@ -742,8 +683,8 @@ static int cms_localize(ll_cubemaps *cms, const std::vector<int> &run, const int
     for (int r = 0; r < R; ++r) {
         const ll_cubemap *cm = cms->cm[map_of ? map_of[run[r]] : run[r]];
         int cc[3], nf[2], valid[125];
-        cms_centre(cm, pose_w7 + 7 * run[r] + 4, cc);
-        const int n_valid = cms_valid_cubes(cc, valid);
+        cm_centre(*cm, pose_w7 + 7 * run[r] + 4, cc);
+        const int n_valid = cm_valid_cubes(cc, valid);
         rc = cms_gather(cms, run[r], cm, valid, n_valid, ops, nf); if (rc) return rc;
         n_from[0][r] = nf[0]; n_from[1][r] = nf[1];
     }

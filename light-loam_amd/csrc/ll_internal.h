@@ -111,6 +111,7 @@ LLLmOpt ll_to_dev_opt(const ll_lm_options *opt);
 /* ll_voxel.hip: the stable sort by key of (keys, vals) (nonzero: its read-back failed); every segment sorted on its own */
 int ll_sort_pairs(unsigned long long *keys, int *vals, unsigned long long *tmp_keys, int *tmp_vals, int n, int *hist, int *tile_sum,
                   unsigned long long *or_and_dev, hipStream_t st);
+bool ll_sort_pairs_reads_back(int n);                         /* would that sort of n pairs synchronise with the host? */
 void ll_sort_pairs_segments(unsigned long long *keys, int *vals, const int *seg_off_dev, int nseg, hipStream_t st);
 int ll_map_rebuild(ll_map *m, int n_corner, int n_surf);      /* grids over the clouds already in d_map[] */
 void ll_map_rebuild_begin(ll_map *m, int n_corner, int n_surf);       /* ... in two halves around the caller's own read-back */

@@ -26,6 +26,7 @@
 #include "ll_cubemap.h"
 #include <chrono>
 #include <cmath>
+#include <numeric>
 
 #define MM_BINS (CM_N + 1)               /* 4851 cubes + "outside the array" */
 #define MM_CHUNK 2048                    /* points per histogram row of the counting sort */
@@ -338,21 +339,24 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
                               std::to_string(live) + " " + mm_type(w) + " points + " + std::to_string(n_add[r]) + " added, pool_points is " + std::to_string(dst->cap_pool));
     }
     /* ---- stage B: one voxel-grid segment per touched cube of every op -- its cloud, then its new points in order */
-    std::vector<int> seg_off[2] = {std::vector<int>(1, 0), std::vector<int>(1, 0)}, seg_cube[2], seg0(nrec, 0), seg1(nrec, 0);
+    std::vector<CmPlan> plan(nrec);
+    std::vector<std::vector<int>> touched(nrec);
+    std::vector<int> seg_off[2] = {std::vector<int>(1, 0), std::vector<int>(1, 0)}, seg0(nrec, 0);
     long long F[2] = {0, 0};
     for (int w = 0; w < 2; ++w) {
         for (int i = 0; i < n_ops; ++i) {
             const int r = 2 * i + w;
             const int *a = addcnt.data() + (size_t)r * MM_BINS;
-            const ll_cubemap *dst = llcms_map(cms, ops[i].dst);
-            seg0[r] = (int)seg_cube[w].size();
-            for (int c = 0; c < CM_N; ++c)
-                if (a[c] > 0) { F[w] += (long long)dst->cnt[w][c] + a[c]; seg_cube[w].push_back(c); seg_off[w].push_back((int)F[w]); }
-            seg1[r] = (int)seg_cube[w].size();
+            for (int c = 0; c < CM_N; ++c) if (a[c] > 0) touched[r].push_back(c);
+            plan[r] = cm_plan(*llcms_map(cms, ops[i].dst), w, touched[r].data(), (int)touched[r].size(), a);
+            seg0[r] = (int)seg_off[w].size() - 1;
+            for (size_t s = 1; s < plan[r].seg_off.size(); ++s) seg_off[w].push_back((int)(F[w] + plan[r].seg_off[s]));
+            F[w] += plan[r].seg_off.back();
         }
         if (F[w] > (long long)(INT_MAX / 2)) return llcms_fail(cms, LL_ERR_CAPACITY, std::string("map merge: the touched ") + mm_type(w) + " cubes hold more points than one filter call takes");
     }
-    G.counts[1] = (long long)(seg_cube[0].size() + seg_cube[1].size());
+    const size_t nseg[2] = {seg_off[0].size() - 1, seg_off[1].size() - 1};
+    G.counts[1] = (long long)(nseg[0] + nseg[1]);
     float4 *d_work[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
     int *d_nout = nullptr;
     LLVoxWork W[2];
@@ -364,7 +368,7 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
             d_nout = B.take<int>(4);
             for (int w = 0; w < 2; ++w) {
                 d_work[w] = B.take<float4>((size_t)F[w]); d_out[w] = B.take<float4>((size_t)F[w]);
-                vox[w] = B.take<unsigned char>(ll_vox_work_bytes((int)F[w], (int)seg_cube[w].size() + 1));
+                vox[w] = B.take<unsigned char>(ll_vox_work_bytes((int)F[w], (int)nseg[w] + 1));
             }
             if (pass == 0) {
                 std::string why;
@@ -372,21 +376,17 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
                 if (!B.p) return llcms_fail(cms, LL_ERR_HIP, why);
             }
         }
-        for (int w = 0; w < 2; ++w) ll_vox_work_carve(vox[w], (int)F[w], (int)seg_cube[w].size() + 1, &W[w]);
+        for (int w = 0; w < 2; ++w) ll_vox_work_carve(vox[w], (int)F[w], (int)nseg[w] + 1, &W[w]);
     }
     std::vector<MmCopy> cp;
     for (int w = 0; w < 2; ++w)
         for (int i = 0; i < n_ops; ++i) {
             const int r = 2 * i + w;
-            const int *a = addcnt.data() + (size_t)r * MM_BINS;
             const ll_cubemap *dst = llcms_map(cms, ops[i].dst);
-            int g = 0;                                            /* the new points of cube c in the record's by-cube order */
-            for (int c = 0, s = seg0[r]; c < CM_N; ++c) {
-                if (a[c] <= 0) continue;
-                float4 *at = d_work[w] + seg_off[w][s++];
-                if (dst->cnt[w][c] > 0) cp.push_back({dst->pool[w][dst->cur[w]] + dst->off[w][c], nullptr, at, dst->cnt[w][c], 0});
-                cp.push_back({d_tp, d_perm + recs[r].first + g, at + dst->cnt[w][c], a[c], 0});
-                g += a[c];
+            for (const CmPiece &e : plan[r].pieces) {             /* the new points of a cube in the record's by-cube order */
+                float4 *at = d_work[w] + seg_off[w][seg0[r]] + e.dst;
+                if (e.old_cnt > 0) cp.push_back({dst->pool[w][dst->cur[w]] + e.old_off, nullptr, at, e.old_cnt, 0});
+                cp.push_back({d_tp, d_perm + recs[r].first + e.new_first, at + e.old_cnt, e.new_cnt, 0});
             }
         }
     MM_HIP(hipEventRecord(G.ev[3], st));
@@ -394,20 +394,18 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
     MM_HIP(hipEventRecord(G.ev[4], st));
     for (int w = 0; w < 2; ++w) {
         if (F[w] <= 0) continue;
-        const int nseg = (int)seg_cube[w].size();
-        int max_seg = 0;
-        for (int s = 0; s < nseg; ++s) max_seg = std::max(max_seg, seg_off[w][(size_t)s + 1] - seg_off[w][(size_t)s]);
+        const int max_seg = nseg[w] > 1 ? cm_max_segment(seg_off[w]) : 0;
         if (!llcms_stage_to(cms, seg_off[w].data(), seg_off[w].size() * sizeof(int), W[w].seg_off)) return LL_ERR_HIP;
         /* the voxel filter's sort reads back once when it cannot stay inside the workgroups (ll_voxel.hip): counted with the syncs */
-        if (!(nseg > 1 && max_seg <= 8192) && F[w] > 65536) llcms_count_sync(cms);
-        if (ll_voxel_grid_segments(d_work[w], (int)F[w], nseg, llcms_leaf(cms)[w], W[w], d_out[w], d_nout + w, st, nseg > 1 ? max_seg : 0))
+        if (ll_voxel_grid_segments_reads_back((int)F[w], (int)nseg[w], max_seg)) llcms_count_sync(cms);
+        if (ll_voxel_grid_segments(d_work[w], (int)F[w], (int)nseg[w], llcms_leaf(cms)[w], W[w], d_out[w], d_nout + w, st, max_seg))
             return llcms_fail(cms, LL_ERR_HIP, "map merge: voxel filter: read-back failed");
     }
     MM_HIP(hipEventRecord(G.ev[5], st));
     MM_HIP(hipGetLastError());
     std::vector<int> seg_count[2];
     {
-        const size_t n0 = seg_cube[0].size(), n1 = seg_cube[1].size();
+        const size_t n0 = nseg[0], n1 = nseg[1];
         int *pin = (int *)ll_pinned_scratch((n0 + n1 + 2) * sizeof(int));
         if (!pin) return llcms_fail(cms, LL_ERR_HIP, "map merge: no page-locked scratch");
         if (n0) MM_HIP(hipMemcpyAsync(pin, W[0].seg_count, n0 * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -423,18 +421,13 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
     for (int w = 0; w < 2; ++w) {
         size_t out_at = 0;
         for (int i = 0; i < n_ops; ++i) {
-            const int r = 2 * i + w, s0 = seg0[r], s1 = seg1[r];
-            if (s1 == s0) continue;
+            const int r = 2 * i + w, n_set = (int)touched[r].size(), *sc = seg_count[w].data() + seg0[r];
+            if (n_set == 0) continue;
             ll_cubemap *dst = llcms_map(cms, ops[i].dst);
-            size_t n = 0;
-            for (int s = s0; s < s1; ++s) { n += (size_t)seg_count[w][s]; dst->cnt[w][seg_cube[w][s]] = 0; }   /* the touched cubes' old clouds are dead: not carried through a compaction */
-            rc = cm_reserve(dst, w, n);
-            if (rc) return llcms_fail(cms, rc, "map merge: op " + std::to_string(i) + ": " + dst->err);
-            float4 *pool = dst->pool[w][dst->cur[w]];
-            if (n > 0) cp.push_back({d_out[w] + out_at, nullptr, pool + dst->top[w], (int)n, 0});
-            size_t at = dst->top[w];
-            for (int s = s0; s < s1; ++s) { const int c = seg_cube[w][s]; dst->off[w][c] = (int)at; dst->cnt[w][c] = seg_count[w][s]; at += (size_t)seg_count[w][s]; }
-            dst->top[w] = at;
+            const size_t n = std::accumulate(sc, sc + n_set, (size_t)0);        /* nothing grows outside the set: this is all the pool takes */
+            const CmCommit K = cm_commit(*dst, w, plan[r], touched[r].data(), n_set, addcnt.data() + (size_t)r * MM_BINS, sc, n);
+            cm_run_moves(dst, w, K.moves);                        /* a compaction: launched at once, the copies below follow it */
+            if (n > 0) cp.push_back({d_out[w] + out_at, nullptr, dst->pool[w][dst->cur[w]] + K.at, (int)n, 0});
             out_at += n; n_out_all += (long long)n;
         }
     }

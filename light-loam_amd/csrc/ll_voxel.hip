@@ -406,6 +406,9 @@ void ll_sort_pairs_segments(unsigned long long *keys, int *vals, const int *seg_
     hipLaunchKernelGGL(k_rs_small, dim3(nseg), dim3(1024), lds, st, keys, vals, 0, seg_off_dev, 0);
 }
 
+/* does ll_sort_pairs of n pairs read back to the host?  Not while it stays inside workgroups: one, or LL_RSM_MAXC chunks and a merge */
+bool ll_sort_pairs_reads_back(int n) { return n > LL_RSM_MAXC * LL_RSS_MAX; }
+
 /* sorts (keys, vals) by keys, stable; the result is in (keys, vals) again.  tmp_* hold n elements, hist 16 * ceil(n/4096)
  * ints, tile_sum as for ll_device_exscan of that, or_and_host is pinned host memory for the varying-bit mask */
 int ll_sort_pairs(unsigned long long *keys, int *vals, unsigned long long *tmp_keys, int *tmp_vals, int n, int *hist, int *tile_sum,
@@ -419,7 +422,7 @@ int ll_sort_pairs(unsigned long long *keys, int *vals, unsigned long long *tmp_k
         hipLaunchKernelGGL(k_rs_small, dim3(1), dim3(1024), lds, st, keys, vals, n, (const int *)nullptr, 0);
         return 0;
     }
-    if (n <= LL_RSM_MAXC * LL_RSS_MAX) {
+    if (!ll_sort_pairs_reads_back(n)) {
         /* up to 64 k pairs (a scan's less-flat cloud is ~33 k): every chunk of 8192 sorted in LDS by its own workgroup, then
          * every pair placed by its rank among ALL chunks -- its place in its chunk plus, by binary search, the number of
          * pairs of the other chunks that go before it (<= K in the chunks before its own, < K in those behind: stable).
@@ -594,6 +597,10 @@ void ll_vox_work_carve(void *base, int cap, int max_seg, LLVoxWork *W)
     W->tile_sum = (int *)take((256 * nblk / 4096 + 2 + (size_t)cap / 4096 + 2) * 4);
 }
 
+/* does ll_voxel_grid_segments(n, nseg, max_seg_len) read back?  Only through the whole call's sort, when the segments are not sorted apart */
+static bool vx_sorts_by_segment(int nseg, int max_seg_len) { return nseg > 1 && max_seg_len > 0 && max_seg_len <= LL_RSS_MAX; }
+bool ll_voxel_grid_segments_reads_back(int n, int nseg, int max_seg_len) { return !vx_sorts_by_segment(nseg, max_seg_len) && ll_sort_pairs_reads_back(n); }
+
 /* pts[0..n): nseg clouds back to back, seg_off (device, nseg + 1 ascending offsets, seg_off[nseg] = n).
  * out: the filtered clouds back to back in segment order; seg_count (W.seg_count, device): points per filtered cloud;
  * *n_out_dev (device int, may alias nothing else): total.  Everything is enqueued on st except the sort's one
@@ -608,7 +615,7 @@ int ll_voxel_grid_segments(const float4 *pts, int n, int nseg, float leaf, const
     hipLaunchKernelGGL(k_vx_params, dim3((nseg + 63) / 64), dim3(64), 0, st, W.bbox, W.seg_off, nseg, inv, W.sp);
     hipLaunchKernelGGL(k_vx_keys, dim3((n + LL_VB - 1) / LL_VB), dim3(LL_VB), 0, st, pts, W.segid, W.seg_off, W.sp, n, inv, W.keys, W.vals, W.pub, W.seg_count, nseg);
     int rc = 0;
-    if (nseg > 1 && max_seg_len > 0 && max_seg_len <= LL_RSS_MAX) ll_sort_pairs_segments(W.keys, W.vals, W.seg_off, nseg, st);   /* the keys lead with the segment */
+    if (vx_sorts_by_segment(nseg, max_seg_len)) ll_sort_pairs_segments(W.keys, W.vals, W.seg_off, nseg, st);   /* the keys lead with the segment */
     else rc = ll_sort_pairs(W.keys, W.vals, W.tmp_keys, W.tmp_vals, n, W.hist, W.tile_sum, W.or_and, st);
     if (n <= LL_VX_FUSED_WGS * LL_VB) {
         hipLaunchKernelGGL(k_vx_finish, dim3((n + LL_VB - 1) / LL_VB), dim3(LL_VB), 0, st, pts, (const unsigned long long *)W.keys, (const int *)W.vals, n, out,

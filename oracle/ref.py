@@ -55,22 +55,35 @@ def _recipe_inputs():
 
 def build(force=False):
     """Builds both variants into oracle/_ref/ when the reference is there and they are missing or older than the recipe,
-    the doubles, the driver or the reference's source.  Returns the list of binaries that exist afterwards."""
+    the doubles, the driver or the reference's source.  Returns the list of binaries that exist afterwards.
+
+    Several processes may call this at once (the ranks of tests/test_distributed_gloo.py, two test runs over one tree): one
+    builds under a file lock while the others wait and then find the binaries fresh; every build works in a directory of its
+    own and a finished binary takes its place in one rename, so that nobody ever runs or links a half-written file."""
     if reference_present():
+        import fcntl
         inc = ["-I", os.path.join(_HERE, "ref_standins"), "-I", os.path.join(_ROOT, "tests", "native", "ros_double")]
         newest = max(os.path.getmtime(p) for p in _recipe_inputs() + [_source()])
         cxx = os.environ.get("CXX", "g++")
-        for variant, extra in VARIANTS.items():
-            exe = binary(variant)
-            if not force and os.path.isfile(exe) and os.path.getmtime(exe) >= newest:
-                continue
-            os.makedirs(OUT, exist_ok=True)
-            obj = os.path.join(OUT, f"scanreg_{variant}.o")
-            subprocess.check_call([cxx] + CXXFLAGS + extra + ["-D", "main=" + MAIN] + inc +
-                                  ["-I", os.path.join(REF_ROOT, "include"), "-c", _source(), "-o", obj])
-            tmp = exe + ".tmp"
-            subprocess.check_call([cxx] + CXXFLAGS + inc + [os.path.join(_HERE, "ref_driver.cpp"), obj, "-o", tmp])
-            os.replace(tmp, exe)
+
+        def fresh(variant):
+            return not force and os.path.isfile(binary(variant)) and os.path.getmtime(binary(variant)) >= newest
+
+        if all(fresh(v) for v in VARIANTS):                     # nothing to write: a read-only tree is fine
+            return [binary(v) for v in VARIANTS if available(v)]
+        os.makedirs(OUT, exist_ok=True)
+        with open(os.path.join(OUT, ".lock"), "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)                    # released when the file is closed
+            for variant, extra in VARIANTS.items():
+                exe = binary(variant)
+                if fresh(variant):                              # built while this process waited for the lock
+                    continue
+                with tempfile.TemporaryDirectory(prefix="build_", dir=OUT) as work:
+                    obj, tmp = os.path.join(work, f"scanreg_{variant}.o"), os.path.join(work, "scanreg_" + variant)
+                    subprocess.check_call([cxx] + CXXFLAGS + extra + ["-D", "main=" + MAIN] + inc +
+                                          ["-I", os.path.join(REF_ROOT, "include"), "-c", _source(), "-o", obj])
+                    subprocess.check_call([cxx] + CXXFLAGS + inc + [os.path.join(_HERE, "ref_driver.cpp"), obj, "-o", tmp])
+                    os.replace(tmp, exe)
     return [binary(v) for v in VARIANTS if available(v)]
 
 

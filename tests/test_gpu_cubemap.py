@@ -149,3 +149,98 @@ def test_a_pool_too_small_for_the_surface_cloud_only_leaves_the_map_as_it_was(ap
     assert all(a.tobytes() == b_.tobytes() for a, b_ in zip(after, before))     # neither cloud type was touched
     dc.prepare(pose[4:], corner, surf)                                          # still usable
     dc.close(); ctx.close()
+
+
+# ---- cubes OUTSIDE the valid set that receive points: old cloud + new points appended unfiltered (:2119-2125 without :2151-2165)
+FAR_POOL = 4096
+FAR_CUBES = {0: (2428,), 1: (2422, 2428, 2488)}                                 # where the far points fall with the centre at (10, 10, 5)
+ORIGIN = np.array([0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0])
+
+
+def far_frame(k, far=True):
+    """6 corner and 200 surf points near the origin, the same in every frame; far=True: points more than 125 m from the pose, beyond
+    the 5 x 5 x 3 valid cubes -- three on +x in both clouds (one moves 1 m per frame), one on -x and one on +y in surf"""
+    rng = np.random.default_rng(20)
+
+    def near(n):
+        p = rng.uniform(-20.0, 20.0, (n, 4)).astype(np.float32)
+        p[:, 2] *= 0.1; p[:, 3] = np.arange(n)
+        return p
+
+    corner, surf = near(6), near(200)
+    if far:
+        both = np.array([[140, 3, 1, 0], [141, 3.2, 1, 0], [140.5 + k, 3.1, 1.2, 0]], np.float32)
+        corner = np.concatenate([corner, both])
+        surf = np.concatenate([surf, both, np.array([[-135, -10, 2, 0], [5, 160, 0, 0]], np.float32)])
+    return corner, surf
+
+
+def _cube_index(pts):
+    """:2108-2125 with the centre at (10, 10, 5)"""
+    idx = []
+    for a, c in enumerate((10, 10, 5)):
+        v = pts[:, a].astype(np.float64) + 25.0
+        i = np.trunc(v / 50.0).astype(np.int64) + c
+        i[v < 0] -= 1
+        idx.append(i)
+    return idx[0] + 21 * idx[1] + 441 * idx[2]
+
+
+def far_oracle_frame(oc, k):
+    """frame k of far_frame on the oracle's cube map, with the conditions the far-cube tests stand on checked from the oracle
+    itself: the :1822 gate stays shut and the pose stays at the origin; every cube outside the valid set that receives points
+    afterwards holds its old cloud followed by those points, unfiltered -> the surf points the frame appends to a pool (the
+    filtered valid cubes, and old + new of the grown cubes)"""
+    corner, surf = far_frame(k)
+    oc.prepare(ORIGIN[4:], corner, surf)
+    assert len(oc.cloud(0)) <= 10                                               # :1822: more than 10 corners from the map to optimise
+    q, t, ran = oc.optimize(ORIGIN[:4], ORIGIN[4:])
+    assert not ran and (q == ORIGIN[:4]).all() and (t == ORIGIN[4:]).all()
+    before = {(s, c): oc.cube(s, c) for s in (0, 1) for c in FAR_CUBES[s]}
+    stack = [oc.cloud(2), oc.cloud(3)]
+    oc.update(q, t)
+    for (s, c), old in before.items():
+        new = stack[s][_cube_index(stack[s]) == c]
+        assert len(new) >= 1
+        assert_bit_equal(oc.cube(s, c), np.concatenate([old, new]), f"oracle frame {k} far cube {s} {c}")
+    valid = [i + 21 * j + 441 * kk for i in range(8, 13) for j in range(8, 13) for kk in range(4, 7)]
+    assert not set(valid) & set(FAR_CUBES[1])
+    return sum(len(oc.cube(1, c)) for c in valid) + sum(len(oc.cube(1, c)) for c in FAR_CUBES[1])
+
+
+def test_far_cubes_grow_unfiltered_through_compactions(api, orc):
+    """prepare / update with the oracle's pose in a pool of 4096: the cubes outside the valid set grow frame after frame, and the
+    surf pool -- compacted when it is 3/4 full -- takes more points than 3072 over the frames, so it compacts at least once with
+    grown clouds in it"""
+    ctx = api.Context(api.default_params(16, batch=1, max_points=4096))
+    dc = api.CubeMap(ctx, 64, 512, pool_points=FAR_POOL)
+    oc = orc.CubeMap()
+    appended = 0
+    for k in range(20):
+        corner, surf = far_frame(k)
+        dc.prepare(ORIGIN[4:], corner, surf)
+        appended += far_oracle_frame(oc, k)
+        dc.update(ORIGIN)
+        assert dc.info()[0] == oc.center() == (10, 10, 5)
+        cubes = _nonempty(oc)
+        assert all((s, c) in cubes for s in (0, 1) for c in FAR_CUBES[s])
+        for s, i in cubes:
+            assert_bit_equal(dc.cube(s, i), oc.cube(s, i), f"frame {k} cube {('corner', 'surf')[s]} {i}")
+        total_d = sum(len(dc.cube(s, i)) for s in (0, 1) for i in range(0, 4851, 97))   # spot check of empty cubes
+        total_o = sum(len(oc.cube(s, i)) for s in (0, 1) for i in range(0, 4851, 97))
+        assert total_d == total_o
+    assert appended > FAR_POOL * 3 // 4, appended
+    for s in (0, 1):
+        for c in FAR_CUBES[s]:
+            assert len(oc.cube(s, c)) >= 20
+    # every cube outside the valid set, the empty ones too: by the pair tables' counts and by the points they point at
+    valid = set(dc.layout()[2].tolist())
+    assert len(valid) == 75 and not valid & {c for s in (0, 1) for c in FAR_CUBES[s]}
+    counts = dc.layout()[1]
+    for s in (0, 1):
+        for c in range(4851):
+            if c not in valid:
+                want = oc.cube(s, c)
+                assert counts[s, c] == len(want), f"cube {s} {c} outside the valid set: {counts[s, c]} points, the oracle has {len(want)}"
+                assert_bit_equal(dc.cube(s, c, cap=max(len(want), 1)), want, f"cube {s} {c} outside the valid set")
+    dc.close(); ctx.close(); oc.close()

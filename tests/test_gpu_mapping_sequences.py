@@ -293,3 +293,59 @@ def test_end_to_end_with_odometry_sequences(api, synth):
     for o in ones:
         o.close()
     many.close(); ctx.close()
+
+
+def test_far_cubes_ragged_lanes_and_a_merge_on_compacted_pools(api, orc):
+    """cubes outside the valid set that receive points (test_gpu_cubemap.far_frame), in pools of 4096 that compact on the way:
+    lane 0 maps the far points, lane 1 the same scans without them, lane 2 sits out the odd frames.  Every lane equals a single
+    map fed the same frames, lane 0 the oracle as well; then lane 0 is merged into lane 1 -- onto a compacted pool, from grown cubes"""
+    from test_gpu_cubemap import FAR_CUBES, FAR_POOL, ORIGIN, far_frame, far_oracle_frame
+    from test_gpu_map_merge import BASE_SYNCS, check_map, expected_merge
+    S, n = 3, 20
+    ctx = api.Context(api.default_params(16, batch=1, max_points=4096))
+    many = api.CubeMaps(ctx, S, 64, 512, pool_points=FAR_POOL)
+    ones = [api.CubeMap(ctx, 64, 512, pool_points=FAR_POOL) for _ in range(S)]
+    oc = orc.CubeMap()
+    guess = np.tile(ORIGIN, (S, 1))
+    appended = 0
+    for k in range(n):
+        scans = [far_frame(k), far_frame(k, far=False), far_frame(k) if k % 2 == 0 else (None, None)]
+        poses, ran = many.process(guess, [c for c, _ in scans], [s for _, s in scans])
+        appended += far_oracle_frame(oc, k)
+        for q in range(S):
+            if scans[q][0] is None:
+                continue
+            p1, r1 = ones[q].process(guess[q], *scans[q])
+            assert not ran[q] and not r1, (k, q)
+            assert_bit_equal(poses[q], p1, f"frame {k} sequence {q} pose")
+            assert_bit_equal(poses[q], ORIGIN, f"frame {k} sequence {q}: the pose moved")
+        for q in range(S):                                                      # the pair tables' view, then the clouds they point at
+            cen, counts, valid = many.layout(q)
+            cen1, counts1, valid1 = ones[q].layout()
+            assert tuple(cen) == tuple(cen1) and (counts == counts1).all() and valid.tolist() == valid1.tolist(), (k, q)
+            for s, i in np.argwhere(counts):
+                assert_bit_equal(many.cube(q, s, i, cap=counts[s, i]), ones[q].cube(s, i, cap=counts[s, i]), f"frame {k} sequence {q} cube {s} {i}")
+        for s, i in _nonempty(oc.cube):
+            assert_bit_equal(many.cube(0, s, i), oc.cube(s, i), f"frame {k} lane 0 cube {s} {i}")
+    assert appended > FAR_POOL * 3 // 4, appended
+    assert _nonempty(oc.cube) == _nonempty(many.cube, 0)
+    for q in range(S):
+        _assert_same(many, q, ones[q], f"sequence {q}")
+    for s in (0, 1):
+        for c in FAR_CUBES[s]:
+            assert len(many.cube(0, s, c)) >= n and len(many.cube(1, s, c)) == 0 and len(many.cube(2, s, c)) >= n // 2
+    cen, _, valid = many.layout(1)
+    want, added, dropped, _ = expected_merge(orc, many, 1, 0, ORIGIN)
+    lane0, lane2 = [[(s, i, many.cube(q, s, i)) for s, i in _nonempty(many.cube, q)] for q in (0, 2)]
+    sy0, f0 = many.stats()
+    got_added, got_dropped = many.merge([(1, 0, ORIGIN)])
+    assert many.stats() == (sy0 + BASE_SYNCS, f0)
+    assert got_added.tolist() == [added] and got_dropped.tolist() == [dropped] and dropped == [0, 0]
+    check_map(many, 1, want, cen, valid, "lane 1 <- lane 0")
+    for q, cubes in ((0, lane0), (2, lane2)):
+        assert [(s, i) for s, i, _ in cubes] == _nonempty(many.cube, q)
+        for s, i, pts in cubes:
+            assert_bit_equal(many.cube(q, s, i), pts, f"after the merge: lane {q} cube {s} {i}")
+    for o in ones:
+        o.close()
+    many.close(); ctx.close(); oc.close()
