@@ -763,6 +763,66 @@ int  ll_cubemaps_align(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops, int 
                        double *T_w7 /* [n_ops][7] out */, int *ran /* [n_ops], may be NULL */, ll_localize_fit *fit /* [n_ops], may be NULL */);
 int  ll_cubemaps_align_timing(const ll_cubemaps *cms, double *ms /* build, search+fit, evaluate+solve, fit */, long long *counts /* stack points, map points, residual blocks */);
 
+/* ---------------------------------------------------------------- place recognition: Scan Context descriptors, exhaustive matching
+ * ll_places answers what comes before align, merge and set_localize: which stored scan is this scan a revisit of, and under which
+ * heading.  It is the descriptor of Kim & Kim, "Scan Context" (IROS 2018) -- not part of the reference -- with an exact search of
+ * every query against every stored place instead of the ring-key prefilter of the CPU implementations.
+ * Descriptor: 20 rings x 60 sectors, desc[ring][sector], 1200 floats.  For a point (x, y, z), in f32 with every product and sum
+ * rounded:  r = sqrtf(x*x + y*y), used iff r < max_radius (a NaN is dropped);  ring i = min(19, (int)(r / w)), w = max_radius / 20.0f
+ * (the min only acts where the rounding of w lets r / w reach 20);  a = atan2f(y, x), +6.2831855f if negative;  sector
+ * j = min(59, (int)(a * k)), k the float nearest to 60 / (2 pi);  desc[i][j] = the maximum over the bin's points of z + z_offset.  A bin
+ * without points is 0.0f; one whose points all lie below -z_offset keeps its negative maximum.  z_offset is the sensor height.
+ * Non-finite z, and non-finite uploaded descriptors, are outside the contract.  The source of ll_places_add_slots is a slot's resident
+ * laserCloud (what ll_download_cloud returns); a slot whose scan was refused or is empty gives the all-zero descriptor, without a
+ * read of its status by the host.  ll_places_add_points describes a host cloud through the same kernel.
+ * Match-ready form, kept beside every descriptor and rebuilt by the same kernel after add and upload: norm_j = sqrtf of the sum over
+ * rings 0 .. 19, in that order, of d*d in f32; column j divided by norm_j; a column with norm_j == 0 stays zero and counts as empty.
+ * Distance of query Q and candidate C at shift s in 0 .. 59: over the columns j for which Q's column (j + s) mod 60 and C's column j
+ * are both not empty (count of them), sim = the sum over j ascending of (unit column (j + s) mod 60 of Q) . (unit column j of C), a dot
+ * product being an fmaf chain over rings 0 .. 19;  d(s) = 1.0f - sim / (float)count, 1.0f when count == 0.  The pair's result is
+ * (min over s of d(s), the lowest s that reaches it).  If the query scan is the candidate scan turned by +phi about z,
+ * p_q = Rz(phi) p_c, the minimum lies at s = phi / 6 degrees.  With P_q, P_c the two scans' poses in their maps, the transform from
+ * the query's map to the candidate's is T0 = P_c Rz(-phi) P_q^-1; its translation is off by the distance between the two sensor
+ * positions (metres), so it goes to ll_cubemaps_align as a small lattice of ops around T0 (n_outer = 0 scores a guess).
+ * A pair's (distance, shift) has the same bits alone or inside any batch, whatever nq, nc and K are.
+ *   ll_places_create     capacity places of 10 KB each in HBM; LL_ERR_ARG (ll_last_error(ctx)) for a capacity outside 1 .. 2^24 or
+ *                        max_radius not positive and finite.  Destroy it before its context.
+ *   ll_places_size       the number of places, ids 0 .. size - 1 (LL_ERR_ARG for NULL);  ll_places_reset: size = 0
+ *   ll_places_add_slots  one place per entry of slots[count], ids consecutive from *first_id (may be NULL); one launch for all
+ *   ll_places_add_points one place from n >= 0 host points
+ *   ll_places_upload     count descriptors to ids first .. first + count - 1, first <= size: overwrites or extends
+ *   ll_places_download   count descriptors from id first
+ *   ll_places_distances  dist[nq][nc], shift[nq][nc] of queries q0 .. q0 + nq - 1 against candidates c0 .. c0 + nc - 1 of the same
+ *                        database; LL_ERR_ARG when nq * nc exceeds 2^26
+ *   ll_places_match      per query the K best candidates (1 <= K <= 8) by (distance, id) ascending: id[nq][K], dist[nq][K],
+ *                        shift[nq][K]; ranks without a candidate hold id = -1, dist = +inf, shift = 0.  c_end NULL, or per query:
+ *                        only candidate ids below c_end[q] are seen (a drive searching its own past without the last N frames).
+ *                        The same nq * nc bound.
+ *   ll_places_timing     ms[3]: device time of the last add / upload (describe + match-ready form; the call waits for it), of the
+ *                        last search's Gram matrices and diagonals, and of the last match's selection; counts[2]: places of that
+ *                        add, pairs of that search.  Either may be NULL.
+ * add and upload enqueue on the context's stream and do not synchronise; download, distances and match synchronise ONCE per call,
+ * whatever the sizes.  Errors are decided before anything is enqueued: LL_ERR_ARG for NULL handles or outputs, a slot outside the
+ * context's batch, ranges outside 0 .. size, K outside 1 .. 8; LL_ERR_CAPACITY when an add or upload would exceed capacity (nothing
+ * is added); LL_ERR_HIP when a workspace cannot be allocated.  ll_places_last_error has the text.
+ * With ll_drives: a lane's laserCloud stays in the slot its raw scan was uploaded to until that row of the ring is reused two steps
+ * later, so ll_places_add_slots takes the values ll_drives_slots returned BEFORE the step, after the step.                         */
+typedef struct ll_places ll_places;
+typedef struct { int capacity; float max_radius, z_offset; } ll_places_params;
+void ll_places_default_params(ll_places_params *p, int capacity);      /* max_radius 80, z_offset 2 */
+int  ll_places_create(ll_ctx *ctx, const ll_places_params *p, ll_places **out);
+void ll_places_destroy(ll_places *db);
+const char *ll_places_last_error(const ll_places *db);
+int  ll_places_size(const ll_places *db);
+int  ll_places_reset(ll_places *db);
+int  ll_places_add_slots(ll_places *db, const int *slots, int count, int *first_id);
+int  ll_places_add_points(ll_places *db, const ll_point *host, int n, int *id);
+int  ll_places_upload(ll_places *db, int first, int count, const float *desc1200);
+int  ll_places_download(ll_places *db, int first, int count, float *desc1200);
+int  ll_places_distances(ll_places *db, int q0, int nq, int c0, int nc, float *dist, unsigned char *shift);
+int  ll_places_match(ll_places *db, int q0, int nq, int c0, int nc, const int *c_end, int K, int *id, float *dist, unsigned char *shift);
+int  ll_places_timing(ll_places *db, double *ms, long long *counts);
+
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),
  * everything device-resident, no host synchronisation inside.  `vote_enable` as above.                   */

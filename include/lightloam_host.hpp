@@ -743,6 +743,71 @@ private:
     ll_drives *d_ = nullptr;
 };
 
+/* Place recognition (ll_places): Scan Context descriptors of resident or uploaded scans, 20 rings x 60 sectors = 1200 floats each, and
+ * the exact search of every query against every stored place.  Ids are 0 .. size() - 1 in the order of the adds.  With Drives:
+ * add_slots takes the values Drives::slots() returned BEFORE the step, after the step.  Destroy it before its Context. */
+class Places {
+public:
+    struct Match { std::vector<int> id; std::vector<float> dist; std::vector<unsigned char> shift; };   /* [nq][K], or [nq][nc] without id */
+    Places(Context &c, int capacity, float max_radius = 80.0f, float z_offset = 2.0f) {
+        ll_places_params p;
+        ll_places_default_params(&p, capacity);
+        p.max_radius = max_radius; p.z_offset = z_offset;
+        c.check(ll_places_create(c.get(), &p, &db_));
+    }
+    ~Places() { ll_places_destroy(db_); }
+    Places(const Places &) = delete;
+    Places &operator=(const Places &) = delete;
+
+    int size() const { return ll_places_size(db_); }
+    void reset() { check(ll_places_reset(db_)); }
+    /* one place per slot from its laserCloud; the first new id */
+    int add_slots(const std::vector<int> &slots) {
+        int first = -1;
+        check(ll_places_add_slots(db_, slots.data(), (int)slots.size(), &first));
+        return first;
+    }
+    int add_points(const std::vector<PointXYZI> &cloud) {
+        int id = -1;
+        check(ll_places_add_points(db_, (const ll_point *)cloud.data(), (int)cloud.size(), &id));
+        return id;
+    }
+    /* desc: a multiple of 1200 floats, to ids first .. (first <= size(): overwrites or extends) */
+    void upload(int first, const std::vector<float> &desc) {
+        if (desc.size() % 1200 != 0) throw Error(LL_ERR_ARG, "descriptors are 1200 floats each");
+        check(ll_places_upload(db_, first, (int)(desc.size() / 1200), desc.data()));
+    }
+    std::vector<float> download(int first, int count) {
+        std::vector<float> desc((size_t)1200 * (count > 0 ? count : 0));
+        check(ll_places_download(db_, first, count, desc.data()));
+        return desc;
+    }
+    /* every query q0 .. q0 + nq - 1 against every candidate c0 .. c0 + nc - 1: dist and shift [nq][nc] */
+    Match distances(int q0, int nq, int c0, int nc) {
+        Match m;
+        const size_t n = (size_t)(nq > 0 ? nq : 0) * (size_t)(nc > 0 ? nc : 0);
+        m.dist.resize(n); m.shift.resize(n);
+        check(ll_places_distances(db_, q0, nq, c0, nc, m.dist.data(), m.shift.data()));
+        return m;
+    }
+    /* per query its K best candidates by (distance, id); ranks without one hold (-1, inf, 0).  c_end: empty, or [nq] -- query q only
+     * sees candidate ids below c_end[q] */
+    Match match(int q0, int nq, int c0, int nc, int K = 1, const std::vector<int> &c_end = std::vector<int>()) {
+        if (!c_end.empty() && (int)c_end.size() != nq) throw Error(LL_ERR_ARG, "one c_end per query");
+        Match m;
+        const size_t n = (size_t)(nq > 0 ? nq : 0) * (size_t)(K > 0 ? K : 0);
+        m.id.resize(n); m.dist.resize(n); m.shift.resize(n);
+        check(ll_places_match(db_, q0, nq, c0, nc, c_end.empty() ? nullptr : c_end.data(), K, m.id.data(), m.dist.data(), m.shift.data()));
+        return m;
+    }
+    /* ms[3]: the last add / upload, the last search's Gram matrices and diagonals, the last match's selection; counts[2]: places, pairs */
+    void timing(double ms[3], long long counts[2]) { check(ll_places_timing(db_, ms, counts)); }
+    ll_places *get() const { return db_; }
+private:
+    void check(int rc) const { if (rc != LL_OK) throw Error(rc, ll_places_last_error(db_)); }
+    ll_places *db_ = nullptr;
+};
+
 }  // namespace lightloam
 
 /* ------------------------------------------------------------------------------------------------------------------

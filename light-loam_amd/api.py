@@ -46,6 +46,9 @@ EXPORTS = [
     "ll_debug_sort_pairs", "ll_debug_exscan", "ll_debug_voxel_segments",
     "ll_set_deskew", "ll_deskew_slots",
     "ll_map_set_vote", "ll_map_download_vote", "ll_map_vote_host", "ll_cubemap_set_vote", "ll_cubemaps_set_vote", "ll_drives_set_map_vote",
+    "ll_places_default_params", "ll_places_create", "ll_places_destroy", "ll_places_last_error", "ll_places_size", "ll_places_reset",
+    "ll_places_add_slots", "ll_places_add_points", "ll_places_upload", "ll_places_download", "ll_places_distances", "ll_places_match",
+    "ll_places_timing",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -153,6 +156,22 @@ def load_library():
         _lib.ll_cubemap_set_vote.argtypes = [C.c_void_p, C.c_int]
         _lib.ll_cubemaps_set_vote.argtypes = [C.c_void_p, C.c_void_p]
         _lib.ll_drives_set_map_vote.argtypes = [C.c_void_p, C.c_int]
+        _lib.ll_places_default_params.restype = None
+        _lib.ll_places_default_params.argtypes = [C.c_void_p, C.c_int]
+        _lib.ll_places_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ll_places_destroy.restype = None
+        _lib.ll_places_destroy.argtypes = [C.c_void_p]
+        _lib.ll_places_last_error.restype = C.c_char_p
+        _lib.ll_places_last_error.argtypes = [C.c_void_p]
+        _lib.ll_places_size.argtypes = [C.c_void_p]
+        _lib.ll_places_reset.argtypes = [C.c_void_p]
+        _lib.ll_places_add_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_places_add_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_places_upload.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.ll_places_download.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.ll_places_distances.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ll_places_match.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ll_places_timing.argtypes = [C.c_void_p] * 3
     return _lib
 
 
@@ -545,6 +564,10 @@ class Context:
             err.n_out = n.value
             raise err
         return out[:n.value].copy(), cnt[:len(so) - 1].copy()
+
+    def places(self, capacity, max_radius=None, z_offset=None):
+        """a Places database of `capacity` Scan Context descriptors on this context (ll_places_create)"""
+        return Places(self, capacity, max_radius, z_offset)
 
     def algorithmic_bytes(self, first=0, count=1):
         b = [C.c_double(0) for _ in range(4)]
@@ -1098,6 +1121,101 @@ class CubeMaps:
     def reset(self, q):
         """sequence q back to a freshly created cube map; the others are untouched"""
         self._ck(self.lib.ll_cubemaps_reset(self.h, int(q)))
+
+
+class PlacesParams(C.Structure):
+    _fields_ = [("capacity", C.c_int), ("max_radius", C.c_float), ("z_offset", C.c_float)]
+
+
+class Places:
+    """One ll_places: Scan Context descriptors (20 rings x 60 sectors) of resident or uploaded scans in HBM, and the exact search of
+    every query against every stored place.  Place ids are 0 .. size - 1 in the order they were added."""
+
+    DESC = (20, 60)
+
+    def __init__(self, ctx, capacity, max_radius=None, z_offset=None):
+        self.ctx = ctx; self.lib = ctx.lib
+        self.params = PlacesParams()
+        self.lib.ll_places_default_params(C.byref(self.params), int(capacity))
+        if max_radius is not None:
+            self.params.max_radius = max_radius
+        if z_offset is not None:
+            self.params.z_offset = z_offset
+        self.h = C.c_void_p()
+        rc = self.lib.ll_places_create(ctx.h, C.byref(self.params), C.byref(self.h))
+        if rc != LL_OK:
+            raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ll_places_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_places_last_error(self.h).decode())
+
+    def __len__(self):
+        return self.lib.ll_places_size(self.h)
+
+    def reset(self):
+        self._ck(self.lib.ll_places_reset(self.h))
+
+    def add_slots(self, slots):
+        """one place per slot from the slots' resident laserCloud -> the first new id.  With Drives: the values slots() returned
+        BEFORE the step"""
+        s = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        first = C.c_int(-1)
+        self._ck(self.lib.ll_places_add_slots(self.h, _ptr(s), len(s), C.byref(first)))
+        return first.value
+
+    def add_points(self, points):
+        """one place from a host cloud (n, 4) float32 -> its id"""
+        a = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        pid = C.c_int(-1)
+        self._ck(self.lib.ll_places_add_points(self.h, _ptr(a), len(a), C.byref(pid)))
+        return pid.value
+
+    def upload(self, first, desc):
+        """descriptors [count, 20, 60] float32 to ids first .. (first <= len(self): overwrites or extends)"""
+        d = np.ascontiguousarray(desc, np.float32).reshape(-1, 1200)
+        self._ck(self.lib.ll_places_upload(self.h, int(first), len(d), _ptr(d)))
+
+    def download(self, first=0, count=None):
+        count = len(self) - int(first) if count is None else int(count)
+        out = np.zeros((max(count, 0), 20, 60), np.float32)
+        self._ck(self.lib.ll_places_download(self.h, int(first), count, _ptr(out)))
+        return out
+
+    def distances(self, q0, nq, c0, nc):
+        """(dist [nq, nc] float32, shift [nq, nc] uint8): queries q0 .. against candidates c0 .."""
+        dist = np.zeros((max(nq, 0), max(nc, 0)), np.float32); shift = np.zeros(dist.shape, np.uint8)
+        self._ck(self.lib.ll_places_distances(self.h, int(q0), int(nq), int(c0), int(nc), _ptr(dist), _ptr(shift)))
+        return dist, shift
+
+    def match(self, q0, nq, c0, nc, K=1, c_end=None):
+        """(id [nq, K] int32, dist [nq, K] float32, shift [nq, K] uint8): per query its K best candidates by (distance, id); ranks
+        without a candidate hold (-1, inf, 0).  c_end [nq]: query q only sees candidate ids below c_end[q]"""
+        shape = (max(nq, 0), int(K))
+        pid = np.zeros(shape, np.int32); dist = np.zeros(shape, np.float32); shift = np.zeros(shape, np.uint8)
+        ce = None if c_end is None else np.ascontiguousarray(c_end, np.int32).reshape(-1)
+        if ce is not None and len(ce) != nq:
+            raise ValueError("c_end must have one entry per query")
+        self._ck(self.lib.ll_places_match(self.h, int(q0), int(nq), int(c0), int(nc), _ptr(ce), int(K), _ptr(pid), _ptr(dist), _ptr(shift)))
+        return pid, dist, shift
+
+    def timing(self):
+        """{"ms": [describe, gram, select], "places": of the last add / upload, "pairs": of the last search} (device events)"""
+        ms = np.zeros(3); cnt = np.zeros(2, np.int64)
+        self._ck(self.lib.ll_places_timing(self.h, _ptr(ms), _ptr(cnt)))
+        return {"ms": ms.tolist(), "places": int(cnt[0]), "pairs": int(cnt[1])}
 
 
 class DrivesParams(C.Structure):
