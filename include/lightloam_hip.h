@@ -823,6 +823,54 @@ int  ll_places_distances(ll_places *db, int q0, int nq, int c0, int nc, float *d
 int  ll_places_match(ll_places *db, int q0, int nq, int c0, int nc, const int *c_end, int K, int *id, float *dist, unsigned char *shift);
 int  ll_places_timing(ll_places *db, double *ms, long long *counts);
 
+/* ---------------------------------------------------------------- pose graphs (ll_posegraph.hip; not in the reference)
+ * Batched SE(3) pose-graph optimisation: what distributes a measured loop closure (ll_places_match + a localising lane) or a set of
+ * session-to-session transforms (ll_cubemaps_align) over a trajectory.  n_graphs independent graphs per call, one workgroup each, the
+ * whole Levenberg-Marquardt solve in one launch.
+ *   A graph has N poses P_k = (q_k, t_k), world from body, in the pose_w7 layout (qx, qy, qz, qw, tx, ty, tz), and E edges.  Edge
+ *   (i, j, Z_w7, sqrt_info, huber): Z measures P_i^-1 P_j; sqrt_info[6] is the DIAGONAL square-root information, rotation first, then
+ *   translation; huber is the width a of ceres::HuberLoss, a <= 0 for none.  With E = Z^-1 P_i^-1 P_j = (q_e, t_e) the residual is
+ *   r = sqrt_info o [2 sgn(w_e) vec(q_e) ; t_e] (sgn(0) = +1) and the cost 1/2 sum_e rho_a(|r_e|^2).  Increments are six per node
+ *   (half-angle vector, then translation), applied as ll_lm_solve_batch applies them: q <- exp(d) (x) q, t <- t + dt.  Quaternions of
+ *   poses and measurements are normalised on entry.  fixed[k] != 0 takes node k out of the problem.
+ *   Layout of a call: node_off and edge_off have n_graphs + 1 ascending entries from 0 (ragged graphs back to back); poses_w7, fixed
+ *   and edges are indexed by them; an edge's i, j are LOCAL to its graph.  fixed == NULL: node 0 of every graph is fixed.
+ *   ll_pg_default_options   Ceres' trust-region defaults as ll_lm_default_options has them, 50 LM iterations, 1000 PCG iterations per
+ *                           LM iteration, eta 0.1 (PCG stops at |r| <= eta |g|).  Needs no device.
+ *   ll_posegraphs_create    device buffers for calls of at most max_graphs graphs with max_nodes_total nodes and max_edges_total
+ *                           edges in all (about 850 B per node, 1.1 KB per edge).
+ *   ll_posegraphs_evaluate  cost[n_graphs], the robustified cost of every graph at poses_w7, and grad6[nodes][6], its gradient with
+ *                           respect to the increments (zeros at fixed nodes).  Solves nothing: the chi-square of a candidate loop edge
+ *                           before it is accepted, and the tests' window onto the Jacobians.
+ *   ll_posegraphs_solve     optimises poses_w7 in place; rec (may be NULL) gets one record per graph: the cost at the start and at the
+ *                           returned poses, the max-norm of Plus(x, -g) - x there, LM iterations, accepted steps, PCG iterations and
+ *                           termination: 0 gradient_tolerance, 1 function_tolerance, 2 parameter_tolerance, 3 max_lm_iterations,
+ *                           4 radius below min_radius, 5 a non-finite cost, gradient or step was met -- the poses are then the last
+ *                           accepted ones (the input, if none was), never NaN.  Fixed nodes, nodes without an edge and every node of
+ *                           a graph no step of which was accepted come back bit for bit.  opt == NULL: the defaults.
+ *   ll_posegraphs_timing    ms[2]: device time of the last evaluate and of the last solve; counts[3]: graphs of the last call, LM and
+ *                           PCG iterations of the last solve summed over its graphs.  Either may be NULL.
+ * A graph's result does not depend on the batch: its poses and record have the same bits alone, in any batch, at any position.
+ * evaluate and solve synchronise with the host ONCE per call, whatever the sizes.  Errors are decided on the host before anything is
+ * enqueued and leave poses_w7 untouched; ll_posegraphs_last_error names the graph and the edge.  LL_ERR_ARG: a NULL pointer, offsets that
+ * do not ascend from 0, an index outside its graph, i == j, a non-finite pose, measurement or weight, a zero quaternion, a graph without
+ * a fixed node, options out of range.  LL_ERR_CAPACITY: the call exceeds a create-time total.  LL_ERR_HIP: an allocation failed.        */
+typedef struct ll_posegraphs ll_posegraphs;
+typedef struct { int i, j; double Z_w7[7]; double sqrt_info[6]; double huber; } ll_pg_edge;   /* i, j local to the graph */
+typedef struct { int max_lm_iterations, max_pcg_iterations; double eta, initial_radius, max_radius, min_radius,
+                 min_relative_decrease, min_lm_diagonal, max_lm_diagonal, function_tolerance, gradient_tolerance,
+                 parameter_tolerance; } ll_pg_options;
+typedef struct { double cost0, cost, grad_max; int lm_iterations, lm_successes, pcg_iterations, termination; } ll_pg_record;
+void ll_pg_default_options(ll_pg_options *o);      /* Ceres' defaults where ll_lm_default_options has them; 50 LM, 1000 PCG, eta 0.1 */
+int  ll_posegraphs_create(ll_ctx *ctx, int max_graphs, int max_nodes_total, int max_edges_total, ll_posegraphs **out);
+void ll_posegraphs_destroy(ll_posegraphs *pg);
+const char *ll_posegraphs_last_error(const ll_posegraphs *pg);
+int  ll_posegraphs_evaluate(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                            const unsigned char *fixed, const ll_pg_edge *edges, double *cost, double *grad6);
+int  ll_posegraphs_solve(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, double *poses_w7,
+                         const unsigned char *fixed, const ll_pg_edge *edges, const ll_pg_options *opt, ll_pg_record *rec);
+int  ll_posegraphs_timing(ll_posegraphs *pg, double *ms2, long long *counts3);
+
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),
  * everything device-resident, no host synchronisation inside.  `vote_enable` as above.                   */

@@ -808,6 +808,92 @@ private:
     ll_places *db_ = nullptr;
 };
 
+/* Pose graphs (ll_posegraphs): many independent SE(3) graphs optimised side by side, one workgroup per graph.  A Graph holds poses
+ * [N][7] (pose_w7, world from body), edges whose i, j index its own poses and whose Z measures P_i^-1 P_j, and an optional fixed flag
+ * per node (empty: node 0 is fixed).  sqrt_info is the caller's choice: nothing in the library produces a covariance.  Destroy it
+ * before its Context. */
+class PoseGraphs {
+public:
+    struct Graph { std::vector<double> poses; std::vector<ll_pg_edge> edges; std::vector<unsigned char> fixed; };
+    struct Evaluation { std::vector<double> cost; std::vector<std::vector<double>> grad; };   /* [graphs], [graphs][N * 6] */
+    PoseGraphs(Context &c, int max_graphs, int max_nodes_total, int max_edges_total) {
+        c.check(ll_posegraphs_create(c.get(), max_graphs, max_nodes_total, max_edges_total, &pg_));
+    }
+    ~PoseGraphs() { ll_posegraphs_destroy(pg_); }
+    PoseGraphs(const PoseGraphs &) = delete;
+    PoseGraphs &operator=(const PoseGraphs &) = delete;
+
+    static ll_pg_options default_options() { ll_pg_options o; ll_pg_default_options(&o); return o; }
+    /* P_i^-1 P_j in the pose_w7 layout: the measurement of an odometry edge between two poses of a chain */
+    static void relative_pose(const double Pi[7], const double Pj[7], double Z[7]) {
+        const double ci[4] = {-Pi[0], -Pi[1], -Pi[2], Pi[3]}, v[3] = {Pj[4] - Pi[4], Pj[5] - Pi[5], Pj[6] - Pi[6]};
+        qmul(ci, Pj, Z);
+        const double tq[4] = {v[0], v[1], v[2], 0.0};
+        double a[4], b[4];
+        const double n2 = Pi[0] * Pi[0] + Pi[1] * Pi[1] + Pi[2] * Pi[2] + Pi[3] * Pi[3];
+        qmul(ci, tq, a); qmul(a, Pi, b);                                    /* q* v q = R(q)^T v |q|^2 */
+        for (int k = 0; k < 3; ++k) Z[4 + k] = b[k] / n2;
+    }
+    static ll_pg_edge edge(int i, int j, const double Z[7], double sqrt_info_rot, double sqrt_info_trans, double huber = 0.0) {
+        ll_pg_edge e;
+        e.i = i; e.j = j; e.huber = huber;
+        for (int k = 0; k < 7; ++k) e.Z_w7[k] = Z[k];
+        for (int k = 0; k < 3; ++k) { e.sqrt_info[k] = sqrt_info_rot; e.sqrt_info[3 + k] = sqrt_info_trans; }
+        return e;
+    }
+    /* the robustified cost of every graph and its gradient per node (6 each, zeros at fixed nodes); solves nothing */
+    Evaluation evaluate(const std::vector<Graph> &graphs) {
+        pack(graphs);
+        Evaluation ev;
+        ev.cost.resize(graphs.size());
+        std::vector<double> grad(poses_.size() / 7 * 6);
+        check(ll_posegraphs_evaluate(pg_, (int)graphs.size(), node_off_.data(), edge_off_.data(), poses_.data(), fixed_ptr(), edges_.data(),
+                                     ev.cost.data(), grad.data()));
+        for (size_t g = 0; g < graphs.size(); ++g)
+            ev.grad.emplace_back(grad.begin() + (size_t)node_off_[g] * 6, grad.begin() + (size_t)node_off_[g + 1] * 6);
+        return ev;
+    }
+    /* optimises every graph's poses in place; one record per graph */
+    std::vector<ll_pg_record> solve(std::vector<Graph> &graphs, const ll_pg_options *opt = nullptr) {
+        pack(graphs);
+        std::vector<ll_pg_record> rec(graphs.size());
+        check(ll_posegraphs_solve(pg_, (int)graphs.size(), node_off_.data(), edge_off_.data(), poses_.data(), fixed_ptr(), edges_.data(), opt, rec.data()));
+        for (size_t g = 0; g < graphs.size(); ++g)
+            std::copy(poses_.begin() + (size_t)node_off_[g] * 7, poses_.begin() + (size_t)node_off_[g + 1] * 7, graphs[g].poses.begin());
+        return rec;
+    }
+    /* ms[2]: the last evaluate, the last solve (device time); counts[3]: graphs, LM iterations, PCG iterations of the last call */
+    void timing(double ms[2], long long counts[3]) { check(ll_posegraphs_timing(pg_, ms, counts)); }
+    ll_posegraphs *get() const { return pg_; }
+private:
+    static void qmul(const double a[4], const double b[4], double o[4]) {
+        o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+        o[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
+        o[2] = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
+        o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+    }
+    /* the ragged packing: graphs back to back; a graph without flags gets node 0 fixed */
+    void pack(const std::vector<Graph> &graphs) {
+        node_off_.assign(1, 0); edge_off_.assign(1, 0); poses_.clear(); edges_.clear(); fixed_.clear();
+        for (const Graph &g : graphs) {
+            if (g.poses.size() % 7 != 0) throw Error(LL_ERR_ARG, "poses are 7 doubles each");
+            const size_t n = g.poses.size() / 7;
+            if (!g.fixed.empty() && g.fixed.size() != n) throw Error(LL_ERR_ARG, "one fixed flag per node");
+            poses_.insert(poses_.end(), g.poses.begin(), g.poses.end());
+            edges_.insert(edges_.end(), g.edges.begin(), g.edges.end());
+            for (size_t k = 0; k < n; ++k) fixed_.push_back(g.fixed.empty() ? (unsigned char)(k == 0) : g.fixed[k]);
+            node_off_.push_back((int)(poses_.size() / 7)); edge_off_.push_back((int)edges_.size());
+        }
+    }
+    const unsigned char *fixed_ptr() const { return fixed_.data(); }
+    void check(int rc) const { if (rc != LL_OK) throw Error(rc, ll_posegraphs_last_error(pg_)); }
+    ll_posegraphs *pg_ = nullptr;
+    std::vector<int> node_off_, edge_off_;
+    std::vector<double> poses_;
+    std::vector<ll_pg_edge> edges_;
+    std::vector<unsigned char> fixed_;
+};
+
 }  // namespace lightloam
 
 /* ------------------------------------------------------------------------------------------------------------------

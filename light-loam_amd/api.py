@@ -49,6 +49,8 @@ EXPORTS = [
     "ll_places_default_params", "ll_places_create", "ll_places_destroy", "ll_places_last_error", "ll_places_size", "ll_places_reset",
     "ll_places_add_slots", "ll_places_add_points", "ll_places_upload", "ll_places_download", "ll_places_distances", "ll_places_match",
     "ll_places_timing",
+    "ll_pg_default_options", "ll_posegraphs_create", "ll_posegraphs_destroy", "ll_posegraphs_last_error", "ll_posegraphs_evaluate",
+    "ll_posegraphs_solve", "ll_posegraphs_timing",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -172,6 +174,16 @@ def load_library():
         _lib.ll_places_distances.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ll_places_match.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ll_places_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_pg_default_options.restype = None
+        _lib.ll_pg_default_options.argtypes = [C.c_void_p]
+        _lib.ll_posegraphs_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.ll_posegraphs_destroy.restype = None
+        _lib.ll_posegraphs_destroy.argtypes = [C.c_void_p]
+        _lib.ll_posegraphs_last_error.restype = C.c_char_p
+        _lib.ll_posegraphs_last_error.argtypes = [C.c_void_p]
+        _lib.ll_posegraphs_evaluate.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        _lib.ll_posegraphs_solve.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        _lib.ll_posegraphs_timing.argtypes = [C.c_void_p] * 3
     return _lib
 
 
@@ -564,6 +576,10 @@ class Context:
             err.n_out = n.value
             raise err
         return out[:n.value].copy(), cnt[:len(so) - 1].copy()
+
+    def posegraphs(self, max_graphs, max_nodes_total, max_edges_total):
+        """a PoseGraphs solver on this context for calls of at most these totals (ll_posegraphs_create)"""
+        return PoseGraphs(self, max_graphs, max_nodes_total, max_edges_total)
 
     def places(self, capacity, max_radius=None, z_offset=None):
         """a Places database of `capacity` Scan Context descriptors on this context (ll_places_create)"""
@@ -1216,6 +1232,133 @@ class Places:
         ms = np.zeros(3); cnt = np.zeros(2, np.int64)
         self._ck(self.lib.ll_places_timing(self.h, _ptr(ms), _ptr(cnt)))
         return {"ms": ms.tolist(), "places": int(cnt[0]), "pairs": int(cnt[1])}
+
+
+class PgEdge(C.Structure):
+    """ll_pg_edge: Z_w7 measures P_i^-1 P_j (i, j local to the graph); sqrt_info: diagonal, rotation first; huber <= 0: no loss"""
+    _fields_ = [("i", C.c_int), ("j", C.c_int), ("Z_w7", C.c_double * 7), ("sqrt_info", C.c_double * 6), ("huber", C.c_double)]
+
+
+class PgOptions(C.Structure):
+    _fields_ = [("max_lm_iterations", C.c_int), ("max_pcg_iterations", C.c_int), ("eta", C.c_double), ("initial_radius", C.c_double),
+                ("max_radius", C.c_double), ("min_radius", C.c_double), ("min_relative_decrease", C.c_double),
+                ("min_lm_diagonal", C.c_double), ("max_lm_diagonal", C.c_double), ("function_tolerance", C.c_double),
+                ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double)]
+
+
+class PgRecord(C.Structure):
+    _fields_ = [("cost0", C.c_double), ("cost", C.c_double), ("grad_max", C.c_double), ("lm_iterations", C.c_int),
+                ("lm_successes", C.c_int), ("pcg_iterations", C.c_int), ("termination", C.c_int)]
+
+
+PG_EDGE = np.dtype([("i", "i4"), ("j", "i4"), ("Z_w7", "f8", (7,)), ("sqrt_info", "f8", (6,)), ("huber", "f8")])     # PgEdge as a numpy record
+PG_TERMINATION = {0: "gradient", 1: "function", 2: "parameter", 3: "iterations", 4: "radius", 5: "non-finite"}
+
+
+def pg_options(**kw):
+    """ll_pg_default_options with the given fields replaced"""
+    o = PgOptions()
+    load_library().ll_pg_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def _quat_mul(a, b):
+    return np.array([a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1],
+                     a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0],
+                     a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3],
+                     a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2]])
+
+
+def relative_pose(Pi, Pj):
+    """P_i^-1 P_j in the pose_w7 layout: the measurement of an odometry edge between two poses of a chain"""
+    Pi = np.asarray(Pi, np.float64); Pj = np.asarray(Pj, np.float64)
+    qi = Pi[:4] / np.linalg.norm(Pi[:4])
+    ci = qi * np.array([-1.0, -1.0, -1.0, 1.0])
+    v = np.concatenate([Pj[4:] - Pi[4:], [0.0]])
+    return np.concatenate([_quat_mul(ci, Pj[:4]), _quat_mul(_quat_mul(ci, v), qi)[:3]])
+
+
+def pg_edges(edges):
+    """a PG_EDGE record array from one, or from a list of (i, j, Z[7], sqrt_info[6] or scalar, huber) tuples"""
+    if isinstance(edges, np.ndarray) and edges.dtype == PG_EDGE:
+        return np.ascontiguousarray(edges).reshape(-1)
+    out = np.zeros(len(edges), PG_EDGE)
+    for k, e in enumerate(edges):
+        out[k] = (int(e[0]), int(e[1]), np.asarray(e[2], np.float64), np.broadcast_to(np.asarray(e[3], np.float64), (6,)), float(e[4]) if len(e) > 4 else 0.0)
+    return out
+
+
+class PoseGraphs:
+    """One ll_posegraphs: many independent SE(3) pose graphs optimised side by side on the device, one workgroup per graph.  A graph
+    is the tuple (poses [N, 7], edges, fixed): poses in the pose_w7 layout (world from body), edges as pg_edges takes them (i, j local to
+    the graph, Z measures P_i^-1 P_j), fixed None (node 0 is fixed) or N flags."""
+
+    def __init__(self, ctx, max_graphs, max_nodes_total, max_edges_total):
+        self.ctx = ctx; self.lib = ctx.lib
+        self.h = C.c_void_p()
+        rc = self.lib.ll_posegraphs_create(ctx.h, int(max_graphs), int(max_nodes_total), int(max_edges_total), C.byref(self.h))
+        if rc != LL_OK:
+            raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ll_posegraphs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_posegraphs_last_error(self.h).decode())
+
+    @staticmethod
+    def _pack(graphs):
+        """the ragged packing: (node_off, edge_off, poses [Nt, 7], fixed [Nt] uint8, edges [Et] PG_EDGE)"""
+        node_off = [0]; edge_off = [0]; poses = []; fixed = []; edges = []
+        for g in graphs:
+            p = np.ascontiguousarray(g[0], np.float64).reshape(-1, 7)
+            e = pg_edges(g[1])
+            f = g[2] if len(g) > 2 else None
+            if f is None:
+                f = np.zeros(len(p), np.uint8); f[:1] = 1
+            f = (np.asarray(f).reshape(-1) != 0).astype(np.uint8)
+            if len(f) != len(p):
+                raise ValueError("fixed must have one entry per node")
+            poses.append(p); fixed.append(f); edges.append(e)
+            node_off.append(node_off[-1] + len(p)); edge_off.append(edge_off[-1] + len(e))
+        cat = lambda parts, empty: np.ascontiguousarray(np.concatenate(parts)) if parts else empty
+        return (np.array(node_off, np.int32), np.array(edge_off, np.int32), cat(poses, np.zeros((0, 7))), cat(fixed, np.zeros(0, np.uint8)),
+                cat(edges, np.zeros(0, PG_EDGE)))
+
+    def evaluate(self, graphs):
+        """(cost [G], [grad [N_g, 6] per graph]): the robustified cost and its gradient per increment (zeros at fixed nodes)"""
+        no, eo, poses, fixed, edges = self._pack(graphs)
+        cost = np.zeros(len(graphs)); grad = np.zeros((len(poses), 6))
+        self._ck(self.lib.ll_posegraphs_evaluate(self.h, len(graphs), _ptr(no), _ptr(eo), _ptr(poses), _ptr(fixed), _ptr(edges), _ptr(cost), _ptr(grad)))
+        return cost, [grad[no[g]:no[g + 1]].copy() for g in range(len(graphs))]
+
+    def solve(self, graphs, options=None):
+        """([poses [N_g, 7] per graph], records [G] of PgRecord): the inputs are not modified.  options: a PgOptions (pg_options(...))"""
+        no, eo, poses, fixed, edges = self._pack(graphs)
+        rec = (PgRecord * max(len(graphs), 1))()
+        self._ck(self.lib.ll_posegraphs_solve(self.h, len(graphs), _ptr(no), _ptr(eo), _ptr(poses), _ptr(fixed), _ptr(edges),
+                                              None if options is None else C.addressof(options), C.addressof(rec)))
+        return [poses[no[g]:no[g + 1]].copy() for g in range(len(graphs))], list(rec)[:len(graphs)]
+
+    def timing(self):
+        """{"ms": [evaluate, solve] of the last such calls (device events), "graphs", "lm_iterations", "pcg_iterations": of the last call}"""
+        ms = np.zeros(2); cnt = np.zeros(3, np.int64)
+        self._ck(self.lib.ll_posegraphs_timing(self.h, _ptr(ms), _ptr(cnt)))
+        return {"ms": ms.tolist(), "graphs": int(cnt[0]), "lm_iterations": int(cnt[1]), "pcg_iterations": int(cnt[2])}
 
 
 class DrivesParams(C.Structure):

@@ -1,0 +1,632 @@
+/*
+ * ll_posegraph.hip -- ll_posegraphs: many independent SE(3) pose graphs optimised side by side, one workgroup per graph, the whole
+ * Levenberg-Marquardt solve in ONE launch.  Not in the reference; the contract is in include/lightloam_hip.h.
+ *
+ * The problem.  Poses P_k = (q_k, t_k), world from body, pose_w7 layout.  Edge e = (i, j, Z, s, a) measures Z ~ P_i^-1 P_j:
+ *     q_e = q_z* (x) q_i* (x) q_j,   t_e = R(q_z)^T (R(q_i)^T (t_j - t_i) - t_z),   r = s o [2 sgn(w_e) vec(q_e) ; t_e],  sgn(0) = +1,
+ *     cost = 1/2 sum_e rho_a(|r_e|^2), rho_a = ceres::HuberLoss(a) (a <= 0: none).
+ * The increment of a node is d = (w, dt), six numbers, applied by ll_pose_plus: q <- exp(w) (x) q with exp(w) = [sin|w| w/|w|, cos|w|]
+ * (w is the HALF-angle vector, the rotation it stands for is R(exp w) = I + 2 [w]x + O(w^2)), t <- t + dt.
+ *
+ * Jacobians (f64, closed form, at d = 0).  Write a = q_z* (x) q_i*, so that q_e = a (x) q_j and R(a) = R(q_z)^T R(q_i)^T, and v = t_j - t_i.
+ *   node j, rotation:  q_j <- [w, 1] (x) q_j  gives  q_e + a (x) [w, 0] (x) q_j, which is linear in w:
+ *                      d r_rot / d w_j = A,  column k of A = 2 sgn(w_e) vec(a (x) e_k (x) q_j),  e_k the pure unit quaternion of axis k.
+ *   node i, rotation:  q_i* <- q_i* (x) [-w, 1]  gives  q_e - a (x) [w, 0] (x) q_j:  d r_rot / d w_i = -A.
+ *                      R(q_i)^T <- R(q_i)^T (I - 2 [w]x):  t_e changes by -2 R(a) (w x v) = 2 R(a) [v]x w:  d t_e / d w_i = 2 R(a) [v]x.
+ *   translations:      d t_e / d t_j = R(a),  d t_e / d t_i = -R(a);  t_e does not depend on w_j, r_rot on no translation.
+ *       J_i = S [ -A  0 ; 2 R(a)[v]x  -R(a) ],   J_j = S [ A  0 ; 0  R(a) ],   S = diag(s).
+ * The Gauss-Newton model takes r and J times sqrt(rho') (ll_huber_scale: Ceres' corrector where rho'' <= 0), so g = J^T r is the
+ * gradient of the robust cost.
+ *
+ * k_pg_solve, graph = blockIdx.x, 256 threads, the per-graph workspace in HBM (at KITTI-00 size a few MB, L2-resident), LDS only for
+ * the reductions.  No grid barrier, no spin, no floating-point atomic; every loop is bounded by an option.  Per LM iteration:
+ *   linearise   a thread per edge: r, J_i, J_j, the Huber scale, then H_ij = J_i^T J_j, H_ii, H_jj (36 doubles each) and the two gradient
+ *               parts into the edge's own slots.  A thread per node then sums its diagonal block and gradient over its incident edges
+ *               in edge order (the CSR list the host built) -- a fixed order, so the bits do not depend on scheduling.
+ *   solve       (H + D / radius) d = -g by preconditioned conjugate gradients, D = the clamped diagonal of H as in ll_lm_step.h, the
+ *               preconditioner block-Jacobi: ll_chol_solve on every node's damped 6 x 6 block.  A thread per node does the mat-vec
+ *               over its incident edges' H_ij.  Dot products: thread-strided partial sums, then a fixed tree over the 256 partials (pg_sum2).
+ *               Stops at |r| <= eta |g|, at max_pcg_iterations, or at a p^T A p that is not positive and finite (the iterate so far
+ *               stays: CG's energy decreases monotonically, so it is the best one).
+ *   accept      ll_lm_step.h's policy over all nodes: model cost change -(g.d + d.H d / 2), the parameter and function tests, rho, the
+ *               radius update by 1 - (2 rho - 1)^3, a decrease factor that doubles with every rejection.  The candidate is judged by a
+ *               cost-only pass over the edges; an accepted one is linearised anew.
+ * Every index is relative to the graph and every sum has a fixed shape, so a graph's poses and record have the same bits alone, in any
+ * batch and at any position.  A non-finite cost, gradient or step ends the graph's solve with termination 5 and the last accepted poses.
+ */
+#include "ll_internal.h"
+#include "ll_factor_math.h"
+#include <cmath>
+
+#define PG_THREADS 256
+#define PG_NODE_DOUBLES 92                    /* x 7, cand 7, Hd 36, g 6, D 6, d 6, r 6, z 6, p 6, Ap 6 */
+#define PG_EDGE_DOUBLES 121                   /* H_ij, H_ii, H_jj 36 each, g_i, g_j 6 each, cost */
+
+struct PgArgs {
+    /* the call's input, as the host packed it */
+    const double *pose_in; const ll_pg_edge *edges; const int *node_off, *edge_off, *inc_off, *inc, *inc_nb; const unsigned char *fixed;
+    /* workspace, [nodes_total] or [edges_total] rows */
+    double *x, *cand, *Hd, *g, *D, *d, *r, *z, *p, *Ap, *eH, *eg, *ecost;
+    /* results: solve -> poses [nodes][7] + records; evaluate -> gradients [nodes][6] + costs */
+    double *out_nodes; ll_pg_record *rec; double *out_cost;
+    ll_pg_options o;
+    int solve;
+};
+
+struct ll_posegraphs {
+    ll_ctx *ctx = nullptr;
+    int max_graphs = 0, max_nodes = 0, max_edges = 0;
+    unsigned char *d_in = nullptr, *d_out = nullptr;
+    double *d_ws = nullptr;
+    size_t in_bytes = 0, out_bytes = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms[2] = {0.0, 0.0};
+    long long counts[3] = {0, 0, 0};
+    std::string err;
+};
+
+/* ------------------------------------------------------------------ device: one edge */
+__device__ __forceinline__ void pg_qmul(const double a[4], const double b[4], double o[4])     /* (x, y, z, w) */
+{
+    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    o[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
+    o[2] = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
+    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+}
+
+/* the weighted residual of edge e at (Pi, Pj); with A != NULL also what the Jacobians are made of: A (3 x 3, see above), Ra = R(a), v */
+__device__ __forceinline__ void pg_residual(const double *Pi, const double *Pj, const ll_pg_edge &e, double r[6], double (*A)[3], double (*Ra)[3], double *v)
+{
+    const double zn = sqrt((e.Z_w7[0] * e.Z_w7[0] + e.Z_w7[1] * e.Z_w7[1]) + (e.Z_w7[2] * e.Z_w7[2] + e.Z_w7[3] * e.Z_w7[3]));
+    const double qzc[4] = {-e.Z_w7[0] / zn, -e.Z_w7[1] / zn, -e.Z_w7[2] / zn, e.Z_w7[3] / zn};
+    const double qic[4] = {-Pi[0], -Pi[1], -Pi[2], Pi[3]};
+    double a[4], qe[4];
+    pg_qmul(qzc, qic, a);
+    pg_qmul(a, Pj, qe);
+    const double sgn = qe[3] < 0.0 ? -1.0 : 1.0;
+    const double x = a[0], y = a[1], z = a[2], w = a[3];
+    const double R[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)},
+                            {2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)},
+                            {2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)}};
+    const double dv[3] = {Pj[4] - Pi[4], Pj[5] - Pi[5], Pj[6] - Pi[6]};
+    double tz[3];
+    ll_rotate(qzc, e.Z_w7 + 4, tz);                               /* R(q_z)^T t_z */
+    for (int k = 0; k < 3; ++k) {
+        r[k] = e.sqrt_info[k] * (2.0 * sgn * qe[k]);
+        r[3 + k] = e.sqrt_info[3 + k] * (((R[k][0] * dv[0] + R[k][1] * dv[1]) + R[k][2] * dv[2]) - tz[k]);
+    }
+    if (!A) return;
+    for (int k = 0; k < 3; ++k) {
+        double ek[4] = {0.0, 0.0, 0.0, 0.0}, ae[4], c[4];
+        ek[k] = 1.0;
+        pg_qmul(a, ek, ae);
+        pg_qmul(ae, Pj, c);
+        for (int m = 0; m < 3; ++m) { A[m][k] = 2.0 * sgn * c[m]; Ra[m][k] = R[m][k]; }
+        v[k] = dv[k];
+    }
+}
+
+__device__ __forceinline__ double pg_edge_cost(const double *Pi, const double *Pj, const ll_pg_edge &e)
+{
+    double r[6], c = 0.0;
+    pg_residual(Pi, Pj, e, r, nullptr, nullptr, nullptr);
+    const double sq = ((r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3])) + (r[4] * r[4] + r[5] * r[5]);
+    (void)ll_huber_scale(sq, e.huber, c);
+    return c;
+}
+
+/* the edge's slots: eH[0] = J_i^T J_j, eH[1] = J_i^T J_i, eH[2] = J_j^T J_j, eg[0] = J_i^T r, eg[1] = J_j^T r, and its cost */
+__device__ __forceinline__ void pg_edge_linearise(const double *Pi, const double *Pj, const ll_pg_edge &e, double *eH, double *eg, double *ecost)
+{
+    double r[6], A[3][3], Ra[3][3], v[3], Ji[6][6], Jj[6][6], c = 0.0;
+    pg_residual(Pi, Pj, e, r, A, Ra, v);
+    const double sq = ((r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3])) + (r[4] * r[4] + r[5] * r[5]);
+    const double w = ll_huber_scale(sq, e.huber, c);
+    *ecost = c;
+    const double vx[3][3] = {{0.0, -v[2], v[1]}, {v[2], 0.0, -v[0]}, {-v[1], v[0], 0.0}};
+    for (int m = 0; m < 3; ++m) {
+        const double sr = w * e.sqrt_info[m], st = w * e.sqrt_info[3 + m];
+        for (int k = 0; k < 3; ++k) {
+            Ji[m][k] = -sr * A[m][k];        Ji[m][3 + k] = 0.0;
+            Jj[m][k] = sr * A[m][k];         Jj[m][3 + k] = 0.0;
+            Ji[3 + m][k] = st * (2.0 * ((Ra[m][0] * vx[0][k] + Ra[m][1] * vx[1][k]) + Ra[m][2] * vx[2][k]));
+            Ji[3 + m][3 + k] = -st * Ra[m][k];
+            Jj[3 + m][k] = 0.0;              Jj[3 + m][3 + k] = st * Ra[m][k];
+        }
+    }
+    for (int m = 0; m < 6; ++m) r[m] *= w;
+    for (int a = 0; a < 6; ++a) {
+        double gi = 0.0, gj = 0.0;
+        for (int m = 0; m < 6; ++m) { gi += Ji[m][a] * r[m]; gj += Jj[m][a] * r[m]; }
+        eg[a] = gi; eg[6 + a] = gj;
+        for (int b = 0; b < 6; ++b) {
+            double hij = 0.0, hii = 0.0, hjj = 0.0;
+            for (int m = 0; m < 6; ++m) { hij += Ji[m][a] * Jj[m][b]; hii += Ji[m][a] * Ji[m][b]; hjj += Jj[m][a] * Jj[m][b]; }
+            eH[a * 6 + b] = hij; eH[36 + a * 6 + b] = hii; eH[72 + a * 6 + b] = hjj;
+        }
+    }
+}
+
+/* ------------------------------------------------------------------ device: the workgroup's sums
+ * A fixed tree over the 256 partials: an xor butterfly inside each wave (a + b == b + a bit for bit, so all 64 lanes end with the same
+ * value), then the four waves' sums as (w0 + w1) + (w2 + w3) by every thread.  sh: 8 doubles. */
+__device__ __forceinline__ void pg_sum2(double &a, double &b, double *sh)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sh[wave] = a; sh[4 + wave] = b; }
+    __syncthreads();
+    a = (sh[0] + sh[1]) + (sh[2] + sh[3]); b = (sh[4] + sh[5]) + (sh[6] + sh[7]);
+    __syncthreads();
+}
+
+__device__ __forceinline__ double pg_max2(double u, double w) { return (u != u || w != w) ? __builtin_nan("") : (u > w ? u : w); }   /* fmax would drop a NaN */
+
+__device__ __forceinline__ double pg_max(double a, double *sh)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) a = pg_max2(a, __shfl_xor(a, o));
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+    __syncthreads();
+    const double m = pg_max2(pg_max2(sh[0], sh[1]), pg_max2(sh[2], sh[3]));
+    __syncthreads();
+    return m;
+}
+
+/* ------------------------------------------------------------------ device: one graph */
+struct PgGraph {                               /* the graph's rows of the workspace */
+    int N, E, n0, e0;
+    const ll_pg_edge *edges; const int *inc_off, *inc, *inc_nb; const unsigned char *fixed;
+    double *x, *cand, *Hd, *g, *D, *d, *r, *z, *p, *Ap, *eH, *eg, *ecost;
+};
+
+/* edges at the poses `P`, then the nodes' sums; -> the cost (every thread) */
+__device__ double pg_linearise(const PgGraph &G, const double *P, const ll_pg_options &o, double *sh)
+{
+    const int tid = threadIdx.x;
+    double c = 0.0, unused = 0.0;
+    for (int e = tid; e < G.E; e += PG_THREADS) {
+        const ll_pg_edge &ed = G.edges[e];
+        pg_edge_linearise(P + (size_t)ed.i * 7, P + (size_t)ed.j * 7, ed, G.eH + (size_t)e * 108, G.eg + (size_t)e * 12, G.ecost + e);
+        c += G.ecost[e];
+    }
+    pg_sum2(c, unused, sh);                                        /* its barriers also publish the edges' slots */
+    for (int n = tid; n < G.N; n += PG_THREADS) {
+        double H[36], g[6];
+        for (int k = 0; k < 36; ++k) H[k] = 0.0;
+        for (int k = 0; k < 6; ++k) g[k] = 0.0;
+        for (int q = G.inc_off[G.n0 + n]; q < G.inc_off[G.n0 + n + 1]; ++q) {      /* ascending edges */
+            const int code = G.inc[q], e = code >> 1, side = code & 1;
+            const double *eH = G.eH + (size_t)e * 108 + 36 + 36 * side, *eg = G.eg + (size_t)e * 12 + 6 * side;
+            for (int k = 0; k < 36; ++k) H[k] += eH[k];
+            for (int k = 0; k < 6; ++k) g[k] += eg[k];
+        }
+        const bool fx = G.fixed[n] != 0;
+        for (int k = 0; k < 36; ++k) G.Hd[(size_t)n * 36 + k] = H[k];
+        for (int k = 0; k < 6; ++k) {
+            G.g[(size_t)n * 6 + k] = fx ? 0.0 : g[k];
+            G.D[(size_t)n * 6 + k] = fmin(fmax(H[k * 6 + k], o.min_lm_diagonal), o.max_lm_diagonal);
+        }
+    }
+    __syncthreads();
+    return c;
+}
+
+/* out = (H + damp D) in, rows of fixed nodes 0 (their `in` is 0 as well); a thread per node */
+__device__ void pg_matvec(const PgGraph &G, const double *in, double *out, double damp)
+{
+    for (int n = threadIdx.x; n < G.N; n += PG_THREADS) {
+        double y[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (!G.fixed[n]) {
+            const double *H = G.Hd + (size_t)n * 36, *u = in + (size_t)n * 6;
+            for (int a = 0; a < 6; ++a) {
+                double s = damp * G.D[(size_t)n * 6 + a] * u[a];
+                for (int b = 0; b < 6; ++b) s += H[a * 6 + b] * u[b];
+                y[a] = s;
+            }
+            for (int q = G.inc_off[G.n0 + n]; q < G.inc_off[G.n0 + n + 1]; ++q) {
+                const int code = G.inc[q], e = code >> 1, side = code & 1;
+                const double *Hij = G.eH + (size_t)e * 108, *w = in + (size_t)G.inc_nb[q] * 6;
+                if (side == 0) { for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) y[a] += Hij[a * 6 + b] * w[b]; }
+                else           { for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) y[a] += Hij[b * 6 + a] * w[b]; }
+            }
+        }
+        for (int a = 0; a < 6; ++a) out[(size_t)n * 6 + a] = y[a];
+    }
+}
+
+/* z = M^-1 r of node n, M = Hd + D / radius; false where M is not positive definite (z = 0 then) */
+__device__ __forceinline__ bool pg_precondition(const PgGraph &G, int n, double inv_radius, const double r[6], double z[6])
+{
+    double M[36], nr[6];
+    for (int k = 0; k < 36; ++k) M[k] = G.Hd[(size_t)n * 36 + k];
+    for (int k = 0; k < 6; ++k) { M[k * 6 + k] += G.D[(size_t)n * 6 + k] * inv_radius; nr[k] = -r[k]; }
+    if (ll_chol_solve(M, nr, z) != 0) { for (int k = 0; k < 6; ++k) z[k] = 0.0; return false; }
+    return true;
+}
+
+__device__ __forceinline__ bool pg_finite(double v) { return v - v == 0.0; }
+
+__global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgArgs A)
+{
+    __shared__ double sh[8];
+    const int tid = threadIdx.x, gi = blockIdx.x;
+    const ll_pg_options &o = A.o;
+    PgGraph G;
+    G.n0 = A.node_off[gi]; G.N = A.node_off[gi + 1] - G.n0;
+    G.e0 = A.edge_off[gi]; G.E = A.edge_off[gi + 1] - G.e0;
+    G.edges = A.edges + G.e0; G.inc_off = A.inc_off; G.inc = A.inc; G.inc_nb = A.inc_nb; G.fixed = A.fixed + G.n0;
+    G.x = A.x + (size_t)G.n0 * 7; G.cand = A.cand + (size_t)G.n0 * 7; G.Hd = A.Hd + (size_t)G.n0 * 36;
+    G.g = A.g + (size_t)G.n0 * 6; G.D = A.D + (size_t)G.n0 * 6; G.d = A.d + (size_t)G.n0 * 6; G.r = A.r + (size_t)G.n0 * 6;
+    G.z = A.z + (size_t)G.n0 * 6; G.p = A.p + (size_t)G.n0 * 6; G.Ap = A.Ap + (size_t)G.n0 * 6;
+    G.eH = A.eH + (size_t)G.e0 * 108; G.eg = A.eg + (size_t)G.e0 * 12; G.ecost = A.ecost + G.e0;
+
+    for (int n = tid; n < G.N; n += PG_THREADS) {                  /* quaternions are normalised on entry */
+        const double *in = A.pose_in + (size_t)(G.n0 + n) * 7;
+        const double qn = sqrt((in[0] * in[0] + in[1] * in[1]) + (in[2] * in[2] + in[3] * in[3]));
+        for (int k = 0; k < 4; ++k) G.x[(size_t)n * 7 + k] = in[k] / qn;
+        for (int k = 4; k < 7; ++k) G.x[(size_t)n * 7 + k] = in[k];
+    }
+    __syncthreads();
+    double cost = pg_linearise(G, G.x, o, sh);
+
+    if (!A.solve) {
+        for (int k = tid; k < G.N * 6; k += PG_THREADS) A.out_nodes[(size_t)G.n0 * 6 + k] = G.g[k];
+        if (tid == 0) A.out_cost[gi] = cost;
+        return;
+    }
+
+    const double cost0 = cost;
+    double radius = o.initial_radius, decrease = 2.0, grad_max = 0.0;
+    int iterations = 0, successes = 0, n_pcg = 0, term = 3;
+    bool lin_ok = true;                                            /* the linearisation at x is finite */
+    for (int iter = 0; iter <= o.max_lm_iterations; ++iter) {     /* every pass below counts one iteration */
+        /* ---- can the minimiser continue?  (non-finite, iteration limit, gradient, radius) */
+        double gm = 0.0, hs = 0.0;
+        for (int n = tid; n < G.N; n += PG_THREADS) {
+            if (G.fixed[n]) continue;
+            double x2[7], ng[6];
+            for (int k = 0; k < 7; ++k) x2[k] = G.x[(size_t)n * 7 + k];
+            for (int k = 0; k < 6; ++k) { ng[k] = -G.g[(size_t)n * 6 + k]; hs += G.Hd[(size_t)n * 36 + k * 7]; }     /* a column's squares: inf or NaN if any entry is */
+            ll_pose_plus(x2, ng);
+            for (int k = 0; k < 7; ++k) { const double dk = fabs(x2[k] - G.x[(size_t)n * 7 + k]); gm = (dk != dk || dk > gm) ? dk : gm; if (gm != gm) break; }
+        }
+        grad_max = pg_max(gm, sh);
+        { double unused = 0.0; pg_sum2(hs, unused, sh); }
+        lin_ok = pg_finite(cost) && pg_finite(grad_max) && pg_finite(hs);
+        if (!lin_ok) { term = 5; break; }
+        if (iter >= o.max_lm_iterations) { term = 3; break; }
+        if (grad_max <= o.gradient_tolerance) { term = 0; break; }
+        if (radius < o.min_radius) { term = 4; break; }
+        ++iterations;
+
+        /* ---- (H + D / radius) d = -g by preconditioned conjugate gradients */
+        const double inv_radius = 1.0 / radius;
+        double rz = 0.0, gg = 0.0;
+        for (int n = tid; n < G.N; n += PG_THREADS) {
+            double r[6], z[6];
+            for (int k = 0; k < 6; ++k) { r[k] = -G.g[(size_t)n * 6 + k]; z[k] = 0.0; }
+            if (!G.fixed[n]) (void)pg_precondition(G, n, inv_radius, r, z);
+            for (int k = 0; k < 6; ++k) {
+                G.d[(size_t)n * 6 + k] = 0.0; G.r[(size_t)n * 6 + k] = r[k]; G.z[(size_t)n * 6 + k] = z[k]; G.p[(size_t)n * 6 + k] = z[k];
+                rz += r[k] * z[k]; gg += r[k] * r[k];
+            }
+        }
+        pg_sum2(rz, gg, sh);                                       /* its barriers publish p */
+        const double stop = o.eta * sqrt(gg);
+        for (int k = 0; k < o.max_pcg_iterations; ++k) {
+            pg_matvec(G, G.p, G.Ap, inv_radius);
+            double pAp = 0.0, unused = 0.0;
+            for (int n = tid; n < G.N; n += PG_THREADS)
+                for (int a = 0; a < 6; ++a) pAp += G.p[(size_t)n * 6 + a] * G.Ap[(size_t)n * 6 + a];
+            pg_sum2(pAp, unused, sh);
+            if (!(pAp > 0.0) || !pg_finite(pAp) || !pg_finite(rz)) break;
+            const double alpha = rz / pAp;
+            double rr = 0.0, rz2 = 0.0;
+            for (int n = tid; n < G.N; n += PG_THREADS) {
+                double r[6], z[6];
+                for (int a = 0; a < 6; ++a) {
+                    G.d[(size_t)n * 6 + a] += alpha * G.p[(size_t)n * 6 + a];
+                    r[a] = G.r[(size_t)n * 6 + a] - alpha * G.Ap[(size_t)n * 6 + a];
+                    G.r[(size_t)n * 6 + a] = r[a]; z[a] = 0.0;
+                }
+                if (!G.fixed[n]) (void)pg_precondition(G, n, inv_radius, r, z);
+                for (int a = 0; a < 6; ++a) { G.z[(size_t)n * 6 + a] = z[a]; rr += r[a] * r[a]; rz2 += r[a] * z[a]; }
+            }
+            pg_sum2(rr, rz2, sh);
+            ++n_pcg;
+            if (!(sqrt(rr) > stop)) break;                         /* converged (inexact Newton), or a NaN */
+            const double beta = rz2 / rz;
+            rz = rz2;
+            for (int n = tid; n < G.N; n += PG_THREADS)
+                for (int a = 0; a < 6; ++a) G.p[(size_t)n * 6 + a] = G.z[(size_t)n * 6 + a] + beta * G.p[(size_t)n * 6 + a];
+            __syncthreads();
+        }
+
+        /* ---- the model's cost change, -(g.d + d.H d / 2), H without the damping */
+        __syncthreads();
+        pg_matvec(G, G.d, G.Ap, 0.0);
+        double gd = 0.0, dHd = 0.0;
+        for (int n = tid; n < G.N; n += PG_THREADS)
+            for (int a = 0; a < 6; ++a) { const double da = G.d[(size_t)n * 6 + a]; gd += G.g[(size_t)n * 6 + a] * da; dHd += da * G.Ap[(size_t)n * 6 + a]; }
+        pg_sum2(gd, dHd, sh);
+        const double mcc = -(gd + 0.5 * dHd);
+        if (!(mcc > 0.0) || !pg_finite(mcc)) { radius *= 0.5; continue; }          /* invalid step */
+
+        /* ---- the candidate, the parameter test, its cost */
+        double step2 = 0.0, x2n = 0.0;
+        for (int n = tid; n < G.N; n += PG_THREADS) {
+            double c7[7];
+            for (int k = 0; k < 7; ++k) c7[k] = G.x[(size_t)n * 7 + k];
+            if (!G.fixed[n]) ll_pose_plus(c7, G.d + (size_t)n * 6);
+            for (int k = 0; k < 7; ++k) {
+                const double xk = G.x[(size_t)n * 7 + k], ek = c7[k] - xk;
+                G.cand[(size_t)n * 7 + k] = c7[k]; step2 += ek * ek; x2n += xk * xk;
+            }
+        }
+        pg_sum2(step2, x2n, sh);                                   /* its barriers publish cand */
+        if (!pg_finite(step2)) { term = 5; break; }
+        if (sqrt(step2) <= o.parameter_tolerance * (sqrt(x2n) + o.parameter_tolerance)) { term = 2; break; }
+        double cc = 0.0, unused = 0.0;
+        for (int e = tid; e < G.E; e += PG_THREADS) {
+            const ll_pg_edge &ed = G.edges[e];
+            cc += pg_edge_cost(G.cand + (size_t)ed.i * 7, G.cand + (size_t)ed.j * 7, ed);
+        }
+        pg_sum2(cc, unused, sh);
+        if (!pg_finite(cc)) { term = 5; break; }
+        if (fabs(cost - cc) <= o.function_tolerance * cost) { term = 1; break; }
+
+        /* ---- accept or reject */
+        const double rho = (cost - cc) / mcc;
+        if (rho > o.min_relative_decrease) {
+            for (int k = tid; k < G.N * 7; k += PG_THREADS) G.x[k] = G.cand[k];
+            __syncthreads();
+            (void)pg_linearise(G, G.x, o, sh);
+            cost = cc;
+            const double f = 1.0 - pow(2.0 * rho - 1.0, 3.0);
+            radius = fmin(radius / fmax(1.0 / 3.0, f), o.max_radius);
+            decrease = 2.0; ++successes;
+        } else {
+            radius = radius / decrease;
+            decrease *= 2.0;
+        }
+    }
+
+    __syncthreads();
+    for (int k = tid; k < G.N * 7; k += PG_THREADS) A.out_nodes[(size_t)G.n0 * 7 + k] = G.x[k];
+    if (tid == 0) {
+        ll_pg_record R;
+        R.cost0 = cost0; R.cost = cost; R.grad_max = grad_max;
+        R.lm_iterations = iterations; R.lm_successes = successes; R.pcg_iterations = n_pcg; R.termination = term;
+        A.rec[gi] = R;
+    }
+}
+
+/* ------------------------------------------------------------------ host side */
+static int pg_fail(ll_posegraphs *pg, int code, const std::string &what) { pg->err = "posegraphs: " + what; return code; }
+
+#define PG_HIP(call)                                                                         \
+    do {                                                                                     \
+        hipError_t e_ = (call);                                                              \
+        if (e_ != hipSuccess) return pg_fail(pg, LL_ERR_HIP, std::string(#call ": ") + hipGetErrorString(e_)); \
+    } while (0)
+
+static size_t pg_up8(size_t b) { return (b + 7) & ~(size_t)7; }
+
+/* the byte offsets of the sections of the upload for (graphs, nodes, edges); [8] = the total */
+static void pg_in_layout(size_t G, size_t N, size_t E, size_t off[9])
+{
+    const size_t sz[8] = {N * 7 * sizeof(double), E * sizeof(ll_pg_edge), (G + 1) * sizeof(int), (G + 1) * sizeof(int),
+                          (N + 1) * sizeof(int), 2 * E * sizeof(int), 2 * E * sizeof(int), N};
+    off[0] = 0;
+    for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + pg_up8(sz[k]);
+}
+
+extern "C" void ll_pg_default_options(ll_pg_options *o)
+{
+    if (!o) return;
+    o->max_lm_iterations = 50; o->max_pcg_iterations = 1000; o->eta = 0.1;
+    o->initial_radius = 1e4; o->max_radius = 1e16; o->min_radius = 1e-32;
+    o->min_relative_decrease = 1e-3; o->min_lm_diagonal = 1e-6; o->max_lm_diagonal = 1e32;
+    o->function_tolerance = 1e-6; o->gradient_tolerance = 1e-10; o->parameter_tolerance = 1e-8;
+}
+
+extern "C" void ll_posegraphs_destroy(ll_posegraphs *pg)
+{
+    if (!pg) return;
+    (void)hipSetDevice(pg->ctx->device);
+    for (void *p : {(void *)pg->d_in, (void *)pg->d_out, (void *)pg->d_ws}) if (p) (void)hipFree(p);
+    for (hipEvent_t e : pg->ev) if (e) (void)hipEventDestroy(e);
+    delete pg;
+}
+
+extern "C" int ll_posegraphs_create(ll_ctx *ctx, int max_graphs, int max_nodes_total, int max_edges_total, ll_posegraphs **out)
+{
+    if (!ctx || !out) return LL_ERR_ARG;
+    *out = nullptr;
+    if (max_graphs < 1 || max_nodes_total < 1 || max_edges_total < 0 || max_graphs > (1 << 20) || max_nodes_total > (1 << 26) || max_edges_total > (1 << 26)) {
+        ctx->err = "posegraphs: max_graphs outside 1 .. 2^20, max_nodes_total outside 1 .. 2^26 or max_edges_total outside 0 .. 2^26";
+        return LL_ERR_ARG;
+    }
+    LL_HIP(hipSetDevice(ctx->device));
+    ll_posegraphs *pg = new ll_posegraphs();
+    pg->ctx = ctx; pg->max_graphs = max_graphs; pg->max_nodes = max_nodes_total; pg->max_edges = max_edges_total;
+    const size_t G = (size_t)max_graphs, N = (size_t)max_nodes_total, E = (size_t)max_edges_total;
+    size_t off[9];
+    pg_in_layout(G, N, E, off);
+    pg->in_bytes = off[8];
+    pg->out_bytes = N * 7 * sizeof(double) + G * sizeof(ll_pg_record);
+    const size_t ws_bytes = (N * PG_NODE_DOUBLES + E * PG_EDGE_DOUBLES + 1) * sizeof(double);
+    bool ok = hipMalloc((void **)&pg->d_in, pg->in_bytes) == hipSuccess && hipMalloc((void **)&pg->d_out, pg->out_bytes) == hipSuccess &&
+              hipMalloc((void **)&pg->d_ws, ws_bytes) == hipSuccess;
+    for (hipEvent_t &e : pg->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        ll_posegraphs_destroy(pg);
+        ctx->err = "posegraphs: allocation failed (" + std::to_string(off[8] + ws_bytes) + " bytes)";
+        return LL_ERR_HIP;
+    }
+    *out = pg;
+    return LL_OK;
+}
+
+extern "C" const char *ll_posegraphs_last_error(const ll_posegraphs *pg) { return pg ? pg->err.c_str() : "posegraphs: NULL handle"; }
+
+static bool pg_finite7(const double *p, int n) { for (int k = 0; k < n; ++k) if (!std::isfinite(p[k])) return false; return true; }
+static bool pg_zero_quat(const double *q) { return q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0; }
+
+static int pg_check_options(ll_posegraphs *pg, const ll_pg_options &o)
+{
+    const double v[10] = {o.eta, o.initial_radius, o.max_radius, o.min_radius, o.min_relative_decrease, o.min_lm_diagonal, o.max_lm_diagonal,
+                          o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance};
+    bool ok = o.max_lm_iterations >= 0 && o.max_pcg_iterations >= 1 && pg_finite7(v, 10);
+    ok = ok && o.eta > 0.0 && o.eta < 1.0 && o.initial_radius > 0.0 && o.max_radius >= o.initial_radius && o.min_radius >= 0.0 &&
+         o.min_relative_decrease >= 0.0 && o.min_relative_decrease < 1.0 && o.min_lm_diagonal > 0.0 && o.max_lm_diagonal >= o.min_lm_diagonal &&
+         o.function_tolerance >= 0.0 && o.gradient_tolerance >= 0.0 && o.parameter_tolerance >= 0.0;
+    return ok ? LL_OK : pg_fail(pg, LL_ERR_ARG, "options out of range (iterations >= 0 / >= 1, 0 < eta < 1, 0 < initial_radius <= max_radius, "
+                                                "0 < min_lm_diagonal <= max_lm_diagonal, tolerances >= 0, all finite)");
+}
+
+/* validate the call, pack it into page-locked scratch, enqueue the upload and the launch, download, synchronise ONCE */
+static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                  const unsigned char *fixed, const ll_pg_edge *edges, const ll_pg_options *opt, double *out_a, void *out_b)
+{
+    if (!pg) return LL_ERR_ARG;
+    const char *who = solve ? "solve: " : "evaluate: ";
+    auto bad = [&](int code, const std::string &what) { return pg_fail(pg, code, who + what); };
+    if (n_graphs < 0 || !node_off || !edge_off) return bad(LL_ERR_ARG, "n_graphs < 0, or node_off / edge_off is NULL");
+    if (n_graphs > pg->max_graphs) return bad(LL_ERR_CAPACITY, std::to_string(n_graphs) + " graphs exceed max_graphs " + std::to_string(pg->max_graphs));
+    if (node_off[0] != 0 || edge_off[0] != 0) return bad(LL_ERR_ARG, "offsets must start at 0");
+    for (int g = 0; g < n_graphs; ++g)
+        if (node_off[g + 1] < node_off[g] || edge_off[g + 1] < edge_off[g]) return bad(LL_ERR_ARG, "graph " + std::to_string(g) + ": offsets do not ascend");
+    const int N = node_off[n_graphs], E = edge_off[n_graphs];
+    if (N > pg->max_nodes) return bad(LL_ERR_CAPACITY, std::to_string(N) + " nodes exceed max_nodes_total " + std::to_string(pg->max_nodes));
+    if (E > pg->max_edges) return bad(LL_ERR_CAPACITY, std::to_string(E) + " edges exceed max_edges_total " + std::to_string(pg->max_edges));
+    if ((N > 0 && !poses_w7) || (E > 0 && !edges)) return bad(LL_ERR_ARG, "poses or edges is NULL");
+    if (solve ? false : (n_graphs > 0 && (!out_a || (N > 0 && !out_b)))) return bad(LL_ERR_ARG, "cost or grad6 is NULL");
+    ll_pg_options o;
+    ll_pg_default_options(&o);
+    if (opt) o = *opt;
+    if (solve) { const int rc = pg_check_options(pg, o); if (rc) return rc; }
+    for (int g = 0; g < n_graphs; ++g) {
+        const int n0 = node_off[g], n = node_off[g + 1] - n0;
+        const std::string gs = "graph " + std::to_string(g);
+        bool any_fixed = !fixed && n > 0;
+        for (int k = 0; k < n; ++k) {
+            const double *p = poses_w7 + (size_t)(n0 + k) * 7;
+            if (!pg_finite7(p, 7)) return bad(LL_ERR_ARG, gs + ", node " + std::to_string(k) + ": the pose is not finite");
+            if (pg_zero_quat(p)) return bad(LL_ERR_ARG, gs + ", node " + std::to_string(k) + ": zero quaternion");
+            if (fixed && fixed[n0 + k]) any_fixed = true;
+        }
+        if (!any_fixed) return bad(LL_ERR_ARG, gs + " has no fixed node");
+        for (int e = edge_off[g]; e < edge_off[g + 1]; ++e) {
+            const ll_pg_edge &ed = edges[e];
+            const std::string es = gs + ", edge " + std::to_string(e - edge_off[g]);
+            if (ed.i < 0 || ed.i >= n || ed.j < 0 || ed.j >= n) return bad(LL_ERR_ARG, es + ": a node index lies outside the graph");
+            if (ed.i == ed.j) return bad(LL_ERR_ARG, es + ": i == j");
+            if (!pg_finite7(ed.Z_w7, 7) || !pg_finite7(ed.sqrt_info, 6) || !std::isfinite(ed.huber)) return bad(LL_ERR_ARG, es + ": the measurement or a weight is not finite");
+            if (pg_zero_quat(ed.Z_w7)) return bad(LL_ERR_ARG, es + ": zero quaternion");
+        }
+    }
+    pg->counts[0] = n_graphs; pg->counts[1] = pg->counts[2] = 0;
+    pg->ms[solve ? 1 : 0] = 0.0;
+    if (n_graphs == 0) return LL_OK;
+
+    /* ---- pack: poses, edges, offsets, the node -> incident-edge lists (edge order), fixed */
+    size_t off[9];
+    pg_in_layout((size_t)n_graphs, (size_t)N, (size_t)E, off);
+    const size_t per_node = solve ? 7 : 6;
+    const size_t out_b_bytes = solve ? (size_t)n_graphs * sizeof(ll_pg_record) : (size_t)n_graphs * sizeof(double);
+    const size_t down = (size_t)N * per_node * sizeof(double) + out_b_bytes;
+    unsigned char *pin = (unsigned char *)ll_pinned_scratch(off[8] + pg_up8(down));
+    if (!pin) return bad(LL_ERR_HIP, "no page-locked scratch");
+    if (N > 0) std::memcpy(pin + off[0], poses_w7, (size_t)N * 7 * sizeof(double));
+    if (E > 0) std::memcpy(pin + off[1], edges, (size_t)E * sizeof(ll_pg_edge));
+    std::memcpy(pin + off[2], node_off, (size_t)(n_graphs + 1) * sizeof(int));
+    std::memcpy(pin + off[3], edge_off, (size_t)(n_graphs + 1) * sizeof(int));
+    int *inc_off = (int *)(pin + off[4]), *inc = (int *)(pin + off[5]), *inc_nb = (int *)(pin + off[6]);
+    unsigned char *fx = pin + off[7];
+    for (int k = 0; k <= N; ++k) inc_off[k] = 0;
+    for (int g = 0; g < n_graphs; ++g)
+        for (int e = edge_off[g]; e < edge_off[g + 1]; ++e) { ++inc_off[node_off[g] + edges[e].i + 1]; ++inc_off[node_off[g] + edges[e].j + 1]; }
+    for (int k = 0; k < N; ++k) inc_off[k + 1] += inc_off[k];
+    {
+        std::vector<int> fill(inc_off, inc_off + N);
+        for (int g = 0; g < n_graphs; ++g)
+            for (int e = edge_off[g]; e < edge_off[g + 1]; ++e) {                  /* ascending e: every node's list is in edge order */
+                const int le = e - edge_off[g], i = edges[e].i, j = edges[e].j;
+                int q = fill[node_off[g] + i]++; inc[q] = le * 2; inc_nb[q] = j;
+                q = fill[node_off[g] + j]++;     inc[q] = le * 2 + 1; inc_nb[q] = i;
+            }
+    }
+    for (int g = 0; g < n_graphs; ++g)
+        for (int k = node_off[g]; k < node_off[g + 1]; ++k) fx[k] = fixed ? (fixed[k] ? 1 : 0) : (k == node_off[g] ? 1 : 0);
+
+    /* ---- enqueue */
+    PG_HIP(hipSetDevice(pg->ctx->device));
+    hipStream_t st = pg->ctx->stream;
+    PG_HIP(hipMemcpyAsync(pg->d_in, pin, off[8], hipMemcpyHostToDevice, st));
+    PgArgs A;
+    A.pose_in = (const double *)(pg->d_in + off[0]); A.edges = (const ll_pg_edge *)(pg->d_in + off[1]);
+    A.node_off = (const int *)(pg->d_in + off[2]); A.edge_off = (const int *)(pg->d_in + off[3]);
+    A.inc_off = (const int *)(pg->d_in + off[4]); A.inc = (const int *)(pg->d_in + off[5]); A.inc_nb = (const int *)(pg->d_in + off[6]);
+    A.fixed = pg->d_in + off[7];
+    double *w = pg->d_ws;
+    const size_t Nn = (size_t)N, En = (size_t)E;
+    A.x = w; w += Nn * 7; A.cand = w; w += Nn * 7; A.Hd = w; w += Nn * 36; A.g = w; w += Nn * 6; A.D = w; w += Nn * 6; A.d = w; w += Nn * 6;
+    A.r = w; w += Nn * 6; A.z = w; w += Nn * 6; A.p = w; w += Nn * 6; A.Ap = w; w += Nn * 6;
+    A.eH = w; w += En * 108; A.eg = w; w += En * 12; A.ecost = w;
+    A.out_nodes = (double *)pg->d_out;
+    A.rec = (ll_pg_record *)(pg->d_out + Nn * per_node * sizeof(double)); A.out_cost = (double *)A.rec;
+    A.o = o; A.solve = solve ? 1 : 0;
+    PG_HIP(hipEventRecord(pg->ev[0], st));
+    hipLaunchKernelGGL(k_pg_solve, dim3((unsigned)n_graphs), dim3(PG_THREADS), 0, st, A);
+    PG_HIP(hipEventRecord(pg->ev[1], st));
+    PG_HIP(hipGetLastError());
+    unsigned char *pout = pin + off[8];
+    PG_HIP(hipMemcpyAsync(pout, pg->d_out, down, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));                              /* the ONE synchronisation */
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, pg->ev[0], pg->ev[1]) == hipSuccess) pg->ms[solve ? 1 : 0] = (double)ms;
+
+    /* ---- hand back */
+    const double *nodes = (const double *)pout;
+    const unsigned char *tail = pout + Nn * per_node * sizeof(double);
+    if (!solve) {
+        std::memcpy(out_b, nodes, Nn * 6 * sizeof(double));
+        std::memcpy(out_a, tail, (size_t)n_graphs * sizeof(double));
+        return LL_OK;
+    }
+    const ll_pg_record *recs = (const ll_pg_record *)tail;
+    double *poses_out = out_a;
+    for (int g = 0; g < n_graphs; ++g) {
+        pg->counts[1] += recs[g].lm_iterations; pg->counts[2] += recs[g].pcg_iterations;
+        if (recs[g].lm_successes == 0) continue;                  /* nothing accepted: the input comes back bit for bit */
+        for (int k = node_off[g]; k < node_off[g + 1]; ++k)       /* so do fixed nodes and nodes without an edge */
+            if (!fx[k] && inc_off[k + 1] > inc_off[k]) std::memcpy(poses_out + (size_t)k * 7, nodes + (size_t)k * 7, 7 * sizeof(double));
+    }
+    if (out_b) std::memcpy(out_b, recs, (size_t)n_graphs * sizeof(ll_pg_record));
+    return LL_OK;
+}
+
+extern "C" int ll_posegraphs_evaluate(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                                      const unsigned char *fixed, const ll_pg_edge *edges, double *cost, double *grad6)
+{
+    return pg_run(pg, false, n_graphs, node_off, edge_off, poses_w7, fixed, edges, nullptr, cost, grad6);
+}
+
+extern "C" int ll_posegraphs_solve(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, double *poses_w7,
+                                   const unsigned char *fixed, const ll_pg_edge *edges, const ll_pg_options *opt, ll_pg_record *rec)
+{
+    return pg_run(pg, true, n_graphs, node_off, edge_off, poses_w7, fixed, edges, opt, poses_w7, rec);
+}
+
+/* ms2: device time of the last evaluate and of the last solve; counts3: graphs of the last call, LM and PCG iterations of the last solve */
+extern "C" int ll_posegraphs_timing(ll_posegraphs *pg, double *ms2, long long *counts3)
+{
+    if (!pg) return LL_ERR_ARG;
+    if (ms2) for (int k = 0; k < 2; ++k) ms2[k] = pg->ms[k];
+    if (counts3) for (int k = 0; k < 3; ++k) counts3[k] = pg->counts[k];
+    return LL_OK;
+}
