@@ -763,6 +763,101 @@ int  ll_cubemaps_align(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops, int 
                        double *T_w7 /* [n_ops][7] out */, int *ran /* [n_ops], may be NULL */, ll_localize_fit *fit /* [n_ops], may be NULL */);
 int  ll_cubemaps_align_timing(const ll_cubemaps *cms, double *ms /* build, search+fit, evaluate+solve, fit */, long long *counts /* stack points, map points, residual blocks */);
 
+/* ---------------------------------------------------------------- keyframes: the clouds every mapped frame contributed, kept on the device
+ * A keyframe is what laserMapping adds to the map in its update (laserMapping.cpp:2103-2125): the frame's down-sized
+ * laserCloudCornerStack and laserCloudSurfStack in the sensor frame -- what ll_cubemaps_download_cloud(q, 2 / 3) shows -- and the
+ * pose_w7 the frame was mapped under.  ll_keyframes keeps them in two point pools in HBM (16 bytes per point, a frame's clouds back
+ * to back in the order they were added) beside a host table; frame ids are 0 .. size - 1.  With them a map can be rebuilt under
+ * corrected poses (ll_cubemaps_insert_keyframes below).  The store belongs to the context it was created on and works with the
+ * ll_cubemaps / ll_drives of that context only (LL_ERR_ARG otherwise).
+ *   ll_keyframes_create        max_frames in 1 .. 2^24, cap_corner / cap_surf (points) in 1 .. 2^30; LL_ERR_ARG (ll_last_error(ctx)) otherwise
+ *   ll_keyframes_size          the number of frames (LL_ERR_ARG for NULL);  ll_keyframes_reset: size = 0, the pools empty
+ *   ll_keyframes_info          frame id's table entry: host only, no launch, no synchronisation
+ *   ll_keyframes_add_cubemaps  one keyframe per sequence with sel[q] = 1, ascending q, ids *first_id .. (first_id may be NULL; -1 when none
+ *                              is selected): the sequence's current stack clouds, device to device in ONE copy launch for all sequences
+ *                              and both types, no host synchronisation -- sizes and poses are host bookkeeping.  pose_w7 [S][7] (rows of
+ *                              selected sequences are read), lane_tag / frame_tag [S] (NULL: the sequence index / -1) go into the table.
+ *                              Between two frames of cms, or two steps of the ll_drives that owns it.
+ *   ll_keyframes_add_points    one keyframe from host clouds (persistence, crafted tests): lane = -1, frame_index = -1; one synchronisation
+ *   ll_keyframes_export        frames first .. first + count - 1 back to back, per frame the corner cloud and then the surf cloud:
+ *                              offsets_out [2 count + 1] (cloud 2 f + w of the range begins at offsets_out[2 f + w]; the last entry is the
+ *                              total) is host bookkeeping and always filled; points_out (host or device memory; NULL: sizes only, nothing
+ *                              is launched) receives the points in one gather, one copy and ONE synchronisation whatever count is.
+ *                              ll_keyframes_add_points of an exported frame stores the same bytes.
+ * Errors, all decided before anything is enqueued; a refused call leaves size, table and pools as they were: LL_ERR_ARG for a NULL
+ * pointer, a sel outside 0 / 1, a negative size, a range outside 0 .. size, a non-finite pose; LL_ERR_CAPACITY when max_frames or a
+ * pool would overflow (last_error names which: "frames", "corner" or "surf"); LL_ERR_STATE for a selected sequence that has run no
+ * frame since create / reset / import, or whose map is unusable.                                                                    */
+typedef struct ll_keyframes ll_keyframes;
+typedef struct { int max_frames; long long cap_corner, cap_surf; } ll_keyframes_params;
+typedef struct { int lane, frame_index; int n[2]; long long offset[2]; double pose_w7[7]; } ll_keyframe_info;   /* n, offset: corner, surf; offset in points into the type's pool */
+int  ll_keyframes_create(ll_ctx *ctx, const ll_keyframes_params *p, ll_keyframes **out);
+void ll_keyframes_destroy(ll_keyframes *kf);
+const char *ll_keyframes_last_error(const ll_keyframes *kf);
+int  ll_keyframes_size(const ll_keyframes *kf);
+int  ll_keyframes_reset(ll_keyframes *kf);
+int  ll_keyframes_info(const ll_keyframes *kf, int id, ll_keyframe_info *info);
+int  ll_keyframes_add_cubemaps(ll_keyframes *kf, ll_cubemaps *cms, const int *sel /* [S] */, const double *pose_w7 /* [S][7] */,
+                               const int *lane_tag /* [S], may be NULL */, const int *frame_tag /* [S], may be NULL */, int *first_id);
+int  ll_keyframes_add_points(ll_keyframes *kf, const ll_point *corner, int n_corner, const ll_point *surf, int n_surf, const double *pose_w7, int *id);
+int  ll_keyframes_export(ll_keyframes *kf, int first, int count, ll_point *points_out, long long *offsets_out /* [2 count + 1] */);
+
+/* ---------------------------------------------------------------- cube maps rebuilt and extended from keyframes
+ * ll_cubemaps_insert_keyframes: op i places the listed frames of a store into map dst, each frame under its own pose.  The semantics
+ * are ll_cubemaps_merge's with the source and the transform per frame.  Per cloud type (0 corner, 1 surf), independently:
+ *   order      the points of the listed frames in list order, each frame's cloud in its own order.  Ids may repeat (the frame then
+ *              contributes twice) and may come in any order;
+ *   transform  pointAssociateToMap (laserMapping.cpp:125-134) in f64 with THAT FRAME's pose -- poses_w7[k] for frames[k], or the pose the
+ *              store holds for the frame when poses_w7 is NULL -- used as given, never normalised; each coordinate rounded to float
+ *              once, the fourth float carried over;
+ *   binning    the cube arithmetic of :2108-2125 with dst's centre; a point outside the 21 x 21 x 11 array is dropped and counted;
+ *   touched    every cube that receives a point becomes its old cloud followed by the new points in that order, passed ONCE
+ *              through the library's VoxelGrid (:2151-2165) with the type's leaf.  A cube that receives nothing keeps its bytes.
+ *   reset = 1  dst is first emptied as ll_cubemaps_reset does and given the centre cen (the array index of the world's origin cube:
+ *              (10, 10, 5) puts the origin in the middle; a rebuild of a drive that has moved far passes the centre its map had,
+ *              ll_cubemaps_layout): the valid list is empty and the four per-frame clouds are of size 0.
+ *   reset = 0  the frames are added to what dst holds, cen is ignored: the map-extension case, and how a rebuild is split over calls.
+ * FILTER ONCE, NOT FRAME BY FRAME: this is the merge's filter-once semantics -- all listed frames enter a cube before its one VoxelGrid
+ * pass -- not the frame-by-frame VoxelGrid of incremental mapping, where every frame's update filters what the frames before left.  A
+ * rebuild under the drive's own poses is therefore a map of the same points, not the same bytes as the incrementally built map.
+ * added[i][w] / dropped[i][w] (either may be NULL): the points of op i, type w that entered a cube (before the filter) / fell outside.
+ * Everything stays on the device: a workgroup of k_kf_assign takes one 1024-point tile of one (frame, type) cloud where it lies in
+ * the store's pool; from the by-cube counting sort to the commit the call runs ll_cubemaps_merge's own stages.  Host synchronisations
+ * per successful call that moves at least one point, whatever n_ops and the number of frames are: THREE (the per-cube counts, the
+ * filtered sizes, the commit), plus the voxel filter's read-back as for a merge; all counted in ll_cubemaps_stats' syncs; frames does
+ * not rise.  An op with no points succeeds (its reset is still made); a call whose ops hold no point at all launches nothing.
+ * The handle from ll_drives_cubemaps(d) is accepted between any two ll_drives_step calls.
+ * A failed call changes nothing, the reset included.  LL_ERR_ARG, before anything is enqueued: a NULL handle, store or ops, a store of
+ * another context, n_ops < 1, n_frames < 0, frames NULL with n_frames > 0, a frame id outside the store, a non-finite pose (given or
+ * stored), a dst outside 0 .. S-1, a dst listed by two ops, reset outside 0 / 1, a cen beyond +-2^24 with reset.  LL_ERR_STATE, also
+ * before anything is enqueued: a dst that is unusable (an earlier update failed half-way).  LL_ERR_CAPACITY, decided for every op and
+ * both types from the per-cube counts before any table changes -- with reset against the empty map --: last_error names the op and
+ * the type.  LL_ERR_HIP: the workspace cannot be allocated (the object stays usable) or a runtime call failed.
+ * ll_cubemaps_insert_timing: as ll_cubemaps_merge_timing, for the last insert.                                                   */
+typedef struct { int dst; int n_frames; const int *frames; const double *poses_w7 /* [n_frames][7], NULL: the stored poses */;
+                 int reset; int cen[3]; } ll_insert_op;
+int  ll_cubemaps_insert_keyframes(ll_cubemaps *cms, const ll_keyframes *kf, const ll_insert_op *ops, int n_ops,
+                                  long long *added /* [n_ops][2], may be NULL */, long long *dropped /* [n_ops][2], may be NULL */);
+int  ll_cubemaps_insert_timing(const ll_cubemaps *cms, double *ms /* assign, sort+gather, filter, commit */, long long *counts /* points in, touched cubes, points out */);
+
+/* ---------------------------------------------------------------- drives: capture while driving, and take a correction
+ * ll_drives_set_keyframes(d, kf, every): from the next step on, at the end of a step every lane that ran a frame -- mapping or
+ * localising -- whose per-lane frame index (0 at START) is a multiple of every (>= 1) is captured into kf: its stack clouds and its
+ * mapped_w7, tagged with lane and frame index, ids ascending with the lane.  One copy launch more per step, no host synchronisation
+ * more.  kf = NULL: off, the default; off changes nothing by a bit.  Before anything of a step is enqueued the store must have room
+ * for max_scan_corner / max_scan_surf points and one frame per lane the step would capture; otherwise the step fails with
+ * LL_ERR_CAPACITY, has not run, and the lanes keep their state (the same commands can be given again).  The store is not part of a
+ * lane checkpoint (the blob format is unchanged), and the setting is not either.  LL_ERR_ARG: every < 1, a store of another context.
+ * ll_drives_correct(d, lanes, C_w7): left-multiplies the map-to-odom pose of every lane with lanes[q] = 1 by C_w7[q] on the device, in
+ * f64: q' = q_C x q_m2o, t' = R(q_C) t_m2o + t_C (the products spelled as transformAssociateToMap spells them).  With
+ * C = P'_last o P_last^-1 -- P_last the lane's last mapped pose, P'_last its corrected value -- the lane's next
+ * transformAssociateToMap lands in the corrected map.  Allowed between any two steps for a lane that ran on the previous step or was
+ * restored.  One tiny launch and one synchronisation (outside a step: not counted).  The identity (0, 0, 0, 1, 0, 0, 0) leaves every bit
+ * of the lane's state unchanged.  LL_ERR_ARG, before anything is enqueued: a selector outside 0 / 1, a non-finite row of a selected
+ * lane; LL_ERR_STATE: a selected lane with no drive.  C is not normalised.                                                        */
+int  ll_drives_set_keyframes(ll_drives *d, ll_keyframes *kf /* NULL: off */, int every);
+int  ll_drives_correct(ll_drives *d, const int *lanes /* [S] */, const double *C_w7 /* [S][7] */);
+
 /* ---------------------------------------------------------------- place recognition: Scan Context descriptors, exhaustive matching
  * ll_places answers what comes before align, merge and set_localize: which stored scan is this scan a revisit of, and under which
  * heading.  It is the descriptor of Kim & Kim, "Scan Context" (IROS 2018) -- not part of the reference -- with an exact search of

@@ -389,6 +389,55 @@ private:
 
 /* ll_cubemaps_layout of one map: the centre, the per-cube point counts [2][4851] (corner, then surf) and the valid list of its
  * last frame */
+/* Keyframes (ll_keyframes): the stack clouds (down-sized corner and surf features, sensor frame) and mapped poses of frames, kept on
+ * the device; ids are 0 .. size() - 1 in the order of the adds.  LaserMappingSequences::insert_keyframes rebuilds cube maps from them
+ * under corrected poses.  Destroy it before its Context, and after every Drives that captures into it. */
+class Keyframes {
+public:
+    struct Exported { std::vector<PointXYZI> points; std::vector<long long> offsets; };   /* cloud w of frame first + f: points[offsets[2 f + w] .. offsets[2 f + w + 1]) */
+    Keyframes(Context &c, int max_frames, long long cap_corner, long long cap_surf) {
+        ll_keyframes_params p;
+        p.max_frames = max_frames; p.cap_corner = cap_corner; p.cap_surf = cap_surf;
+        c.check(ll_keyframes_create(c.get(), &p, &kf_));
+    }
+    ~Keyframes() { ll_keyframes_destroy(kf_); }
+    Keyframes(const Keyframes &) = delete;
+    Keyframes &operator=(const Keyframes &) = delete;
+
+    int size() const { return ll_keyframes_size(kf_); }
+    void reset() { check(ll_keyframes_reset(kf_)); }
+    ll_keyframe_info info(int id) const {
+        ll_keyframe_info e;
+        check(ll_keyframes_info(kf_, id, &e));
+        return e;
+    }
+    /* one keyframe per sequence with sel[q] != 0 from the stack clouds of its last frame and pose_w7 [S][7]: one copy launch, no
+     * synchronisation; the first new id (-1: none selected).  cms: LaserMappingSequences::get() or Drives::cubemaps() */
+    int add_cubemaps(ll_cubemaps *cms, const std::vector<int> &sel, const double *pose_w7, const int *lane_tag = nullptr, const int *frame_tag = nullptr) {
+        int first = -1;
+        check(ll_keyframes_add_cubemaps(kf_, cms, sel.data(), pose_w7, lane_tag, frame_tag, &first));
+        return first;
+    }
+    int add_points(const std::vector<PointXYZI> &corner, const std::vector<PointXYZI> &surf, const double *pose_w7) {
+        int id = -1;
+        check(ll_keyframes_add_points(kf_, (const ll_point *)corner.data(), (int)corner.size(), (const ll_point *)surf.data(), (int)surf.size(), pose_w7, &id));
+        return id;
+    }
+    /* frames first .. first + count - 1 back to back, per frame the corner cloud, then the surf cloud: one gather, one copy, one synchronisation */
+    Exported export_frames(int first, int count) {
+        Exported x;
+        x.offsets.assign((size_t)2 * (count > 0 ? count : 0) + 1, 0);
+        check(ll_keyframes_export(kf_, first, count, nullptr, x.offsets.data()));
+        x.points.resize((size_t)x.offsets.back());
+        if (!x.points.empty()) check(ll_keyframes_export(kf_, first, count, (ll_point *)x.points.data(), x.offsets.data()));
+        return x;
+    }
+    ll_keyframes *get() const { return kf_; }
+private:
+    void check(int rc) const { if (rc != LL_OK) throw Error(rc, ll_keyframes_last_error(kf_)); }
+    ll_keyframes *kf_ = nullptr;
+};
+
 struct MapLayout {
     enum { N_COUNTS = 2 * 4851 };
     int cen[3] = {10, 10, 5};
@@ -506,6 +555,20 @@ public:
         if (added) added->assign(2 * ops.size(), 0);
         if (dropped) dropped->assign(2 * ops.size(), 0);
         return ll_cubemaps_merge(cms, ops.data(), (int)ops.size(), added ? added->data() : nullptr, dropped ? dropped->data() : nullptr);
+    }
+    /* ll_cubemaps_insert_keyframes: op i places the listed frames of the store into map ops[i].dst, each frame under its own pose
+     * (ops[i].poses_w7, or the stored poses when NULL), after emptying dst when ops[i].reset is set; every cube that received a point is
+     * filtered ONCE over its old cloud and all new points (the merge's semantics, not frame-by-frame mapping).  added / dropped
+     * [n_ops][2] (corner, surf) when given.  Everything on the device */
+    void insert_keyframes(const Keyframes &kf, const std::vector<ll_insert_op> &ops, std::vector<long long> *added = nullptr, std::vector<long long> *dropped = nullptr) {
+        const int rc = insert_into(cms_, kf, ops, added, dropped);
+        if (rc != LL_OK) check(rc);
+    }
+    /* the same on a borrowed handle (Drives::cubemaps(), between two steps); returns the status */
+    static int insert_into(ll_cubemaps *cms, const Keyframes &kf, const std::vector<ll_insert_op> &ops, std::vector<long long> *added = nullptr, std::vector<long long> *dropped = nullptr) {
+        if (added) added->assign(2 * ops.size(), 0);
+        if (dropped) dropped->assign(2 * ops.size(), 0);
+        return ll_cubemaps_insert_keyframes(cms, kf.get(), ops.data(), (int)ops.size(), added ? added->data() : nullptr, dropped ? dropped->data() : nullptr);
     }
     /* ll_cubemaps_align: op i estimates the transform that takes map ops[i].src's world frame into map ops[i].dst's, starting at
      * ops[i].T_w7 -- laserMapping's optimisation over the whole of both maps, read-only.  T [n_ops][7]; ran [n_ops] and fit [n_ops]
@@ -685,6 +748,16 @@ public:
     /* the mapping lanes vote their plane blocks in frames whose per-lane index is > from_frame (the reference's gate: 20); negative: off.
      * Not part of a checkpoint: set it again after restore */
     void set_map_vote(int from_frame) { check(ll_drives_set_map_vote(d_, from_frame)); }
+    /* from the next step on every lane that ran a frame whose per-lane index is a multiple of `every` is captured into kf (its stack
+     * clouds and mapped pose, tagged with lane and frame index); nullptr: off.  A step for which the store has no room is refused
+     * (LL_ERR_CAPACITY) before it runs.  Not part of a checkpoint */
+    void set_keyframes(Keyframes *kf, int every = 1) { check(ll_drives_set_keyframes(d_, kf ? kf->get() : nullptr, every)); }
+    /* the map-to-odom pose of every lane with lanes[q] != 0 left-multiplied by C_w7[q] ([S][7]): with C = P'_last o P_last^-1 the lane's
+     * drive continues in a map rebuilt under corrected poses.  Between any two steps */
+    void correct(const std::vector<int> &lanes, const double *C_w7) {
+        if ((int)lanes.size() != S) throw Error(LL_ERR_ARG, "one selection per lane");
+        check(ll_drives_correct(d_, lanes.data(), C_w7));
+    }
     /* the last step's fit records [S]: zeros for lanes that mapped, sat out or did not optimise */
     std::vector<ll_localize_fit> fit() {
         std::vector<ll_localize_fit> f((size_t)S);

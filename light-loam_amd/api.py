@@ -51,6 +51,9 @@ EXPORTS = [
     "ll_places_timing",
     "ll_pg_default_options", "ll_posegraphs_create", "ll_posegraphs_destroy", "ll_posegraphs_last_error", "ll_posegraphs_evaluate",
     "ll_posegraphs_solve", "ll_posegraphs_timing",
+    "ll_keyframes_create", "ll_keyframes_destroy", "ll_keyframes_last_error", "ll_keyframes_size", "ll_keyframes_reset", "ll_keyframes_info",
+    "ll_keyframes_add_cubemaps", "ll_keyframes_add_points", "ll_keyframes_export",
+    "ll_cubemaps_insert_keyframes", "ll_cubemaps_insert_timing", "ll_drives_set_keyframes", "ll_drives_correct",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -90,6 +93,20 @@ class LocalizeFit(C.Structure):
 class MergeOp(C.Structure):
     """ll_merge_op: map src goes into map dst under the pose T_w7 (qx, qy, qz, qw, tx, ty, tz)"""
     _fields_ = [("dst", C.c_int), ("src", C.c_int), ("T_w7", C.c_double * 7)]
+
+
+class KeyframesParams(C.Structure):
+    _fields_ = [("max_frames", C.c_int), ("cap_corner", C.c_longlong), ("cap_surf", C.c_longlong)]
+
+
+class KeyframeInfo(C.Structure):
+    """ll_keyframe_info: n, offset per cloud type (corner, surf); offset in points into the type's pool"""
+    _fields_ = [("lane", C.c_int), ("frame_index", C.c_int), ("n", C.c_int * 2), ("offset", C.c_longlong * 2), ("pose_w7", C.c_double * 7)]
+
+
+class InsertOp(C.Structure):
+    """ll_insert_op: the listed frames of a Keyframes store go into map dst, frame k under poses_w7[k] (NULL: its stored pose)"""
+    _fields_ = [("dst", C.c_int), ("n_frames", C.c_int), ("frames", C.c_void_p), ("poses_w7", C.c_void_p), ("reset", C.c_int), ("cen", C.c_int * 3)]
 
 
 class SeqLayout(C.Structure):
@@ -184,6 +201,21 @@ def load_library():
         _lib.ll_posegraphs_evaluate.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         _lib.ll_posegraphs_solve.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         _lib.ll_posegraphs_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_keyframes_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ll_keyframes_destroy.restype = None
+        _lib.ll_keyframes_destroy.argtypes = [C.c_void_p]
+        _lib.ll_keyframes_last_error.restype = C.c_char_p
+        _lib.ll_keyframes_last_error.argtypes = [C.c_void_p]
+        _lib.ll_keyframes_size.argtypes = [C.c_void_p]
+        _lib.ll_keyframes_reset.argtypes = [C.c_void_p]
+        _lib.ll_keyframes_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_keyframes_add_cubemaps.argtypes = [C.c_void_p] * 7
+        _lib.ll_keyframes_add_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ll_keyframes_export.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ll_cubemaps_insert_keyframes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ll_cubemaps_insert_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_drives_set_keyframes.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        _lib.ll_drives_correct.argtypes = [C.c_void_p] * 3
     return _lib
 
 
@@ -584,6 +616,10 @@ class Context:
     def places(self, capacity, max_radius=None, z_offset=None):
         """a Places database of `capacity` Scan Context descriptors on this context (ll_places_create)"""
         return Places(self, capacity, max_radius, z_offset)
+
+    def keyframes(self, max_frames, cap_corner, cap_surf):
+        """a Keyframes store on this context: up to max_frames frames, cap_corner / cap_surf points per cloud type (ll_keyframes_create)"""
+        return Keyframes(self, max_frames, cap_corner, cap_surf)
 
     def algorithmic_bytes(self, first=0, count=1):
         b = [C.c_double(0) for _ in range(4)]
@@ -1096,6 +1132,35 @@ class CubeMaps:
         self._ck(self.lib.ll_cubemaps_merge_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
         return tuple(ms), tuple(int(c) for c in cnt)
 
+    def insert_keyframes(self, kf, ops):
+        """ops: a list of (dst, frames, poses, reset, cen) -- the frames (ids of the Keyframes store kf, in this order; they may repeat)
+        go into map dst, frame k under poses[k] ([n, 7]; None: the poses the store holds); reset: dst is first emptied and given the
+        centre cen (ignored without reset; None: (10, 10, 5)).  Every cube that received a point is voxel-filtered ONCE over its old
+        cloud and all new points (the merge's semantics, not frame-by-frame mapping) -> (added [n_ops, 2], dropped [n_ops, 2]) int64.
+        Everything on the device; three synchronisations whatever len(ops) and the number of frames are"""
+        rec = (InsertOp * max(len(ops), 1))()
+        keep = []
+        for i, (dst, frames, poses, reset, cen) in enumerate(ops):
+            f = np.ascontiguousarray(frames, np.int32).reshape(-1)
+            p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+            if p is not None and len(p) != len(f):
+                raise ValueError("poses must have one row per listed frame")
+            keep += [f, p]
+            rec[i].dst = int(dst); rec[i].n_frames = len(f); rec[i].frames = f.ctypes.data
+            rec[i].poses_w7 = None if p is None else p.ctypes.data
+            rec[i].reset = int(reset)
+            for k, v in enumerate((10, 10, 5) if cen is None else cen):
+                rec[i].cen[k] = int(v)
+        added = np.zeros((len(ops), 2), np.int64); dropped = np.zeros((len(ops), 2), np.int64)
+        self._ck(self.lib.ll_cubemaps_insert_keyframes(self.h, kf.h, C.addressof(rec), len(ops), added.ctypes.data, dropped.ctypes.data))
+        return added, dropped
+
+    def insert_timing(self):
+        """the last insert_keyframes: ((assign ms, sort + gather ms, filter ms, commit ms), (points in, touched cubes, points out))"""
+        ms = np.zeros(4); cnt = np.zeros(3, np.int64)
+        self._ck(self.lib.ll_cubemaps_insert_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
+        return tuple(ms), tuple(int(c) for c in cnt)
+
     def align(self, ops, n_outer=2, opt=None, fit=True):
         """ops: a list of (dst, src, guess_w7) -- the rigid transform that takes map src's world frame into map dst's, by
         laserMapping's scan-to-map optimisation over the whole of both maps from the guess (local registration: the guess must lie
@@ -1137,6 +1202,84 @@ class CubeMaps:
     def reset(self, q):
         """sequence q back to a freshly created cube map; the others are untouched"""
         self._ck(self.lib.ll_cubemaps_reset(self.h, int(q)))
+
+
+class Keyframes:
+    """One ll_keyframes: the stack clouds (down-sized corner and surf features, sensor frame) and mapped poses of frames, on the device;
+    frame ids are 0 .. len(self) - 1 in the order they were added.  CubeMaps.insert_keyframes rebuilds maps from them"""
+
+    def __init__(self, ctx, max_frames, cap_corner, cap_surf):
+        self.ctx = ctx; self.lib = ctx.lib
+        self.params = KeyframesParams(int(max_frames), int(cap_corner), int(cap_surf))
+        self.h = C.c_void_p()
+        rc = self.lib.ll_keyframes_create(ctx.h, C.byref(self.params), C.byref(self.h))
+        if rc != LL_OK:
+            raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ll_keyframes_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_keyframes_last_error(self.h).decode())
+
+    def __len__(self):
+        return self.lib.ll_keyframes_size(self.h)
+
+    size = __len__
+
+    def reset(self):
+        self._ck(self.lib.ll_keyframes_reset(self.h))
+
+    def info(self, i):
+        """frame i: {"lane", "frame_index", "n": (corner, surf), "offset": (corner, surf), "pose": [7]}; host only"""
+        e = KeyframeInfo()
+        self._ck(self.lib.ll_keyframes_info(self.h, int(i), C.byref(e)))
+        return {"lane": e.lane, "frame_index": e.frame_index, "n": tuple(e.n), "offset": tuple(e.offset), "pose": np.array(e.pose_w7[:])}
+
+    def add_cubemaps(self, cms, sel, poses, lane_tag=None, frame_tag=None):
+        """one keyframe per sequence with sel[q] = 1 from the stack clouds of its last frame (CubeMaps.cloud(q, 2 / 3)) and poses[q]
+        -> the first new id (-1: none selected).  One copy launch, no synchronisation"""
+        S = cms.n_seq
+        s = np.ascontiguousarray(sel).astype(np.int32)
+        if s.shape != (S,):
+            raise ValueError("sel must have one entry per sequence")
+        p = np.ascontiguousarray(poses, np.float64).reshape(S, 7)
+        lt = None if lane_tag is None else np.ascontiguousarray(lane_tag, np.int32).reshape(S)
+        ft = None if frame_tag is None else np.ascontiguousarray(frame_tag, np.int32).reshape(S)
+        first = C.c_int(-1)
+        self._ck(self.lib.ll_keyframes_add_cubemaps(self.h, cms.h, s.ctypes.data, p.ctypes.data, None if lt is None else lt.ctypes.data,
+                                                    None if ft is None else ft.ctypes.data, C.addressof(first)))
+        return first.value
+
+    def add_points(self, corner, surf, pose):
+        """one keyframe from host clouds (n, 4) float32 -> its id"""
+        c = np.ascontiguousarray(corner, np.float32).reshape(-1, 4); s = np.ascontiguousarray(surf, np.float32).reshape(-1, 4)
+        p = np.ascontiguousarray(pose, np.float64).reshape(7)
+        i = C.c_int(-1)
+        self._ck(self.lib.ll_keyframes_add_points(self.h, c.ctypes.data if len(c) else None, len(c), s.ctypes.data if len(s) else None, len(s),
+                                                  p.ctypes.data, C.addressof(i)))
+        return i.value
+
+    def export(self, first=0, count=None):
+        """(points [N, 4] float32, offsets [count, 2] + total as int64 [2 count + 1]): frames first .. back to back, per frame the
+        corner cloud and then the surf cloud; cloud w of frame first + f is points[offsets[2 f + w]:offsets[2 f + w + 1]].  One gather,
+        one copy, one synchronisation"""
+        count = len(self) - int(first) if count is None else int(count)
+        off = np.zeros(2 * max(count, 0) + 1, np.int64)
+        self._ck(self.lib.ll_keyframes_export(self.h, int(first), count, None, off.ctypes.data))
+        out = np.zeros((max(int(off[-1]), 1), 4), np.float32)
+        self._ck(self.lib.ll_keyframes_export(self.h, int(first), count, out.ctypes.data, off.ctypes.data))
+        return out[:int(off[-1])], off
 
 
 class PlacesParams(C.Structure):
@@ -1446,6 +1589,19 @@ class Drives:
         """the mapping lanes vote their plane blocks in frames whose per-lane index is > from_frame (the reference's gate: 20); negative:
         off, the default (ll_drives_set_map_vote).  Not part of a checkpoint: set it again after restore"""
         self._ck(self.lib.ll_drives_set_map_vote(self.h, int(from_frame)))
+
+    def set_keyframes(self, kf, every=1):
+        """from the next step on every lane that ran a frame whose per-lane index is a multiple of `every` is captured into the
+        Keyframes store kf (its stack clouds and mapped pose, tagged with lane and frame index); None: off, the default"""
+        self._kf = kf                                                # keeps the store alive while the drives object points at it
+        self._ck(self.lib.ll_drives_set_keyframes(self.h, None if kf is None else kf.h, int(every)))
+
+    def correct(self, lanes, C_w7):
+        """left-multiplies the map-to-odom pose of every lane with lanes[q] = 1 by C_w7[q] ([S, 7]): with C = P'_last o P_last^-1 the
+        lane's drive continues in a map rebuilt under corrected poses.  Between any two steps"""
+        sel = self._lanes(lanes)
+        c = np.ascontiguousarray(C_w7, np.float64).reshape(self.n_lanes, 7)
+        self._ck(self.lib.ll_drives_correct(self.h, sel.ctypes.data, c.ctypes.data))
 
     def fit(self):
         """the last step's LocalizeFit records [S]: zeros for lanes that mapped, sat out or did not optimise"""

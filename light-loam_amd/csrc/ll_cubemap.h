@@ -86,8 +86,23 @@ struct LLMapMerge {
     hipEvent_t ev[LL_MM_EVENTS] = {}; bool have_ev = false;
     double ms[4] = {0.0, 0.0, 0.0, 0.0};          /* the last merge: assign, sort + gather, filter, commit (events) */
     long long counts[3] = {0, 0, 0};              /* points in, touched cubes, points out */
+    double ins_ms[4] = {0.0, 0.0, 0.0, 0.0};      /* the same of the last ll_cubemaps_insert_keyframes, which runs in the same workspace */
+    long long ins_counts[3] = {0, 0, 0};
 };
 
+/* keyframes (ll_keyframes.hip): the stack clouds of mapped frames, type w in region w of ONE allocation (region 1 begins at
+ * cap[0]), a frame's cloud at tab[id].offset[w] of its region; top: the regions' fill.  X: the export's staging buffer, table pair
+ * and events (the calls that use it synchronise) */
+struct ll_keyframes {
+    ll_ctx *ctx = nullptr;
+    int max_frames = 0;
+    long long cap[2] = {0, 0}, top[2] = {0, 0};
+    float4 *pool = nullptr;
+    std::vector<ll_keyframe_info> tab;
+    LLMapExport X;
+    std::string err;
+    float4 *region(int w) const { return pool + (w ? cap[0] : 0); }
+};
 /* map alignment (ll_map_align.hip): what an aligning object keeps between calls -- one device buffer grown to the need (search
  * tables, cell-ordered dst points, flat src stacks, per-op fit results, residual blocks and partial sums), the events around the
  * stages (two more per outer iteration), the last call's figures */
@@ -119,6 +134,7 @@ struct ll_cubemap : CmTables {                   /* the pair tables (ll_cubemap_
     std::vector<void *> allocs;
     std::string err;
     bool broken = false;                          /* an update failed half-way: the pair tables no longer describe the pools */
+    bool has_frame = false;                       /* a frame has run since create / reset / import: the stack clouds are one frame's (ll_keyframes) */
 };
 
 #define CM_HIP(call)                                                                         \
@@ -131,6 +147,8 @@ struct ll_cubemap : CmTables {                   /* the pair tables (ll_cubemap_
 void cm_run_moves(ll_cubemap *cm, int w, const std::vector<CmPiece> &moves);
 
 #define LL_HIDDEN __attribute__((visibility("hidden")))
+/* ll_keyframes.hip, for ll_drives.hip: room for n_frames more frames of at most max_pts[w] points each?  LL_OK or LL_ERR_CAPACITY (kf->err set) */
+LL_HIDDEN int llkf_room(ll_keyframes *kf, int n_frames, const int max_pts[2]);
 /* ll_map_export.hip: the tile size of this call; the segments of one map in output order (returns its points; segs == nullptr:
  * sizes only); the single map's table upload; the gather + copy + the one synchronisation; the last call's figures */
 LL_HIDDEN int llx_tile();

@@ -378,6 +378,7 @@ static int cms_prepare_finish(ll_cubemaps *cms, const std::vector<int> &run, con
     for (int r = 0; r < R; ++r) {
         ll_map *m = cms->cm[run[r]]->map;
         for (int w = 0; w < 2; ++w) { m->M.n_map[w] = n_from[w][r]; m->M.n_stk[w] = n_stk[w][r]; }
+        cms->cm[run[r]]->has_frame = true;
         ll_map_rebuild_finish(m, bbox.data() + 12 * r);                            /* kdtree setInputCloud (:1826-1827) */
     }
     for (int w = 0; w < 2; ++w) {
@@ -817,7 +818,7 @@ extern "C" int ll_cubemaps_reset(ll_cubemaps *cms, int q)
         cm->map->M.n_map[w] = 0; cm->map->M.n_stk[w] = 0;
     }
     cm->n_valid = 0;
-    cm->broken = false;
+    cm->broken = false; cm->has_frame = false;
     return LL_OK;
 }
 

@@ -95,6 +95,21 @@ __global__ __launch_bounds__(256) void k_drives_register(LLView V, const DrvReg 
     out[(size_t)L.lane * V.CS + off + i] = make_float4(sx, sy, sz, p.w);
 }
 
+/* ll_drives_correct: the map-to-odom pose of every selected lane left-multiplied by its C (q_C, t_C), spelled as
+ * transformAssociateToMap spells its products: q' = q_C * q_m2o, t' = R(q_C) t_m2o + t_C */
+__global__ __launch_bounds__(64) void k_drives_correct(int S, const int *sel, const double *C, double *m2o)
+{
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    if (q >= S || !sel[q]) return;
+    const double *Cq = C + (size_t)q * 7;
+    double *M = m2o + (size_t)q * 7;
+    double P[7], r[3];
+    drv_qmul(Cq, M, P);
+    ll_rotate(Cq, M + 4, r);
+    for (int k = 0; k < 3; ++k) P[4 + k] = r[k] + Cq[4 + k];
+    for (int k = 0; k < 7; ++k) M[k] = P[k];
+}
+
 /* ll_drives_restore: the state of one record out of the uploaded blob -- the slot's pose and header (as ll_upload_features
  * leaves one), the lane's two poses and frame counter */
 struct DrvRestore { long long src_state; int slot, lane; ScanHdr hdr; };
@@ -114,6 +129,7 @@ struct ll_drives {
     ll_cubemaps *cms = nullptr;
     int S = 0, base = 0, n_outer = 3, keep_registered = 0;
     int map_vote_from = -1;                       /* ll_drives_set_map_vote: a mapping lane votes its plane blocks in frames with index > this; < 0: never */
+    ll_keyframes *kf = nullptr; int kf_every = 1;  /* ll_drives_set_keyframes: the store every kf_every-th frame of a lane is captured into (nullptr: off) */
     int row = 0;                                  /* the row the next step reads */
     std::vector<int> ran_prev, fidx, reg_n;       /* per lane: ran on the last step, frame index of its last frame, registered points */
     std::vector<DrvFeat> feat;                    /* per lane: the feature counts of its previous-row slot (from the step's header read-back, or a restore) */
@@ -341,6 +357,18 @@ extern "C" int ll_drives_step(ll_drives *d, const int *cmd, const double *pose0,
             return LL_ERR_ARG;
         }
     }
+    std::vector<int> capture(S, 0), frame_tag(S, 0);                                    /* the lanes this step captures: room for them, or the step does not run */
+    if (d->kf) {
+        int n_cap = 0;
+        for (int q = 0; q < S; ++q) {
+            if (cmd[q] == LL_DRIVE_IDLE) continue;
+            frame_tag[q] = cmd[q] == LL_DRIVE_START ? 0 : d->fidx[q] + 1;
+            capture[q] = frame_tag[q] % d->kf_every == 0;
+            n_cap += capture[q];
+        }
+        const ll_cubemap *cm = llcms_map(d->cms, 0);
+        if (n_cap > 0 && llkf_room(d->kf, n_cap, cm->cap_last)) { d->err = "the step has not run: " + std::string(ll_keyframes_last_error(d->kf)); return LL_ERR_CAPACITY; }
+    }
     std::fill(d->fit.begin(), d->fit.end(), ll_localize_fit());
     const double nan = std::nan("");
     std::vector<double> odom((size_t)S * 7, nan), mapped((size_t)S * 7, nan), p0((size_t)S * 7, 0.0);
@@ -363,6 +391,10 @@ extern "C" int ll_drives_step(ll_drives *d, const int *cmd, const double *pose0,
             return rc;
         }
         ++d->frames;
+        if (d->kf) {                                                                    /* one copy launch, no synchronisation: the stack clouds stay as they are until the lane's next frame */
+            rc = ll_keyframes_add_cubemaps(d->kf, d->cms, capture.data(), mapped.data(), nullptr, frame_tag.data(), nullptr);
+            if (rc) { d->err = "capture: " + std::string(ll_keyframes_last_error(d->kf)); return rc; }
+        }
     }
     for (int q = 0; q < S; ++q) {
         d->ran_prev[q] = cmd[q] != LL_DRIVE_IDLE;
@@ -399,6 +431,46 @@ extern "C" int ll_drives_set_localize(ll_drives *d, const int *map_of, const dou
     DRV_HIP(hipMemcpyAsync(d->d_start, start.data(), start.size() * sizeof(double), hipMemcpyHostToDevice, d->ctx->stream));
     DRV_HIP(hipStreamSynchronize(d->ctx->stream));                                      /* `start` goes away */
     d->map_of.assign(map_of, map_of + S);
+    return LL_OK;
+}
+
+extern "C" int ll_drives_set_keyframes(ll_drives *d, ll_keyframes *kf, int every)
+{
+    if (!d) return LL_ERR_ARG;
+    if (kf && every < 1) { d->err = "keyframes: every must be >= 1"; return LL_ERR_ARG; }
+    if (kf && kf->ctx != d->ctx) { d->err = "keyframes: the store belongs to another context"; return LL_ERR_ARG; }
+    d->kf = kf; d->kf_every = kf ? every : 1;
+    return LL_OK;
+}
+
+extern "C" int ll_drives_correct(ll_drives *d, const int *lanes, const double *C_w7)
+{
+    if (!d) return LL_ERR_ARG;
+    if (!lanes || !C_w7) { d->err = "correct: lanes or C_w7 is NULL"; return LL_ERR_ARG; }
+    const int S = d->S;
+    static const double ident[7] = {0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+    std::vector<int> sel(S, 0);
+    std::vector<double> C((size_t)S * 7, 0.0);
+    int n_sel = 0;
+    for (int q = 0; q < S; ++q) {
+        if (lanes[q] != 0 && lanes[q] != 1) { d->err = "correct: lane " + std::to_string(q) + ": the selector must be 0 or 1"; return LL_ERR_ARG; }
+        if (!lanes[q]) continue;
+        const double *Cq = C_w7 + (size_t)q * 7;
+        for (int k = 0; k < 7; ++k) if (!std::isfinite(Cq[k])) { d->err = "correct: lane " + std::to_string(q) + ": non-finite C"; return LL_ERR_ARG; }
+        if (!d->ran_prev[q]) { d->err = "correct: lane " + std::to_string(q) + " has no drive (it neither ran on the previous step nor was restored)"; return LL_ERR_STATE; }
+        if (std::equal(Cq, Cq + 7, ident)) continue;                                    /* the identity is not applied: every bit stays, a -0.0 included */
+        sel[q] = 1; ++n_sel;
+        std::copy(Cq, Cq + 7, C.begin() + (size_t)q * 7);
+    }
+    if (n_sel == 0) return LL_OK;
+    DRV_HIP(hipSetDevice(d->ctx->device));
+    llcms_begin(d->cms);
+    const int *d_sel = (const int *)llcms_stage(d->cms, sel.data(), sel.size() * sizeof(int));
+    const double *d_C = (const double *)llcms_stage(d->cms, C.data(), C.size() * sizeof(double));
+    if (!d_sel || !d_C) { d->err = llcms_err(d->cms); return LL_ERR_HIP; }
+    hipLaunchKernelGGL(k_drives_correct, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, d->ctx->stream, S, d_sel, d_C, d->d_m2o);
+    DRV_HIP(hipGetLastError());
+    DRV_HIP(hipStreamSynchronize(d->ctx->stream));                                      /* outside a step: not counted */
     return LL_OK;
 }
 

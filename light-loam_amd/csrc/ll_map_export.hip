@@ -301,7 +301,7 @@ void llx_import_commit(ll_cubemap *cm, const int *cen3, const int *counts, const
     }
     cm->n_valid = n_valid;
     for (int v = 0; v < n_valid; ++v) cm->valid[v] = valid[v];
-    cm->broken = false;
+    cm->broken = false; cm->has_frame = false;
 }
 
 float4 *llx_reserve(LLMapExport &X, size_t n, std::string &err)

@@ -22,10 +22,18 @@
  *                 per touched cube its old cloud, then its new points in order -- and, after the filters, the commit copy.
  * The host synchronises three times per call whatever the number of ops: the per-cube counts, the filtered sizes, the commit;
  * plus the voxel filter's read-back when a filter call is above 65 536 points and cannot sort inside its workgroups.
+ *
+ * ll_cubemaps_insert_keyframes (a map rebuilt or extended from the frames of an ll_keyframes store, each frame under its own pose) is
+ * the same machine with the source and the transform per frame: k_kf_assign is k_mm_assign over the (frame, type) clouds where they
+ * lie in the store's pool, with a pose per SEGMENT; a record's flat order is its listed frames back to back.  Everything from
+ * k_mm_cstart to the commit is mm_run, which both entry points call; an op may ask for its dst to be emptied first, which mm_run
+ * does once the capacity decision has passed and takes back if the call fails before its commit.
  */
 #include "ll_cubemap.h"
 #include <chrono>
+#include <climits>
 #include <cmath>
+#include <functional>
 #include <numeric>
 
 #define MM_BINS (CM_N + 1)               /* 4851 cubes + "outside the array" */
@@ -34,6 +42,7 @@
 
 struct MmRec { double T[7]; int cen[3]; int first, n, chunk0, nchunk, pad; };      /* first: its first point in the flat order */
 struct MmSeg { const float4 *src; int dst, cnt; unsigned tile0; int rec; };        /* one source cloud; dst: flat index of its first point */
+struct KfSeg { const float4 *src; int dst, cnt; unsigned tile0; int rec; double T[7]; };   /* keyframe insert: one (frame, type) cloud and that frame's pose */
 struct MmChunk { int first, cnt, rec, pad; };
 struct MmCopy { const float4 *src; const int *index; float4 *dst; int cnt; unsigned tile0; };   /* dst[i] = index ? src[index[i]] : src[i] */
 
@@ -49,18 +58,18 @@ __device__ __forceinline__ int mm_find(const S *seg, int nseg, unsigned t)
     return lo;
 }
 
-__global__ __launch_bounds__(256) void k_mm_assign(const MmSeg *seg, int nseg, const MmRec *recs, float4 *tp, int *keys, int *addcnt)
+/* tile `tile` of a source cloud of cnt points whose first point has the flat index dst, under the pose Tsrc and the centre of record rec */
+__device__ __forceinline__ void mm_assign_tile(const float4 *src, int dst, int cnt, int tile, const double *Tsrc, const MmRec *recs, int rec, float4 *tp, int *keys, int *addcnt)
 {
-    const MmSeg s = seg[mm_find(seg, nseg, blockIdx.x)];
-    const MmRec &R = recs[s.rec];
-    const int first = (int)(blockIdx.x - s.tile0) * MM_TILE, n = min(MM_TILE, s.cnt - first);
+    const MmRec &R = recs[rec];
+    const int first = tile * MM_TILE, n = min(MM_TILE, cnt - first);
     double T[7]; int cen[3];                                      /* like the points: every load before the first store */
-    for (int k = 0; k < 7; ++k) T[k] = R.T[k];
+    for (int k = 0; k < 7; ++k) T[k] = Tsrc[k];
     for (int k = 0; k < 3; ++k) cen[k] = R.cen[k];
-    int *cnt = addcnt + (size_t)s.rec * MM_BINS;
+    int *count = addcnt + (size_t)rec * MM_BINS;
     float4 po[MM_TILE / 256];
 #pragma unroll
-    for (int k = 0; k < MM_TILE / 256; ++k) po[k] = s.src[first + min(k * 256 + (int)threadIdx.x, n - 1)];   /* every load before the first store */
+    for (int k = 0; k < MM_TILE / 256; ++k) po[k] = src[first + min(k * 256 + (int)threadIdx.x, n - 1)];   /* every load before the first store */
 #pragma unroll
     for (int k = 0; k < MM_TILE / 256; ++k) {
         const int i = k * 256 + (int)threadIdx.x;
@@ -70,14 +79,29 @@ __global__ __launch_bounds__(256) void k_mm_assign(const MmSeg *seg, int nseg, c
              * pose is used as given, never normalised */
             float sx, sy, sz;
             ll_map_to_world(T, po[k], sx, sy, sz);
-            tp[s.dst + first + i] = make_float4(sx, sy, sz, po[k].w);
+            tp[dst + first + i] = make_float4(sx, sy, sz, po[k].w);
             int ci, cj, ck;
             cube = cm_cube_of(sx, sy, sz, cen, &ci, &cj, &ck);
             if (cube < 0) cube = CM_N;                            /* outside the array: a bin of its own */
-            keys[s.dst + first + i] = cube;
+            keys[dst + first + i] = cube;
         }
-        cm_wave_count(cube, cnt);                                 /* one add per wave and cube */
+        cm_wave_count(cube, count);                               /* one add per wave and cube */
     }
+}
+
+__global__ __launch_bounds__(256) void k_mm_assign(const MmSeg *seg, int nseg, const MmRec *recs, float4 *tp, int *keys, int *addcnt)
+{
+    const MmSeg s = seg[mm_find(seg, nseg, blockIdx.x)];
+    mm_assign_tile(s.src, s.dst, s.cnt, (int)(blockIdx.x - s.tile0), recs[s.rec].T, recs, s.rec, tp, keys, addcnt);
+}
+
+/* keyframe insert: the same for one tile of one (frame, type) cloud where it lies in the store's pool; the pose is its SEGMENT's --
+ * every listed frame has its own -- and the record (op, type) gives the centre and the count table.  A record's flat order is its
+ * frames back to back, so the chunks of the counting sort below run across frame boundaries */
+__global__ __launch_bounds__(256) void k_kf_assign(const KfSeg *seg, int nseg, const MmRec *recs, float4 *tp, int *keys, int *addcnt)
+{
+    const KfSeg *s = seg + mm_find(seg, nseg, blockIdx.x);
+    mm_assign_tile(s->src, s->dst, s->cnt, (int)(blockIdx.x - s->tile0), s->T, recs, s->rec, tp, keys, addcnt);
 }
 
 /* cstart[r][b] = addcnt[r][0] + .. + addcnt[r][b - 1]: one workgroup per record */
@@ -211,80 +235,82 @@ static const char *mm_type(int w) { return w ? "surf" : "corner"; }
 #define MM_HIP(call)                                                                         \
     do {                                                                                     \
         hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return llcms_fail(cms, LL_ERR_HIP, std::string("map merge: " #call ": ") + hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) return llcms_fail(cms, LL_ERR_HIP, J.what + #call ": " + hipGetErrorString(e_)); \
     } while (0)
 
-static int mm_gather(ll_cubemaps *cms, std::vector<MmCopy> &ops, hipStream_t st)
+static int mm_gather(ll_cubemaps *cms, const std::string &what, std::vector<MmCopy> &ops, hipStream_t st)
 {
     unsigned long long tile = 0;
     for (MmCopy &o : ops) { o.tile0 = (unsigned)tile; tile += (unsigned long long)((o.cnt + MM_TILE - 1) / MM_TILE); }
     if (ops.empty()) return LL_OK;
-    if (tile > 0x7fffffffull) return llcms_fail(cms, LL_ERR_CAPACITY, "map merge: too many tiles for one launch");
+    if (tile > 0x7fffffffull) return llcms_fail(cms, LL_ERR_CAPACITY, what + "too many tiles for one launch");
     const MmCopy *d = (const MmCopy *)llcms_stage(cms, ops.data(), ops.size() * sizeof(MmCopy));
     if (!d) return LL_ERR_HIP;
     hipLaunchKernelGGL(k_mm_gather, dim3((unsigned)tile), dim3(256), 0, st, d, (int)ops.size());
     return LL_OK;
 }
 
-extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops, long long *added, long long *dropped)
-{
-    if (!cms) return LL_ERR_ARG;
-    if (!ops || n_ops < 1) return llcms_fail(cms, LL_ERR_ARG, "map merge: ops is NULL or n_ops < 1");
-    const int S = llcms_size(cms);
-    /* ---- every refusal that needs no look at a point: before anything is enqueued */
-    std::vector<int> role(S, 0);                                  /* 1: src of some op, 2: dst of one */
-    for (int i = 0; i < n_ops; ++i) {
-        const ll_merge_op &o = ops[i];
-        const std::string who = "map merge: op " + std::to_string(i) + ": ";
-        if (o.dst < 0 || o.dst >= S || o.src < 0 || o.src >= S) return llcms_fail(cms, LL_ERR_ARG, who + "dst or src is no map");
-        if (o.dst == o.src) return llcms_fail(cms, LL_ERR_ARG, who + "dst and src are the same map");
-        for (int k = 0; k < 7; ++k) if (!std::isfinite(o.T_w7[k])) return llcms_fail(cms, LL_ERR_ARG, who + "T is not finite");
-        if (role[o.dst] == 2) return llcms_fail(cms, LL_ERR_ARG, who + "map " + std::to_string(o.dst) + " is dst of two ops");
-        if (role[o.dst] == 1 || role[o.src] == 2) return llcms_fail(cms, LL_ERR_ARG, who + "a map is dst of one op and src of another");
-        role[o.dst] = 2; role[o.src] = 1;
+/* what ll_cubemaps_merge and ll_cubemaps_insert_keyframes hand to the stages they share: per op its dst map, whether dst is first
+ * emptied (reset, with the centre cen: keyframe insert only) and how last_error names the op; the records (one per (op, type), their
+ * points back to back in one flat index space of N points) and the chunks of the counting sort; `assign`, which stages the
+ * caller's own segment table (`stage`) and launches its assign kernel over d_recs into tp / keys / addcnt; where the call's figures go */
+struct MmOp { int dst, reset, cen[3]; std::string who; };
+struct MmJob {
+    std::string what;                                             /* "map merge: " */
+    std::vector<MmOp> ops;
+    std::vector<MmRec> recs;
+    std::vector<MmChunk> chunks;
+    long long N = 0;
+    std::function<bool()> stage;                                  /* the caller's segment table into the call's arena; false: failed */
+    std::function<void(const MmRec *d_recs, float4 *d_tp, int *d_keys, int *d_addcnt, hipStream_t st)> assign;
+    double *ms = nullptr; long long *counts = nullptr;            /* [4], [3] of LLMapMerge */
+};
+
+/* a reset made once the capacity decision has passed is taken back when the call fails before its commit: the tables and the
+ * per-frame counts as they were (no pool has been written by then) */
+struct MmUndo {
+    struct Saved { ll_cubemap *cm; CmTables t; int n_map[2], n_stk[2]; bool broken, has_frame; };
+    std::vector<Saved> saved;
+    void keep(ll_cubemap *cm) { saved.push_back({cm, *cm, {cm->map->M.n_map[0], cm->map->M.n_map[1]}, {cm->map->M.n_stk[0], cm->map->M.n_stk[1]}, cm->broken, cm->has_frame}); }
+    void done() { saved.clear(); }
+    ~MmUndo()
+    {
+        for (Saved &s : saved) {
+            static_cast<CmTables &>(*s.cm) = s.t;
+            for (int w = 0; w < 2; ++w) { s.cm->map->M.n_map[w] = s.n_map[w]; s.cm->map->M.n_stk[w] = s.n_stk[w]; }
+            s.cm->broken = s.broken; s.cm->has_frame = s.has_frame;
+        }
     }
-    for (int i = 0; i < n_ops; ++i)
-        for (const int q : {ops[i].dst, ops[i].src})
-            if (llcms_map(cms, q)->broken) return llcms_fail(cms, LL_ERR_STATE, "map merge: op " + std::to_string(i) + ": map " + std::to_string(q) + " is unusable, an earlier update failed half-way");
+};
+
+static void mm_reset(ll_cubemaps *cms, const MmOp &o)
+{
+    (void)ll_cubemaps_reset(cms, o.dst);
+    for (int k = 0; k < 3; ++k) llcms_map(cms, o.dst)->cen[k] = o.cen[k];
+}
+
+/* everything after the refusals that need no look at a point: workspace, the assign stage, then from k_mm_cstart to the commit --
+ * count read-back, capacity decision, plan, gather, filter, commit */
+static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropped)
+{
     LLMapMerge &G = llcms_merge_state(cms);
     ll_ctx *ctx = llcms_map(cms, 0)->ctx;
     hipStream_t st = ctx->stream;
-    const int nrec = 2 * n_ops;
-    /* ---- the records, the source clouds where they lie, the chunks of the counting sort */
-    std::vector<MmRec> recs(nrec);
-    std::vector<MmSeg> segs;
-    std::vector<MmChunk> chunks;
-    unsigned long long tile = 0;
-    long long N = 0;
-    for (int i = 0; i < n_ops; ++i) {
-        const ll_cubemap *src = llcms_map(cms, ops[i].src), *dst = llcms_map(cms, ops[i].dst);
-        for (int w = 0; w < 2; ++w) {
-            MmRec &R = recs[2 * i + w];
-            for (int k = 0; k < 7; ++k) R.T[k] = ops[i].T_w7[k];
-            for (int k = 0; k < 3; ++k) R.cen[k] = dst->cen[k];
-            R.first = (int)N; R.pad = 0;
-            long long n = 0;
-            for (int c = 0; c < CM_N; ++c) {
-                const int cnt = src->cnt[w][c];
-                if (cnt <= 0) continue;
-                if (N + n + cnt > (1ll << 30)) return llcms_fail(cms, LL_ERR_CAPACITY, "map merge: more than 2^30 source points in one call");
-                segs.push_back({src->pool[w][src->cur[w]] + src->off[w][c], (int)(N + n), cnt, (unsigned)tile, 2 * i + w});
-                tile += (unsigned long long)((cnt + MM_TILE - 1) / MM_TILE);
-                n += cnt;
-            }
-            R.n = (int)n; R.chunk0 = (int)chunks.size(); R.nchunk = (int)((n + MM_CHUNK - 1) / MM_CHUNK);
-            for (int k = 0; k < R.nchunk; ++k) chunks.push_back({(int)(N + (long long)k * MM_CHUNK), (int)std::min<long long>(MM_CHUNK, n - (long long)k * MM_CHUNK), 2 * i + w, 0});
-            N += n;
-        }
-    }
-    G.ms[0] = G.ms[1] = G.ms[2] = G.ms[3] = 0.0; G.counts[0] = N; G.counts[1] = G.counts[2] = 0;
+    const int n_ops = (int)J.ops.size(), nrec = 2 * n_ops;
+    const std::vector<MmRec> &recs = J.recs;
+    const std::vector<MmChunk> &chunks = J.chunks;
+    const long long N = J.N;
+    J.ms[0] = J.ms[1] = J.ms[2] = J.ms[3] = 0.0; J.counts[0] = N; J.counts[1] = J.counts[2] = 0;
     if (added) std::fill(added, added + nrec, 0ll);
     if (dropped) std::fill(dropped, dropped + nrec, 0ll);
-    if (N == 0) return LL_OK;                                     /* empty sources: nothing to move */
+    if (N == 0) {                                                 /* empty sources: nothing to move */
+        for (const MmOp &o : J.ops) if (o.reset) mm_reset(cms, o);
+        return LL_OK;
+    }
     MM_HIP(hipSetDevice(ctx->device));
     if (!G.have_ev) {
         for (int k = 0; k < LL_MM_EVENTS; ++k)
-            if (hipEventCreate(&G.ev[k]) != hipSuccess) { for (int j = 0; j < k; ++j) (void)hipEventDestroy(G.ev[j]); return llcms_fail(cms, LL_ERR_HIP, "map merge: hipEventCreate failed"); }
+            if (hipEventCreate(&G.ev[k]) != hipSuccess) { for (int j = 0; j < k; ++j) (void)hipEventDestroy(G.ev[j]); return llcms_fail(cms, LL_ERR_HIP, J.what + "hipEventCreate failed"); }
         G.have_ev = true;
     }
     MmCarve A{nullptr};                                           /* first the size, then the pointers */
@@ -301,13 +327,12 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
     int *d_addcnt = A.take<int>((size_t)nrec * MM_BINS), *d_cstart = A.take<int>((size_t)nrec * MM_BINS), *d_H = A.take<int>(chunks.size() * MM_BINS);
     llcms_begin(cms);
     const MmRec *d_recs = (const MmRec *)llcms_stage(cms, recs.data(), recs.size() * sizeof(MmRec));
-    const MmSeg *d_segs = (const MmSeg *)llcms_stage(cms, segs.data(), segs.size() * sizeof(MmSeg));
     const MmChunk *d_chunks = (const MmChunk *)llcms_stage(cms, chunks.data(), chunks.size() * sizeof(MmChunk));
-    if (!d_recs || !d_segs || !d_chunks) return LL_ERR_HIP;
+    if (!d_recs || !d_chunks || !J.stage()) return LL_ERR_HIP;
     /* ---- stage A: points -> cubes, by-cube order; host: the cubes' new-point counts of every record */
     MM_HIP(hipMemsetAsync(d_addcnt, 0, (size_t)nrec * MM_BINS * sizeof(int), st));
     MM_HIP(hipEventRecord(G.ev[0], st));
-    hipLaunchKernelGGL(k_mm_assign, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt);
+    J.assign(d_recs, d_tp, d_keys, d_addcnt, st);
     MM_HIP(hipEventRecord(G.ev[1], st));
     hipLaunchKernelGGL(k_mm_cstart, dim3(nrec), dim3(256), 0, st, (const int *)d_addcnt, d_cstart);
     hipLaunchKernelGGL(k_mm_hist, dim3((unsigned)chunks.size()), dim3(256), 0, st, d_chunks, (const int *)d_keys, d_H);
@@ -318,25 +343,35 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
     std::vector<int> addcnt((size_t)nrec * MM_BINS);
     {
         int *pin = (int *)ll_pinned_scratch(addcnt.size() * sizeof(int));
-        if (!pin) return llcms_fail(cms, LL_ERR_HIP, "map merge: no page-locked scratch");
+        if (!pin) return llcms_fail(cms, LL_ERR_HIP, J.what + "no page-locked scratch");
         MM_HIP(hipMemcpyAsync(pin, d_addcnt, addcnt.size() * sizeof(int), hipMemcpyDeviceToHost, st));
         const int rc = llcms_sync(cms); if (rc) return rc;
         std::memcpy(addcnt.data(), pin, addcnt.size() * sizeof(int));
     }
     /* ---- will it fit?  Every op and both types, before any pair table changes: a dst pool must hold what the map holds of the
-     * type plus the added points, so that the commit below cannot fail whatever the filters leave */
+     * type (nothing, when the op resets it) plus the added points, so that the commit below cannot fail whatever the filters leave */
     std::vector<long long> n_add(nrec, 0);
+    long long bound[2] = {0, 0};
+    bool any_reset = false;
     for (int r = 0; r < nrec; ++r) {
         const int *a = addcnt.data() + (size_t)r * MM_BINS;
-        const ll_cubemap *dst = llcms_map(cms, ops[r / 2].dst);
+        const MmOp &o = J.ops[r / 2];
+        const ll_cubemap *dst = llcms_map(cms, o.dst);
         const int w = r & 1;
         long long live = 0;
-        for (int c = 0; c < CM_N; ++c) { n_add[r] += a[c]; live += dst->cnt[w][c]; }
+        for (int c = 0; c < CM_N; ++c) { n_add[r] += a[c]; if (!o.reset) live += dst->cnt[w][c]; }
         if (added) added[r] = n_add[r];
         if (dropped) dropped[r] = a[CM_N];
         if (live + n_add[r] > (long long)dst->cap_pool)
-            return llcms_fail(cms, LL_ERR_CAPACITY, "map merge: op " + std::to_string(r / 2) + " (map " + std::to_string(ops[r / 2].dst) + " <- map " + std::to_string(ops[r / 2].src) + "): " +
+            return llcms_fail(cms, LL_ERR_CAPACITY, J.what + "op " + std::to_string(r / 2) + " (" + o.who + "): " +
                               std::to_string(live) + " " + mm_type(w) + " points + " + std::to_string(n_add[r]) + " added, pool_points is " + std::to_string(dst->cap_pool));
+        bound[w] += live + n_add[r]; any_reset = any_reset || o.reset;
+    }
+    MmUndo undo;
+    if (any_reset) {                                              /* the filter call's own limit (below), decided while nothing has changed */
+        for (int w = 0; w < 2; ++w)
+            if (bound[w] > (long long)(INT_MAX / 2)) return llcms_fail(cms, LL_ERR_CAPACITY, J.what + "the touched " + mm_type(w) + " cubes hold more points than one filter call takes");
+        for (const MmOp &o : J.ops) if (o.reset) { undo.keep(llcms_map(cms, o.dst)); mm_reset(cms, o); }
     }
     /* ---- stage B: one voxel-grid segment per touched cube of every op -- its cloud, then its new points in order */
     std::vector<CmPlan> plan(nrec);
@@ -348,15 +383,15 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
             const int r = 2 * i + w;
             const int *a = addcnt.data() + (size_t)r * MM_BINS;
             for (int c = 0; c < CM_N; ++c) if (a[c] > 0) touched[r].push_back(c);
-            plan[r] = cm_plan(*llcms_map(cms, ops[i].dst), w, touched[r].data(), (int)touched[r].size(), a);
+            plan[r] = cm_plan(*llcms_map(cms, J.ops[i].dst), w, touched[r].data(), (int)touched[r].size(), a);
             seg0[r] = (int)seg_off[w].size() - 1;
             for (size_t s = 1; s < plan[r].seg_off.size(); ++s) seg_off[w].push_back((int)(F[w] + plan[r].seg_off[s]));
             F[w] += plan[r].seg_off.back();
         }
-        if (F[w] > (long long)(INT_MAX / 2)) return llcms_fail(cms, LL_ERR_CAPACITY, std::string("map merge: the touched ") + mm_type(w) + " cubes hold more points than one filter call takes");
+        if (F[w] > (long long)(INT_MAX / 2)) return llcms_fail(cms, LL_ERR_CAPACITY, J.what + "the touched " + mm_type(w) + " cubes hold more points than one filter call takes");
     }
     const size_t nseg[2] = {seg_off[0].size() - 1, seg_off[1].size() - 1};
-    G.counts[1] = (long long)(nseg[0] + nseg[1]);
+    J.counts[1] = (long long)(nseg[0] + nseg[1]);
     float4 *d_work[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
     int *d_nout = nullptr;
     LLVoxWork W[2];
@@ -382,7 +417,7 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
     for (int w = 0; w < 2; ++w)
         for (int i = 0; i < n_ops; ++i) {
             const int r = 2 * i + w;
-            const ll_cubemap *dst = llcms_map(cms, ops[i].dst);
+            const ll_cubemap *dst = llcms_map(cms, J.ops[i].dst);
             for (const CmPiece &e : plan[r].pieces) {             /* the new points of a cube in the record's by-cube order */
                 float4 *at = d_work[w] + seg_off[w][seg0[r]] + e.dst;
                 if (e.old_cnt > 0) cp.push_back({dst->pool[w][dst->cur[w]] + e.old_off, nullptr, at, e.old_cnt, 0});
@@ -390,7 +425,7 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
             }
         }
     MM_HIP(hipEventRecord(G.ev[3], st));
-    int rc = mm_gather(cms, cp, st); if (rc) return rc;
+    int rc = mm_gather(cms, J.what, cp, st); if (rc) return rc;
     MM_HIP(hipEventRecord(G.ev[4], st));
     for (int w = 0; w < 2; ++w) {
         if (F[w] <= 0) continue;
@@ -399,7 +434,7 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
         /* the voxel filter's sort reads back once when it cannot stay inside the workgroups (ll_voxel.hip): counted with the syncs */
         if (ll_voxel_grid_segments_reads_back((int)F[w], (int)nseg[w], max_seg)) llcms_count_sync(cms);
         if (ll_voxel_grid_segments(d_work[w], (int)F[w], (int)nseg[w], llcms_leaf(cms)[w], W[w], d_out[w], d_nout + w, st, max_seg))
-            return llcms_fail(cms, LL_ERR_HIP, "map merge: voxel filter: read-back failed");
+            return llcms_fail(cms, LL_ERR_HIP, J.what + "voxel filter: read-back failed");
     }
     MM_HIP(hipEventRecord(G.ev[5], st));
     MM_HIP(hipGetLastError());
@@ -407,7 +442,7 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
     {
         const size_t n0 = nseg[0], n1 = nseg[1];
         int *pin = (int *)ll_pinned_scratch((n0 + n1 + 2) * sizeof(int));
-        if (!pin) return llcms_fail(cms, LL_ERR_HIP, "map merge: no page-locked scratch");
+        if (!pin) return llcms_fail(cms, LL_ERR_HIP, J.what + "no page-locked scratch");
         if (n0) MM_HIP(hipMemcpyAsync(pin, W[0].seg_count, n0 * sizeof(int), hipMemcpyDeviceToHost, st));
         if (n1) MM_HIP(hipMemcpyAsync(pin + n0, W[1].seg_count, n1 * sizeof(int), hipMemcpyDeviceToHost, st));
         rc = llcms_sync(cms); if (rc) return rc;
@@ -415,7 +450,8 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
     }
     /* ---- commit: from here on a failure leaves the pair tables half-updated (the dst maps are marked unusable).  The capacity
      * decision above covers it: the filtered clouds are never larger than what went into the filters */
-    for (int i = 0; i < n_ops; ++i) llcms_map(cms, ops[i].dst)->broken = true;
+    undo.done();
+    for (int i = 0; i < n_ops; ++i) llcms_map(cms, J.ops[i].dst)->broken = true;
     cp.clear();
     long long n_out_all = 0;
     for (int w = 0; w < 2; ++w) {
@@ -423,7 +459,7 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
         for (int i = 0; i < n_ops; ++i) {
             const int r = 2 * i + w, n_set = (int)touched[r].size(), *sc = seg_count[w].data() + seg0[r];
             if (n_set == 0) continue;
-            ll_cubemap *dst = llcms_map(cms, ops[i].dst);
+            ll_cubemap *dst = llcms_map(cms, J.ops[i].dst);
             const size_t n = std::accumulate(sc, sc + n_set, (size_t)0);        /* nothing grows outside the set: this is all the pool takes */
             const CmCommit K = cm_commit(*dst, w, plan[r], touched[r].data(), n_set, addcnt.data() + (size_t)r * MM_BINS, sc, n);
             cm_run_moves(dst, w, K.moves);                        /* a compaction: launched at once, the copies below follow it */
@@ -432,14 +468,160 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
         }
     }
     MM_HIP(hipEventRecord(G.ev[6], st));
-    rc = mm_gather(cms, cp, st); if (rc) return rc;              /* after every compaction above: stream order */
+    rc = mm_gather(cms, J.what, cp, st); if (rc) return rc;      /* after every compaction above: stream order */
     MM_HIP(hipEventRecord(G.ev[7], st));
     MM_HIP(hipGetLastError());
     rc = llcms_sync(cms); if (rc) return rc;                      /* the copy has landed: the maps are whole again, the events can be read */
-    for (int i = 0; i < n_ops; ++i) llcms_map(cms, ops[i].dst)->broken = false;
+    for (int i = 0; i < n_ops; ++i) llcms_map(cms, J.ops[i].dst)->broken = false;
     auto span = [&](int a, int b) { float ms = 0.0f; return hipEventElapsedTime(&ms, G.ev[a], G.ev[b]) == hipSuccess ? (double)ms : 0.0; };
-    G.ms[0] = span(0, 1); G.ms[1] = span(1, 2) + span(3, 4); G.ms[2] = span(4, 5); G.ms[3] = span(6, 7);
-    G.counts[2] = n_out_all;
+    J.ms[0] = span(0, 1); J.ms[1] = span(1, 2) + span(3, 4); J.ms[2] = span(4, 5); J.ms[3] = span(6, 7);
+    J.counts[2] = n_out_all;
+    return LL_OK;
+}
+
+/* the chunks of the counting sort for a record of n points whose first point has the flat index N */
+static void mm_close_record(MmRec &R, int rec, long long N, long long n, std::vector<MmChunk> &chunks)
+{
+    R.first = (int)N; R.pad = 0;
+    R.n = (int)n; R.chunk0 = (int)chunks.size(); R.nchunk = (int)((n + MM_CHUNK - 1) / MM_CHUNK);
+    for (int k = 0; k < R.nchunk; ++k) chunks.push_back({(int)(N + (long long)k * MM_CHUNK), (int)std::min<long long>(MM_CHUNK, n - (long long)k * MM_CHUNK), rec, 0});
+}
+
+extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops, long long *added, long long *dropped)
+{
+    if (!cms) return LL_ERR_ARG;
+    if (!ops || n_ops < 1) return llcms_fail(cms, LL_ERR_ARG, "map merge: ops is NULL or n_ops < 1");
+    const int S = llcms_size(cms);
+    /* ---- every refusal that needs no look at a point: before anything is enqueued */
+    std::vector<int> role(S, 0);                                  /* 1: src of some op, 2: dst of one */
+    for (int i = 0; i < n_ops; ++i) {
+        const ll_merge_op &o = ops[i];
+        const std::string who = "map merge: op " + std::to_string(i) + ": ";
+        if (o.dst < 0 || o.dst >= S || o.src < 0 || o.src >= S) return llcms_fail(cms, LL_ERR_ARG, who + "dst or src is no map");
+        if (o.dst == o.src) return llcms_fail(cms, LL_ERR_ARG, who + "dst and src are the same map");
+        for (int k = 0; k < 7; ++k) if (!std::isfinite(o.T_w7[k])) return llcms_fail(cms, LL_ERR_ARG, who + "T is not finite");
+        if (role[o.dst] == 2) return llcms_fail(cms, LL_ERR_ARG, who + "map " + std::to_string(o.dst) + " is dst of two ops");
+        if (role[o.dst] == 1 || role[o.src] == 2) return llcms_fail(cms, LL_ERR_ARG, who + "a map is dst of one op and src of another");
+        role[o.dst] = 2; role[o.src] = 1;
+    }
+    for (int i = 0; i < n_ops; ++i)
+        for (const int q : {ops[i].dst, ops[i].src})
+            if (llcms_map(cms, q)->broken) return llcms_fail(cms, LL_ERR_STATE, "map merge: op " + std::to_string(i) + ": map " + std::to_string(q) + " is unusable, an earlier update failed half-way");
+    LLMapMerge &G = llcms_merge_state(cms);
+    /* ---- the records, the source clouds where they lie, the chunks of the counting sort */
+    MmJob J;
+    J.what = "map merge: "; J.ms = G.ms; J.counts = G.counts;
+    J.recs.resize(2 * n_ops);
+    std::vector<MmSeg> segs;
+    unsigned long long tile = 0;
+    long long N = 0;
+    for (int i = 0; i < n_ops; ++i) {
+        const ll_cubemap *src = llcms_map(cms, ops[i].src), *dst = llcms_map(cms, ops[i].dst);
+        J.ops.push_back({ops[i].dst, 0, {0, 0, 0}, "map " + std::to_string(ops[i].dst) + " <- map " + std::to_string(ops[i].src)});
+        for (int w = 0; w < 2; ++w) {
+            MmRec &R = J.recs[2 * i + w];
+            for (int k = 0; k < 7; ++k) R.T[k] = ops[i].T_w7[k];
+            for (int k = 0; k < 3; ++k) R.cen[k] = dst->cen[k];
+            long long n = 0;
+            for (int c = 0; c < CM_N; ++c) {
+                const int cnt = src->cnt[w][c];
+                if (cnt <= 0) continue;
+                if (N + n + cnt > (1ll << 30)) return llcms_fail(cms, LL_ERR_CAPACITY, "map merge: more than 2^30 source points in one call");
+                segs.push_back({src->pool[w][src->cur[w]] + src->off[w][c], (int)(N + n), cnt, (unsigned)tile, 2 * i + w});
+                tile += (unsigned long long)((cnt + MM_TILE - 1) / MM_TILE);
+                n += cnt;
+            }
+            mm_close_record(R, 2 * i + w, N, n, J.chunks);
+            N += n;
+        }
+    }
+    J.N = N;
+    const MmSeg *d_segs = nullptr;
+    J.stage = [&]() { d_segs = (const MmSeg *)llcms_stage(cms, segs.data(), segs.size() * sizeof(MmSeg)); return d_segs != nullptr; };
+    J.assign = [&](const MmRec *d_recs, float4 *d_tp, int *d_keys, int *d_addcnt, hipStream_t st) {
+        hipLaunchKernelGGL(k_mm_assign, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt);
+    };
+    return mm_run(cms, J, added, dropped);
+}
+
+/* ------------------------------------------------------------------ keyframe insert: one transform per frame through the same stages */
+extern "C" int ll_cubemaps_insert_keyframes(ll_cubemaps *cms, const ll_keyframes *kf, const ll_insert_op *ops, int n_ops, long long *added, long long *dropped)
+{
+    if (!cms) return LL_ERR_ARG;
+    const std::string what = "keyframe insert: ";
+    if (!kf || !ops || n_ops < 1) return llcms_fail(cms, LL_ERR_ARG, what + "kf or ops is NULL, or n_ops < 1");
+    if (kf->ctx != llcms_map(cms, 0)->ctx) return llcms_fail(cms, LL_ERR_ARG, what + "the store belongs to another context");
+    const int S = llcms_size(cms), size = (int)kf->tab.size();
+    /* ---- every refusal that needs no look at a point: before anything is enqueued */
+    std::vector<char> is_dst(S, 0);
+    for (int i = 0; i < n_ops; ++i) {
+        const ll_insert_op &o = ops[i];
+        const std::string who = what + "op " + std::to_string(i) + ": ";
+        if (o.dst < 0 || o.dst >= S) return llcms_fail(cms, LL_ERR_ARG, who + "dst is no map");
+        if (is_dst[o.dst]) return llcms_fail(cms, LL_ERR_ARG, who + "map " + std::to_string(o.dst) + " is dst of two ops");
+        is_dst[o.dst] = 1;
+        if (o.n_frames < 0 || (o.n_frames > 0 && !o.frames)) return llcms_fail(cms, LL_ERR_ARG, who + "n_frames < 0 or frames is NULL");
+        if (o.reset != 0 && o.reset != 1) return llcms_fail(cms, LL_ERR_ARG, who + "reset must be 0 or 1");
+        if (o.reset)
+            for (int k = 0; k < 3; ++k)
+                if (o.cen[k] < -(1 << 24) || o.cen[k] > (1 << 24)) return llcms_fail(cms, LL_ERR_ARG, who + "cen[" + std::to_string(k) + "] = " + std::to_string(o.cen[k]) + " is outside the cube array's reach");
+        for (int f = 0; f < o.n_frames; ++f) {
+            if (o.frames[f] < 0 || o.frames[f] >= size) return llcms_fail(cms, LL_ERR_ARG, who + "frame " + std::to_string(o.frames[f]) + " is not in the store (size " + std::to_string(size) + ")");
+            const double *P = o.poses_w7 ? o.poses_w7 + (size_t)f * 7 : kf->tab[o.frames[f]].pose_w7;
+            for (int k = 0; k < 7; ++k) if (!std::isfinite(P[k])) return llcms_fail(cms, LL_ERR_ARG, who + "the pose of list entry " + std::to_string(f) + " is not finite");
+        }
+    }
+    for (int i = 0; i < n_ops; ++i)
+        if (llcms_map(cms, ops[i].dst)->broken) return llcms_fail(cms, LL_ERR_STATE, what + "op " + std::to_string(i) + ": map " + std::to_string(ops[i].dst) + " is unusable, an earlier update failed half-way");
+    LLMapMerge &G = llcms_merge_state(cms);
+    /* ---- the records, the frames' clouds where they lie in the store, each with its frame's pose, the chunks of the counting sort */
+    MmJob J;
+    J.what = what; J.ms = G.ins_ms; J.counts = G.ins_counts;
+    J.recs.resize(2 * n_ops);
+    std::vector<KfSeg> segs;
+    unsigned long long tile = 0;
+    long long N = 0;
+    for (int i = 0; i < n_ops; ++i) {
+        const ll_insert_op &o = ops[i];
+        const ll_cubemap *dst = llcms_map(cms, o.dst);
+        J.ops.push_back({o.dst, o.reset, {o.cen[0], o.cen[1], o.cen[2]}, "map " + std::to_string(o.dst) + " <- " + std::to_string(o.n_frames) + " keyframes"});
+        for (int w = 0; w < 2; ++w) {
+            MmRec &R = J.recs[2 * i + w];
+            for (int k = 0; k < 7; ++k) R.T[k] = 0.0;             /* not read: the pose is the segment's */
+            for (int k = 0; k < 3; ++k) R.cen[k] = o.reset ? o.cen[k] : dst->cen[k];
+            long long n = 0;
+            for (int f = 0; f < o.n_frames; ++f) {
+                const ll_keyframe_info &e = kf->tab[o.frames[f]];
+                const int cnt = e.n[w];
+                if (cnt <= 0) continue;
+                if (N + n + cnt > (1ll << 30)) return llcms_fail(cms, LL_ERR_CAPACITY, what + "more than 2^30 source points in one call");
+                KfSeg s = {kf->region(w) + e.offset[w], (int)(N + n), cnt, (unsigned)tile, 2 * i + w, {}};
+                const double *P = o.poses_w7 ? o.poses_w7 + (size_t)f * 7 : e.pose_w7;
+                for (int k = 0; k < 7; ++k) s.T[k] = P[k];
+                segs.push_back(s);
+                tile += (unsigned long long)((cnt + MM_TILE - 1) / MM_TILE);
+                n += cnt;
+            }
+            mm_close_record(R, 2 * i + w, N, n, J.chunks);
+            N += n;
+        }
+    }
+    if (tile > 0x7fffffffull) return llcms_fail(cms, LL_ERR_CAPACITY, what + "too many tiles for one launch");
+    J.N = N;
+    const KfSeg *d_segs = nullptr;
+    J.stage = [&]() { d_segs = (const KfSeg *)llcms_stage(cms, segs.data(), segs.size() * sizeof(KfSeg)); return d_segs != nullptr; };
+    J.assign = [&](const MmRec *d_recs, float4 *d_tp, int *d_keys, int *d_addcnt, hipStream_t st) {
+        hipLaunchKernelGGL(k_kf_assign, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt);
+    };
+    return mm_run(cms, J, added, dropped);
+}
+
+extern "C" int ll_cubemaps_insert_timing(const ll_cubemaps *cms, double *ms4, long long *counts3)
+{
+    if (!cms) return LL_ERR_ARG;
+    const LLMapMerge &G = llcms_merge_state(const_cast<ll_cubemaps *>(cms));
+    if (ms4) for (int k = 0; k < 4; ++k) ms4[k] = G.ins_ms[k];
+    if (counts3) for (int k = 0; k < 3; ++k) counts3[k] = G.ins_counts[k];
     return LL_OK;
 }
 
