@@ -763,6 +763,52 @@ int  ll_cubemaps_align(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops, int 
                        double *T_w7 /* [n_ops][7] out */, int *ran /* [n_ops], may be NULL */, ll_localize_fit *fit /* [n_ops], may be NULL */);
 int  ll_cubemaps_align_timing(const ll_cubemaps *cms, double *ms /* build, search+fit, evaluate+solve, fit */, long long *counts /* stack points, map points, residual blocks */);
 
+/* ---------------------------------------------------------------- measured information of a scan-to-map solve
+ * ll_pose_info describes the residual blocks rebuilt at the FINAL pose of a localisation or an alignment -- the association pass the
+ * fit record triggers, shared when both are asked for:
+ *   H, g     what ll_map_normal_equations reports there: the Gauss-Newton Hessian J^T J, 6 x 6 row-major, and the gradient J^T r over the
+ *            increment d = (w, dt) that ll_lm_solve_batch applies (q <- exp(w) (x) q with w the HALF-angle vector, t <- t + dt),
+ *            HuberLoss(0.1) applied.  The same device functions sum them (ll_map_neq.h), in the solve's own order.
+ *   rows     3 n_edge + n_plane
+ *   sigma2   (sq_edge + sq_plane) / (rows - 6), the residual variance in m^2 (ll_localize_fit's sums, loss not applied); 0 when rows <= 6
+ *   eig      the eigenvalues of H, ascending: cyclic Jacobi in f64 on one thread, 12 sweeps, the 15 rotations of a sweep in the order
+ *            (0,1) (0,2) .. (4,5) -- the bits depend on H alone.  eig[0] small against eig[5] says that one direction of the pose is
+ *            hardly constrained (a corridor, a straight road): the degeneracy test of Zhang, Kaess and Singh (ICRA 2016).
+ *   flags    bit 0: H is not finite (eig is then all zero); bit 1: rows <= 6
+ * WHAT IT IS: the information of the blocks at the final association.  It is right in SHAPE -- which directions the measurement fixes
+ * and which it does not -- and optimistic in SCALE: wrong associations and errors of the map are not modelled, and neighbouring
+ * residuals are far from independent.  ll_pg_edge_from_info's sigma is the caller's handle on the scale.
+ *   ll_cubemaps_localize_slots_info   ll_cubemaps_localize_slots with info [S] (may be NULL: then it IS that call).  info != NULL adds one
+ *            reduction launch (k_cms_info) behind the association pass at the final poses; the records come back in the copy that brings
+ *            poses and fit, so the synchronisations stay three.  Poses, ran and fit are the same bits with or without info; a sequence
+ *            that sat out or did not optimise gets an all-zero record; a view's record is the same bits alone and in any batch.
+ *   ll_cubemaps_align_info            ll_cubemaps_align with info [n_ops] (may be NULL): k_al_eval<false> once more at the final T over the
+ *            (op, chunk) workgroups, a one-wave sum per op in chunk order.  Still ONE synchronisation; n_outer = 0 gives the information
+ *            at T0.  An op behind a shut gate gets an all-zero record.
+ *   ll_drives_set_info / ll_drives_info   as ll_drives_fit: the last step's records [S], zeros for lanes that mapped, sat out or did not
+ *            optimise.  Off after create; while off no launch is added and no bit changes, and ll_drives_info gives zeros.  Not part of a
+ *            checkpoint.
+ *   ll_pg_edge_from_info   the square-root information of the pose-graph edge (i -> j, Z = P_i^-1 X) that a record stands for; plain host
+ *            arithmetic, no device, no context.  X_w7 is the solved pose H's increments refer to: the localised pose of the scan, or the
+ *            aligned T (the quaternion is normalised here).  The edge error e = [2 sgn(w_e) vec(q_e) ; t_e] of E = X^-1 X' is, to first
+ *            order in the increment d of X, e = M d with M = blkdiag(2 R(X)^T, R(X)^T); hence in the edge's own tangent
+ *                Lambda = M^-T H M^-1 / sigma^2 + floor I,    M^-1 = blkdiag(R(X) / 2, R(X)),
+ *            and S36 (row-major) is the upper-triangular Cholesky factor, S^T S = Lambda, for ll_pg_edge6.S.
+ *            sigma > 0: the caller's residual standard deviation in metres; sigma <= 0: sqrt(info->sigma2), LL_ERR_STATE if that is 0.
+ *            floor >= 0 is added to Lambda's diagonal and keeps a degenerate direction from making it singular.
+ *            LL_ERR_STATE: flags bit 0, or Lambda is not positive definite.  LL_ERR_ARG: a NULL pointer, a non-finite argument or entry of
+ *            X, a negative floor, a zero quaternion.                                                                                  */
+typedef struct { double H[36]; double g[6]; double eig[6]; double sigma2; int rows; int flags; } ll_pose_info;
+int  ll_cubemaps_localize_slots_info(ll_cubemaps *cms, const int *slots /* [S] */, const int *map_of /* [S], NULL: own map */,
+                                     double *pose_w7 /* [S][7] */, int *ran /* [S], may be NULL */, ll_localize_fit *fit /* [S], may be NULL */,
+                                     ll_pose_info *info /* [S], may be NULL */);
+int  ll_cubemaps_align_info(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops, int n_outer, const ll_lm_options *opt /* NULL: defaults */,
+                            double *T_w7 /* [n_ops][7] out */, int *ran /* [n_ops], may be NULL */, ll_localize_fit *fit /* [n_ops], may be NULL */,
+                            ll_pose_info *info /* [n_ops], may be NULL */);
+int  ll_drives_set_info(ll_drives *d, int on);
+int  ll_drives_info(ll_drives *d, ll_pose_info *info /* [S] */);
+int  ll_pg_edge_from_info(const ll_pose_info *info, const double *X_w7, double sigma, double floor, double S36[36]);
+
 /* ---------------------------------------------------------------- keyframes: the clouds every mapped frame contributed, kept on the device
  * A keyframe is what laserMapping adds to the map in its update (laserMapping.cpp:2103-2125): the frame's down-sized
  * laserCloudCornerStack and laserCloudSurfStack in the sensor frame -- what ll_cubemaps_download_cloud(q, 2 / 3) shows -- and the
@@ -933,7 +979,7 @@ int  ll_places_timing(ll_places *db, double *ms, long long *counts);
  *   ll_pg_default_options   Ceres' trust-region defaults as ll_lm_default_options has them, 50 LM iterations, 1000 PCG iterations per
  *                           LM iteration, eta 0.1 (PCG stops at |r| <= eta |g|).  Needs no device.
  *   ll_posegraphs_create    device buffers for calls of at most max_graphs graphs with max_nodes_total nodes and max_edges_total
- *                           edges in all (about 850 B per node, 1.1 KB per edge).
+ *                           edges in all (about 850 B per node, 1.35 KB per edge: the upload holds either edge type).
  *   ll_posegraphs_evaluate  cost[n_graphs], the robustified cost of every graph at poses_w7, and grad6[nodes][6], its gradient with
  *                           respect to the increments (zeros at fixed nodes).  Solves nothing: the chi-square of a candidate loop edge
  *                           before it is accepted, and the tests' window onto the Jacobians.
@@ -965,6 +1011,17 @@ int  ll_posegraphs_evaluate(ll_posegraphs *pg, int n_graphs, const int *node_off
 int  ll_posegraphs_solve(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, double *poses_w7,
                          const unsigned char *fixed, const ll_pg_edge *edges, const ll_pg_options *opt, ll_pg_record *rec);
 int  ll_posegraphs_timing(ll_posegraphs *pg, double *ms2, long long *counts3);
+/* The same two calls for edges with a FULL square-root information: r = S e with e = [2 sgn(w_e) vec(q_e) ; t_e] and S any finite 6 x 6
+ * matrix, row-major (ll_pg_edge_from_info gives an upper-triangular one; diag(sqrt_info) is ll_pg_edge's residual).  Everything else --
+ * the Huber scale, the slots, the node sums, PCG, the acceptance, the record, one workgroup per graph, one launch, no floating-point
+ * atomic, the same bits alone and in any batch, ONE synchronisation, the errors and their order -- is the text above: the kernel is the
+ * same template instantiated for this edge type, and ll_posegraphs_evaluate / _solve keep their own instantiation and bits.  A non-finite
+ * entry of S is LL_ERR_ARG (last_error names the graph and the edge); an all-zero S is allowed: an edge that says nothing.              */
+typedef struct { int i, j; double Z_w7[7]; double S[36]; double huber; } ll_pg_edge6;          /* i, j local to the graph */
+int  ll_posegraphs_evaluate6(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                             const unsigned char *fixed, const ll_pg_edge6 *edges, double *cost, double *grad6);
+int  ll_posegraphs_solve6(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, double *poses_w7,
+                          const unsigned char *fixed, const ll_pg_edge6 *edges, const ll_pg_options *opt, ll_pg_record *rec);
 
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),

@@ -30,6 +30,7 @@ namespace lightloam {
 struct PointXYZI { float x, y, z, intensity; };                      /* pcl::PointXYZI without the SSE padding */
 static_assert(sizeof(PointXYZI) == sizeof(ll_point), "layout");
 typedef PointXYZI PointType;                                          /* common.h:7 */
+typedef ll_pose_info PoseInfo;                                        /* the measured information of a scan-to-map solve (lightloam_hip.h) */
 
 typedef struct {                                                      /* common.h:20-31 */
     int index;
@@ -506,6 +507,15 @@ public:
         check(ll_cubemaps_localize_slots(cms_, slots.data(), map_of.empty() ? nullptr : map_of.data(), parameters.data(), ran.data(),
                                          want_fit ? fit.data() : nullptr));
     }
+    /* the same with the information of every solve at its final pose (ll_cubemaps_localize_slots_info): info [S], zeros for a sequence
+     * that sat out or did not optimise.  PoseGraphs::edge_from_info turns a record and the row's pose into an edge's weight */
+    void localize_slots(const std::vector<int> &slots, const std::vector<int> &map_of, bool want_fit, std::vector<PoseInfo> *info) {
+        if ((int)slots.size() != S || (!map_of.empty() && (int)map_of.size() != S)) throw Error(LL_ERR_ARG, "one slot (and one map) per sequence");
+        if (want_fit && fit.empty()) fit.assign((size_t)S, ll_localize_fit());
+        if (info) info->assign((size_t)S, PoseInfo());
+        check(ll_cubemaps_localize_slots_info(cms_, slots.data(), map_of.empty() ? nullptr : map_of.data(), parameters.data(), ran.data(),
+                                              want_fit ? fit.data() : nullptr, info ? info->data() : nullptr));
+    }
     /* the same from host clouds; an empty pair of clouds with run[q] == 0 (or both pointers NULL) skips sequence q */
     void process(const std::vector<const std::vector<PointXYZI> *> &corner_last, const std::vector<const std::vector<PointXYZI> *> &surf_last) {
         if ((int)corner_last.size() != S || (int)surf_last.size() != S) throw Error(LL_ERR_ARG, "one cloud pair per sequence");
@@ -577,6 +587,17 @@ public:
                     std::vector<ll_localize_fit> *fit = nullptr, const ll_lm_options *opt = nullptr) {
         const int rc = align_into(cms_, ops, n_outer, T, ran, fit, opt);
         if (rc != LL_OK) check(rc);
+    }
+    /* the same with the information of every op at its final T (ll_cubemaps_align_info): info [n_ops] */
+    void align_maps(const std::vector<ll_merge_op> &ops, int n_outer, std::vector<double> *T, std::vector<int> *ran,
+                    std::vector<ll_localize_fit> *fit, std::vector<PoseInfo> *info, const ll_lm_options *opt = nullptr) {
+        if (!T) check(LL_ERR_ARG);
+        T->assign(7 * ops.size(), 0.0);
+        if (ran) ran->assign(ops.size(), 0);
+        if (fit) fit->assign(ops.size(), ll_localize_fit());
+        if (info) info->assign(ops.size(), PoseInfo());
+        check(ll_cubemaps_align_info(cms_, ops.data(), (int)ops.size(), n_outer, opt, T->data(), ran ? ran->data() : nullptr,
+                                     fit ? fit->data() : nullptr, info ? info->data() : nullptr));
     }
     /* the same on a borrowed handle (Drives::cubemaps(), between two steps); returns the status */
     static int align_into(ll_cubemaps *cms, const std::vector<ll_merge_op> &ops, int n_outer, std::vector<double> *T, std::vector<int> *ran = nullptr,
@@ -764,6 +785,14 @@ public:
         check(ll_drives_fit(d_, f.data()));
         return f;
     }
+    /* the localising lanes' steps also fill information records (off after create; not part of a checkpoint) */
+    void set_info(bool on) { check(ll_drives_set_info(d_, on ? 1 : 0)); }
+    /* the last step's information records [S]: zeros for lanes that mapped, sat out or did not optimise, and while set_info is off */
+    std::vector<PoseInfo> info() {
+        std::vector<PoseInfo> f((size_t)S, PoseInfo());
+        check(ll_drives_info(d_, f.data()));
+        return f;
+    }
     /* lane q's mapped pose of the last step, as the trajectory file takes it */
     WorldPose mapped_pose(int q) const {
         WorldPose w;
@@ -883,11 +912,13 @@ private:
 
 /* Pose graphs (ll_posegraphs): many independent SE(3) graphs optimised side by side, one workgroup per graph.  A Graph holds poses
  * [N][7] (pose_w7, world from body), edges whose i, j index its own poses and whose Z measures P_i^-1 P_j, and an optional fixed flag
- * per node (empty: node 0 is fixed).  sqrt_info is the caller's choice: nothing in the library produces a covariance.  Destroy it
- * before its Context. */
+ * per node (empty: node 0 is fixed).  An odometry edge's sqrt_info is the caller's choice; the weight of a loop or session edge can be
+ * MEASURED: edge_from_info turns the PoseInfo of the localisation or alignment behind it into a full 6 x 6 square-root information
+ * (Graph6 / edge6).  Destroy it before its Context. */
 class PoseGraphs {
 public:
     struct Graph { std::vector<double> poses; std::vector<ll_pg_edge> edges; std::vector<unsigned char> fixed; };
+    struct Graph6 { std::vector<double> poses; std::vector<ll_pg_edge6> edges; std::vector<unsigned char> fixed; };   /* full-information edges */
     struct Evaluation { std::vector<double> cost; std::vector<std::vector<double>> grad; };   /* [graphs], [graphs][N * 6] */
     PoseGraphs(Context &c, int max_graphs, int max_nodes_total, int max_edges_total) {
         c.check(ll_posegraphs_create(c.get(), max_graphs, max_nodes_total, max_edges_total, &pg_));
@@ -914,9 +945,51 @@ public:
         for (int k = 0; k < 3; ++k) { e.sqrt_info[k] = sqrt_info_rot; e.sqrt_info[3 + k] = sqrt_info_trans; }
         return e;
     }
+    /* an edge with the full square-root information S [36] (row-major, r = S e) */
+    static ll_pg_edge6 edge6(int i, int j, const double Z[7], const double S[36], double huber = 0.0) {
+        ll_pg_edge6 e;
+        e.i = i; e.j = j; e.huber = huber;
+        for (int k = 0; k < 7; ++k) e.Z_w7[k] = Z[k];
+        for (int k = 0; k < 36; ++k) e.S[k] = S[k];
+        return e;
+    }
+    /* a diagonal edge as a full one: S = diag(sqrt_info) */
+    static ll_pg_edge6 edge6(const ll_pg_edge &d) {
+        ll_pg_edge6 e;
+        e.i = d.i; e.j = d.j; e.huber = d.huber;
+        for (int k = 0; k < 7; ++k) e.Z_w7[k] = d.Z_w7[k];
+        for (int k = 0; k < 36; ++k) e.S[k] = (k % 7 == 0) ? d.sqrt_info[k / 7] : 0.0;
+        return e;
+    }
+    /* ll_pg_edge_from_info: S [36] of the edge (i, j, Z = P_i^-1 X) whose measurement the record describes; X: the localised pose or the
+     * aligned T; sigma: the residual standard deviation in metres (<= 0: sqrt(info.sigma2)); floor: added to the information's diagonal */
+    static void edge_from_info(const PoseInfo &info, const double X_w7[7], double sigma, double floor, double S[36]) {
+        const int rc = ll_pg_edge_from_info(&info, X_w7, sigma, floor, S);
+        if (rc != LL_OK) throw Error(rc, rc == LL_ERR_STATE ? "edge_from_info: the record is not finite, sigma2 is 0 with sigma <= 0, or the information is not positive definite"
+                                                            : "edge_from_info: a non-finite argument, a negative floor or a zero quaternion");
+    }
     /* the robustified cost of every graph and its gradient per node (6 each, zeros at fixed nodes); solves nothing */
+    Evaluation evaluate(const std::vector<Graph6> &graphs) {
+        pack(graphs, edges6_);
+        Evaluation ev;
+        ev.cost.resize(graphs.size());
+        std::vector<double> grad(poses_.size() / 7 * 6);
+        check(ll_posegraphs_evaluate6(pg_, (int)graphs.size(), node_off_.data(), edge_off_.data(), poses_.data(), fixed_ptr(), edges6_.data(),
+                                      ev.cost.data(), grad.data()));
+        for (size_t g = 0; g < graphs.size(); ++g)
+            ev.grad.emplace_back(grad.begin() + (size_t)node_off_[g] * 6, grad.begin() + (size_t)node_off_[g + 1] * 6);
+        return ev;
+    }
+    std::vector<ll_pg_record> solve(std::vector<Graph6> &graphs, const ll_pg_options *opt = nullptr) {
+        pack(graphs, edges6_);
+        std::vector<ll_pg_record> rec(graphs.size());
+        check(ll_posegraphs_solve6(pg_, (int)graphs.size(), node_off_.data(), edge_off_.data(), poses_.data(), fixed_ptr(), edges6_.data(), opt, rec.data()));
+        for (size_t g = 0; g < graphs.size(); ++g)
+            std::copy(poses_.begin() + (size_t)node_off_[g] * 7, poses_.begin() + (size_t)node_off_[g + 1] * 7, graphs[g].poses.begin());
+        return rec;
+    }
     Evaluation evaluate(const std::vector<Graph> &graphs) {
-        pack(graphs);
+        pack(graphs, edges_);
         Evaluation ev;
         ev.cost.resize(graphs.size());
         std::vector<double> grad(poses_.size() / 7 * 6);
@@ -928,7 +1001,7 @@ public:
     }
     /* optimises every graph's poses in place; one record per graph */
     std::vector<ll_pg_record> solve(std::vector<Graph> &graphs, const ll_pg_options *opt = nullptr) {
-        pack(graphs);
+        pack(graphs, edges_);
         std::vector<ll_pg_record> rec(graphs.size());
         check(ll_posegraphs_solve(pg_, (int)graphs.size(), node_off_.data(), edge_off_.data(), poses_.data(), fixed_ptr(), edges_.data(), opt, rec.data()));
         for (size_t g = 0; g < graphs.size(); ++g)
@@ -946,9 +1019,10 @@ private:
         o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
     }
     /* the ragged packing: graphs back to back; a graph without flags gets node 0 fixed */
-    void pack(const std::vector<Graph> &graphs) {
+    template <class G, class E>
+    void pack(const std::vector<G> &graphs, std::vector<E> &edges_) {
         node_off_.assign(1, 0); edge_off_.assign(1, 0); poses_.clear(); edges_.clear(); fixed_.clear();
-        for (const Graph &g : graphs) {
+        for (const G &g : graphs) {
             if (g.poses.size() % 7 != 0) throw Error(LL_ERR_ARG, "poses are 7 doubles each");
             const size_t n = g.poses.size() / 7;
             if (!g.fixed.empty() && g.fixed.size() != n) throw Error(LL_ERR_ARG, "one fixed flag per node");
@@ -964,6 +1038,7 @@ private:
     std::vector<int> node_off_, edge_off_;
     std::vector<double> poses_;
     std::vector<ll_pg_edge> edges_;
+    std::vector<ll_pg_edge6> edges6_;
     std::vector<unsigned char> fixed_;
 };
 

@@ -41,6 +41,8 @@ EXPORTS = [
     "ll_cubemaps_layout", "ll_cubemaps_import", "ll_cubemap_layout", "ll_cubemap_import",
     "ll_drives_save_size", "ll_drives_save", "ll_drives_restore", "ll_checkpoint_describe",
     "ll_cubemaps_localize_slots", "ll_drives_set_localize", "ll_drives_fit",
+    "ll_cubemaps_localize_slots_info", "ll_cubemaps_align_info", "ll_drives_set_info", "ll_drives_info", "ll_pg_edge_from_info",
+    "ll_posegraphs_evaluate6", "ll_posegraphs_solve6",
     "ll_cubemaps_merge", "ll_cubemaps_merge_timing",
     "ll_cubemaps_align", "ll_cubemaps_align_timing",
     "ll_debug_sort_pairs", "ll_debug_exscan", "ll_debug_voxel_segments",
@@ -88,6 +90,12 @@ class PairInfo(C.Structure):
 class LocalizeFit(C.Structure):
     """ll_localize_fit: how a localised pose fits the frozen map (residual blocks, Huber cost, sums of squared residuals)"""
     _fields_ = [("n_edge", C.c_int), ("n_plane", C.c_int), ("cost", C.c_double), ("sq_edge", C.c_double), ("sq_plane", C.c_double)]
+
+
+class PoseInfo(C.Structure):
+    """ll_pose_info: the Gauss-Newton information of a scan-to-map solve at its final pose (H 6 x 6 row-major and g over the
+    increment (half-angle vector, translation), its eigenvalues ascending, the residual variance, rows, flags)"""
+    _fields_ = [("H", C.c_double * 36), ("g", C.c_double * 6), ("eig", C.c_double * 6), ("sigma2", C.c_double), ("rows", C.c_int), ("flags", C.c_int)]
 
 
 class MergeOp(C.Structure):
@@ -158,6 +166,13 @@ def load_library():
         _lib.ll_drives_save.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
         _lib.ll_drives_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
         _lib.ll_cubemaps_localize_slots.argtypes = [C.c_void_p] * 6
+        _lib.ll_cubemaps_localize_slots_info.argtypes = [C.c_void_p] * 7
+        _lib.ll_cubemaps_align_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+        _lib.ll_drives_set_info.argtypes = [C.c_void_p, C.c_int]
+        _lib.ll_drives_info.argtypes = [C.c_void_p] * 2
+        _lib.ll_pg_edge_from_info.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
+        _lib.ll_posegraphs_evaluate6.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        _lib.ll_posegraphs_solve6.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         _lib.ll_drives_set_localize.argtypes = [C.c_void_p] * 3
         _lib.ll_drives_fit.argtypes = [C.c_void_p] * 2
         _lib.ll_checkpoint_describe.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
@@ -994,10 +1009,11 @@ class CubeMaps:
         self._ck(self.lib.ll_cubemaps_process_slots(self.h, _ptr(s), _ptr(p), _ptr(ran)))
         return p, ran.astype(bool)
 
-    def localize_slots(self, pose_w, slots, map_of=None, fit=True):
+    def localize_slots(self, pose_w, slots, map_of=None, fit=True, info=False):
         """A read-only frame: sequence q localises the extracted slot slots[q] (-1: it sits out) against map map_of[q] (None: its
         own) from the guess pose_w[q]; no map changes -> (poses [S, 7], ran [S] bool, fit: a LocalizeFit array [S], or None with
-        fit=False -- then the extra association pass and the reduction are not launched)"""
+        fit=False -- then the extra association pass and the reduction are not launched).  info=True appends a PoseInfo array [S]:
+        the information of every solve at its final pose (edge_from_info turns a record into a pose-graph edge's weight)"""
         p, ran = self._poses(pose_w)
         s = np.ascontiguousarray(slots, np.int32)
         if s.shape != (self.n_seq,):
@@ -1006,9 +1022,17 @@ class CubeMaps:
         if m is not None and m.shape != (self.n_seq,):
             raise ValueError("map_of must have one entry per sequence")
         rec = (LocalizeFit * self.n_seq)() if fit else None
+        if info:
+            return self._localize_slots_info(s, m, p, ran, rec)
         self._ck(self.lib.ll_cubemaps_localize_slots(self.h, s.ctypes.data, None if m is None else m.ctypes.data, p.ctypes.data,
                                                      ran.ctypes.data, C.addressof(rec) if fit else None))
         return p, ran.astype(bool), rec
+
+    def _localize_slots_info(self, s, m, p, ran, rec):
+        inf = (PoseInfo * self.n_seq)()
+        self._ck(self.lib.ll_cubemaps_localize_slots_info(self.h, s.ctypes.data, None if m is None else m.ctypes.data, p.ctypes.data,
+                                                          ran.ctypes.data, None if rec is None else C.addressof(rec), C.addressof(inf)))
+        return p, ran.astype(bool), rec, inf
 
     def process(self, pose_w, corners, surfs):
         """corners / surfs: one (n, 4) float32 cloud per sequence, None for a sequence that does not run"""
@@ -1161,12 +1185,13 @@ class CubeMaps:
         self._ck(self.lib.ll_cubemaps_insert_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
         return tuple(ms), tuple(int(c) for c in cnt)
 
-    def align(self, ops, n_outer=2, opt=None, fit=True):
+    def align(self, ops, n_outer=2, opt=None, fit=True, info=False):
         """ops: a list of (dst, src, guess_w7) -- the rigid transform that takes map src's world frame into map dst's, by
         laserMapping's scan-to-map optimisation over the whole of both maps from the guess (local registration: the guess must lie
         inside the basin of the 1 m association radius) -> (T [n_ops, 7], ran [n_ops] bool, fit: a LocalizeFit array [n_ops], or
         None with fit=False -- then the extra pass at the final poses is not launched).  n_outer = 0 scores the guess.  No map
-        changes; everything on the device; one synchronisation whatever len(ops) and n_outer are"""
+        changes; everything on the device; one synchronisation whatever len(ops) and n_outer are.  info=True appends a PoseInfo
+        array [n_ops]: the information of every op at its final T"""
         rec = (MergeOp * max(len(ops), 1))()
         for i, (dst, src, pose) in enumerate(ops):
             p = np.ascontiguousarray(pose, np.float64).reshape(7)
@@ -1175,6 +1200,11 @@ class CubeMaps:
                 rec[i].T_w7[k] = p[k]
         T = np.zeros((len(ops), 7)); ran = np.zeros(len(ops), np.int32)
         out = (LocalizeFit * max(len(ops), 1))() if fit else None
+        if info:
+            inf = (PoseInfo * max(len(ops), 1))()
+            self._ck(self.lib.ll_cubemaps_align_info(self.h, C.addressof(rec), len(ops), int(n_outer), None if opt is None else C.addressof(opt),
+                                                     T.ctypes.data, ran.ctypes.data, C.addressof(out) if fit else None, C.addressof(inf)))
+            return T, ran.astype(bool), out, inf
         self._ck(self.lib.ll_cubemaps_align(self.h, C.addressof(rec), len(ops), int(n_outer), None if opt is None else C.addressof(opt),
                                             T.ctypes.data, ran.ctypes.data, C.addressof(out) if fit else None))
         return T, ran.astype(bool), out
@@ -1382,6 +1412,11 @@ class PgEdge(C.Structure):
     _fields_ = [("i", C.c_int), ("j", C.c_int), ("Z_w7", C.c_double * 7), ("sqrt_info", C.c_double * 6), ("huber", C.c_double)]
 
 
+class PgEdge6(C.Structure):
+    """ll_pg_edge6: the same edge with a full square-root information: r = S e, S 6 x 6 row-major, any finite matrix"""
+    _fields_ = [("i", C.c_int), ("j", C.c_int), ("Z_w7", C.c_double * 7), ("S", C.c_double * 36), ("huber", C.c_double)]
+
+
 class PgOptions(C.Structure):
     _fields_ = [("max_lm_iterations", C.c_int), ("max_pcg_iterations", C.c_int), ("eta", C.c_double), ("initial_radius", C.c_double),
                 ("max_radius", C.c_double), ("min_radius", C.c_double), ("min_relative_decrease", C.c_double),
@@ -1395,6 +1430,7 @@ class PgRecord(C.Structure):
 
 
 PG_EDGE = np.dtype([("i", "i4"), ("j", "i4"), ("Z_w7", "f8", (7,)), ("sqrt_info", "f8", (6,)), ("huber", "f8")])     # PgEdge as a numpy record
+PG_EDGE6 = np.dtype([("i", "i4"), ("j", "i4"), ("Z_w7", "f8", (7,)), ("S", "f8", (6, 6)), ("huber", "f8")])          # PgEdge6 as a numpy record
 PG_TERMINATION = {0: "gradient", 1: "function", 2: "parameter", 3: "iterations", 4: "radius", 5: "non-finite"}
 
 
@@ -1426,13 +1462,47 @@ def relative_pose(Pi, Pj):
 
 
 def pg_edges(edges):
-    """a PG_EDGE record array from one, or from a list of (i, j, Z[7], sqrt_info[6] or scalar, huber) tuples"""
-    if isinstance(edges, np.ndarray) and edges.dtype == PG_EDGE:
+    """a PG_EDGE record array from one, or from a list of (i, j, Z[7], sqrt_info[6] or scalar, huber) tuples.  If the sqrt_info of
+    any tuple is a 6 x 6 array, a PG_EDGE6 record array comes back, the diagonal weights of the others promoted to diag(sqrt_info)"""
+    if isinstance(edges, np.ndarray) and edges.dtype in (PG_EDGE, PG_EDGE6):
         return np.ascontiguousarray(edges).reshape(-1)
+    if any(np.ndim(e[3]) == 2 for e in edges):
+        out = np.zeros(len(edges), PG_EDGE6)
+        for k, e in enumerate(edges):
+            w = np.asarray(e[3], np.float64)
+            S = w.reshape(6, 6) if w.ndim == 2 else np.diag(np.broadcast_to(w, (6,)))
+            out[k] = (int(e[0]), int(e[1]), np.asarray(e[2], np.float64), S, float(e[4]) if len(e) > 4 else 0.0)
+        return out
     out = np.zeros(len(edges), PG_EDGE)
     for k, e in enumerate(edges):
         out[k] = (int(e[0]), int(e[1]), np.asarray(e[2], np.float64), np.broadcast_to(np.asarray(e[3], np.float64), (6,)), float(e[4]) if len(e) > 4 else 0.0)
     return out
+
+
+def pg_edges6(edges):
+    """a PG_EDGE6 record array from what pg_edges gives: full edges as they are, diagonal ones with S = diag(sqrt_info)"""
+    e = pg_edges(edges)
+    if e.dtype == PG_EDGE6:
+        return e
+    out = np.zeros(len(e), PG_EDGE6)
+    out["i"] = e["i"]; out["j"] = e["j"]; out["Z_w7"] = e["Z_w7"]; out["huber"] = e["huber"]
+    for k in range(6):
+        out["S"][:, k, k] = e["sqrt_info"][:, k]
+    return out
+
+
+def edge_from_info(info, X, sigma=0.0, floor=0.0):
+    """ll_pg_edge_from_info: the upper-triangular S [6, 6] with S^T S = the information, in the tangent of a pose-graph edge
+    (i, j, Z = relative_pose(P_i, X)), of the solve the PoseInfo record describes; X: the localised pose or the aligned T.
+    sigma: the residual standard deviation in metres (<= 0: sqrt(info.sigma2)); floor: added to the information's diagonal.
+    Host arithmetic: needs no device"""
+    x = np.ascontiguousarray(X, np.float64).reshape(7)
+    S = np.zeros((6, 6))
+    rc = load_library().ll_pg_edge_from_info(C.addressof(info), x.ctypes.data, float(sigma), float(floor), S.ctypes.data)
+    if rc != LL_OK:
+        raise LightLoamError(rc, "edge_from_info: the record is not finite, sigma2 is 0 with sigma <= 0, or the information is not positive definite"
+                             if rc == -7 else "edge_from_info: a non-finite argument, a negative floor or a zero quaternion")
+    return S
 
 
 class PoseGraphs:
@@ -1465,7 +1535,8 @@ class PoseGraphs:
 
     @staticmethod
     def _pack(graphs):
-        """the ragged packing: (node_off, edge_off, poses [Nt, 7], fixed [Nt] uint8, edges [Et] PG_EDGE)"""
+        """the ragged packing: (node_off, edge_off, poses [Nt, 7], fixed [Nt] uint8, edges [Et] PG_EDGE -- or PG_EDGE6, the diagonal
+        edges promoted, if any edge of the call has a 6 x 6 sqrt_info)"""
         node_off = [0]; edge_off = [0]; poses = []; fixed = []; edges = []
         for g in graphs:
             p = np.ascontiguousarray(g[0], np.float64).reshape(-1, 7)
@@ -1478,6 +1549,8 @@ class PoseGraphs:
                 raise ValueError("fixed must have one entry per node")
             poses.append(p); fixed.append(f); edges.append(e)
             node_off.append(node_off[-1] + len(p)); edge_off.append(edge_off[-1] + len(e))
+        if any(e.dtype == PG_EDGE6 for e in edges):
+            edges = [pg_edges6(e) for e in edges]
         cat = lambda parts, empty: np.ascontiguousarray(np.concatenate(parts)) if parts else empty
         return (np.array(node_off, np.int32), np.array(edge_off, np.int32), cat(poses, np.zeros((0, 7))), cat(fixed, np.zeros(0, np.uint8)),
                 cat(edges, np.zeros(0, PG_EDGE)))
@@ -1486,15 +1559,17 @@ class PoseGraphs:
         """(cost [G], [grad [N_g, 6] per graph]): the robustified cost and its gradient per increment (zeros at fixed nodes)"""
         no, eo, poses, fixed, edges = self._pack(graphs)
         cost = np.zeros(len(graphs)); grad = np.zeros((len(poses), 6))
-        self._ck(self.lib.ll_posegraphs_evaluate(self.h, len(graphs), _ptr(no), _ptr(eo), _ptr(poses), _ptr(fixed), _ptr(edges), _ptr(cost), _ptr(grad)))
+        fn = self.lib.ll_posegraphs_evaluate6 if edges.dtype == PG_EDGE6 else self.lib.ll_posegraphs_evaluate
+        self._ck(fn(self.h, len(graphs), _ptr(no), _ptr(eo), _ptr(poses), _ptr(fixed), _ptr(edges), _ptr(cost), _ptr(grad)))
         return cost, [grad[no[g]:no[g + 1]].copy() for g in range(len(graphs))]
 
     def solve(self, graphs, options=None):
         """([poses [N_g, 7] per graph], records [G] of PgRecord): the inputs are not modified.  options: a PgOptions (pg_options(...))"""
         no, eo, poses, fixed, edges = self._pack(graphs)
         rec = (PgRecord * max(len(graphs), 1))()
-        self._ck(self.lib.ll_posegraphs_solve(self.h, len(graphs), _ptr(no), _ptr(eo), _ptr(poses), _ptr(fixed), _ptr(edges),
-                                              None if options is None else C.addressof(options), C.addressof(rec)))
+        fn = self.lib.ll_posegraphs_solve6 if edges.dtype == PG_EDGE6 else self.lib.ll_posegraphs_solve
+        self._ck(fn(self.h, len(graphs), _ptr(no), _ptr(eo), _ptr(poses), _ptr(fixed), _ptr(edges),
+                    None if options is None else C.addressof(options), C.addressof(rec)))
         return [poses[no[g]:no[g + 1]].copy() for g in range(len(graphs))], list(rec)[:len(graphs)]
 
     def timing(self):
@@ -1607,6 +1682,16 @@ class Drives:
         """the last step's LocalizeFit records [S]: zeros for lanes that mapped, sat out or did not optimise"""
         rec = (LocalizeFit * self.n_lanes)()
         self._ck(self.lib.ll_drives_fit(self.h, C.addressof(rec)))
+        return rec
+
+    def set_info(self, on=True):
+        """the localising lanes' steps also fill PoseInfo records (info()); off after create, not part of a checkpoint"""
+        self._ck(self.lib.ll_drives_set_info(self.h, 1 if on else 0))
+
+    def info(self):
+        """the last step's PoseInfo records [S]: zeros for lanes that mapped, sat out or did not optimise, and while set_info is off"""
+        rec = (PoseInfo * self.n_lanes)()
+        self._ck(self.lib.ll_drives_info(self.h, C.addressof(rec)))
         return rec
 
     def registered(self, lane):

@@ -212,6 +212,8 @@ LL_HIDDEN int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double
                                       size_t extra_bytes, ScanHdr *hdr_out);
 /* the same for ll_cubemaps_localize_slots (map_of [S], read for the running sequences; fit [S], rows of the running sequences) */
 LL_HIDDEN int llcms_localize_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit,
-                                       const void *extra_dev, void *extra_host, size_t extra_bytes, ScanHdr *hdr_out);
+                                       ll_pose_info *info /* [S], may be NULL: rows of the running sequences */, const void *extra_dev, void *extra_host, size_t extra_bytes, ScanHdr *hdr_out);
 /* ll_localize.hip: one k_cms_fit workgroup per view; view v's record goes to d_fit[(views[v].pose - d_pose0) / 7] */
 LL_HIDDEN void ll_launch_cms_fit(const LLMapView *d_views, int n_views, const double *d_pose0, ll_localize_fit *d_fit, hipStream_t st);
+/* behind it: one k_cms_info workgroup per view; the record goes to d_info[the same index] and reads d_fit[it] */
+LL_HIDDEN void ll_launch_cms_info(const LLMapView *d_views, int n_views, const double *d_pose0, const ll_localize_fit *d_fit, ll_pose_info *d_info, hipStream_t st);

@@ -143,6 +143,7 @@ __global__ __launch_bounds__(256) void k_cms_assign(const CmsAssign *recs, const
  * one has synchronised, so no copy of it can still be in flight; a table that does not fit moves to a larger arena (the old one
  * is kept until destroy: copies and kernels of this call may still read it) */
 static_assert(sizeof(ll_localize_fit) == 4 * sizeof(double), "the fit records lie behind the poses as 4 doubles each");
+static_assert(sizeof(ll_pose_info) == 50 * sizeof(double), "the information records lie behind the fit records as 50 doubles each");
 struct CmsArena { unsigned char *h = nullptr, *d = nullptr; size_t cap = 0, used = 0; };
 
 struct ll_cubemaps {
@@ -159,6 +160,7 @@ struct ll_cubemaps {
     int *d_addcnt = nullptr, *d_nout = nullptr, *d_bbox = nullptr;
     double *d_pose = nullptr;                     /* [S][7]: the pose every stage of a frame reads */
     ll_localize_fit *d_fit = nullptr;             /* [S], right behind d_pose: one copy brings both to the host */
+    ll_pose_info *d_info = nullptr;               /* [S], right behind d_fit: the same copy brings them too */
     LLVoxWork W[2], WS;                           /* per cloud type: prepare's and update's filters; WS: the by-cube sort */
     CmsArena ar[2]; int par = 0;
     LLMapExport X;                                /* ll_cubemaps_export's staging buffer and events */
@@ -279,8 +281,8 @@ extern "C" int ll_cubemaps_create(ll_ctx *ctx, int n_seq, float line_res, float 
         ok = ok && cms_alloc(cms, cms->d_work[w], S * cap_from_map) && cms_alloc(cms, cms->d_out[w], S * cap_from_map);
     }
     ok = ok && cms_alloc(cms, cms->d_addcnt, S * 2 * (CM_N + 1)) && cms_alloc(cms, cms->d_nout, 4) && cms_alloc(cms, cms->d_bbox, S * 12) &&
-         cms_alloc(cms, cms->d_pose, S * 7 + S * (sizeof(ll_localize_fit) / sizeof(double)));
-    if (ok) cms->d_fit = (ll_localize_fit *)(cms->d_pose + S * 7);
+         cms_alloc(cms, cms->d_pose, S * 7 + S * (sizeof(ll_localize_fit) / sizeof(double)) + S * (sizeof(ll_pose_info) / sizeof(double)));
+    if (ok) { cms->d_fit = (ll_localize_fit *)(cms->d_pose + S * 7); cms->d_info = (ll_pose_info *)(cms->d_fit + S); }
     for (int w = 0; w < 2 && ok; ++w) {
         unsigned char *p = nullptr;
         ok = cms_alloc(cms, p, ll_vox_work_bytes((int)(S * cap_from_map), (int)(S * 125)));
@@ -395,8 +397,10 @@ static int cms_prepare_finish(ll_cubemaps *cms, const std::vector<int> &run, con
 
 /* optimize (:1822-2100) for the prepared sequences: the :1822 gate, 2 x {knn, compact, LM}, all poses back in ONE synchronisation.
  * fit != nullptr: the residual blocks once more at the final poses and k_cms_fit (ll_localize.hip); the records come back in the
- * poses' copy -- rows of the running sequences, zeros where the gate was shut */
-static int cms_optimize(ll_cubemaps *cms, const std::vector<int> &run, double *pose_w7, int *ran, ll_localize_fit *fit, bool may_vote)
+ * poses' copy -- rows of the running sequences, zeros where the gate was shut.  info != nullptr: the same pass, k_cms_fit (whose
+ * squares the record needs) and k_cms_info behind it; the records ride in the same copy */
+static int cms_optimize(ll_cubemaps *cms, const std::vector<int> &run, double *pose_w7, int *ran, ll_localize_fit *fit, bool may_vote,
+                        ll_pose_info *info = nullptr)
 {
     hipStream_t st = cms->ctx->stream;
     const int R = (int)run.size();
@@ -409,6 +413,7 @@ static int cms_optimize(ll_cubemaps *cms, const std::vector<int> &run, double *p
     }
     const int O = (int)opt_r.size();
     if (fit) for (int r = 0; r < R; ++r) std::memset(fit + run[r], 0, sizeof(ll_localize_fit));
+    if (info) for (int r = 0; r < R; ++r) std::memset(info + run[r], 0, sizeof(ll_pose_info));
     if (O > 0) {
         std::vector<LLMapView> views;
         std::vector<int4> blk;
@@ -431,19 +436,22 @@ static int cms_optimize(ll_cubemaps *cms, const std::vector<int> &run, double *p
             if (n_vote > 0) ll_map_launch_vote(d_views, O, max_vote_stk, st);      /* the views without ctr return at once */
             hipLaunchKernelGGL(k_cms_lm, dim3(O), dim3(256), 0, st, d_views, o);
         }
-        if (fit) {                                                                 /* the blocks at the final pose, reduced */
+        if (fit || info) {                                                         /* the blocks at the final pose, reduced */
             if (!blk.empty()) hipLaunchKernelGGL(k_cms_knn, dim3((unsigned)blk.size()), dim3(LL_KNNB), 0, st, d_views, d_blk);
             hipLaunchKernelGGL(k_cms_compact, dim3(2 * O), dim3(256), 0, st, d_views);
             ll_launch_cms_fit(d_views, O, cms->d_pose, cms->d_fit, st);
+            if (info) ll_launch_cms_info(d_views, O, cms->d_pose, cms->d_fit, cms->d_info, st);
         }
         CMS_HIP(hipGetLastError());
-        const size_t pose_bytes = (size_t)cms->S * 7 * sizeof(double), bytes = pose_bytes + (fit ? (size_t)cms->S * sizeof(ll_localize_fit) : 0);
+        const size_t pose_bytes = (size_t)cms->S * 7 * sizeof(double), fit_bytes = (size_t)cms->S * sizeof(ll_localize_fit);
+        const size_t bytes = pose_bytes + (fit || info ? fit_bytes : 0) + (info ? (size_t)cms->S * sizeof(ll_pose_info) : 0);
         double *pin = (double *)ll_pinned_scratch(bytes);
         if (!pin) { cms->err = "no page-locked scratch"; return LL_ERR_HIP; }
         CMS_HIP(hipMemcpyAsync(pin, cms->d_pose, bytes, hipMemcpyDeviceToHost, st));
         rc = cms_sync(cms); if (rc) return rc;
         for (int k = 0; k < O; ++k) std::memcpy(pose_w7 + 7 * run[opt_r[k]], pin + 7 * run[opt_r[k]], 7 * sizeof(double));
         if (fit) for (int k = 0; k < O; ++k) std::memcpy(fit + run[opt_r[k]], (const unsigned char *)pin + pose_bytes + (size_t)run[opt_r[k]] * sizeof(ll_localize_fit), sizeof(ll_localize_fit));
+        if (info) for (int k = 0; k < O; ++k) std::memcpy(info + run[opt_r[k]], (const unsigned char *)pin + pose_bytes + fit_bytes + (size_t)run[opt_r[k]] * sizeof(ll_pose_info), sizeof(ll_pose_info));
     }
     int bad = -1;
     for (int r = 0, k = 0; r < R; ++r) {
@@ -675,7 +683,8 @@ extern "C" int ll_cubemaps_process(ll_cubemaps *cms, const ll_point *const *corn
  * prepare and optimize, no update.  Nothing of any ll_cubemap is written: the valid list is a local, the workspace is the
  * reader's ll_map.  Every refusal comes before the first launch. */
 static int cms_localize(ll_cubemaps *cms, const std::vector<int> &run, const int *map_of, const std::vector<const float4 *> src[2],
-                        const std::vector<int> n_in[2], const std::vector<int> &flat_slot, double *pose_w7, int *ran, ll_localize_fit *fit)
+                        const std::vector<int> n_in[2], const std::vector<int> &flat_slot, double *pose_w7, int *ran, ll_localize_fit *fit,
+                        ll_pose_info *info)
 {
     const int R = (int)run.size();
     int rc = cms_check_scans(cms, run, n_in); if (rc) return rc;
@@ -690,7 +699,7 @@ static int cms_localize(ll_cubemaps *cms, const std::vector<int> &run, const int
         n_from[0][r] = nf[0]; n_from[1][r] = nf[1];
     }
     rc = cms_prepare_finish(cms, run, src, n_in, flat_slot, ops, n_from); if (rc) return rc;
-    return cms_optimize(cms, run, pose_w7, ran, fit, false);
+    return cms_optimize(cms, run, pose_w7, ran, fit, false, info);
 }
 
 /* the maps the running sequences read: inside 0..S-1 and usable */
@@ -709,7 +718,14 @@ static int cms_check_read_maps(ll_cubemaps *cms, const std::vector<int> &run, co
 
 extern "C" int ll_cubemaps_localize_slots(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit)
 {
+    return ll_cubemaps_localize_slots_info(cms, slots, map_of, pose_w7, ran, fit, nullptr);
+}
+
+extern "C" int ll_cubemaps_localize_slots_info(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit,
+                                               ll_pose_info *info)
+{
     if (!cms || !slots || !pose_w7) return LL_ERR_ARG;
+    if (info) std::memset(info, 0, (size_t)cms->S * sizeof(ll_pose_info));          /* also for a sequence that sits out, and when the call is refused */
     ll_ctx *ctx = cms->ctx;
     std::vector<int> run;
     std::vector<char> used(ctx->p.batch, 0);
@@ -744,7 +760,7 @@ extern "C" int ll_cubemaps_localize_slots(ll_cubemaps *cms, const int *slots, co
         n_in[1][r] = h[r].n_less_flat;
         if (h[r].lf_strided) { src[1][r] = nullptr; flat[r] = s; } else src[1][r] = V.lflat + (size_t)s * V.LFS;
     }
-    return cms_localize(cms, run, map_of, src, n_in, flat, pose_w7, ran, fit);
+    return cms_localize(cms, run, map_of, src, n_in, flat, pose_w7, ran, fit, info);
 }
 
 static int cms_seq(ll_cubemaps *cms, int q)
@@ -955,7 +971,7 @@ void llcms_count_sync(ll_cubemaps *cms) { ++cms->syncs; }
  * running sequences; llcms_begin called): they come to the host with the slot headers, in the same synchronisation, together
  * with extra_bytes from extra_dev into extra_host.  A slot whose extract status is LL_ERR_EMPTY runs with empty clouds.
  * hdr_out[q]: the header of slots[q] (running sequences). */
-static int cms_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit,
+static int cms_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit, ll_pose_info *info,
                          const void *extra_dev, void *extra_host, size_t extra_bytes, ScanHdr *hdr_out)
 {
     ll_ctx *ctx = cms->ctx;
@@ -994,17 +1010,17 @@ static int cms_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, 
         n_in[1][r] = empty ? 0 : h[r].n_less_flat;
         if (h[r].lf_strided) { src[1][r] = nullptr; flat[r] = s; } else src[1][r] = V.lflat + (size_t)s * V.LFS;
     }
-    return map_of ? cms_localize(cms, run, map_of, src, n_in, flat, pose_w7, ran, fit) : cms_frame(cms, run, src, n_in, flat, pose_w7, ran);
+    return map_of ? cms_localize(cms, run, map_of, src, n_in, flat, pose_w7, ran, fit, info) : cms_frame(cms, run, src, n_in, flat, pose_w7, ran);
 }
 
 int llcms_process_slots_dev(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran, const void *extra_dev, void *extra_host,
                             size_t extra_bytes, ScanHdr *hdr_out)
 {
-    return cms_slots_dev(cms, slots, nullptr, pose_w7, ran, nullptr, extra_dev, extra_host, extra_bytes, hdr_out);
+    return cms_slots_dev(cms, slots, nullptr, pose_w7, ran, nullptr, nullptr, extra_dev, extra_host, extra_bytes, hdr_out);
 }
 
-int llcms_localize_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit,
+int llcms_localize_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, double *pose_w7, int *ran, ll_localize_fit *fit, ll_pose_info *info,
                              const void *extra_dev, void *extra_host, size_t extra_bytes, ScanHdr *hdr_out)
 {
-    return cms_slots_dev(cms, slots, map_of, pose_w7, ran, fit, extra_dev, extra_host, extra_bytes, hdr_out);
+    return cms_slots_dev(cms, slots, map_of, pose_w7, ran, fit, info, extra_dev, extra_host, extra_bytes, hdr_out);
 }

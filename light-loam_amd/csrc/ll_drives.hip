@@ -137,6 +137,7 @@ struct ll_drives {
     double *d_start = nullptr;                    /* [S][7]: the map-to-odom pose START gives a lane (identity unless ll_drives_set_localize said otherwise) */
     std::vector<int> map_of;                      /* per lane: -1 maps into its own map; m >= 0 localises against lane m's map */
     std::vector<ll_localize_fit> fit;             /* per lane: the last step's fit record (zeros unless the lane localised and optimised) */
+    std::vector<ll_pose_info> info; int info_on = 0;   /* ll_drives_set_info: the same for the information records; off: zeros, nothing launched */
     int *d_fidx = nullptr;                        /* [S]: the frame counter, mirrored on the device */
     int *d_ck_bad = nullptr;                      /* [1]: ll_drives_save's pack launch found a less-flat table that disagrees with its header */
     float4 *d_reg = nullptr;                      /* [S][CS] registered clouds (keep_registered) */
@@ -190,7 +191,7 @@ extern "C" int ll_drives_create(ll_ctx *ctx, const ll_drives_params *p, ll_drive
     ll_drives *d = new ll_drives();
     d->ctx = ctx; d->cms = cms; d->S = S; d->base = p->base; d->n_outer = p->n_outer; d->keep_registered = p->keep_registered;
     d->ran_prev.assign(S, 0); d->fidx.assign(S, 0); d->reg_n.assign(S, 0); d->feat.assign(S, DrvFeat());
-    d->map_of.assign(S, -1); d->fit.assign(S, ll_localize_fit());
+    d->map_of.assign(S, -1); d->fit.assign(S, ll_localize_fit()); d->info.assign(S, ll_pose_info());
     bool ok = drv_alloc(d, d->d_odom, (size_t)S * 7) && drv_alloc(d, d->d_m2o, (size_t)S * 7) && drv_alloc(d, d->d_fidx, (size_t)S) && drv_alloc(d, d->d_ck_bad, 1) &&
               drv_alloc(d, d->d_start, (size_t)S * 7);
     if (ok) {
@@ -301,7 +302,8 @@ static int drv_run(ll_drives *d, const int *cmd, const std::vector<double> &p0, 
         if (rc) { d->err = "mapping: " + drv_lane_msg(llcms_err(d->cms)); return rc; }
     }
     if (n_loc > 0) {                                                                    /* the step's guard: no map read here was written above */
-        rc = llcms_localize_slots_dev(d->cms, loc_slots.data(), d->map_of.data(), mapped.data(), ran.data(), d->fit.data(), d->d_odom, odom.data(),
+        rc = llcms_localize_slots_dev(d->cms, loc_slots.data(), d->map_of.data(), mapped.data(), ran.data(), d->fit.data(), d->info_on ? d->info.data() : nullptr,
+                                      d->d_odom, odom.data(),
                                       (size_t)S * 7 * sizeof(double), hdr.data());
         if (rc) { d->err = "localising: " + drv_lane_msg(llcms_err(d->cms)); return rc; }
     }
@@ -370,6 +372,7 @@ extern "C" int ll_drives_step(ll_drives *d, const int *cmd, const double *pose0,
         if (n_cap > 0 && llkf_room(d->kf, n_cap, cm->cap_last)) { d->err = "the step has not run: " + std::string(ll_keyframes_last_error(d->kf)); return LL_ERR_CAPACITY; }
     }
     std::fill(d->fit.begin(), d->fit.end(), ll_localize_fit());
+    std::fill(d->info.begin(), d->info.end(), ll_pose_info());
     const double nan = std::nan("");
     std::vector<double> odom((size_t)S * 7, nan), mapped((size_t)S * 7, nan), p0((size_t)S * 7, 0.0);
     std::vector<int> r(S, 0);
@@ -388,6 +391,7 @@ extern "C" int ll_drives_step(ll_drives *d, const int *cmd, const double *pose0,
         if (rc) {                                                                       /* the step is lost: its lanes are stopped */
             for (int q = 0; q < S; ++q) { d->ran_prev[q] = 0; if (cmd[q] != LL_DRIVE_IDLE) d->reg_n[q] = 0; }
             std::fill(d->fit.begin(), d->fit.end(), ll_localize_fit());
+            std::fill(d->info.begin(), d->info.end(), ll_pose_info());
             return rc;
         }
         ++d->frames;
@@ -479,6 +483,24 @@ extern "C" int ll_drives_fit(ll_drives *d, ll_localize_fit *fit)
     if (!d) return LL_ERR_ARG;
     if (!fit) { d->err = "no fit array"; return LL_ERR_ARG; }
     std::memcpy(fit, d->fit.data(), d->fit.size() * sizeof(ll_localize_fit));
+    return LL_OK;
+}
+
+/* the information records of the localising lanes: off after create; not part of a checkpoint */
+extern "C" int ll_drives_set_info(ll_drives *d, int on)
+{
+    if (!d) return LL_ERR_ARG;
+    if (on != 0 && on != 1) { d->err = "set_info: on must be 0 or 1"; return LL_ERR_ARG; }
+    d->info_on = on;
+    if (!on) std::fill(d->info.begin(), d->info.end(), ll_pose_info());
+    return LL_OK;
+}
+
+extern "C" int ll_drives_info(ll_drives *d, ll_pose_info *info)
+{
+    if (!d) return LL_ERR_ARG;
+    if (!info) { d->err = "no info array"; return LL_ERR_ARG; }
+    std::memcpy(info, d->info.data(), d->info.size() * sizeof(ll_pose_info));
     return LL_OK;
 }
 

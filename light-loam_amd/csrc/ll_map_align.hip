@@ -30,7 +30,8 @@
  *                 thread.  The order of every sum is fixed by (AL_CHUNK, chunk index): an op's pose has the same bits alone or
  *                 among others, and from call to call.
  * No kernel waits on another workgroup.  The fit record is one more knn / cscan / place at the final pose, k_al_eval's second
- * form (cost, sq_edge, sq_plane) and k_al_fitsum.
+ * form (cost, sq_edge, sq_plane) and k_al_fitsum; the information record (ll_pose_info) is k_al_eval's first form once more on those
+ * blocks and k_al_infosum (ll_pose_info.h), which reads the squares k_al_fitsum left.
  * The host synchronises ONCE per call, for the poses, the records and the block counts: the cube counts and offsets are host
  * bookkeeping, so the launches and the workspace are planned without a read-back.
  */
@@ -38,6 +39,7 @@
 #include "ll_factor_math.h"
 #include "ll_map_neq.h"
 #include "ll_map_search.h"
+#include "ll_pose_info.h"
 #include <cmath>
 
 #define AL_SIDE 40                           /* cells per cube side: 50 m / 1.25 m */
@@ -327,6 +329,19 @@ __global__ __launch_bounds__(64) void k_al_fitsum(const LLMapView *views, const 
     }
 }
 
+/* one wave per op: the ll_pose_info record (ll_pose_info.h) from the partials of k_al_eval<false> at the final T, summed in chunk
+ * order, and the squares k_al_fitsum left in fit[] -- launched behind it */
+__global__ __launch_bounds__(64) void k_al_infosum(const LLMapView *views, const AlOp *ops, const double *part, const ll_localize_fit *fit, ll_pose_info *info)
+{
+    const LLMapView &M = views[blockIdx.x];
+    const int tid = threadIdx.x, n_e = M.counts[0], n_p = M.counts[1];
+    const int used = (n_e + n_p + AL_CHUNK - 1) / AL_CHUNK;
+    __shared__ double stot[LL_NACC], work[LL_NEQ_STRIDE];
+    if (tid < LL_NACC) stot[tid] = ll_partials_sum(part + (size_t)ops[blockIdx.x].chunk0 * LL_NACC, used, tid);
+    __syncthreads();
+    if (tid == 0) ll_info_finish(stot, fit[blockIdx.x], work, info + blockIdx.x);
+}
+
 /* ------------------------------------------------------------------ host side */
 void llal_free(LLMapAlign &A)
 {
@@ -351,6 +366,12 @@ struct AlCloud { int map, w; long long n, first; int slot0, nslot; };
 
 extern "C" int ll_cubemaps_align(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops, int n_outer, const ll_lm_options *opt,
                                  double *T_w7, int *ran, ll_localize_fit *fit)
+{
+    return ll_cubemaps_align_info(cms, ops, n_ops, n_outer, opt, T_w7, ran, fit, nullptr);
+}
+
+extern "C" int ll_cubemaps_align_info(ll_cubemaps *cms, const ll_merge_op *ops, int n_ops, int n_outer, const ll_lm_options *opt,
+                                      double *T_w7, int *ran, ll_localize_fit *fit, ll_pose_info *info)
 {
     if (!cms) return LL_ERR_ARG;
     if (n_ops < 0) return llcms_fail(cms, LL_ERR_ARG, "map align: n_ops < 0");
@@ -378,6 +399,7 @@ extern "C" int ll_cubemaps_align(ll_cubemaps *cms, const ll_merge_op *ops, int n
         std::memcpy(T_w7 + 7 * i, ops[i].T_w7, 7 * sizeof(double));
         if (ran) ran[i] = 0;
         if (fit) std::memset(fit + i, 0, sizeof(ll_localize_fit));
+        if (info) std::memset(info + i, 0, sizeof(ll_pose_info));
     }
     /* ---- the :1822 gate on the host's own counts; the clouds of the ops that pass: dst clouds (searched), src clouds (stacks) */
     auto total = [&](int q, int w) { long long n = 0; const ll_cubemap *cm = llcms_map(cms, q); for (int c = 0; c < CM_N; ++c) n += cm->cnt[w][c]; return n; };
@@ -433,7 +455,8 @@ extern "C" int ll_cubemaps_align(ll_cubemaps *cms, const ll_merge_op *ops, int n
         A.ev.push_back(e);
     }
     static_assert(sizeof(ll_localize_fit) == 4 * sizeof(double), "the records lie behind the poses as 4 doubles each");
-    const size_t res_doubles = (size_t)O * (7 + 4 + 1);            /* poses, records, the two block counts of every op */
+    static_assert(sizeof(ll_pose_info) == 50 * sizeof(double), "the information records lie behind the counts as 50 doubles each");
+    const size_t res_doubles = (size_t)O * (7 + 4 + 1) + (info ? (size_t)O * 50 : 0);   /* poses, records, the two block counts of every op, the information records */
     int *d_T = nullptr, *d_blkcnt = nullptr, *d_blkbase = nullptr;
     float4 *d_sorted = nullptr, *d_flat = nullptr;
     double *d_res = nullptr, *d_part = nullptr, *d_lm = nullptr;
@@ -474,6 +497,7 @@ extern "C" int ll_cubemaps_align(ll_cubemaps *cms, const ll_merge_op *ops, int n
         W.p = A.d_mem;
     }
     ll_localize_fit *d_fit = (ll_localize_fit *)(d_res + (size_t)O * 7);
+    ll_pose_info *d_info = (ll_pose_info *)(d_res + (size_t)O * 12);
     /* ---- the tables: segments (dst cubes first), slots, cube -> slot, ops, views, block rows, chunks, the guesses */
     std::vector<AlSeg> segs;
     std::vector<int> slot_base((size_t)n_slot), c2s(grids.size() * (size_t)CM_N, -1);
@@ -555,10 +579,14 @@ extern "C" int ll_cubemaps_align(ll_cubemaps *cms, const ll_merge_op *ops, int n
         }
         AL_HIP(hipEventRecord(A.ev[e++], st));
     }
-    if (fit) {                                                     /* the blocks at the final pose, reduced */
+    if (fit || info) {                                             /* the blocks at the final pose, reduced */
         associate();
         if (!chunks.empty()) hipLaunchKernelGGL(k_al_eval<true>, dim3((unsigned)chunks.size()), dim3(256), 0, st, d_views, d_chunks, d_part);
         hipLaunchKernelGGL(k_al_fitsum, dim3(O), dim3(64), 0, st, d_views, d_ops, (const double *)d_part, d_fit);
+    }
+    if (info) {                                                    /* the same blocks' normal equations; the partials are free again */
+        if (!chunks.empty()) hipLaunchKernelGGL(k_al_eval<false>, dim3((unsigned)chunks.size()), dim3(256), 0, st, d_views, d_chunks, d_part);
+        hipLaunchKernelGGL(k_al_infosum, dim3(O), dim3(64), 0, st, d_views, d_ops, (const double *)d_part, (const ll_localize_fit *)d_fit, d_info);
     }
     AL_HIP(hipEventRecord(A.ev[e++], st));
     AL_HIP(hipGetLastError());
@@ -580,9 +608,10 @@ extern "C" int ll_cubemaps_align(ll_cubemaps *cms, const ll_merge_op *ops, int n
         for (int k = 0; k < 7; ++k) nan = nan || std::isnan(pin[7 * (size_t)r + k]);
         std::memcpy(T_w7 + 7 * i, pin + 7 * (size_t)r, 7 * sizeof(double));
         if (fit) std::memcpy(fit + i, pin + (size_t)O * 7 + 4 * (size_t)r, sizeof(ll_localize_fit));
+        if (info) std::memcpy(info + i, pin + (size_t)O * 12 + 50 * (size_t)r, sizeof(ll_pose_info));
         if (ran) ran[i] = !nan;
         if (nan && bad < 0) bad = i;
-        if (n_outer > 0 || fit) A.counts[2] += (long long)cnt[2 * r] + cnt[2 * r + 1];
+        if (n_outer > 0 || fit || info) A.counts[2] += (long long)cnt[2 * r] + cnt[2 * r + 1];
     }
     if (bad >= 0) return llcms_fail(cms, LL_ERR_STATE, "map align: op " + std::to_string(bad) + ": the solve returned an undefined pose (NaN)");
     return LL_OK;

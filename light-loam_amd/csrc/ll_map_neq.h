@@ -3,7 +3,7 @@
  * three sums of a fit record), the workgroup reduction behind them, the order of the partial sums, the 44-double record and one
  * round of the trust-region solve on it.  The library is built with -ffp-contract=off: the operation order written here IS the
  * result, so the kernels that call these functions -- k_map_normal_eq, k_map_lm_solve (ll_mapping.hip), k_cms_lm (ll_cubemaps.hip),
- * k_cms_fit (ll_localize.hip), k_al_eval / k_al_solve / k_al_fitsum (ll_map_align.hip) -- agree bit for bit because they share
+ * k_cms_fit / k_cms_info (ll_localize.hip), k_al_eval / k_al_solve / k_al_fitsum / k_al_infosum (ll_map_align.hip) -- agree bit for bit because they share
  * this text, not because copies were kept alike.  What stays in a kernel is mechanism: which blocks a thread takes, how partial sums
  * travel between workgroups, when a round begins.  ll_neq_eval (ll_neq.h: the odometry's blocks, on the flagship path) keeps its own
  * text of the reduction and the record: sharing them re-schedules k_normal_equations / k_lm_solve / k_vote_lm_rows (ll_sequences.hip).

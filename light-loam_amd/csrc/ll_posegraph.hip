@@ -15,6 +15,9 @@
  *                      R(q_i)^T <- R(q_i)^T (I - 2 [w]x):  t_e changes by -2 R(a) (w x v) = 2 R(a) [v]x w:  d t_e / d w_i = 2 R(a) [v]x.
  *   translations:      d t_e / d t_j = R(a),  d t_e / d t_i = -R(a);  t_e does not depend on w_j, r_rot on no translation.
  *       J_i = S [ -A  0 ; 2 R(a)[v]x  -R(a) ],   J_j = S [ A  0 ; 0  R(a) ],   S = diag(s).
+ * An ll_pg_edge6 carries a full 6 x 6 matrix S in place of diag(s): r = S e and J = S J^e with e and J^e the unweighted error and
+ * Jacobians above (pg_error yields them for both edge types).  Everything from the Huber scale on is one text, the kernel a template
+ * over the edge type; the diagonal calls keep their own instantiation.
  * The Gauss-Newton model takes r and J times sqrt(rho') (ll_huber_scale: Ceres' corrector where rho'' <= 0), so g = J^T r is the
  * gradient of the robust cost.
  *
@@ -42,9 +45,10 @@
 #define PG_NODE_DOUBLES 92                    /* x 7, cand 7, Hd 36, g 6, D 6, d 6, r 6, z 6, p 6, Ap 6 */
 #define PG_EDGE_DOUBLES 121                   /* H_ij, H_ii, H_jj 36 each, g_i, g_j 6 each, cost */
 
+template <typename Edge>                      /* ll_pg_edge: diagonal square-root information; ll_pg_edge6: a full 6 x 6 one */
 struct PgArgs {
     /* the call's input, as the host packed it */
-    const double *pose_in; const ll_pg_edge *edges; const int *node_off, *edge_off, *inc_off, *inc, *inc_nb; const unsigned char *fixed;
+    const double *pose_in; const Edge *edges; const int *node_off, *edge_off, *inc_off, *inc, *inc_nb; const unsigned char *fixed;
     /* workspace, [nodes_total] or [edges_total] rows */
     double *x, *cand, *Hd, *g, *D, *d, *r, *z, *p, *Ap, *eH, *eg, *ecost;
     /* results: solve -> poses [nodes][7] + records; evaluate -> gradients [nodes][6] + costs */
@@ -74,11 +78,12 @@ __device__ __forceinline__ void pg_qmul(const double a[4], const double b[4], do
     o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
 }
 
-/* the weighted residual of edge e at (Pi, Pj); with A != NULL also what the Jacobians are made of: A (3 x 3, see above), Ra = R(a), v */
-__device__ __forceinline__ void pg_residual(const double *Pi, const double *Pj, const ll_pg_edge &e, double r[6], double (*A)[3], double (*Ra)[3], double *v)
+/* the UNWEIGHTED error er = [2 sgn(w_e) vec(q_e) ; t_e] of an edge with measurement Z at (Pi, Pj); with A != NULL also what the
+ * Jacobians are made of: A (3 x 3, see above), Ra = R(a), v */
+__device__ __forceinline__ void pg_error(const double *Pi, const double *Pj, const double *Z_w7, double er[6], double (*A)[3], double (*Ra)[3], double *v)
 {
-    const double zn = sqrt((e.Z_w7[0] * e.Z_w7[0] + e.Z_w7[1] * e.Z_w7[1]) + (e.Z_w7[2] * e.Z_w7[2] + e.Z_w7[3] * e.Z_w7[3]));
-    const double qzc[4] = {-e.Z_w7[0] / zn, -e.Z_w7[1] / zn, -e.Z_w7[2] / zn, e.Z_w7[3] / zn};
+    const double zn = sqrt((Z_w7[0] * Z_w7[0] + Z_w7[1] * Z_w7[1]) + (Z_w7[2] * Z_w7[2] + Z_w7[3] * Z_w7[3]));
+    const double qzc[4] = {-Z_w7[0] / zn, -Z_w7[1] / zn, -Z_w7[2] / zn, Z_w7[3] / zn};
     const double qic[4] = {-Pi[0], -Pi[1], -Pi[2], Pi[3]};
     double a[4], qe[4];
     pg_qmul(qzc, qic, a);
@@ -90,10 +95,10 @@ __device__ __forceinline__ void pg_residual(const double *Pi, const double *Pj, 
                             {2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)}};
     const double dv[3] = {Pj[4] - Pi[4], Pj[5] - Pi[5], Pj[6] - Pi[6]};
     double tz[3];
-    ll_rotate(qzc, e.Z_w7 + 4, tz);                               /* R(q_z)^T t_z */
+    ll_rotate(qzc, Z_w7 + 4, tz);                                 /* R(q_z)^T t_z */
     for (int k = 0; k < 3; ++k) {
-        r[k] = e.sqrt_info[k] * (2.0 * sgn * qe[k]);
-        r[3 + k] = e.sqrt_info[3 + k] * (((R[k][0] * dv[0] + R[k][1] * dv[1]) + R[k][2] * dv[2]) - tz[k]);
+        er[k] = 2.0 * sgn * qe[k];
+        er[3 + k] = ((R[k][0] * dv[0] + R[k][1] * dv[1]) + R[k][2] * dv[2]) - tz[k];
     }
     if (!A) return;
     for (int k = 0; k < 3; ++k) {
@@ -106,7 +111,26 @@ __device__ __forceinline__ void pg_residual(const double *Pi, const double *Pj, 
     }
 }
 
-__device__ __forceinline__ double pg_edge_cost(const double *Pi, const double *Pj, const ll_pg_edge &e)
+/* the weighted residual r = S er: diag(sqrt_info), or the full matrix row by row, columns ascending */
+__device__ __forceinline__ void pg_residual(const double *Pi, const double *Pj, const ll_pg_edge &e, double r[6], double (*A)[3], double (*Ra)[3], double *v)
+{
+    double er[6];
+    pg_error(Pi, Pj, e.Z_w7, er, A, Ra, v);
+    for (int k = 0; k < 6; ++k) r[k] = e.sqrt_info[k] * er[k];
+}
+__device__ __forceinline__ void pg_residual(const double *Pi, const double *Pj, const ll_pg_edge6 &e, double r[6], double (*A)[3], double (*Ra)[3], double *v)
+{
+    double er[6];
+    pg_error(Pi, Pj, e.Z_w7, er, A, Ra, v);
+    for (int m = 0; m < 6; ++m) {
+        double s = 0.0;
+        for (int k = 0; k < 6; ++k) s += e.S[m * 6 + k] * er[k];
+        r[m] = s;
+    }
+}
+
+template <typename Edge>
+__device__ __forceinline__ double pg_edge_cost(const double *Pi, const double *Pj, const Edge &e)
 {
     double r[6], c = 0.0;
     pg_residual(Pi, Pj, e, r, nullptr, nullptr, nullptr);
@@ -116,6 +140,20 @@ __device__ __forceinline__ double pg_edge_cost(const double *Pi, const double *P
 }
 
 /* the edge's slots: eH[0] = J_i^T J_j, eH[1] = J_i^T J_i, eH[2] = J_j^T J_j, eg[0] = J_i^T r, eg[1] = J_j^T r, and its cost */
+__device__ __forceinline__ void pg_edge_products(const double (*Ji)[6], const double (*Jj)[6], const double *r, double *eH, double *eg)
+{
+    for (int a = 0; a < 6; ++a) {
+        double gi = 0.0, gj = 0.0;
+        for (int m = 0; m < 6; ++m) { gi += Ji[m][a] * r[m]; gj += Jj[m][a] * r[m]; }
+        eg[a] = gi; eg[6 + a] = gj;
+        for (int b = 0; b < 6; ++b) {
+            double hij = 0.0, hii = 0.0, hjj = 0.0;
+            for (int m = 0; m < 6; ++m) { hij += Ji[m][a] * Jj[m][b]; hii += Ji[m][a] * Ji[m][b]; hjj += Jj[m][a] * Jj[m][b]; }
+            eH[a * 6 + b] = hij; eH[36 + a * 6 + b] = hii; eH[72 + a * 6 + b] = hjj;
+        }
+    }
+}
+
 __device__ __forceinline__ void pg_edge_linearise(const double *Pi, const double *Pj, const ll_pg_edge &e, double *eH, double *eg, double *ecost)
 {
     double r[6], A[3][3], Ra[3][3], v[3], Ji[6][6], Jj[6][6], c = 0.0;
@@ -135,16 +173,34 @@ __device__ __forceinline__ void pg_edge_linearise(const double *Pi, const double
         }
     }
     for (int m = 0; m < 6; ++m) r[m] *= w;
-    for (int a = 0; a < 6; ++a) {
-        double gi = 0.0, gj = 0.0;
-        for (int m = 0; m < 6; ++m) { gi += Ji[m][a] * r[m]; gj += Jj[m][a] * r[m]; }
-        eg[a] = gi; eg[6 + a] = gj;
-        for (int b = 0; b < 6; ++b) {
-            double hij = 0.0, hii = 0.0, hjj = 0.0;
-            for (int m = 0; m < 6; ++m) { hij += Ji[m][a] * Jj[m][b]; hii += Ji[m][a] * Ji[m][b]; hjj += Jj[m][a] * Jj[m][b]; }
-            eH[a * 6 + b] = hij; eH[36 + a * 6 + b] = hii; eH[72 + a * 6 + b] = hjj;
+    pg_edge_products(Ji, Jj, r, eH, eg);
+}
+
+/* the full variant: the unweighted Jacobians Je_i = [ -A  0 ; 2 R(a)[v]x  -R(a) ], Je_j = [ A  0 ; 0  R(a) ], then J = w S Je */
+__device__ __forceinline__ void pg_edge_linearise(const double *Pi, const double *Pj, const ll_pg_edge6 &e, double *eH, double *eg, double *ecost)
+{
+    double r[6], A[3][3], Ra[3][3], v[3], Jei[6][6], Jej[6][6], Ji[6][6], Jj[6][6], c = 0.0;
+    pg_residual(Pi, Pj, e, r, A, Ra, v);
+    const double sq = ((r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3])) + (r[4] * r[4] + r[5] * r[5]);
+    const double w = ll_huber_scale(sq, e.huber, c);
+    *ecost = c;
+    const double vx[3][3] = {{0.0, -v[2], v[1]}, {v[2], 0.0, -v[0]}, {-v[1], v[0], 0.0}};
+    for (int m = 0; m < 3; ++m)
+        for (int k = 0; k < 3; ++k) {
+            Jei[m][k] = -A[m][k];            Jei[m][3 + k] = 0.0;
+            Jej[m][k] = A[m][k];             Jej[m][3 + k] = 0.0;
+            Jei[3 + m][k] = 2.0 * ((Ra[m][0] * vx[0][k] + Ra[m][1] * vx[1][k]) + Ra[m][2] * vx[2][k]);
+            Jei[3 + m][3 + k] = -Ra[m][k];
+            Jej[3 + m][k] = 0.0;             Jej[3 + m][3 + k] = Ra[m][k];
         }
-    }
+    for (int m = 0; m < 6; ++m)
+        for (int k = 0; k < 6; ++k) {
+            double si = 0.0, sj = 0.0;
+            for (int n = 0; n < 6; ++n) { si += e.S[m * 6 + n] * Jei[n][k]; sj += e.S[m * 6 + n] * Jej[n][k]; }
+            Ji[m][k] = w * si; Jj[m][k] = w * sj;
+        }
+    for (int m = 0; m < 6; ++m) r[m] *= w;
+    pg_edge_products(Ji, Jj, r, eH, eg);
 }
 
 /* ------------------------------------------------------------------ device: the workgroup's sums
@@ -175,19 +231,21 @@ __device__ __forceinline__ double pg_max(double a, double *sh)
 }
 
 /* ------------------------------------------------------------------ device: one graph */
+template <typename Edge>
 struct PgGraph {                               /* the graph's rows of the workspace */
     int N, E, n0, e0;
-    const ll_pg_edge *edges; const int *inc_off, *inc, *inc_nb; const unsigned char *fixed;
+    const Edge *edges; const int *inc_off, *inc, *inc_nb; const unsigned char *fixed;
     double *x, *cand, *Hd, *g, *D, *d, *r, *z, *p, *Ap, *eH, *eg, *ecost;
 };
 
 /* edges at the poses `P`, then the nodes' sums; -> the cost (every thread) */
-__device__ double pg_linearise(const PgGraph &G, const double *P, const ll_pg_options &o, double *sh)
+template <typename Edge>
+__device__ double pg_linearise(const PgGraph<Edge> &G, const double *P, const ll_pg_options &o, double *sh)
 {
     const int tid = threadIdx.x;
     double c = 0.0, unused = 0.0;
     for (int e = tid; e < G.E; e += PG_THREADS) {
-        const ll_pg_edge &ed = G.edges[e];
+        const Edge &ed = G.edges[e];
         pg_edge_linearise(P + (size_t)ed.i * 7, P + (size_t)ed.j * 7, ed, G.eH + (size_t)e * 108, G.eg + (size_t)e * 12, G.ecost + e);
         c += G.ecost[e];
     }
@@ -214,7 +272,8 @@ __device__ double pg_linearise(const PgGraph &G, const double *P, const ll_pg_op
 }
 
 /* out = (H + damp D) in, rows of fixed nodes 0 (their `in` is 0 as well); a thread per node */
-__device__ void pg_matvec(const PgGraph &G, const double *in, double *out, double damp)
+template <typename Edge>
+__device__ void pg_matvec(const PgGraph<Edge> &G, const double *in, double *out, double damp)
 {
     for (int n = threadIdx.x; n < G.N; n += PG_THREADS) {
         double y[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -237,7 +296,8 @@ __device__ void pg_matvec(const PgGraph &G, const double *in, double *out, doubl
 }
 
 /* z = M^-1 r of node n, M = Hd + D / radius; false where M is not positive definite (z = 0 then) */
-__device__ __forceinline__ bool pg_precondition(const PgGraph &G, int n, double inv_radius, const double r[6], double z[6])
+template <typename Edge>
+__device__ __forceinline__ bool pg_precondition(const PgGraph<Edge> &G, int n, double inv_radius, const double r[6], double z[6])
 {
     double M[36], nr[6];
     for (int k = 0; k < 36; ++k) M[k] = G.Hd[(size_t)n * 36 + k];
@@ -248,12 +308,13 @@ __device__ __forceinline__ bool pg_precondition(const PgGraph &G, int n, double 
 
 __device__ __forceinline__ bool pg_finite(double v) { return v - v == 0.0; }
 
-__global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgArgs A)
+template <typename Edge>
+__global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgArgs<Edge> A)
 {
     __shared__ double sh[8];
     const int tid = threadIdx.x, gi = blockIdx.x;
     const ll_pg_options &o = A.o;
-    PgGraph G;
+    PgGraph<Edge> G;
     G.n0 = A.node_off[gi]; G.N = A.node_off[gi + 1] - G.n0;
     G.e0 = A.edge_off[gi]; G.E = A.edge_off[gi + 1] - G.e0;
     G.edges = A.edges + G.e0; G.inc_off = A.inc_off; G.inc = A.inc; G.inc_nb = A.inc_nb; G.fixed = A.fixed + G.n0;
@@ -370,7 +431,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgArgs A)
         if (sqrt(step2) <= o.parameter_tolerance * (sqrt(x2n) + o.parameter_tolerance)) { term = 2; break; }
         double cc = 0.0, unused = 0.0;
         for (int e = tid; e < G.E; e += PG_THREADS) {
-            const ll_pg_edge &ed = G.edges[e];
+            const Edge &ed = G.edges[e];
             cc += pg_edge_cost(G.cand + (size_t)ed.i * 7, G.cand + (size_t)ed.j * 7, ed);
         }
         pg_sum2(cc, unused, sh);
@@ -415,9 +476,9 @@ static int pg_fail(ll_posegraphs *pg, int code, const std::string &what) { pg->e
 static size_t pg_up8(size_t b) { return (b + 7) & ~(size_t)7; }
 
 /* the byte offsets of the sections of the upload for (graphs, nodes, edges); [8] = the total */
-static void pg_in_layout(size_t G, size_t N, size_t E, size_t off[9])
+static void pg_in_layout(size_t G, size_t N, size_t E, size_t edge_bytes, size_t off[9])
 {
-    const size_t sz[8] = {N * 7 * sizeof(double), E * sizeof(ll_pg_edge), (G + 1) * sizeof(int), (G + 1) * sizeof(int),
+    const size_t sz[8] = {N * 7 * sizeof(double), E * edge_bytes, (G + 1) * sizeof(int), (G + 1) * sizeof(int),
                           (N + 1) * sizeof(int), 2 * E * sizeof(int), 2 * E * sizeof(int), N};
     off[0] = 0;
     for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + pg_up8(sz[k]);
@@ -454,7 +515,7 @@ extern "C" int ll_posegraphs_create(ll_ctx *ctx, int max_graphs, int max_nodes_t
     pg->ctx = ctx; pg->max_graphs = max_graphs; pg->max_nodes = max_nodes_total; pg->max_edges = max_edges_total;
     const size_t G = (size_t)max_graphs, N = (size_t)max_nodes_total, E = (size_t)max_edges_total;
     size_t off[9];
-    pg_in_layout(G, N, E, off);
+    pg_in_layout(G, N, E, sizeof(ll_pg_edge6), off);              /* room for either edge type */
     pg->in_bytes = off[8];
     pg->out_bytes = N * 7 * sizeof(double) + G * sizeof(ll_pg_record);
     const size_t ws_bytes = (N * PG_NODE_DOUBLES + E * PG_EDGE_DOUBLES + 1) * sizeof(double);
@@ -489,8 +550,12 @@ static int pg_check_options(ll_posegraphs *pg, const ll_pg_options &o)
 }
 
 /* validate the call, pack it into page-locked scratch, enqueue the upload and the launch, download, synchronise ONCE */
+static bool pg_finite_weights(const ll_pg_edge &e) { return pg_finite7(e.sqrt_info, 6); }
+static bool pg_finite_weights(const ll_pg_edge6 &e) { return pg_finite7(e.S, 36); }
+
+template <typename Edge>
 static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
-                  const unsigned char *fixed, const ll_pg_edge *edges, const ll_pg_options *opt, double *out_a, void *out_b)
+                  const unsigned char *fixed, const Edge *edges, const ll_pg_options *opt, double *out_a, void *out_b)
 {
     if (!pg) return LL_ERR_ARG;
     const char *who = solve ? "solve: " : "evaluate: ";
@@ -521,11 +586,11 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
         }
         if (!any_fixed) return bad(LL_ERR_ARG, gs + " has no fixed node");
         for (int e = edge_off[g]; e < edge_off[g + 1]; ++e) {
-            const ll_pg_edge &ed = edges[e];
+            const Edge &ed = edges[e];
             const std::string es = gs + ", edge " + std::to_string(e - edge_off[g]);
             if (ed.i < 0 || ed.i >= n || ed.j < 0 || ed.j >= n) return bad(LL_ERR_ARG, es + ": a node index lies outside the graph");
             if (ed.i == ed.j) return bad(LL_ERR_ARG, es + ": i == j");
-            if (!pg_finite7(ed.Z_w7, 7) || !pg_finite7(ed.sqrt_info, 6) || !std::isfinite(ed.huber)) return bad(LL_ERR_ARG, es + ": the measurement or a weight is not finite");
+            if (!pg_finite7(ed.Z_w7, 7) || !pg_finite_weights(ed) || !std::isfinite(ed.huber)) return bad(LL_ERR_ARG, es + ": the measurement or a weight is not finite");
             if (pg_zero_quat(ed.Z_w7)) return bad(LL_ERR_ARG, es + ": zero quaternion");
         }
     }
@@ -535,14 +600,14 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
 
     /* ---- pack: poses, edges, offsets, the node -> incident-edge lists (edge order), fixed */
     size_t off[9];
-    pg_in_layout((size_t)n_graphs, (size_t)N, (size_t)E, off);
+    pg_in_layout((size_t)n_graphs, (size_t)N, (size_t)E, sizeof(Edge), off);
     const size_t per_node = solve ? 7 : 6;
     const size_t out_b_bytes = solve ? (size_t)n_graphs * sizeof(ll_pg_record) : (size_t)n_graphs * sizeof(double);
     const size_t down = (size_t)N * per_node * sizeof(double) + out_b_bytes;
     unsigned char *pin = (unsigned char *)ll_pinned_scratch(off[8] + pg_up8(down));
     if (!pin) return bad(LL_ERR_HIP, "no page-locked scratch");
     if (N > 0) std::memcpy(pin + off[0], poses_w7, (size_t)N * 7 * sizeof(double));
-    if (E > 0) std::memcpy(pin + off[1], edges, (size_t)E * sizeof(ll_pg_edge));
+    if (E > 0) std::memcpy(pin + off[1], edges, (size_t)E * sizeof(Edge));
     std::memcpy(pin + off[2], node_off, (size_t)(n_graphs + 1) * sizeof(int));
     std::memcpy(pin + off[3], edge_off, (size_t)(n_graphs + 1) * sizeof(int));
     int *inc_off = (int *)(pin + off[4]), *inc = (int *)(pin + off[5]), *inc_nb = (int *)(pin + off[6]);
@@ -567,8 +632,8 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
     PG_HIP(hipSetDevice(pg->ctx->device));
     hipStream_t st = pg->ctx->stream;
     PG_HIP(hipMemcpyAsync(pg->d_in, pin, off[8], hipMemcpyHostToDevice, st));
-    PgArgs A;
-    A.pose_in = (const double *)(pg->d_in + off[0]); A.edges = (const ll_pg_edge *)(pg->d_in + off[1]);
+    PgArgs<Edge> A;
+    A.pose_in = (const double *)(pg->d_in + off[0]); A.edges = (const Edge *)(pg->d_in + off[1]);
     A.node_off = (const int *)(pg->d_in + off[2]); A.edge_off = (const int *)(pg->d_in + off[3]);
     A.inc_off = (const int *)(pg->d_in + off[4]); A.inc = (const int *)(pg->d_in + off[5]); A.inc_nb = (const int *)(pg->d_in + off[6]);
     A.fixed = pg->d_in + off[7];
@@ -581,7 +646,7 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
     A.rec = (ll_pg_record *)(pg->d_out + Nn * per_node * sizeof(double)); A.out_cost = (double *)A.rec;
     A.o = o; A.solve = solve ? 1 : 0;
     PG_HIP(hipEventRecord(pg->ev[0], st));
-    hipLaunchKernelGGL(k_pg_solve, dim3((unsigned)n_graphs), dim3(PG_THREADS), 0, st, A);
+    hipLaunchKernelGGL(k_pg_solve<Edge>, dim3((unsigned)n_graphs), dim3(PG_THREADS), 0, st, A);
     PG_HIP(hipEventRecord(pg->ev[1], st));
     PG_HIP(hipGetLastError());
     unsigned char *pout = pin + off[8];
@@ -618,6 +683,58 @@ extern "C" int ll_posegraphs_evaluate(ll_posegraphs *pg, int n_graphs, const int
 
 extern "C" int ll_posegraphs_solve(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, double *poses_w7,
                                    const unsigned char *fixed, const ll_pg_edge *edges, const ll_pg_options *opt, ll_pg_record *rec)
+{
+    return pg_run(pg, true, n_graphs, node_off, edge_off, poses_w7, fixed, edges, opt, poses_w7, rec);
+}
+
+/* ll_pose_info -> the square-root information of the edge it stands for (the contract and the derivation are in the header):
+ * Lambda = M^-T H M^-1 / sigma^2 + floor I with M^-1 = blkdiag(R(X) / 2, R(X)), then its upper Cholesky factor.  Host arithmetic only. */
+extern "C" int ll_pg_edge_from_info(const ll_pose_info *info, const double *X_w7, double sigma, double floor, double S36[36])
+{
+    if (!info || !X_w7 || !S36) return LL_ERR_ARG;
+    if (!pg_finite7(X_w7, 7) || !std::isfinite(sigma) || !std::isfinite(floor) || floor < 0.0 || pg_zero_quat(X_w7)) return LL_ERR_ARG;
+    if (info->flags & 1) return LL_ERR_STATE;
+    double s2 = sigma * sigma;
+    if (!(sigma > 0.0)) {
+        if (!(info->sigma2 > 0.0) || !std::isfinite(info->sigma2)) return LL_ERR_STATE;
+        s2 = info->sigma2;
+    }
+    const double qn = std::sqrt((X_w7[0] * X_w7[0] + X_w7[1] * X_w7[1]) + (X_w7[2] * X_w7[2] + X_w7[3] * X_w7[3]));
+    const double x = X_w7[0] / qn, y = X_w7[1] / qn, z = X_w7[2] / qn, w = X_w7[3] / qn;
+    const double R[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)},
+                            {2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)},
+                            {2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)}};
+    double Mi[6][6] = {}, HM[6][6], L[6][6];
+    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { Mi[a][b] = 0.5 * R[a][b]; Mi[3 + a][3 + b] = R[a][b]; }
+    for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) { double s = 0.0; for (int k = 0; k < 6; ++k) s += info->H[a * 6 + k] * Mi[k][b]; HM[a][b] = s; }
+    for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) { double s = 0.0; for (int k = 0; k < 6; ++k) s += Mi[k][a] * HM[k][b]; L[a][b] = s / s2; }
+    for (int a = 0; a < 6; ++a) for (int b = a + 1; b < 6; ++b) { const double m = 0.5 * (L[a][b] + L[b][a]); L[a][b] = m; L[b][a] = m; }
+    for (int a = 0; a < 6; ++a) L[a][a] += floor;
+    double U[6][6] = {};                                           /* U^T U = Lambda, row by row */
+    for (int a = 0; a < 6; ++a) {
+        double d = L[a][a];
+        for (int k = 0; k < a; ++k) d -= U[k][a] * U[k][a];
+        if (!(d > 0.0) || !std::isfinite(d)) return LL_ERR_STATE;
+        U[a][a] = std::sqrt(d);
+        for (int b = a + 1; b < 6; ++b) {
+            double s = L[a][b];
+            for (int k = 0; k < a; ++k) s -= U[k][a] * U[k][b];
+            U[a][b] = s / U[a][a];
+        }
+    }
+    for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) { if (!std::isfinite(U[a][b])) return LL_ERR_STATE; }
+    for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) S36[a * 6 + b] = U[a][b];
+    return LL_OK;
+}
+
+extern "C" int ll_posegraphs_evaluate6(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                                       const unsigned char *fixed, const ll_pg_edge6 *edges, double *cost, double *grad6)
+{
+    return pg_run(pg, false, n_graphs, node_off, edge_off, poses_w7, fixed, edges, nullptr, cost, grad6);
+}
+
+extern "C" int ll_posegraphs_solve6(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, double *poses_w7,
+                                    const unsigned char *fixed, const ll_pg_edge6 *edges, const ll_pg_options *opt, ll_pg_record *rec)
 {
     return pg_run(pg, true, n_graphs, node_off, edge_off, poses_w7, fixed, edges, opt, poses_w7, rec);
 }

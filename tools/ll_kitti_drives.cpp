@@ -4,7 +4,7 @@
 // A lane starts the next directory of the queue when its drive ends.  Directory i's mapped trajectory goes to <result_dir>/<i>.txt
 // in the reference's trajectory-file format (laserMapping.cpp:2284-2325), byte for byte what ll_odometry_kitti writes for it.
 //
-//   ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose "qx qy qz qw x y z"]]
+//   ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose "qx qy qz qw x y z"] [--info]]
 //                   [--distortion {0,1}] [--deskew {0,1,2}] [--map-vote N] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...
 //
 // --checkpoint FILE --checkpoint-at N: after step N (N >= 1 steps done) the lanes that ran on it are saved (ll_drives_save) to FILE
@@ -25,6 +25,9 @@
 // w, then x y z; identity when absent).  The trajectories are written as ever -- poses in the map's frame -- and beside each,
 // <result_dir>/<i>_fit.txt with one line per frame: ran n_edge n_plane cost sq_edge sq_plane (ll_localize_fit), the answer to
 // "am I still on the map?".  Not together with --checkpoint, --resume or --maps.
+// --info (needs --localize-in): beside it <result_dir>/<i>_info.txt with one line per frame: eig[0] eig[5] sigma2 of the frame's
+// ll_pose_info -- the smallest and the largest eigenvalue of the solve's Gauss-Newton Hessian and the residual variance in m^2 (zeros
+// for a frame that did not optimise): "in which direction do I hardly know where I am?".
 //
 // --distortion 1: the reference's DISTORTION 1 path (ll_params.distortion) for a lidar whose scans are NOT motion-compensated (KITTI's
 // are: leave it at 0).  --deskew 1 | 2 (needs --distortion 1, refused otherwise): TransformToEnd after every solved frame
@@ -97,13 +100,14 @@ static void read_checkpoint(const std::string &path, long long &steps, int &next
 
 int main(int argc, char **argv)
 {
-    bool maps = false;
+    bool maps = false, want_info = false;
     std::string ck_path, resume_path, loc_path, start_text;
     long long ck_at = -1;
     int distortion = 0, deskew = 0, map_vote = -1;
     while (argc > 1 && std::strncmp(argv[1], "--", 2) == 0) {
         const std::string opt = argv[1];
         if (opt == "--maps") { maps = true; --argc; ++argv; continue; }
+        if (opt == "--info") { want_info = true; --argc; ++argv; continue; }
         if (argc < 3) { std::cerr << opt << " needs a value\n"; return 2; }
         if (opt == "--checkpoint") ck_path = argv[2];
         else if (opt == "--checkpoint-at") ck_at = std::atoll(argv[2]);
@@ -118,6 +122,7 @@ int main(int argc, char **argv)
     }
     if (ck_path.empty() != (ck_at < 1)) { std::cerr << "--checkpoint FILE and --checkpoint-at N (>= 1) go together\n"; return 2; }
     if (!loc_path.empty() && (maps || !ck_path.empty() || !resume_path.empty())) { std::cerr << "--localize-in does not go with --maps, --checkpoint or --resume\n"; return 2; }
+    if (want_info && loc_path.empty()) { std::cerr << "--info needs --localize-in: only a localising lane measures its information\n"; return 2; }
     if (distortion < 0 || distortion > 1 || deskew < 0 || deskew > 2) { std::cerr << "--distortion takes 0 or 1, --deskew 0, 1 or 2\n"; return 2; }
     if (deskew != 0 && distortion == 0) { std::cerr << "--deskew " << deskew << " needs --distortion 1: without per-point interpolation ratios there is nothing to compensate\n"; return 2; }
     double start7[7] = {0, 0, 0, 1, 0, 0, 0};
@@ -127,7 +132,7 @@ int main(int argc, char **argv)
         while (got < 7 && (in >> start7[got])) ++got;
         if (got != 7 || loc_path.empty()) { std::cerr << "--start-pose takes seven numbers in one argument and needs --localize-in\n"; return 2; }
     }
-    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose \"qx qy qz qw x y z\"]] [--distortion {0,1}] [--deskew {0,1,2}] [--map-vote N] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
+    if (argc < 7) { std::cerr << "usage: ll_kitti_drives [--maps] [--checkpoint FILE --checkpoint-at N] [--resume FILE] [--localize-in BLOB [--start-pose \"qx qy qz qw x y z\"] [--info]] [--distortion {0,1}] [--deskew {0,1,2}] [--map-vote N] <result_dir> <scan_line> <first-guess tx> <max_ring_points> <lanes> <dir>...\n"; return 2; }
     const std::string result_dir = argv[1];
     const int scan_line = std::atoi(argv[2]);
     const double tx0 = std::atof(argv[3]);
@@ -169,7 +174,8 @@ int main(int argc, char **argv)
             d.restore(blob, into);
         }
         int first_lane = 0;                                                                /* --localize-in: the lanes below hold the frozen maps */
-        std::vector<std::unique_ptr<std::ofstream>> fit_out(drives.size());
+        std::vector<std::unique_ptr<std::ofstream>> fit_out(drives.size()), info_out(drives.size());
+        if (want_info) d.set_info(true);
         if (!loc_path.empty()) {
             std::vector<unsigned char> blob;
             try {                                                                          /* a file --checkpoint wrote ... */
@@ -206,6 +212,7 @@ int main(int argc, char **argv)
                     std::remove(path.c_str());
                     out[drive_of[q]].reset(new TrajectoryWriter(path));
                     if (!loc_path.empty()) fit_out[drive_of[q]].reset(new std::ofstream(result_dir + "/" + std::to_string(drive_of[q]) + "_fit.txt", std::ios::trunc));
+                    if (want_info) info_out[drive_of[q]].reset(new std::ofstream(result_dir + "/" + std::to_string(drive_of[q]) + "_info.txt", std::ios::trunc));
                 }
             }
             if (std::all_of(cmd.begin(), cmd.end(), [](int c) { return c == LL_DRIVE_IDLE; })) break;
@@ -218,6 +225,7 @@ int main(int argc, char **argv)
             d.step(cmd, pose0.data());
             ++steps;
             const std::vector<ll_localize_fit> fit = loc_path.empty() ? std::vector<ll_localize_fit>() : d.fit();
+            const std::vector<PoseInfo> info = want_info ? d.info() : std::vector<PoseInfo>();
             for (int q = 0; q < lanes; ++q) {
                 if (cmd[q] == LL_DRIVE_IDLE) continue;
                 out[drive_of[q]]->append(d.mapped_pose(q));
@@ -226,6 +234,10 @@ int main(int argc, char **argv)
                     std::snprintf(line, sizeof(line), "%d %d %d %.9e %.9e %.9e\n", d.ran[(size_t)q], fit[(size_t)q].n_edge, fit[(size_t)q].n_plane, fit[(size_t)q].cost,
                                   fit[(size_t)q].sq_edge, fit[(size_t)q].sq_plane);
                     *fit_out[drive_of[q]] << line << std::flush;
+                    if (want_info) {
+                        std::snprintf(line, sizeof(line), "%.9e %.9e %.9e\n", info[(size_t)q].eig[0], info[(size_t)q].eig[5], info[(size_t)q].sigma2);
+                        *info_out[drive_of[q]] << line << std::flush;
+                    }
                 }
                 ++frame[q];
             }
