@@ -1022,6 +1022,45 @@ int  ll_posegraphs_evaluate6(ll_posegraphs *pg, int n_graphs, const int *node_of
                              const unsigned char *fixed, const ll_pg_edge6 *edges, double *cost, double *grad6);
 int  ll_posegraphs_solve6(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, double *poses_w7,
                           const unsigned char *fixed, const ll_pg_edge6 *edges, const ll_pg_options *opt, ll_pg_record *rec);
+/* The preconditioner of the solves' conjugate gradients, a switch on the object (ll_pg_options and ll_pg_record keep their sizes).
+ * LL_PG_PRECOND_BLOCK_JACOBI, the default, is the text above, unchanged by a bit.  LL_PG_PRECOND_CHAIN solves with M, the block-
+ * tridiagonal part of A = H + D / radius in node order:
+ *   diagonal block n     Hd[n] + diag(D[n]) / radius, what block-Jacobi inverts;
+ *   coupling M[n][n+1]   the sum, in ascending edge order, over every edge whose endpoints are {n, n + 1} and both free: H_ij of an edge
+ *                        with i == n, its transpose of one with i == n + 1 (duplicate edges sum);
+ *   fixed nodes          an identity block, no coupling, a zero right-hand side: the chain breaks there;
+ *   every other edge     (loop edges, edges that span more than one index) enters M through the diagonal blocks alone.
+ * M is symmetric positive definite: the whole J^T J of the chain edges, plus the positive semi-definite diagonal parts of the others,
+ * plus D / radius > 0.  A - M has rank at most 12 per other edge, so PCG needs at most 12 L + 1 iterations in exact arithmetic for L of
+ * them, and one for a graph that is a chain; a graph without a chain edge gets block-Jacobi.  M^-1 is applied by block cyclic reduction
+ * over the 6 x 6 blocks inside the graph's workgroup -- factorised once per LM iteration (M depends on the radius), applied once per PCG
+ * iteration, ceil(log2 N) levels each way --: the same one launch, no grid barrier, no floating-point atomic, every sum of a fixed shape,
+ * so a graph keeps the same bits alone, in any batch, at any position.  A Cholesky pivot that is not positive and finite (impossible in
+ * exact arithmetic) makes the whole workgroup use block-Jacobi for that LM iteration, and is counted.
+ *   ll_posegraphs_set_preconditioner  applies to _solve and _solve6 from the next call on; _evaluate and _evaluate6 solve nothing and do
+ *                           not change.  The workspace (about 1.25 KB per node of max_nodes_total) is allocated when the chain is first
+ *                           asked for.  LL_ERR_ARG: another kind; LL_ERR_HIP: the workspace cannot be allocated.  The old kind then stays.
+ *   ll_posegraphs_preconditioner      the current kind, or a negative error code for a NULL handle.
+ *   ll_posegraphs_precond_stats       counts2[0]: factorisations of M, counts2[1]: LM iterations that fell back to block-Jacobi, both
+ *                           summed over the graphs of the last solve (zeros after a solve under block-Jacobi).
+ *   ll_posegraphs_chain_solve         the solver alone, for direct tests and for callers with block-tridiagonal systems of their own:
+ *                           n_systems independent symmetric positive definite systems, one workgroup each, through the device functions
+ *                           the solves use.  node_off: n_systems + 1 ascending entries from 0, as above; diag36 [nodes][36]: the diagonal
+ *                           blocks, row-major (the LOWER triangle is read); upper36 [nodes][36]: M[n][n+1], the last block of every
+ *                           system ignored; rhs6 and out6 [nodes][6]; status [n_systems]: 0, or 1 where a pivot was not positive and
+ *                           finite -- out6 of that system is then all zeros, the other systems are not touched by it.  A system's out6
+ *                           has the same bits alone and in any batch.  ONE synchronisation.  Decided on the host before anything is
+ *                           enqueued: LL_ERR_ARG for a NULL pointer, offsets that do not ascend from 0 or a non-finite entry (the ignored
+ *                           blocks excepted); LL_ERR_CAPACITY for more than max_graphs systems or max_nodes_total nodes.  Allocates the
+ *                           workspace if nothing has yet (LL_ERR_HIP).  Does not change the preconditioner of the solves.              */
+#define LL_PG_PRECOND_BLOCK_JACOBI 0
+#define LL_PG_PRECOND_CHAIN        1
+int  ll_posegraphs_set_preconditioner(ll_posegraphs *pg, int kind);
+int  ll_posegraphs_preconditioner(const ll_posegraphs *pg);
+int  ll_posegraphs_precond_stats(ll_posegraphs *pg, long long counts2[2]);
+int  ll_posegraphs_chain_solve(ll_posegraphs *pg, int n_systems, const int *node_off,
+                               const double *diag36, const double *upper36,
+                               const double *rhs6, double *out6, int *status);
 
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),

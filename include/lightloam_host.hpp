@@ -1010,6 +1010,24 @@ public:
     }
     /* ms[2]: the last evaluate, the last solve (device time); counts[3]: graphs, LM iterations, PCG iterations of the last call */
     void timing(double ms[2], long long counts[3]) { check(ll_posegraphs_timing(pg_, ms, counts)); }
+    /* LL_PG_PRECOND_BLOCK_JACOBI (the default) or LL_PG_PRECOND_CHAIN: the preconditioner of the solves from the next call on */
+    void set_preconditioner(int kind) { check(ll_posegraphs_set_preconditioner(pg_, kind)); }
+    int preconditioner() const { return ll_posegraphs_preconditioner(pg_); }
+    /* counts[2]: factorisations of the chain matrix, LM iterations that fell back to block-Jacobi, over the graphs of the last solve */
+    void precond_stats(long long counts[2]) { check(ll_posegraphs_precond_stats(pg_, counts)); }
+    /* ll_posegraphs_chain_solve: block-tridiagonal SPD systems back to back; diag36, upper36 [nodes][36], rhs6 [nodes][6] -> x [nodes][6];
+     * status[s] is 1 where a pivot of system s failed (its x is zeros) */
+    struct ChainSolution { std::vector<double> x; std::vector<int> status; };
+    ChainSolution chain_solve(const std::vector<int> &node_off, const std::vector<double> &diag36, const std::vector<double> &upper36,
+                              const std::vector<double> &rhs6) {
+        if (node_off.empty()) throw Error(LL_ERR_ARG, "node_off has one entry per system and one more");
+        const size_t n = (size_t)node_off.back();
+        if (diag36.size() != n * 36 || upper36.size() != n * 36 || rhs6.size() != n * 6) throw Error(LL_ERR_ARG, "36, 36 and 6 doubles per node");
+        ChainSolution s;
+        s.x.assign(n * 6, 0.0); s.status.assign(node_off.size() - 1, 0);
+        check(ll_posegraphs_chain_solve(pg_, (int)node_off.size() - 1, node_off.data(), diag36.data(), upper36.data(), rhs6.data(), s.x.data(), s.status.data()));
+        return s;
+    }
     ll_posegraphs *get() const { return pg_; }
 private:
     static void qmul(const double a[4], const double b[4], double o[4]) {

@@ -53,6 +53,7 @@ EXPORTS = [
     "ll_places_timing",
     "ll_pg_default_options", "ll_posegraphs_create", "ll_posegraphs_destroy", "ll_posegraphs_last_error", "ll_posegraphs_evaluate",
     "ll_posegraphs_solve", "ll_posegraphs_timing",
+    "ll_posegraphs_set_preconditioner", "ll_posegraphs_preconditioner", "ll_posegraphs_precond_stats", "ll_posegraphs_chain_solve",
     "ll_keyframes_create", "ll_keyframes_destroy", "ll_keyframes_last_error", "ll_keyframes_size", "ll_keyframes_reset", "ll_keyframes_info",
     "ll_keyframes_add_cubemaps", "ll_keyframes_add_points", "ll_keyframes_export",
     "ll_cubemaps_insert_keyframes", "ll_cubemaps_insert_timing", "ll_drives_set_keyframes", "ll_drives_correct",
@@ -216,6 +217,10 @@ def load_library():
         _lib.ll_posegraphs_evaluate.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         _lib.ll_posegraphs_solve.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         _lib.ll_posegraphs_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_posegraphs_set_preconditioner.argtypes = [C.c_void_p, C.c_int]
+        _lib.ll_posegraphs_preconditioner.argtypes = [C.c_void_p]
+        _lib.ll_posegraphs_precond_stats.argtypes = [C.c_void_p] * 2
+        _lib.ll_posegraphs_chain_solve.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
         _lib.ll_keyframes_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ll_keyframes_destroy.restype = None
         _lib.ll_keyframes_destroy.argtypes = [C.c_void_p]
@@ -1432,6 +1437,8 @@ class PgRecord(C.Structure):
 PG_EDGE = np.dtype([("i", "i4"), ("j", "i4"), ("Z_w7", "f8", (7,)), ("sqrt_info", "f8", (6,)), ("huber", "f8")])     # PgEdge as a numpy record
 PG_EDGE6 = np.dtype([("i", "i4"), ("j", "i4"), ("Z_w7", "f8", (7,)), ("S", "f8", (6, 6)), ("huber", "f8")])          # PgEdge6 as a numpy record
 PG_TERMINATION = {0: "gradient", 1: "function", 2: "parameter", 3: "iterations", 4: "radius", 5: "non-finite"}
+PG_PRECOND_BLOCK_JACOBI, PG_PRECOND_CHAIN = 0, 1                    # LL_PG_PRECOND_*: the preconditioner of a PoseGraphs' solves
+PG_PRECOND_NAMES = {"jacobi": PG_PRECOND_BLOCK_JACOBI, "chain": PG_PRECOND_CHAIN}
 
 
 def pg_options(**kw):
@@ -1577,6 +1584,41 @@ class PoseGraphs:
         ms = np.zeros(2); cnt = np.zeros(3, np.int64)
         self._ck(self.lib.ll_posegraphs_timing(self.h, _ptr(ms), _ptr(cnt)))
         return {"ms": ms.tolist(), "graphs": int(cnt[0]), "lm_iterations": int(cnt[1]), "pcg_iterations": int(cnt[2])}
+
+    def set_preconditioner(self, kind):
+        """PG_PRECOND_BLOCK_JACOBI (0, the default) or PG_PRECOND_CHAIN (1: the block-tridiagonal chain, by cyclic reduction), or the
+        names "jacobi" / "chain"; applies to the solves from the next call on, evaluate does not change"""
+        self._ck(self.lib.ll_posegraphs_set_preconditioner(self.h, int(PG_PRECOND_NAMES.get(kind, kind))))
+
+    @property
+    def preconditioner(self):
+        return int(self.lib.ll_posegraphs_preconditioner(self.h))
+
+    def precond_stats(self):
+        """{"factorisations", "fallbacks"}: factorisations of the chain matrix and LM iterations that fell back to block-Jacobi, summed
+        over the graphs of the last solve"""
+        cnt = np.zeros(2, np.int64)
+        self._ck(self.lib.ll_posegraphs_precond_stats(self.h, _ptr(cnt)))
+        return {"factorisations": int(cnt[0]), "fallbacks": int(cnt[1])}
+
+    def chain_solve(self, systems):
+        """ll_posegraphs_chain_solve: the chain preconditioner's solver alone.  systems: a list of (diag [N, 6, 6], upper [N, 6, 6] or
+        [N - 1, 6, 6] -- M[n][n+1] --, rhs [N, 6]) -> ([x [N, 6] per system], status [S] int32: 1 where a pivot failed, x zeros then)"""
+        node_off = [0]; diag = []; upper = []; rhs = []
+        for d, u, r in systems:
+            d = np.ascontiguousarray(d, np.float64).reshape(-1, 36)
+            u = np.asarray(u, np.float64).reshape(-1, 36)
+            if len(u) == len(d) - 1:
+                u = np.concatenate([u, np.zeros((1, 36))])
+            r = np.ascontiguousarray(r, np.float64).reshape(-1, 6)
+            if len(u) != len(d) or len(r) != len(d):
+                raise ValueError("diag, upper and rhs must have one block per node (upper may leave out the last)")
+            diag.append(d); upper.append(u); rhs.append(r); node_off.append(node_off[-1] + len(d))
+        cat = lambda parts, w: np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, w))
+        no = np.array(node_off, np.int32); diag = cat(diag, 36); upper = cat(upper, 36); rhs = cat(rhs, 6)
+        out = np.zeros_like(rhs); status = np.zeros(max(len(systems), 1), np.int32)
+        self._ck(self.lib.ll_posegraphs_chain_solve(self.h, len(systems), _ptr(no), _ptr(diag), _ptr(upper), _ptr(rhs), _ptr(out), _ptr(status)))
+        return [out[no[g]:no[g + 1]].copy() for g in range(len(systems))], status[:len(systems)]
 
 
 class DrivesParams(C.Structure):

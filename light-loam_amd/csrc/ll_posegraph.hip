@@ -30,7 +30,9 @@
  *               preconditioner block-Jacobi: ll_chol_solve on every node's damped 6 x 6 block.  A thread per node does the mat-vec
  *               over its incident edges' H_ij.  Dot products: thread-strided partial sums, then a fixed tree over the 256 partials (pg_sum2).
  *               Stops at |r| <= eta |g|, at max_pcg_iterations, or at a p^T A p that is not positive and finite (the iterate so far
- *               stays: CG's energy decreases monotonically, so it is the best one).
+ *               stays: CG's energy decreases monotonically, so it is the best one).  With ll_posegraphs_set_preconditioner(CHAIN) the
+ *               second instantiation of the kernel preconditions with the block-tridiagonal part of the matrix instead, by block
+ *               cyclic reduction inside the workgroup (further down); the block-Jacobi instantiation is the text as it was.
  *   accept      ll_lm_step.h's policy over all nodes: model cost change -(g.d + d.H d / 2), the parameter and function tests, rho, the
  *               radius update by 1 - (2 rho - 1)^3, a decrease factor that doubles with every rejection.  The candidate is judged by a
  *               cost-only pass over the edges; an accepted one is linearised anew.
@@ -55,6 +57,8 @@ struct PgArgs {
     double *out_nodes; ll_pg_record *rec; double *out_cost;
     ll_pg_options o;
     int solve;
+    /* the chain preconditioner's workspace, [nodes_total] rows, and its counts [graphs][2]; NULL under block-Jacobi */
+    double *cD, *cWL, *cWR, *cC, *cr; int *cstat;
 };
 
 struct ll_posegraphs {
@@ -66,6 +70,9 @@ struct ll_posegraphs {
     hipEvent_t ev[2] = {nullptr, nullptr};
     double ms[2] = {0.0, 0.0};
     long long counts[3] = {0, 0, 0};
+    int precond = LL_PG_PRECOND_BLOCK_JACOBI;
+    double *d_chain = nullptr;                 /* allocated when the chain preconditioner (or ll_posegraphs_chain_solve) is first asked for */
+    long long pc_counts[2] = {0, 0};
     std::string err;
 };
 
@@ -308,7 +315,246 @@ __device__ __forceinline__ bool pg_precondition(const PgGraph<Edge> &G, int n, d
 
 __device__ __forceinline__ bool pg_finite(double v) { return v - v == 0.0; }
 
+/* ------------------------------------------------------------------ device: the chain preconditioner
+ * M = the block-tridiagonal part of H + D / radius in node order (the contract is in the header), solved by block cyclic reduction
+ * inside the workgroup.  Level l, stride s = 2^l: the nodes n = s, 3s, 5s, ... are eliminated -- D_n is factored in place (Cholesky,
+ * lower triangle, the reciprocals of L's diagonal on the diagonal), W_left = M[n-s][n] D_n^-1 and W_right = M[n+s][n] D_n^-1 are formed
+ * a row at a time --, then every survivor a = 0, 2s, 4s, ... takes D_a -= W M[n][a] from its left eliminated neighbour, then from its
+ * right one, and the coupling to the next survivor, M[a][a+2s] = -W_left(a+s) M[a+s][a+2s].  C[a] is M[a][a + s] of the level at hand.
+ * Everything is relative to the system and every sum has a fixed shape; a thread holds one triangular factor and one row at a time. */
+struct PgChain { int N; double *D, *WL, *WR, *C, *r; };           /* one system's rows of the workspace */
+
+/* the lower triangle of A (row-major 6 x 6, in memory) -> L with L L^T = A, kept in registers as L[i * 6 + j], j < i, and 1 / L_ii on
+ * the diagonal; false at a pivot that is not positive and finite (L is not to be used then) */
+__device__ __forceinline__ bool pg_chol6(const double *A, double L[36])
+{
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double acc = A[i * 6 + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) acc -= L[i * 6 + k] * L[j * 6 + k];
+            if (i == j) { ok = ok && acc > 0.0 && pg_finite(acc); L[i * 6 + i] = 1.0 / sqrt(acc); }
+            else L[i * 6 + j] = acc * L[j * 6 + j];
+        }
+    return ok;
+}
+
+__device__ __forceinline__ void pg_chol6_store(const double L[36], double *A)
+{
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) A[i * 6 + j] = L[i * 6 + j];
+}
+
+__device__ __forceinline__ void pg_chol6_load(const double *A, double L[36])
+{
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) L[i * 6 + j] = A[i * 6 + j];
+}
+
+/* v <- (L L^T)^-1 v */
+__device__ __forceinline__ void pg_chol6_solve(const double L[36], double v[6])
+{
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double acc = v[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) acc -= L[i * 6 + k] * v[k];
+        v[i] = acc * L[i * 6 + i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double acc = v[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) acc -= L[k * 6 + i] * v[k];
+        v[i] = acc * L[i * 6 + i];
+    }
+}
+
+/* y -= W x (t == 0) or y -= W^T x (t == 1), W row-major in memory */
+__device__ __forceinline__ void pg_sub_matvec6(const double *W, const double *x, double y[6], int t)
+{
+    double u[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) u[k] = x[k];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        double acc = y[a];
+#pragma unroll
+        for (int b = 0; b < 6; ++b) acc -= (t ? W[b * 6 + a] : W[a * 6 + b]) * u[b];
+        y[a] = acc;
+    }
+}
+
+/* Factorises the system whose diagonal blocks are in S.D and couplings M[n][n+1] in S.C (the last one is not read); both are overwritten.
+ * -> true, the same in every thread, iff every pivot was positive and finite.  Ends behind a barrier. */
+__device__ bool pg_chain_factor(const PgChain &S, double *sh)
+{
+    const long long N = S.N;
+    double bad = 0.0;
+    for (long long s = 1; s < N; s <<= 1) {
+        for (long long n = s + 2 * s * threadIdx.x; n < N; n += 2 * s * PG_THREADS) {           /* eliminate */
+            double L[36], v[6];
+            double *Dn = S.D + (size_t)n * 36;
+            if (!pg_chol6(Dn, L)) bad = 1.0;
+            pg_chol6_store(L, Dn);
+            const double *Ca = S.C + (size_t)(n - s) * 36, *Cn = S.C + (size_t)n * 36;
+            double *WL = S.WL + (size_t)n * 36, *WR = S.WR + (size_t)n * 36;
+#pragma unroll 1
+            for (int i = 0; i < 6; ++i) {                          /* row i of M[n-s][n] D_n^-1 = (D_n^-1 row_i(M[n-s][n])^T)^T */
+#pragma unroll
+                for (int k = 0; k < 6; ++k) v[k] = Ca[i * 6 + k];
+                pg_chol6_solve(L, v);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) WL[i * 6 + k] = v[k];
+            }
+            if (n + s < N) {
+#pragma unroll 1
+                for (int i = 0; i < 6; ++i) {                      /* M[n+s][n] = M[n][n+s]^T: its row i is column i of C[n] */
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) v[k] = Cn[k * 6 + i];
+                    pg_chol6_solve(L, v);
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) WR[i * 6 + k] = v[k];
+                }
+            }
+        }
+        __syncthreads();
+        for (long long a = 2 * s * threadIdx.x; a < N; a += 2 * s * PG_THREADS) {               /* gather: left neighbour, then right */
+            double *Da = S.D + (size_t)a * 36, *Ca = S.C + (size_t)a * 36;
+            if (a >= s) {
+                const double *W = S.WR + (size_t)(a - s) * 36, *Cl = S.C + (size_t)(a - s) * 36;           /* M[a][l] D_l^-1, M[l][a] */
+#pragma unroll 1
+                for (int i = 0; i < 6; ++i) {
+                    double w[6];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) w[k] = W[i * 6 + k];
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) {
+                        double acc = Da[i * 6 + j];
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) acc -= w[k] * Cl[k * 6 + j];
+                        Da[i * 6 + j] = acc;
+                    }
+                }
+            }
+            if (a + s < N) {
+                const double *W = S.WL + (size_t)(a + s) * 36, *Cr = S.C + (size_t)(a + s) * 36;           /* M[a][rt] D_rt^-1, M[rt][a+2s] */
+#pragma unroll 1
+                for (int i = 0; i < 6; ++i) {
+                    double w[6];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) w[k] = W[i * 6 + k];
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) {                  /* M[rt][a] = C[a]^T */
+                        double acc = Da[i * 6 + j];
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) acc -= w[k] * Ca[j * 6 + k];
+                        Da[i * 6 + j] = acc;
+                    }
+                }
+                if (a + 2 * s < N) {
+#pragma unroll 1
+                    for (int i = 0; i < 6; ++i) {                  /* C[a] is read no more: the next level's coupling goes there */
+                        double w[6];
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) w[k] = W[i * 6 + k];
+#pragma unroll
+                        for (int j = 0; j < 6; ++j) {
+                            double acc = 0.0;
+#pragma unroll
+                            for (int k = 0; k < 6; ++k) acc -= w[k] * Cr[k * 6 + j];
+                            Ca[i * 6 + j] = acc;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double L[36];
+        if (!pg_chol6(S.D, L)) bad = 1.0;
+        pg_chol6_store(L, S.D);
+    }
+    return !(pg_max(bad, sh) > 0.0);                              /* its barriers publish node 0's factor */
+}
+
+/* z = M^-1 r by the factors pg_chain_factor left: S.r holds r on entry (published) and is used up; z [N][6].  Ends behind a barrier. */
+__device__ void pg_chain_apply(const PgChain &S, double *z)
+{
+    const long long N = S.N;
+    long long top = 0;
+    for (long long s = 1; s < N; s <<= 1) {
+        top = s;
+        for (long long a = 2 * s * threadIdx.x; a < N; a += 2 * s * PG_THREADS) {
+            double y[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) y[k] = S.r[(size_t)a * 6 + k];
+            if (a >= s) pg_sub_matvec6(S.WR + (size_t)(a - s) * 36, S.r + (size_t)(a - s) * 6, y, 0);
+            if (a + s < N) pg_sub_matvec6(S.WL + (size_t)(a + s) * 36, S.r + (size_t)(a + s) * 6, y, 0);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) S.r[(size_t)a * 6 + k] = y[k];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double L[36], y[6];
+        pg_chol6_load(S.D, L);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) y[k] = S.r[k];
+        pg_chol6_solve(L, y);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) z[k] = y[k];
+    }
+    __syncthreads();
+    for (long long s = top; s >= 1; s >>= 1) {
+        for (long long n = s + 2 * s * threadIdx.x; n < N; n += 2 * s * PG_THREADS) {
+            double L[36], y[6];
+            pg_chol6_load(S.D + (size_t)n * 36, L);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) y[k] = S.r[(size_t)n * 6 + k];
+            pg_chol6_solve(L, y);
+            pg_sub_matvec6(S.WL + (size_t)n * 36, z + (size_t)(n - s) * 6, y, 1);
+            if (n + s < N) pg_sub_matvec6(S.WR + (size_t)n * 36, z + (size_t)(n + s) * 6, y, 1);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) z[(size_t)n * 6 + k] = y[k];
+        }
+        __syncthreads();
+    }
+}
+
+/* the graph's M at 1 / radius into S.D and S.C: fixed nodes an identity block and no coupling; C[n] = the sum over the edges between n
+ * and n + 1, both free, in edge order (the node's incident list), H_ij where i == n and its transpose where i == n + 1 */
 template <typename Edge>
+__device__ void pg_chain_matrix(const PgGraph<Edge> &G, const PgChain &S, double inv_radius)
+{
+    for (int n = threadIdx.x; n < G.N; n += PG_THREADS) {
+        double *Dn = S.D + (size_t)n * 36, *Cn = S.C + (size_t)n * 36;
+        const bool fx = G.fixed[n] != 0;
+        for (int k = 0; k < 36; ++k) { Dn[k] = fx ? 0.0 : G.Hd[(size_t)n * 36 + k]; Cn[k] = 0.0; }
+        for (int k = 0; k < 6; ++k) Dn[k * 7] = fx ? 1.0 : Dn[k * 7] + G.D[(size_t)n * 6 + k] * inv_radius;
+        if (fx || n + 1 >= G.N || G.fixed[n + 1]) continue;
+        for (int q = G.inc_off[G.n0 + n]; q < G.inc_off[G.n0 + n + 1]; ++q) {
+            if (G.inc_nb[q] != n + 1) continue;
+            const int code = G.inc[q], e = code >> 1, side = code & 1;
+            const double *Hij = G.eH + (size_t)e * 108;
+            if (side == 0) { for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) Cn[a * 6 + b] += Hij[a * 6 + b]; }
+            else           { for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) Cn[a * 6 + b] += Hij[b * 6 + a]; }
+        }
+    }
+    __syncthreads();
+}
+
+/* Precond: LL_PG_PRECOND_BLOCK_JACOBI (0) is the text as it was; LL_PG_PRECOND_CHAIN (1) factorises M once per LM iteration and applies
+ * it once per PCG iteration, block-Jacobi for the iteration where a pivot failed */
+template <typename Edge, int Precond>
 __global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgArgs<Edge> A)
 {
     __shared__ double sh[8];
@@ -342,6 +588,12 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgArgs<Edge> A)
     double radius = o.initial_radius, decrease = 2.0, grad_max = 0.0;
     int iterations = 0, successes = 0, n_pcg = 0, term = 3;
     bool lin_ok = true;                                            /* the linearisation at x is finite */
+    PgChain S;
+    int n_factor = 0, n_fallback = 0;
+    if constexpr (Precond == LL_PG_PRECOND_CHAIN) {
+        S.N = G.N; S.D = A.cD + (size_t)G.n0 * 36; S.WL = A.cWL + (size_t)G.n0 * 36; S.WR = A.cWR + (size_t)G.n0 * 36;
+        S.C = A.cC + (size_t)G.n0 * 36; S.r = A.cr + (size_t)G.n0 * 6;
+    }
     for (int iter = 0; iter <= o.max_lm_iterations; ++iter) {     /* every pass below counts one iteration */
         /* ---- can the minimiser continue?  (non-finite, iteration limit, gradient, radius) */
         double gm = 0.0, hs = 0.0;
@@ -365,6 +617,28 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgArgs<Edge> A)
         /* ---- (H + D / radius) d = -g by preconditioned conjugate gradients */
         const double inv_radius = 1.0 / radius;
         double rz = 0.0, gg = 0.0;
+        bool chain = false;                                        /* M is factored: this iteration's preconditioner is the chain */
+        if constexpr (Precond == LL_PG_PRECOND_CHAIN) {            /* M depends on the radius: once per LM iteration */
+            pg_chain_matrix(G, S, inv_radius);
+            chain = pg_chain_factor(S, sh);
+            ++n_factor;
+            if (!chain) ++n_fallback;
+            if (chain) {
+                for (int k = tid; k < G.N * 6; k += PG_THREADS) S.r[k] = G.fixed[k / 6] ? 0.0 : -G.g[k];
+                __syncthreads();
+                pg_chain_apply(S, G.z);
+            }
+        }
+        if (chain) {
+            for (int n = tid; n < G.N; n += PG_THREADS) {
+                const bool fx = G.fixed[n] != 0;
+                for (int k = 0; k < 6; ++k) {
+                    const double r = -G.g[(size_t)n * 6 + k], z = fx ? 0.0 : G.z[(size_t)n * 6 + k];
+                    G.d[(size_t)n * 6 + k] = 0.0; G.r[(size_t)n * 6 + k] = r; G.z[(size_t)n * 6 + k] = z; G.p[(size_t)n * 6 + k] = z;
+                    rz += r * z; gg += r * r;
+                }
+            }
+        } else                                                     /* block-Jacobi, the text as it was */
         for (int n = tid; n < G.N; n += PG_THREADS) {
             double r[6], z[6];
             for (int k = 0; k < 6; ++k) { r[k] = -G.g[(size_t)n * 6 + k]; z[k] = 0.0; }
@@ -385,6 +659,24 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgArgs<Edge> A)
             if (!(pAp > 0.0) || !pg_finite(pAp) || !pg_finite(rz)) break;
             const double alpha = rz / pAp;
             double rr = 0.0, rz2 = 0.0;
+            if (chain) {
+                for (int n = tid; n < G.N; n += PG_THREADS)
+                    for (int a = 0; a < 6; ++a) {
+                        G.d[(size_t)n * 6 + a] += alpha * G.p[(size_t)n * 6 + a];
+                        const double r = G.r[(size_t)n * 6 + a] - alpha * G.Ap[(size_t)n * 6 + a];
+                        G.r[(size_t)n * 6 + a] = r; S.r[(size_t)n * 6 + a] = G.fixed[n] ? 0.0 : r;
+                        rr += r * r;
+                    }
+                __syncthreads();
+                pg_chain_apply(S, G.z);
+                for (int n = tid; n < G.N; n += PG_THREADS) {
+                    const bool fx = G.fixed[n] != 0;
+                    for (int a = 0; a < 6; ++a) {
+                        const double z = fx ? 0.0 : G.z[(size_t)n * 6 + a];
+                        G.z[(size_t)n * 6 + a] = z; rz2 += G.r[(size_t)n * 6 + a] * z;
+                    }
+                }
+            } else                                                 /* block-Jacobi, the text as it was */
             for (int n = tid; n < G.N; n += PG_THREADS) {
                 double r[6], z[6];
                 for (int a = 0; a < 6; ++a) {
@@ -461,7 +753,25 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgArgs<Edge> A)
         R.cost0 = cost0; R.cost = cost; R.grad_max = grad_max;
         R.lm_iterations = iterations; R.lm_successes = successes; R.pcg_iterations = n_pcg; R.termination = term;
         A.rec[gi] = R;
+        if constexpr (Precond == LL_PG_PRECOND_CHAIN) { A.cstat[gi * 2] = n_factor; A.cstat[gi * 2 + 1] = n_fallback; }
     }
+}
+
+/* ll_posegraphs_chain_solve: system = blockIdx.x; its diagonal blocks, couplings and right-hand side are in the workspace's D, C and r */
+__global__ __launch_bounds__(PG_THREADS) void k_pg_chain_solve(const int *node_off, double *cD, double *cWL, double *cWR, double *cC, double *cr,
+                                                               double *cz, int *status)
+{
+    __shared__ double sh[8];
+    const int n0 = node_off[blockIdx.x];
+    PgChain S;
+    S.N = node_off[blockIdx.x + 1] - n0;
+    S.D = cD + (size_t)n0 * 36; S.WL = cWL + (size_t)n0 * 36; S.WR = cWR + (size_t)n0 * 36; S.C = cC + (size_t)n0 * 36; S.r = cr + (size_t)n0 * 6;
+    double *z = cz + (size_t)n0 * 6;
+    if (S.N < 1) { if (threadIdx.x == 0) status[blockIdx.x] = 0; return; }
+    const bool ok = pg_chain_factor(S, sh);
+    if (ok) pg_chain_apply(S, z);
+    else for (int k = threadIdx.x; k < S.N * 6; k += PG_THREADS) z[k] = 0.0;
+    if (threadIdx.x == 0) status[blockIdx.x] = ok ? 0 : 1;
 }
 
 /* ------------------------------------------------------------------ host side */
@@ -497,7 +807,7 @@ extern "C" void ll_posegraphs_destroy(ll_posegraphs *pg)
 {
     if (!pg) return;
     (void)hipSetDevice(pg->ctx->device);
-    for (void *p : {(void *)pg->d_in, (void *)pg->d_out, (void *)pg->d_ws}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)pg->d_in, (void *)pg->d_out, (void *)pg->d_ws, (void *)pg->d_chain}) if (p) (void)hipFree(p);
     for (hipEvent_t e : pg->ev) if (e) (void)hipEventDestroy(e);
     delete pg;
 }
@@ -533,6 +843,54 @@ extern "C" int ll_posegraphs_create(ll_ctx *ctx, int max_graphs, int max_nodes_t
 }
 
 extern "C" const char *ll_posegraphs_last_error(const ll_posegraphs *pg) { return pg ? pg->err.c_str() : "posegraphs: NULL handle"; }
+
+/* the chain preconditioner's workspace for max_nodes and max_graphs: per node the factored block, both W and the coupling (36 doubles
+ * each), the right-hand side and z of ll_posegraphs_chain_solve (6 each); per graph the offsets and status of chain_solve and 2 counts */
+struct PgChainWs { double *D, *WL, *WR, *C, *r, *z; int *node_off, *stat, *status; size_t bytes; };
+
+static PgChainWs pg_chain_ws(const ll_posegraphs *pg)
+{
+    const size_t N = (size_t)pg->max_nodes, G = (size_t)pg->max_graphs;
+    PgChainWs w;
+    double *d = pg->d_chain;
+    w.D = d; d += N * 36; w.WL = d; d += N * 36; w.WR = d; d += N * 36; w.C = d; d += N * 36; w.r = d; d += N * 6; w.z = d; d += N * 6;
+    int *i = (int *)d;
+    w.node_off = i; i += G + 1; w.stat = i; i += 2 * G; w.status = i; i += G;
+    w.bytes = N * 156 * sizeof(double) + (4 * G + 1) * sizeof(int);
+    return w;
+}
+
+static int pg_chain_alloc(ll_posegraphs *pg)
+{
+    if (pg->d_chain) return LL_OK;
+    const size_t bytes = pg_chain_ws(pg).bytes;
+    if (hipSetDevice(pg->ctx->device) != hipSuccess || hipMalloc((void **)&pg->d_chain, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        pg->d_chain = nullptr;
+        return pg_fail(pg, LL_ERR_HIP, "the chain preconditioner's workspace could not be allocated (" + std::to_string(bytes) + " bytes)");
+    }
+    return LL_OK;
+}
+
+extern "C" int ll_posegraphs_set_preconditioner(ll_posegraphs *pg, int kind)
+{
+    if (!pg) return LL_ERR_ARG;
+    if (kind != LL_PG_PRECOND_BLOCK_JACOBI && kind != LL_PG_PRECOND_CHAIN)
+        return pg_fail(pg, LL_ERR_ARG, "set_preconditioner: kind " + std::to_string(kind) + " is neither LL_PG_PRECOND_BLOCK_JACOBI nor LL_PG_PRECOND_CHAIN");
+    if (kind == LL_PG_PRECOND_CHAIN) { const int rc = pg_chain_alloc(pg); if (rc) return rc; }
+    pg->precond = kind;
+    return LL_OK;
+}
+
+extern "C" int ll_posegraphs_preconditioner(const ll_posegraphs *pg) { return pg ? pg->precond : LL_ERR_ARG; }
+
+/* counts2: factorisations of M, and LM iterations that fell back to block-Jacobi, over the graphs of the last solve */
+extern "C" int ll_posegraphs_precond_stats(ll_posegraphs *pg, long long counts2[2])
+{
+    if (!pg || !counts2) return LL_ERR_ARG;
+    counts2[0] = pg->pc_counts[0]; counts2[1] = pg->pc_counts[1];
+    return LL_OK;
+}
 
 static bool pg_finite7(const double *p, int n) { for (int k = 0; k < n; ++k) if (!std::isfinite(p[k])) return false; return true; }
 static bool pg_zero_quat(const double *q) { return q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0; }
@@ -596,7 +954,9 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
     }
     pg->counts[0] = n_graphs; pg->counts[1] = pg->counts[2] = 0;
     pg->ms[solve ? 1 : 0] = 0.0;
+    if (solve) pg->pc_counts[0] = pg->pc_counts[1] = 0;
     if (n_graphs == 0) return LL_OK;
+    const bool chain = solve && pg->precond == LL_PG_PRECOND_CHAIN;                /* evaluate solves nothing */
 
     /* ---- pack: poses, edges, offsets, the node -> incident-edge lists (edge order), fixed */
     size_t off[9];
@@ -604,7 +964,8 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
     const size_t per_node = solve ? 7 : 6;
     const size_t out_b_bytes = solve ? (size_t)n_graphs * sizeof(ll_pg_record) : (size_t)n_graphs * sizeof(double);
     const size_t down = (size_t)N * per_node * sizeof(double) + out_b_bytes;
-    unsigned char *pin = (unsigned char *)ll_pinned_scratch(off[8] + pg_up8(down));
+    const size_t stat_bytes = chain ? (size_t)n_graphs * 2 * sizeof(int) : 0;
+    unsigned char *pin = (unsigned char *)ll_pinned_scratch(off[8] + pg_up8(down) + stat_bytes);
     if (!pin) return bad(LL_ERR_HIP, "no page-locked scratch");
     if (N > 0) std::memcpy(pin + off[0], poses_w7, (size_t)N * 7 * sizeof(double));
     if (E > 0) std::memcpy(pin + off[1], edges, (size_t)E * sizeof(Edge));
@@ -645,12 +1006,20 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
     A.out_nodes = (double *)pg->d_out;
     A.rec = (ll_pg_record *)(pg->d_out + Nn * per_node * sizeof(double)); A.out_cost = (double *)A.rec;
     A.o = o; A.solve = solve ? 1 : 0;
+    A.cD = A.cWL = A.cWR = A.cC = A.cr = nullptr; A.cstat = nullptr;
+    if (chain) {
+        const PgChainWs cw = pg_chain_ws(pg);
+        A.cD = cw.D; A.cWL = cw.WL; A.cWR = cw.WR; A.cC = cw.C; A.cr = cw.r; A.cstat = cw.stat;
+    }
     PG_HIP(hipEventRecord(pg->ev[0], st));
-    hipLaunchKernelGGL(k_pg_solve<Edge>, dim3((unsigned)n_graphs), dim3(PG_THREADS), 0, st, A);
+    if (chain) hipLaunchKernelGGL((k_pg_solve<Edge, LL_PG_PRECOND_CHAIN>), dim3((unsigned)n_graphs), dim3(PG_THREADS), 0, st, A);
+    else hipLaunchKernelGGL((k_pg_solve<Edge, LL_PG_PRECOND_BLOCK_JACOBI>), dim3((unsigned)n_graphs), dim3(PG_THREADS), 0, st, A);
     PG_HIP(hipEventRecord(pg->ev[1], st));
     PG_HIP(hipGetLastError());
     unsigned char *pout = pin + off[8];
     PG_HIP(hipMemcpyAsync(pout, pg->d_out, down, hipMemcpyDeviceToHost, st));
+    const int *pstat = (const int *)(pout + pg_up8(down));
+    if (chain) PG_HIP(hipMemcpyAsync((void *)pstat, A.cstat, stat_bytes, hipMemcpyDeviceToHost, st));
     PG_HIP(hipStreamSynchronize(st));                              /* the ONE synchronisation */
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, pg->ev[0], pg->ev[1]) == hipSuccess) pg->ms[solve ? 1 : 0] = (double)ms;
@@ -667,6 +1036,7 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
     double *poses_out = out_a;
     for (int g = 0; g < n_graphs; ++g) {
         pg->counts[1] += recs[g].lm_iterations; pg->counts[2] += recs[g].pcg_iterations;
+        if (chain) { pg->pc_counts[0] += pstat[2 * g]; pg->pc_counts[1] += pstat[2 * g + 1]; }
         if (recs[g].lm_successes == 0) continue;                  /* nothing accepted: the input comes back bit for bit */
         for (int k = node_off[g]; k < node_off[g + 1]; ++k)       /* so do fixed nodes and nodes without an edge */
             if (!fx[k] && inc_off[k + 1] > inc_off[k]) std::memcpy(poses_out + (size_t)k * 7, nodes + (size_t)k * 7, 7 * sizeof(double));
@@ -745,5 +1115,56 @@ extern "C" int ll_posegraphs_timing(ll_posegraphs *pg, double *ms2, long long *c
     if (!pg) return LL_ERR_ARG;
     if (ms2) for (int k = 0; k < 2; ++k) ms2[k] = pg->ms[k];
     if (counts3) for (int k = 0; k < 3; ++k) counts3[k] = pg->counts[k];
+    return LL_OK;
+}
+
+/* the chain preconditioner's solver alone: n_systems block-tridiagonal systems, one workgroup each, the device functions k_pg_solve
+ * uses.  Validates, packs into page-locked scratch, uploads into the workspace, launches, downloads, synchronises ONCE. */
+extern "C" int ll_posegraphs_chain_solve(ll_posegraphs *pg, int n_systems, const int *node_off, const double *diag36, const double *upper36,
+                                         const double *rhs6, double *out6, int *status)
+{
+    if (!pg) return LL_ERR_ARG;
+    auto bad = [&](int code, const std::string &what) { return pg_fail(pg, code, "chain_solve: " + what); };
+    if (n_systems < 0 || !node_off) return bad(LL_ERR_ARG, "n_systems < 0, or node_off is NULL");
+    if (n_systems > pg->max_graphs) return bad(LL_ERR_CAPACITY, std::to_string(n_systems) + " systems exceed max_graphs " + std::to_string(pg->max_graphs));
+    if (node_off[0] != 0) return bad(LL_ERR_ARG, "offsets must start at 0");
+    for (int g = 0; g < n_systems; ++g)
+        if (node_off[g + 1] < node_off[g]) return bad(LL_ERR_ARG, "system " + std::to_string(g) + ": offsets do not ascend");
+    const int N = node_off[n_systems];
+    if (N > pg->max_nodes) return bad(LL_ERR_CAPACITY, std::to_string(N) + " nodes exceed max_nodes_total " + std::to_string(pg->max_nodes));
+    if (n_systems > 0 && !status) return bad(LL_ERR_ARG, "status is NULL");
+    if (N > 0 && (!diag36 || !upper36 || !rhs6 || !out6)) return bad(LL_ERR_ARG, "diag36, upper36, rhs6 or out6 is NULL");
+    for (int g = 0; g < n_systems; ++g)
+        for (int k = node_off[g]; k < node_off[g + 1]; ++k) {
+            const bool last = k + 1 == node_off[g + 1];            /* its coupling is not read */
+            if (!pg_finite7(diag36 + (size_t)k * 36, 36) || (!last && !pg_finite7(upper36 + (size_t)k * 36, 36)) || !pg_finite7(rhs6 + (size_t)k * 6, 6))
+                return bad(LL_ERR_ARG, "system " + std::to_string(g) + ", node " + std::to_string(k - node_off[g]) + ": a block or the right-hand side is not finite");
+        }
+    if (n_systems == 0) return LL_OK;
+    { const int rc = pg_chain_alloc(pg); if (rc) return rc; }
+
+    const size_t Nn = (size_t)N, b36 = Nn * 36 * sizeof(double), b6 = Nn * 6 * sizeof(double);
+    const size_t boff = pg_up8((size_t)(n_systems + 1) * sizeof(int)), bstat = pg_up8((size_t)n_systems * sizeof(int));
+    unsigned char *pin = (unsigned char *)ll_pinned_scratch(boff + 2 * b36 + 2 * b6 + bstat);
+    if (!pin) return bad(LL_ERR_HIP, "no page-locked scratch");
+    unsigned char *p_diag = pin + boff, *p_up = p_diag + b36, *p_rhs = p_up + b36, *p_out = p_rhs + b6, *p_stat = p_out + b6;
+    std::memcpy(pin, node_off, (size_t)(n_systems + 1) * sizeof(int));
+    if (N > 0) { std::memcpy(p_diag, diag36, b36); std::memcpy(p_up, upper36, b36); std::memcpy(p_rhs, rhs6, b6); }
+    const PgChainWs cw = pg_chain_ws(pg);
+    PG_HIP(hipSetDevice(pg->ctx->device));
+    hipStream_t st = pg->ctx->stream;
+    PG_HIP(hipMemcpyAsync(cw.node_off, pin, (size_t)(n_systems + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (N > 0) {
+        PG_HIP(hipMemcpyAsync(cw.D, p_diag, b36, hipMemcpyHostToDevice, st));
+        PG_HIP(hipMemcpyAsync(cw.C, p_up, b36, hipMemcpyHostToDevice, st));
+        PG_HIP(hipMemcpyAsync(cw.r, p_rhs, b6, hipMemcpyHostToDevice, st));
+    }
+    hipLaunchKernelGGL(k_pg_chain_solve, dim3((unsigned)n_systems), dim3(PG_THREADS), 0, st, cw.node_off, cw.D, cw.WL, cw.WR, cw.C, cw.r, cw.z, cw.status);
+    PG_HIP(hipGetLastError());
+    if (N > 0) PG_HIP(hipMemcpyAsync(p_out, cw.z, b6, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipMemcpyAsync(p_stat, cw.status, (size_t)n_systems * sizeof(int), hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));                              /* the ONE synchronisation */
+    if (N > 0) std::memcpy(out6, p_out, b6);
+    std::memcpy(status, p_stat, (size_t)n_systems * sizeof(int));
     return LL_OK;
 }

@@ -18,8 +18,19 @@
 The capability is new, so there is no earlier figure to compare with.  `restatement` is the wall time of the numpy dense LM of
 tests/posegraphcases.py on the 512-node graph: an independent restatement that the tests use as their reference, not a competitor.
 Prints one JSON line and writes it to --out.
+
+    python tools/bench_posegraph.py --preconditioner both [--parent-root DIR] [--out profiles/posegraph_chain.json]
+
+  --preconditioner  jacobi (the default: everything above, unchanged), chain (the same figures under LL_PG_PRECOND_CHAIN), or both:
+             the same graphs under each kind, every (kind, repeat) a fresh process as above, kinds alternating.  With --parent-root DIR
+             (a built checkout of the parent commit, as tools/bench_info.py takes it) the parent's library solves them too, under its
+             only preconditioner, and `default_bits_equal_parent` says per configuration whether this tree's block-Jacobi poses and
+             records are byte for byte the parent's (a SHA-256 over graph 0 .. batch - 1 of every process).  The file holds, per kind
+             and (N, batch): device ms (median, minimum, maximum), LM and PCG iterations, factorisations and fallbacks, the final cost
+             and the largest lap gap, and `chain_over_jacobi`, the ratio of the median device times.
 """
 import argparse
+import hashlib
 import json
 import os
 import subprocess
@@ -29,7 +40,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# a child of --preconditioner both that measures the parent's library imports the parent's package
+sys.path.insert(0, sys.argv[sys.argv.index("--root") + 1] if "--root" in sys.argv[:-1] else ROOT)
 import lightloam_amd  # noqa: E402,F401
 from lightloam_amd import api  # noqa: E402
 
@@ -75,6 +87,8 @@ def child(a):
     ctx = api.Context(api.default_params(16, batch=1, max_points=1024))
     nmax, bmax = max(nodes), max(batches)
     pg = ctx.posegraphs(bmax, nmax * bmax, (nmax + nmax // 100) * bmax)
+    if a.kind == "chain":
+        pg.set_preconditioner(api.PG_PRECOND_CHAIN)
     pg.solve([lap_graph(min(nodes), 0)])
     out = {}
     for n in nodes:
@@ -92,6 +106,13 @@ def child(a):
                                      "termination": r.termination, "cost0": r.cost0, "cost": r.cost,
                                      "lm_iterations_batch": t["lm_iterations"], "pcg_iterations_batch": t["pcg_iterations"],
                                      "lap_gap_before_m": drift0, "lap_gap_after_m": drift1}
+            if a.kind:                                              # the comparison's extras; the parent's package has no precond_stats
+                h = hashlib.sha256()
+                for g in range(b):
+                    h.update(x[g].tobytes()); h.update(bytes(memoryview(rec[g])))
+                stats = pg.precond_stats() if hasattr(pg, "precond_stats") else {"factorisations": 0, "fallbacks": 0}
+                out["%dx%d" % (n, b)].update({"sha256": h.hexdigest(), "factorisations_batch": stats["factorisations"],
+                                              "fallbacks_batch": stats["fallbacks"]})
             print("# %dx%d: %s" % (n, b, out["%dx%d" % (n, b)]), file=sys.stderr, flush=True)
     pg.close(); ctx.close()
     print(json.dumps(out))
@@ -108,6 +129,50 @@ def restatement(n):
             "nodes": n, "wall_s": time.perf_counter() - t0, "iterations": it, "gradient_max": gmax}
 
 
+def compare(a):
+    """--preconditioner chain / both: per kind the children's figures side by side"""
+    kinds = [("jacobi", ROOT), ("chain", ROOT)] if a.preconditioner == "both" else [("chain", ROOT)]
+    if a.parent_root:
+        if not os.path.exists(os.path.join(a.parent_root, "light-loam_amd", "liblightloam_hip.so")):
+            sys.exit("--parent-root must name a built checkout of the parent commit (light-loam_amd/liblightloam_hip.so in it)")
+        kinds.insert(0, ("parent", os.path.abspath(a.parent_root)))
+    runs = {k: [] for k, _ in kinds}
+    for p in range(a.processes):                                   # fresh processes, one after the other, the kinds alternating
+        for kind, root in kinds:
+            env = dict(os.environ); env.pop("LIGHTLOAM_HIP_LIB", None)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--nodes", a.nodes, "--batches", a.batches,
+                                "--kind", "chain" if kind == "chain" else "jacobi", "--root", root],
+                               stdout=subprocess.PIPE, check=True, timeout=1500, env=env, cwd=root)
+            runs[kind].append(json.loads(r.stdout.decode().strip().splitlines()[-1]))
+    keep = ("nodes", "edges", "batch", "lm_iterations", "lm_successes", "pcg_iterations", "termination", "cost0", "cost", "lm_iterations_batch",
+            "pcg_iterations_batch", "factorisations_batch", "fallbacks_batch", "lap_gap_before_m", "lap_gap_after_m")
+    res = {"tool": "tools/bench_posegraph.py", "preconditioner": a.preconditioner, "processes": a.processes,
+           "what": "device ms of the solve's one launch (ll_posegraphs_timing), median over fresh processes; iterations, cost and lap gap of "
+                   "graph 0, *_batch summed over the batch; parent = the parent commit's library (block-Jacobi only)",
+           "kinds": {}}
+    for kind, _ in kinds:
+        res["kinds"][kind] = {}
+        for key in runs[kind][0]:
+            ms = [r[key]["device_ms"] for r in runs[kind]]
+            e = {k: runs[kind][0][key][k] for k in keep}
+            e.update({"device_ms": float(np.median(ms)), "device_ms_min": min(ms), "device_ms_max": max(ms),
+                      "same_bits_in_every_process": len({r[key]["sha256"] for r in runs[kind]}) == 1})
+            res["kinds"][kind][key] = e
+    K = res["kinds"]
+    if "jacobi" in K:
+        res["chain_over_jacobi"] = {key: K["chain"][key]["device_ms"] / K["jacobi"][key]["device_ms"] for key in K["chain"]}
+    if "parent" in K and "jacobi" in K:
+        res["default_bits_equal_parent"] = {key: {r[key]["sha256"] for r in runs["jacobi"]} == {r[key]["sha256"] for r in runs["parent"]}
+                                            and K["jacobi"][key]["same_bits_in_every_process"] for key in K["jacobi"]}
+        res["jacobi_over_parent"] = {key: K["jacobi"][key]["device_ms"] / K["parent"][key]["device_ms"] for key in K["jacobi"]}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", default="512,2048,4541")
@@ -115,10 +180,18 @@ def main():
     ap.add_argument("--processes", type=int, default=5)
     ap.add_argument("--restatement-nodes", type=int, default=512)
     ap.add_argument("--child", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "posegraph.json"))
+    ap.add_argument("--out", default=None, help="profiles/posegraph.json; profiles/posegraph_chain.json for --preconditioner chain or both")
+    ap.add_argument("--preconditioner", choices=["jacobi", "chain", "both"], default="jacobi")
+    ap.add_argument("--parent-root", help="with --preconditioner both: a built checkout of the parent commit, measured beside this tree")
+    ap.add_argument("--kind", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--root", default=ROOT, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
         return child(a)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "posegraph.json" if a.preconditioner == "jacobi" else "posegraph_chain.json")
+    if a.preconditioner != "jacobi":
+        return compare(a)
     runs = []
     for p in range(a.processes):                                   # fresh processes, one after the other
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--nodes", a.nodes, "--batches", a.batches],
