@@ -982,7 +982,8 @@ int  ll_places_timing(ll_places *db, double *ms, long long *counts);
  *                           edges in all (about 850 B per node, 1.35 KB per edge: the upload holds either edge type).
  *   ll_posegraphs_evaluate  cost[n_graphs], the robustified cost of every graph at poses_w7, and grad6[nodes][6], its gradient with
  *                           respect to the increments (zeros at fixed nodes).  Solves nothing: the chi-square of a candidate loop edge
- *                           before it is accepted, and the tests' window onto the Jacobians.
+ *                           before it is accepted -- by the candidate's own information alone; ll_pg_edge_gate, below, also weighs
+ *                           how uncertain the graph is about the two poses -- and the tests' window onto the Jacobians.
  *   ll_posegraphs_solve     optimises poses_w7 in place; rec (may be NULL) gets one record per graph: the cost at the start and at the
  *                           returned poses, the max-norm of Plus(x, -g) - x there, LM iterations, accepted steps, PCG iterations and
  *                           termination: 0 gradient_tolerance, 1 function_tolerance, 2 parameter_tolerance, 3 max_lm_iterations,
@@ -1061,6 +1062,61 @@ int  ll_posegraphs_precond_stats(ll_posegraphs *pg, long long counts2[2]);
 int  ll_posegraphs_chain_solve(ll_posegraphs *pg, int n_systems, const int *node_off,
                                const double *diag36, const double *upper36,
                                const double *rhs6, double *out6, int *status);
+/* The graph's own covariance: joint covariances of pose pairs (g2o's computeMarginals, Ceres' Covariance, GTSAM's Marginals), and the
+ * Mahalanobis gate on a candidate loop edge that they make possible.
+ *   H is the Gauss-Newton matrix the solves linearise at poses_w7: J^T J with the Huber scale, over the free nodes only, WITHOUT damping.
+ *   Sigma = H^-1 is taken in the increments' own tangent: per node the half-angle vector, then the translation, applied on the left as
+ *   the solves apply them (q <- exp(w) (x) q, t <- t + dt).  The rotation a half-angle vector w stands for is 2 w, so the covariance of
+ *   the ROTATION VECTOR is 4 x the rotation block (and 2 x the rotation-translation blocks).
+ *   ll_posegraphs_covariances   the call's layout is that of the solves (node_off, edge_off, poses_w7, fixed, edges; nothing is
+ *                           modified).  q[n_queries]: (graph, a, b), a and b local to the graph, b < 0: node a alone.  joint144[q] is the
+ *                           row-major 12 x 12 matrix [[S_aa, S_ab], [S_ba, S_bb]]; for b < 0 or b == a, S_aa sits in the top-left block
+ *                           and the rest is zero.  A fixed node has zero rows and columns.  rec (may be NULL) gets one record per query:
+ *                           status 0: every column converged; 1: some column stopped at max_pcg_iterations, the blocks are what the
+ *                           conjugate gradients had; 2: breakdown (a p^T H p that is not positive and finite: H is singular or not
+ *                           finite), the query's 144 numbers are zeros, never NaN.  pcg_iterations: summed over the query's columns (6 per
+ *                           free node); residual: the largest final |r| among them.  opt == NULL: the defaults.
+ *                           How: the (graph, node) sources of all queries are deduplicated on the host; k_pg_cov_prepare linearises every
+ *                           queried graph once (and, under LL_PG_PRECOND_CHAIN, factorises the chain matrix at 1 / radius = 0 once); then
+ *                           one workgroup per (source, k), k = 0 .. 5, solves H x = e_(source, k) by the solves' preconditioned conjugate
+ *                           gradients under the object's preconditioner, until |r| <= tolerance (|b| = 1) -- the columns are independent
+ *                           and fill the device where a lone solve uses one workgroup; a last kernel builds the 12 x 12: the diagonal
+ *                           blocks symmetrised as (X + X^T) / 2, the cross block always from the columns of the smaller node index, so the
+ *                           queries (a, b) and (b, a) are exact permutations of one another.  A graph whose chain matrix has a pivot that
+ *                           is not positive and finite gets block-Jacobi for its columns.  Three launches, ONE synchronisation.  Every
+ *                           index is relative to the graph and every sum has a fixed shape, without a floating-point atomic: a query's
+ *                           144 numbers and record have the same bits alone, in any batch, at any position, beside any other queries.
+ *                           The columns' workspace (1 728 B per source and node of its graph) is allocated at the first call and grown
+ *                           when a call needs more; ll_posegraphs_create's sizes and the other calls' memory do not change.
+ *                           Decided on the host before anything is enqueued, outputs untouched: the errors of the solves, and LL_ERR_ARG
+ *                           for NULL queries or joint144, options out of range (max_pcg_iterations >= 1, tolerance >= 0 and finite), a
+ *                           query's graph or node outside its range (a == b is allowed), or a queried node that no path of edges joins to
+ *                           a fixed node -- H is singular there; last_error names the query and the node.  LL_ERR_HIP: the workspace cannot
+ *                           be allocated.  n_queries == 0 is LL_OK and launches nothing.
+ *   ll_posegraphs_covariances6  the same for ll_pg_edge6 graphs.
+ *   ll_posegraphs_cov_timing    ms2: device time of the last call's prepare and of its columns; counts3: its queries, its deduplicated
+ *                           free sources, the PCG iterations of all its columns.  Either may be NULL.
+ *   ll_pg_edge_gate         plain host arithmetic, needs no device.  For a candidate edge a -> b with measurement Z_w7 and square-root
+ *                           information S36 (row-major 6 x 6, r = S e; NULL: none) between poses whose joint covariance is joint144:
+ *                           e is the edge's unweighted error, J = [J_a J_b] its unweighted Jacobians in the increments' tangent,
+ *                           C = J Sigma J^T + (S^T S)^-1 (the second term absent for S36 == NULL), *chi2 = e^T C^-1 e, to be compared
+ *                           with a chi-square quantile of 6 degrees of freedom (22.46 at 0.999); cov36 (may be NULL) gets C.  This is a
+ *                           chi-square only for an edge that is NOT in the graph: Sigma of a graph that already holds the edge is not
+ *                           independent of its error.  LL_ERR_ARG: a NULL pointer, a non-finite input, a zero quaternion, or a C or
+ *                           S^T S that is not positive definite; the outputs are untouched then.                                     */
+typedef struct { int graph, a, b; } ll_pg_cov_query;                  /* a, b local to the graph; b < 0: node a alone */
+typedef struct { int max_pcg_iterations; double tolerance; } ll_pg_cov_options;          /* defaults 1000, 1e-10 */
+typedef struct { int status, pcg_iterations; double residual; } ll_pg_cov_record;
+void ll_pg_cov_default_options(ll_pg_cov_options *o);
+int  ll_posegraphs_covariances(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                               const unsigned char *fixed, const ll_pg_edge *edges, int n_queries, const ll_pg_cov_query *q,
+                               const ll_pg_cov_options *opt, double *joint144, ll_pg_cov_record *rec);
+int  ll_posegraphs_covariances6(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                                const unsigned char *fixed, const ll_pg_edge6 *edges, int n_queries, const ll_pg_cov_query *q,
+                                const ll_pg_cov_options *opt, double *joint144, ll_pg_cov_record *rec);
+int  ll_posegraphs_cov_timing(ll_posegraphs *pg, double ms2[2], long long counts3[3]);
+int  ll_pg_edge_gate(const double *Pa_w7, const double *Pb_w7, const double *Z_w7, const double *S36, const double joint144[144],
+                     double *chi2, double cov36[36]);
 
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),

@@ -1028,6 +1028,37 @@ public:
         check(ll_posegraphs_chain_solve(pg_, (int)node_off.size() - 1, node_off.data(), diag36.data(), upper36.data(), rhs6.data(), s.x.data(), s.status.data()));
         return s;
     }
+    /* ll_posegraphs_covariances: joint[q * 144 ..] is the row-major 12 x 12 [[S_aa, S_ab], [S_ba, S_bb]] of query q = (graph, a, b) in the
+     * increments' tangent (half-angle vector, translation; a rotation-vector covariance is 4 x the rotation block), b < 0: node a alone.
+     * records[q].status: 0 converged, 1 a column hit max_pcg_iterations, 2 breakdown (zeros).  The object's preconditioner applies */
+    struct Covariances { std::vector<double> joint; std::vector<ll_pg_cov_record> records; };
+    static ll_pg_cov_options default_cov_options() { ll_pg_cov_options o; ll_pg_cov_default_options(&o); return o; }
+    Covariances covariances(const std::vector<Graph> &graphs, const std::vector<ll_pg_cov_query> &queries, const ll_pg_cov_options *opt = nullptr) {
+        pack(graphs, edges_);
+        Covariances c;
+        c.joint.assign(queries.size() * 144, 0.0); c.records.resize(queries.size());
+        check(ll_posegraphs_covariances(pg_, (int)graphs.size(), node_off_.data(), edge_off_.data(), poses_.data(), fixed_ptr(), edges_.data(),
+                                        (int)queries.size(), queries.data(), opt, c.joint.data(), c.records.data()));
+        return c;
+    }
+    Covariances covariances(const std::vector<Graph6> &graphs, const std::vector<ll_pg_cov_query> &queries, const ll_pg_cov_options *opt = nullptr) {
+        pack(graphs, edges6_);
+        Covariances c;
+        c.joint.assign(queries.size() * 144, 0.0); c.records.resize(queries.size());
+        check(ll_posegraphs_covariances6(pg_, (int)graphs.size(), node_off_.data(), edge_off_.data(), poses_.data(), fixed_ptr(), edges6_.data(),
+                                         (int)queries.size(), queries.data(), opt, c.joint.data(), c.records.data()));
+        return c;
+    }
+    /* ms[2]: the last covariances call's prepare and columns (device time); counts[3]: its queries, sources, PCG iterations */
+    void cov_timing(double ms[2], long long counts[3]) { check(ll_posegraphs_cov_timing(pg_, ms, counts)); }
+    /* ll_pg_edge_gate: chi2 (6 degrees of freedom) of the candidate edge a -> b (Z, S36 or NULL) against the joint covariance of the two
+     * poses; C36 (may be NULL) gets J Sigma J^T + (S^T S)^-1.  A chi-square only for an edge that is NOT in the graph.  Needs no device */
+    static double edge_gate(const double Pa[7], const double Pb[7], const double Z[7], const double *S36, const double *joint144, double *C36 = nullptr) {
+        double chi2 = 0.0;
+        const int rc = ll_pg_edge_gate(Pa, Pb, Z, S36, joint144, &chi2, C36);
+        if (rc != LL_OK) throw Error(rc, "edge_gate: a non-finite input, a zero quaternion, or a covariance or information that is not positive definite");
+        return chi2;
+    }
     ll_posegraphs *get() const { return pg_; }
 private:
     static void qmul(const double a[4], const double b[4], double o[4]) {

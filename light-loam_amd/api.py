@@ -54,6 +54,7 @@ EXPORTS = [
     "ll_pg_default_options", "ll_posegraphs_create", "ll_posegraphs_destroy", "ll_posegraphs_last_error", "ll_posegraphs_evaluate",
     "ll_posegraphs_solve", "ll_posegraphs_timing",
     "ll_posegraphs_set_preconditioner", "ll_posegraphs_preconditioner", "ll_posegraphs_precond_stats", "ll_posegraphs_chain_solve",
+    "ll_pg_cov_default_options", "ll_posegraphs_covariances", "ll_posegraphs_covariances6", "ll_posegraphs_cov_timing", "ll_pg_edge_gate",
     "ll_keyframes_create", "ll_keyframes_destroy", "ll_keyframes_last_error", "ll_keyframes_size", "ll_keyframes_reset", "ll_keyframes_info",
     "ll_keyframes_add_cubemaps", "ll_keyframes_add_points", "ll_keyframes_export",
     "ll_cubemaps_insert_keyframes", "ll_cubemaps_insert_timing", "ll_drives_set_keyframes", "ll_drives_correct",
@@ -221,6 +222,12 @@ def load_library():
         _lib.ll_posegraphs_preconditioner.argtypes = [C.c_void_p]
         _lib.ll_posegraphs_precond_stats.argtypes = [C.c_void_p] * 2
         _lib.ll_posegraphs_chain_solve.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        _lib.ll_pg_cov_default_options.restype = None
+        _lib.ll_pg_cov_default_options.argtypes = [C.c_void_p]
+        _lib.ll_posegraphs_covariances.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4
+        _lib.ll_posegraphs_covariances6.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4
+        _lib.ll_posegraphs_cov_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_pg_edge_gate.argtypes = [C.c_void_p] * 7
         _lib.ll_keyframes_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ll_keyframes_destroy.restype = None
         _lib.ll_keyframes_destroy.argtypes = [C.c_void_p]
@@ -1434,6 +1441,22 @@ class PgRecord(C.Structure):
                 ("lm_successes", C.c_int), ("pcg_iterations", C.c_int), ("termination", C.c_int)]
 
 
+class PgCovQuery(C.Structure):
+    """ll_pg_cov_query: the joint covariance of nodes a and b of a graph of the call (local indices); b < 0: node a alone"""
+    _fields_ = [("graph", C.c_int), ("a", C.c_int), ("b", C.c_int)]
+
+
+class PgCovOptions(C.Structure):
+    _fields_ = [("max_pcg_iterations", C.c_int), ("tolerance", C.c_double)]
+
+
+class PgCovRecord(C.Structure):
+    """ll_pg_cov_record: status 0 converged, 1 some column hit max_pcg_iterations, 2 breakdown (the blocks are zeros)"""
+    _fields_ = [("status", C.c_int), ("pcg_iterations", C.c_int), ("residual", C.c_double)]
+
+
+PG_COV_QUERY = np.dtype([("graph", "i4"), ("a", "i4"), ("b", "i4")])                                                   # PgCovQuery as a numpy record
+PG_COV_STATUS = {0: "converged", 1: "iterations", 2: "breakdown"}
 PG_EDGE = np.dtype([("i", "i4"), ("j", "i4"), ("Z_w7", "f8", (7,)), ("sqrt_info", "f8", (6,)), ("huber", "f8")])     # PgEdge as a numpy record
 PG_EDGE6 = np.dtype([("i", "i4"), ("j", "i4"), ("Z_w7", "f8", (7,)), ("S", "f8", (6, 6)), ("huber", "f8")])          # PgEdge6 as a numpy record
 PG_TERMINATION = {0: "gradient", 1: "function", 2: "parameter", 3: "iterations", 4: "radius", 5: "non-finite"}
@@ -1445,6 +1468,17 @@ def pg_options(**kw):
     """ll_pg_default_options with the given fields replaced"""
     o = PgOptions()
     load_library().ll_pg_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def pg_cov_options(**kw):
+    """ll_pg_cov_default_options (1000 PCG iterations per column, tolerance 1e-10) with the given fields replaced"""
+    o = PgCovOptions()
+    load_library().ll_pg_cov_default_options(C.byref(o))
     for k, v in kw.items():
         if not hasattr(o, k):
             raise AttributeError(k)
@@ -1510,6 +1544,25 @@ def edge_from_info(info, X, sigma=0.0, floor=0.0):
         raise LightLoamError(rc, "edge_from_info: the record is not finite, sigma2 is 0 with sigma <= 0, or the information is not positive definite"
                              if rc == -7 else "edge_from_info: a non-finite argument, a negative floor or a zero quaternion")
     return S
+
+
+def edge_gate(Pa, Pb, Z, S, joint, with_cov=False):
+    """ll_pg_edge_gate: chi2 = e^T C^-1 e of the candidate edge a -> b with measurement Z [7] and square-root information S ([6, 6], [6]
+    for a diagonal one, or None) against the joint covariance [12, 12] of the two poses (PoseGraphs.covariances), C = J Sigma J^T +
+    (S^T S)^-1; 6 degrees of freedom.  with_cov: (chi2, C [6, 6]).  A chi-square only for an edge that is NOT in the graph.
+    Host arithmetic: needs no device"""
+    pa = np.ascontiguousarray(Pa, np.float64).reshape(7); pb = np.ascontiguousarray(Pb, np.float64).reshape(7)
+    z = np.ascontiguousarray(Z, np.float64).reshape(7); jt = np.ascontiguousarray(joint, np.float64).reshape(144)
+    s = None
+    if S is not None:
+        s = np.asarray(S, np.float64)
+        s = np.ascontiguousarray(s.reshape(6, 6) if s.size == 36 else np.diag(np.broadcast_to(s, (6,))))
+    chi2 = C.c_double(0.0); cov = np.zeros((6, 6))
+    rc = load_library().ll_pg_edge_gate(pa.ctypes.data, pb.ctypes.data, z.ctypes.data, None if s is None else s.ctypes.data, jt.ctypes.data,
+                                        C.addressof(chi2), cov.ctypes.data if with_cov else None)
+    if rc != LL_OK:
+        raise LightLoamError(rc, "edge_gate: a non-finite input, a zero quaternion, or a covariance or information that is not positive definite")
+    return (chi2.value, cov) if with_cov else chi2.value
 
 
 class PoseGraphs:
@@ -1584,6 +1637,30 @@ class PoseGraphs:
         ms = np.zeros(2); cnt = np.zeros(3, np.int64)
         self._ck(self.lib.ll_posegraphs_timing(self.h, _ptr(ms), _ptr(cnt)))
         return {"ms": ms.tolist(), "graphs": int(cnt[0]), "lm_iterations": int(cnt[1]), "pcg_iterations": int(cnt[2])}
+
+    def covariances(self, graphs, queries, options=None):
+        """(joint [Q, 12, 12], records [Q] of PgCovRecord): ll_posegraphs_covariances at the graphs' poses.  queries: (graph, a, b) tuples
+        or a PG_COV_QUERY record array, a and b local to the graph, b < 0 (or left out): node a alone.  joint[q] = [[S_aa, S_ab], [S_ba,
+        S_bb]] of Sigma = H^-1 in the increments' tangent (half-angle vector, translation); zeros at fixed nodes.  options: a PgCovOptions
+        (pg_cov_options(...)).  The object's preconditioner applies"""
+        no, eo, poses, fixed, edges = self._pack(graphs)
+        if isinstance(queries, np.ndarray) and queries.dtype == PG_COV_QUERY:
+            q = np.ascontiguousarray(queries).reshape(-1)
+        else:
+            q = np.zeros(len(queries), PG_COV_QUERY)
+            for k, t in enumerate(queries):
+                q[k] = (int(t[0]), int(t[1]), int(t[2]) if len(t) > 2 else -1)
+        joint = np.zeros((len(q), 12, 12)); rec = (PgCovRecord * max(len(q), 1))()
+        fn = self.lib.ll_posegraphs_covariances6 if edges.dtype == PG_EDGE6 else self.lib.ll_posegraphs_covariances
+        self._ck(fn(self.h, len(graphs), _ptr(no), _ptr(eo), _ptr(poses), _ptr(fixed), _ptr(edges), len(q), _ptr(q),
+                    None if options is None else C.addressof(options), _ptr(joint), C.addressof(rec)))
+        return joint, list(rec)[:len(q)]
+
+    def cov_timing(self):
+        """{"ms": [prepare, columns] of the last covariances call (device events), "queries", "sources", "pcg_iterations": of that call}"""
+        ms = np.zeros(2); cnt = np.zeros(3, np.int64)
+        self._ck(self.lib.ll_posegraphs_cov_timing(self.h, _ptr(ms), _ptr(cnt)))
+        return {"ms": ms.tolist(), "queries": int(cnt[0]), "sources": int(cnt[1]), "pcg_iterations": int(cnt[2])}
 
     def set_preconditioner(self, kind):
         """PG_PRECOND_BLOCK_JACOBI (0, the default) or PG_PRECOND_CHAIN (1: the block-tridiagonal chain, by cyclic reduction), or the

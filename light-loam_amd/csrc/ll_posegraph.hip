@@ -41,7 +41,9 @@
  */
 #include "ll_internal.h"
 #include "ll_factor_math.h"
+#include <algorithm>
 #include <cmath>
+#include <numeric>
 
 #define PG_THREADS 256
 #define PG_NODE_DOUBLES 92                    /* x 7, cand 7, Hd 36, g 6, D 6, d 6, r 6, z 6, p 6, Ap 6 */
@@ -73,6 +75,11 @@ struct ll_posegraphs {
     int precond = LL_PG_PRECOND_BLOCK_JACOBI;
     double *d_chain = nullptr;                 /* allocated when the chain preconditioner (or ll_posegraphs_chain_solve) is first asked for */
     long long pc_counts[2] = {0, 0};
+    unsigned char *d_cov = nullptr;            /* the covariances' tables and columns: allocated at the first call, grown when a call needs more */
+    size_t cov_bytes = 0;
+    hipEvent_t cov_ev[3] = {nullptr, nullptr, nullptr};
+    double cov_ms[2] = {0.0, 0.0};
+    long long cov_counts[3] = {0, 0, 0};
     std::string err;
 };
 
@@ -774,6 +781,205 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_chain_solve(const int *node_o
     if (threadIdx.x == 0) status[blockIdx.x] = ok ? 0 : 1;
 }
 
+/* ------------------------------------------------------------------ device: covariances (ll_posegraphs_covariances; the contract is in the header)
+ * Sigma = H^-1 with H the matrix of pg_matvec at damp 0, at the poses of the call.  Three launches:
+ *   k_pg_cov_prepare   a workgroup per graph that has a query: normalise, pg_linearise into the solves' workspace, and under the chain
+ *                      preconditioner pg_chain_matrix at 1 / radius = 0 and pg_chain_factor, once per graph; a flag per graph for a failed pivot.
+ *   k_pg_cov_columns   a workgroup per (source, k): H x = e_(node, k) by the PCG of k_pg_solve.  Hd, eH, D and the chain's factors are shared
+ *                      and only read; d, r, z, p, Ap and the chain's r are the column's own rows (36 doubles per node of the graph).
+ *                      pg_chain_apply writes S.r and z and nothing else, which is what lets the columns of a graph share its factors.
+ *   k_pg_cov_gather    a small workgroup per query puts the 12 x 12 together from the columns' d.
+ * A column depends on its graph alone: every index is relative to the graph, every sum has a fixed shape. */
+struct PgCovSource { long long row; int graph, node, n, pad; };   /* row: the first of the source's 6 n rows; node local to the graph of n nodes */
+struct PgCovQuery { int sa, sb, a, b; };                           /* the sources of a and b (-1: fixed, or no b), the nodes */
+
+template <typename Edge>
+__device__ __forceinline__ void pg_cov_graph(const PgArgs<Edge> &A, int gi, PgGraph<Edge> &G)
+{
+    G.n0 = A.node_off[gi]; G.N = A.node_off[gi + 1] - G.n0;
+    G.e0 = A.edge_off[gi]; G.E = A.edge_off[gi + 1] - G.e0;
+    G.edges = A.edges + G.e0; G.inc_off = A.inc_off; G.inc = A.inc; G.inc_nb = A.inc_nb; G.fixed = A.fixed + G.n0;
+    G.x = A.x + (size_t)G.n0 * 7; G.cand = A.cand + (size_t)G.n0 * 7; G.Hd = A.Hd + (size_t)G.n0 * 36;
+    G.g = A.g + (size_t)G.n0 * 6; G.D = A.D + (size_t)G.n0 * 6; G.d = A.d + (size_t)G.n0 * 6; G.r = A.r + (size_t)G.n0 * 6;
+    G.z = A.z + (size_t)G.n0 * 6; G.p = A.p + (size_t)G.n0 * 6; G.Ap = A.Ap + (size_t)G.n0 * 6;
+    G.eH = A.eH + (size_t)G.e0 * 108; G.eg = A.eg + (size_t)G.e0 * 12; G.ecost = A.ecost + G.e0;
+}
+
+template <typename Edge, int Precond>
+__global__ __launch_bounds__(PG_THREADS) void k_pg_cov_prepare(PgArgs<Edge> A, const int *graphs, int *flags)
+{
+    __shared__ double sh[8];
+    const int tid = threadIdx.x, gi = graphs[blockIdx.x];
+    PgGraph<Edge> G;
+    pg_cov_graph(A, gi, G);
+    for (int n = tid; n < G.N; n += PG_THREADS) {                  /* quaternions are normalised on entry */
+        const double *in = A.pose_in + (size_t)(G.n0 + n) * 7;
+        const double qn = sqrt((in[0] * in[0] + in[1] * in[1]) + (in[2] * in[2] + in[3] * in[3]));
+        for (int k = 0; k < 4; ++k) G.x[(size_t)n * 7 + k] = in[k] / qn;
+        for (int k = 4; k < 7; ++k) G.x[(size_t)n * 7 + k] = in[k];
+    }
+    __syncthreads();
+    (void)pg_linearise(G, G.x, A.o, sh);
+    bool ok = true;
+    if constexpr (Precond == LL_PG_PRECOND_CHAIN) {
+        PgChain S;
+        S.N = G.N; S.D = A.cD + (size_t)G.n0 * 36; S.WL = A.cWL + (size_t)G.n0 * 36; S.WR = A.cWR + (size_t)G.n0 * 36;
+        S.C = A.cC + (size_t)G.n0 * 36; S.r = A.cr + (size_t)G.n0 * 6;
+        pg_chain_matrix(G, S, 0.0);
+        ok = pg_chain_factor(S, sh);
+    }
+    if (tid == 0) flags[gi] = ok ? 0 : 1;
+}
+
+template <typename Edge, int Precond>
+__global__ __launch_bounds__(PG_THREADS) void k_pg_cov_columns(PgArgs<Edge> A, const PgCovSource *src, const int *flags, double *rows,
+                                                               ll_pg_cov_record *col, int max_iterations, double tolerance)
+{
+    __shared__ double sh[8];
+    const int tid = threadIdx.x, k = blockIdx.x % 6;
+    const PgCovSource sc = src[blockIdx.x / 6];
+    PgGraph<Edge> G;
+    pg_cov_graph(A, sc.graph, G);
+    const size_t N6 = (size_t)G.N * 6;
+    double *w = rows + ((size_t)sc.row + (size_t)k * G.N) * 36;   /* the column's own rows */
+    G.d = w; G.r = w + N6; G.z = w + 2 * N6; G.p = w + 3 * N6; G.Ap = w + 4 * N6;
+    PgChain S;
+    bool chain = false;
+    if constexpr (Precond == LL_PG_PRECOND_CHAIN) {
+        S.N = G.N; S.D = A.cD + (size_t)G.n0 * 36; S.WL = A.cWL + (size_t)G.n0 * 36; S.WR = A.cWR + (size_t)G.n0 * 36;
+        S.C = A.cC + (size_t)G.n0 * 36; S.r = w + 5 * N6;
+        chain = flags[sc.graph] == 0;                              /* a failed pivot: block-Jacobi for the graph's columns */
+    }
+    const int unit = sc.node * 6 + k;
+
+    double rz = 0.0, unused = 0.0;
+    if (chain) {
+        for (int i = tid; i < G.N * 6; i += PG_THREADS) S.r[i] = i == unit ? 1.0 : 0.0;
+        __syncthreads();
+        pg_chain_apply(S, G.z);
+        for (int n = tid; n < G.N; n += PG_THREADS) {
+            const bool fx = G.fixed[n] != 0;
+            for (int a = 0; a < 6; ++a) {
+                const double r = n * 6 + a == unit ? 1.0 : 0.0, z = fx ? 0.0 : G.z[(size_t)n * 6 + a];
+                G.d[(size_t)n * 6 + a] = 0.0; G.r[(size_t)n * 6 + a] = r; G.z[(size_t)n * 6 + a] = z; G.p[(size_t)n * 6 + a] = z;
+                rz += r * z;
+            }
+        }
+    } else
+    for (int n = tid; n < G.N; n += PG_THREADS) {
+        double r[6], z[6];
+        for (int a = 0; a < 6; ++a) { r[a] = n * 6 + a == unit ? 1.0 : 0.0; z[a] = 0.0; }
+        if (!G.fixed[n]) (void)pg_precondition(G, n, 0.0, r, z);
+        for (int a = 0; a < 6; ++a) {
+            G.d[(size_t)n * 6 + a] = 0.0; G.r[(size_t)n * 6 + a] = r[a]; G.z[(size_t)n * 6 + a] = z[a]; G.p[(size_t)n * 6 + a] = z[a];
+            rz += r[a] * z[a];
+        }
+    }
+    pg_sum2(rz, unused, sh);                                       /* its barriers publish p */
+
+    double rnorm = 1.0;                                            /* |e_(node, k)| */
+    int it = 0, status;
+    for (;;) {
+        if (rnorm <= tolerance) { status = 0; break; }
+        if (it >= max_iterations) { status = 1; break; }
+        pg_matvec(G, G.p, G.Ap, 0.0);
+        double pAp = 0.0;
+        unused = 0.0;
+        for (int n = tid; n < G.N; n += PG_THREADS)
+            for (int a = 0; a < 6; ++a) pAp += G.p[(size_t)n * 6 + a] * G.Ap[(size_t)n * 6 + a];
+        pg_sum2(pAp, unused, sh);
+        if (!(pAp > 0.0) || !pg_finite(pAp) || !pg_finite(rz)) { status = 2; break; }
+        const double alpha = rz / pAp;
+        double rr = 0.0, rz2 = 0.0;
+        if (chain) {
+            for (int n = tid; n < G.N; n += PG_THREADS)
+                for (int a = 0; a < 6; ++a) {
+                    G.d[(size_t)n * 6 + a] += alpha * G.p[(size_t)n * 6 + a];
+                    const double r = G.r[(size_t)n * 6 + a] - alpha * G.Ap[(size_t)n * 6 + a];
+                    G.r[(size_t)n * 6 + a] = r; S.r[(size_t)n * 6 + a] = G.fixed[n] ? 0.0 : r;
+                    rr += r * r;
+                }
+            __syncthreads();
+            pg_chain_apply(S, G.z);
+            for (int n = tid; n < G.N; n += PG_THREADS) {
+                const bool fx = G.fixed[n] != 0;
+                for (int a = 0; a < 6; ++a) {
+                    const double z = fx ? 0.0 : G.z[(size_t)n * 6 + a];
+                    G.z[(size_t)n * 6 + a] = z; rz2 += G.r[(size_t)n * 6 + a] * z;
+                }
+            }
+        } else
+        for (int n = tid; n < G.N; n += PG_THREADS) {
+            double r[6], z[6];
+            for (int a = 0; a < 6; ++a) {
+                G.d[(size_t)n * 6 + a] += alpha * G.p[(size_t)n * 6 + a];
+                r[a] = G.r[(size_t)n * 6 + a] - alpha * G.Ap[(size_t)n * 6 + a];
+                G.r[(size_t)n * 6 + a] = r[a]; z[a] = 0.0;
+            }
+            if (!G.fixed[n]) (void)pg_precondition(G, n, 0.0, r, z);
+            for (int a = 0; a < 6; ++a) { G.z[(size_t)n * 6 + a] = z[a]; rr += r[a] * r[a]; rz2 += r[a] * z[a]; }
+        }
+        pg_sum2(rr, rz2, sh);
+        ++it;
+        if (!pg_finite(rr)) { status = 2; break; }
+        rnorm = sqrt(rr);
+        const double beta = rz2 / rz;
+        rz = rz2;
+        for (int n = tid; n < G.N; n += PG_THREADS)
+            for (int a = 0; a < 6; ++a) G.p[(size_t)n * 6 + a] = G.z[(size_t)n * 6 + a] + beta * G.p[(size_t)n * 6 + a];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        ll_pg_cov_record R;
+        R.status = status; R.pcg_iterations = it; R.residual = rnorm;
+        col[blockIdx.x] = R;
+    }
+}
+
+/* query = blockIdx.x, 64 threads over the 144 entries.  Sigma[(m, c)][(n, k)] is entry (m, c) of column k of source n; the diagonal
+ * blocks are symmetrised, the cross block is read from the columns of the smaller node index whichever way round the query names them */
+__global__ __launch_bounds__(64) void k_pg_cov_gather(const PgCovQuery *qry, const PgCovSource *src, const double *rows,
+                                                      const ll_pg_cov_record *col, double *joint, ll_pg_cov_record *rec)
+{
+    const PgCovQuery q = qry[blockIdx.x];
+    int status = 0, iterations = 0;
+    double residual = 0.0;
+    for (int side = 0; side < 2; ++side) {
+        const int s = side ? q.sb : q.sa;
+        if (s < 0 || (side && s == q.sa)) continue;
+        for (int k = 0; k < 6; ++k) {
+            const ll_pg_cov_record c = col[s * 6 + k];
+            status = c.status > status ? c.status : status; iterations += c.pcg_iterations; residual = pg_max2(residual, c.residual);
+        }
+    }
+    const double *da = nullptr, *db = nullptr;                     /* column k of a source: + k * n * 36, entry (m, c): + m * 6 + c */
+    size_t stride = 0;
+    if (q.sa >= 0) { const PgCovSource s = src[q.sa]; da = rows + (size_t)s.row * 36; stride = (size_t)s.n * 36; }
+    if (q.sb >= 0) { const PgCovSource s = src[q.sb]; db = rows + (size_t)s.row * 36; stride = (size_t)s.n * 36; }
+    for (int t = threadIdx.x; t < 144; t += 64) {
+        const int R = t / 12, Cc = t % 12, br = R / 6, bc = Cc / 6, c = R % 6, k = Cc % 6;
+        double v = 0.0;
+        if (status != 2) {
+            if (br == 0 && bc == 0) { if (da) v = 0.5 * (da[k * stride + q.a * 6 + c] + da[c * stride + q.a * 6 + k]); }
+            else if (br == 1 && bc == 1) { if (db) v = 0.5 * (db[k * stride + q.b * 6 + c] + db[c * stride + q.b * 6 + k]); }
+            else if (da && db) {
+                const bool a_low = q.a < q.b;
+                const double *lo = a_low ? da : db;
+                const int hi = a_low ? q.b : q.a;
+                /* (br, bc) = (0, 1) is S_ab; with a low it is the transpose of what a's columns hold at b, with b low what b's hold at a */
+                const bool direct = (br == 1) == a_low;
+                v = direct ? lo[k * stride + hi * 6 + c] : lo[c * stride + hi * 6 + k];
+            }
+        }
+        joint[(size_t)blockIdx.x * 144 + t] = v;
+    }
+    if (threadIdx.x == 0) {
+        ll_pg_cov_record r;
+        r.status = status; r.pcg_iterations = iterations; r.residual = residual;
+        rec[blockIdx.x] = r;
+    }
+}
+
 /* ------------------------------------------------------------------ host side */
 static int pg_fail(ll_posegraphs *pg, int code, const std::string &what) { pg->err = "posegraphs: " + what; return code; }
 
@@ -807,8 +1013,9 @@ extern "C" void ll_posegraphs_destroy(ll_posegraphs *pg)
 {
     if (!pg) return;
     (void)hipSetDevice(pg->ctx->device);
-    for (void *p : {(void *)pg->d_in, (void *)pg->d_out, (void *)pg->d_ws, (void *)pg->d_chain}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)pg->d_in, (void *)pg->d_out, (void *)pg->d_ws, (void *)pg->d_chain, (void *)pg->d_cov}) if (p) (void)hipFree(p);
     for (hipEvent_t e : pg->ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : pg->cov_ev) if (e) (void)hipEventDestroy(e);
     delete pg;
 }
 
@@ -907,16 +1114,14 @@ static int pg_check_options(ll_posegraphs *pg, const ll_pg_options &o)
                                                 "0 < min_lm_diagonal <= max_lm_diagonal, tolerances >= 0, all finite)");
 }
 
-/* validate the call, pack it into page-locked scratch, enqueue the upload and the launch, download, synchronise ONCE */
 static bool pg_finite_weights(const ll_pg_edge &e) { return pg_finite7(e.sqrt_info, 6); }
 static bool pg_finite_weights(const ll_pg_edge6 &e) { return pg_finite7(e.S, 36); }
 
+/* the checks every call shares, in two parts (a call's own checks of its outputs and options lie between them): the layout ... */
 template <typename Edge>
-static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
-                  const unsigned char *fixed, const Edge *edges, const ll_pg_options *opt, double *out_a, void *out_b)
+static int pg_check_layout(ll_posegraphs *pg, const char *who, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                           const Edge *edges)
 {
-    if (!pg) return LL_ERR_ARG;
-    const char *who = solve ? "solve: " : "evaluate: ";
     auto bad = [&](int code, const std::string &what) { return pg_fail(pg, code, who + what); };
     if (n_graphs < 0 || !node_off || !edge_off) return bad(LL_ERR_ARG, "n_graphs < 0, or node_off / edge_off is NULL");
     if (n_graphs > pg->max_graphs) return bad(LL_ERR_CAPACITY, std::to_string(n_graphs) + " graphs exceed max_graphs " + std::to_string(pg->max_graphs));
@@ -927,11 +1132,15 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
     if (N > pg->max_nodes) return bad(LL_ERR_CAPACITY, std::to_string(N) + " nodes exceed max_nodes_total " + std::to_string(pg->max_nodes));
     if (E > pg->max_edges) return bad(LL_ERR_CAPACITY, std::to_string(E) + " edges exceed max_edges_total " + std::to_string(pg->max_edges));
     if ((N > 0 && !poses_w7) || (E > 0 && !edges)) return bad(LL_ERR_ARG, "poses or edges is NULL");
-    if (solve ? false : (n_graphs > 0 && (!out_a || (N > 0 && !out_b)))) return bad(LL_ERR_ARG, "cost or grad6 is NULL");
-    ll_pg_options o;
-    ll_pg_default_options(&o);
-    if (opt) o = *opt;
-    if (solve) { const int rc = pg_check_options(pg, o); if (rc) return rc; }
+    return LL_OK;
+}
+
+/* ... and every graph's poses, fixed node and edges */
+template <typename Edge>
+static int pg_check_graphs(ll_posegraphs *pg, const char *who, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                           const unsigned char *fixed, const Edge *edges)
+{
+    auto bad = [&](int code, const std::string &what) { return pg_fail(pg, code, who + what); };
     for (int g = 0; g < n_graphs; ++g) {
         const int n0 = node_off[g], n = node_off[g + 1] - n0;
         const std::string gs = "graph " + std::to_string(g);
@@ -952,21 +1161,18 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
             if (pg_zero_quat(ed.Z_w7)) return bad(LL_ERR_ARG, es + ": zero quaternion");
         }
     }
-    pg->counts[0] = n_graphs; pg->counts[1] = pg->counts[2] = 0;
-    pg->ms[solve ? 1 : 0] = 0.0;
-    if (solve) pg->pc_counts[0] = pg->pc_counts[1] = 0;
-    if (n_graphs == 0) return LL_OK;
-    const bool chain = solve && pg->precond == LL_PG_PRECOND_CHAIN;                /* evaluate solves nothing */
+    return LL_OK;
+}
 
-    /* ---- pack: poses, edges, offsets, the node -> incident-edge lists (edge order), fixed */
-    size_t off[9];
-    pg_in_layout((size_t)n_graphs, (size_t)N, (size_t)E, sizeof(Edge), off);
-    const size_t per_node = solve ? 7 : 6;
-    const size_t out_b_bytes = solve ? (size_t)n_graphs * sizeof(ll_pg_record) : (size_t)n_graphs * sizeof(double);
-    const size_t down = (size_t)N * per_node * sizeof(double) + out_b_bytes;
-    const size_t stat_bytes = chain ? (size_t)n_graphs * 2 * sizeof(int) : 0;
-    unsigned char *pin = (unsigned char *)ll_pinned_scratch(off[8] + pg_up8(down) + stat_bytes);
-    if (!pin) return bad(LL_ERR_HIP, "no page-locked scratch");
+/* the upload of a call in page-locked memory at `pin`, laid out by `off` (pg_in_layout): poses, edges, offsets, the node -> incident-edge
+ * lists (edge order), fixed */
+struct PgPacked { int *inc_off, *inc, *inc_nb; unsigned char *fx; };
+
+template <typename Edge>
+static PgPacked pg_pack(unsigned char *pin, const size_t off[9], int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                        const unsigned char *fixed, const Edge *edges)
+{
+    const int N = node_off[n_graphs], E = edge_off[n_graphs];
     if (N > 0) std::memcpy(pin + off[0], poses_w7, (size_t)N * 7 * sizeof(double));
     if (E > 0) std::memcpy(pin + off[1], edges, (size_t)E * sizeof(Edge));
     std::memcpy(pin + off[2], node_off, (size_t)(n_graphs + 1) * sizeof(int));
@@ -988,21 +1194,65 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
     }
     for (int g = 0; g < n_graphs; ++g)
         for (int k = node_off[g]; k < node_off[g + 1]; ++k) fx[k] = fixed ? (fixed[k] ? 1 : 0) : (k == node_off[g] ? 1 : 0);
+    PgPacked P = {inc_off, inc, inc_nb, fx};
+    return P;
+}
+
+/* the kernels' view of the upload in d_in and of the workspace, for a call of N nodes and E edges */
+template <typename Edge>
+static void pg_device_views(const ll_posegraphs *pg, const size_t off[9], size_t Nn, size_t En, PgArgs<Edge> &A)
+{
+    A.pose_in = (const double *)(pg->d_in + off[0]); A.edges = (const Edge *)(pg->d_in + off[1]);
+    A.node_off = (const int *)(pg->d_in + off[2]); A.edge_off = (const int *)(pg->d_in + off[3]);
+    A.inc_off = (const int *)(pg->d_in + off[4]); A.inc = (const int *)(pg->d_in + off[5]); A.inc_nb = (const int *)(pg->d_in + off[6]);
+    A.fixed = pg->d_in + off[7];
+    double *w = pg->d_ws;
+    A.x = w; w += Nn * 7; A.cand = w; w += Nn * 7; A.Hd = w; w += Nn * 36; A.g = w; w += Nn * 6; A.D = w; w += Nn * 6; A.d = w; w += Nn * 6;
+    A.r = w; w += Nn * 6; A.z = w; w += Nn * 6; A.p = w; w += Nn * 6; A.Ap = w; w += Nn * 6;
+    A.eH = w; w += En * 108; A.eg = w; w += En * 12; A.ecost = w;
+}
+
+/* validate the call, pack it into page-locked scratch, enqueue the upload and the launch, download, synchronise ONCE */
+template <typename Edge>
+static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                  const unsigned char *fixed, const Edge *edges, const ll_pg_options *opt, double *out_a, void *out_b)
+{
+    if (!pg) return LL_ERR_ARG;
+    const char *who = solve ? "solve: " : "evaluate: ";
+    auto bad = [&](int code, const std::string &what) { return pg_fail(pg, code, who + what); };
+    { const int rc = pg_check_layout(pg, who, n_graphs, node_off, edge_off, poses_w7, edges); if (rc) return rc; }
+    const int N = node_off[n_graphs], E = edge_off[n_graphs];
+    if (solve ? false : (n_graphs > 0 && (!out_a || (N > 0 && !out_b)))) return bad(LL_ERR_ARG, "cost or grad6 is NULL");
+    ll_pg_options o;
+    ll_pg_default_options(&o);
+    if (opt) o = *opt;
+    if (solve) { const int rc = pg_check_options(pg, o); if (rc) return rc; }
+    { const int rc = pg_check_graphs(pg, who, n_graphs, node_off, edge_off, poses_w7, fixed, edges); if (rc) return rc; }
+    pg->counts[0] = n_graphs; pg->counts[1] = pg->counts[2] = 0;
+    pg->ms[solve ? 1 : 0] = 0.0;
+    if (solve) pg->pc_counts[0] = pg->pc_counts[1] = 0;
+    if (n_graphs == 0) return LL_OK;
+    const bool chain = solve && pg->precond == LL_PG_PRECOND_CHAIN;                /* evaluate solves nothing */
+
+    /* ---- pack: poses, edges, offsets, the node -> incident-edge lists (edge order), fixed */
+    size_t off[9];
+    pg_in_layout((size_t)n_graphs, (size_t)N, (size_t)E, sizeof(Edge), off);
+    const size_t per_node = solve ? 7 : 6;
+    const size_t out_b_bytes = solve ? (size_t)n_graphs * sizeof(ll_pg_record) : (size_t)n_graphs * sizeof(double);
+    const size_t down = (size_t)N * per_node * sizeof(double) + out_b_bytes;
+    const size_t stat_bytes = chain ? (size_t)n_graphs * 2 * sizeof(int) : 0;
+    unsigned char *pin = (unsigned char *)ll_pinned_scratch(off[8] + pg_up8(down) + stat_bytes);
+    if (!pin) return bad(LL_ERR_HIP, "no page-locked scratch");
+    const PgPacked P = pg_pack(pin, off, n_graphs, node_off, edge_off, poses_w7, fixed, edges);
+    const int *inc_off = P.inc_off; const unsigned char *fx = P.fx;
 
     /* ---- enqueue */
     PG_HIP(hipSetDevice(pg->ctx->device));
     hipStream_t st = pg->ctx->stream;
     PG_HIP(hipMemcpyAsync(pg->d_in, pin, off[8], hipMemcpyHostToDevice, st));
     PgArgs<Edge> A;
-    A.pose_in = (const double *)(pg->d_in + off[0]); A.edges = (const Edge *)(pg->d_in + off[1]);
-    A.node_off = (const int *)(pg->d_in + off[2]); A.edge_off = (const int *)(pg->d_in + off[3]);
-    A.inc_off = (const int *)(pg->d_in + off[4]); A.inc = (const int *)(pg->d_in + off[5]); A.inc_nb = (const int *)(pg->d_in + off[6]);
-    A.fixed = pg->d_in + off[7];
-    double *w = pg->d_ws;
     const size_t Nn = (size_t)N, En = (size_t)E;
-    A.x = w; w += Nn * 7; A.cand = w; w += Nn * 7; A.Hd = w; w += Nn * 36; A.g = w; w += Nn * 6; A.D = w; w += Nn * 6; A.d = w; w += Nn * 6;
-    A.r = w; w += Nn * 6; A.z = w; w += Nn * 6; A.p = w; w += Nn * 6; A.Ap = w; w += Nn * 6;
-    A.eH = w; w += En * 108; A.eg = w; w += En * 12; A.ecost = w;
+    pg_device_views(pg, off, Nn, En, A);
     A.out_nodes = (double *)pg->d_out;
     A.rec = (ll_pg_record *)(pg->d_out + Nn * per_node * sizeof(double)); A.out_cost = (double *)A.rec;
     A.o = o; A.solve = solve ? 1 : 0;
@@ -1166,5 +1416,307 @@ extern "C" int ll_posegraphs_chain_solve(ll_posegraphs *pg, int n_systems, const
     PG_HIP(hipStreamSynchronize(st));                              /* the ONE synchronisation */
     if (N > 0) std::memcpy(out6, p_out, b6);
     std::memcpy(status, p_stat, (size_t)n_systems * sizeof(int));
+    return LL_OK;
+}
+
+/* ------------------------------------------------------------------ covariances: host side */
+extern "C" void ll_pg_cov_default_options(ll_pg_cov_options *o)
+{
+    if (!o) return;
+    o->max_pcg_iterations = 1000; o->tolerance = 1e-10;
+}
+
+/* validate, deduplicate the sources, pack, upload, three launches, download, synchronise ONCE */
+template <typename Edge>
+static int pg_cov_run(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7, const unsigned char *fixed,
+                      const Edge *edges, int n_queries, const ll_pg_cov_query *q, const ll_pg_cov_options *opt, double *joint144, ll_pg_cov_record *rec)
+{
+    if (!pg) return LL_ERR_ARG;
+    const char *who = "covariances: ";
+    auto bad = [&](int code, const std::string &what) { return pg_fail(pg, code, who + what); };
+    { const int rc = pg_check_layout(pg, who, n_graphs, node_off, edge_off, poses_w7, edges); if (rc) return rc; }
+    const int N = node_off[n_graphs], E = edge_off[n_graphs];
+    if (n_queries < 0 || (n_queries > 0 && (!q || !joint144))) return bad(LL_ERR_ARG, "n_queries < 0, or queries / joint144 is NULL");
+    ll_pg_cov_options co;
+    ll_pg_cov_default_options(&co);
+    if (opt) co = *opt;
+    if (co.max_pcg_iterations < 1 || !std::isfinite(co.tolerance) || co.tolerance < 0.0)
+        return bad(LL_ERR_ARG, "options out of range (max_pcg_iterations >= 1, tolerance >= 0 and finite)");
+    { const int rc = pg_check_graphs(pg, who, n_graphs, node_off, edge_off, poses_w7, fixed, edges); if (rc) return rc; }
+    auto is_fixed = [&](int g, int n) { return fixed ? fixed[node_off[g] + n] != 0 : n == 0; };
+    for (int k = 0; k < n_queries; ++k) {
+        const std::string qs = "query " + std::to_string(k);
+        if (q[k].graph < 0 || q[k].graph >= n_graphs) return bad(LL_ERR_ARG, qs + ": graph " + std::to_string(q[k].graph) + " lies outside the call");
+        const int n = node_off[q[k].graph + 1] - node_off[q[k].graph];
+        if (q[k].a < 0 || q[k].a >= n) return bad(LL_ERR_ARG, qs + ": node " + std::to_string(q[k].a) + " lies outside graph " + std::to_string(q[k].graph));
+        if (q[k].b >= n) return bad(LL_ERR_ARG, qs + ": node " + std::to_string(q[k].b) + " lies outside graph " + std::to_string(q[k].graph));
+    }
+    /* H is singular on a component without a fixed node: union-find over the edges of every queried graph */
+    std::vector<int> qgraphs;
+    for (int k = 0; k < n_queries; ++k) qgraphs.push_back(q[k].graph);
+    std::sort(qgraphs.begin(), qgraphs.end());
+    qgraphs.erase(std::unique(qgraphs.begin(), qgraphs.end()), qgraphs.end());
+    std::vector<int> parent((size_t)N);
+    std::vector<unsigned char> anchored((size_t)N, 0);
+    std::iota(parent.begin(), parent.end(), 0);
+    auto find = [&](int v) { while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; } return v; };
+    for (int g : qgraphs) {
+        const int n0 = node_off[g];
+        for (int e = edge_off[g]; e < edge_off[g + 1]; ++e) {
+            const int a = find(n0 + edges[e].i), b = find(n0 + edges[e].j);
+            if (a != b) parent[a > b ? a : b] = a > b ? b : a;
+        }
+        for (int n = n0; n < node_off[g + 1]; ++n) if (is_fixed(g, n - n0)) anchored[find(n)] = 1;
+    }
+    for (int k = 0; k < n_queries; ++k)
+        for (int node : {q[k].a, q[k].b})
+            if (node >= 0 && !anchored[find(node_off[q[k].graph] + node)])
+                return bad(LL_ERR_ARG, "query " + std::to_string(k) + ": node " + std::to_string(node) + " of graph " + std::to_string(q[k].graph) +
+                                       " is not connected to a fixed node through the edges (H is singular there)");
+    pg->cov_counts[0] = n_queries; pg->cov_counts[1] = pg->cov_counts[2] = 0;
+    pg->cov_ms[0] = pg->cov_ms[1] = 0.0;
+    if (n_queries == 0) return LL_OK;
+
+    /* ---- the sources: every free (graph, node) some query names, once, in ascending order */
+    std::vector<std::pair<int, int>> keys;
+    for (int k = 0; k < n_queries; ++k)
+        for (int node : {q[k].a, q[k].b})
+            if (node >= 0 && !is_fixed(q[k].graph, node)) keys.emplace_back(q[k].graph, node);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    const size_t n_src = keys.size(), n_qg = qgraphs.size(), Q = (size_t)n_queries;
+    auto source_of = [&](int g, int node) {
+        if (node < 0 || is_fixed(g, node)) return -1;
+        return (int)(std::lower_bound(keys.begin(), keys.end(), std::make_pair(g, node)) - keys.begin());
+    };
+    size_t total_rows = 0;                                         /* 36 doubles each */
+    for (const auto &kq : keys) total_rows += 6 * (size_t)(node_off[kq.first + 1] - node_off[kq.first]);
+
+    /* ---- the layout of d_cov: [graphs | sources | queries] uploaded, flags, [columns' records | joint | records] downloaded, rows */
+    const size_t o_graphs = 0, o_src = o_graphs + pg_up8(n_qg * sizeof(int)), o_qry = o_src + n_src * sizeof(PgCovSource);
+    const size_t up = o_qry + pg_up8(Q * sizeof(PgCovQuery));
+    const size_t o_flags = up, o_col = o_flags + pg_up8((size_t)n_graphs * sizeof(int)), o_joint = o_col + n_src * 6 * sizeof(ll_pg_cov_record);
+    const size_t o_rec = o_joint + Q * 144 * sizeof(double), o_rows = o_rec + Q * sizeof(ll_pg_cov_record);
+    const size_t down = o_rows - o_col, need = o_rows + total_rows * 36 * sizeof(double);
+    PG_HIP(hipSetDevice(pg->ctx->device));
+    if (need > pg->cov_bytes) {
+        if (pg->d_cov) (void)hipFree(pg->d_cov);
+        pg->d_cov = nullptr; pg->cov_bytes = 0;
+        if (hipMalloc((void **)&pg->d_cov, need) != hipSuccess) {
+            (void)hipGetLastError();
+            pg->d_cov = nullptr;
+            return bad(LL_ERR_HIP, "the columns' workspace could not be allocated (" + std::to_string(need) + " bytes)");
+        }
+        pg->cov_bytes = need;
+    }
+    for (hipEvent_t &e : pg->cov_ev) if (!e) PG_HIP(hipEventCreate(&e));
+
+    size_t off[9];
+    pg_in_layout((size_t)n_graphs, (size_t)N, (size_t)E, sizeof(Edge), off);
+    unsigned char *pin = (unsigned char *)ll_pinned_scratch(off[8] + up + down);
+    if (!pin) return bad(LL_ERR_HIP, "no page-locked scratch");
+    (void)pg_pack(pin, off, n_graphs, node_off, edge_off, poses_w7, fixed, edges);
+    unsigned char *ptab = pin + off[8], *pout = ptab + up;
+    std::memset(ptab, 0, up);
+    std::memcpy(ptab + o_graphs, qgraphs.data(), n_qg * sizeof(int));
+    PgCovSource *hs = (PgCovSource *)(ptab + o_src);
+    long long row = 0;
+    for (size_t s = 0; s < n_src; ++s) {
+        const int n = node_off[keys[s].first + 1] - node_off[keys[s].first];
+        hs[s].row = row; hs[s].graph = keys[s].first; hs[s].node = keys[s].second; hs[s].n = n; hs[s].pad = 0;
+        row += 6LL * n;
+    }
+    PgCovQuery *hq = (PgCovQuery *)(ptab + o_qry);
+    for (int k = 0; k < n_queries; ++k) {
+        const bool pair = q[k].b >= 0 && q[k].b != q[k].a;
+        hq[k].sa = source_of(q[k].graph, q[k].a); hq[k].sb = pair ? source_of(q[k].graph, q[k].b) : -1;
+        hq[k].a = q[k].a; hq[k].b = pair ? q[k].b : -1;
+    }
+
+    /* ---- enqueue */
+    const bool chain = pg->precond == LL_PG_PRECOND_CHAIN;         /* its workspace exists: set_preconditioner allocated it */
+    hipStream_t st = pg->ctx->stream;
+    PG_HIP(hipMemcpyAsync(pg->d_in, pin, off[8], hipMemcpyHostToDevice, st));
+    PG_HIP(hipMemcpyAsync(pg->d_cov, ptab, up, hipMemcpyHostToDevice, st));
+    PgArgs<Edge> A;
+    pg_device_views(pg, off, (size_t)N, (size_t)E, A);
+    A.out_nodes = nullptr; A.rec = nullptr; A.out_cost = nullptr; A.solve = 0;
+    ll_pg_default_options(&A.o);
+    A.cD = A.cWL = A.cWR = A.cC = A.cr = nullptr; A.cstat = nullptr;
+    if (chain) {
+        const PgChainWs cw = pg_chain_ws(pg);
+        A.cD = cw.D; A.cWL = cw.WL; A.cWR = cw.WR; A.cC = cw.C; A.cr = cw.r; A.cstat = cw.stat;
+    }
+    const int *d_graphs = (const int *)(pg->d_cov + o_graphs);
+    const PgCovSource *d_src = (const PgCovSource *)(pg->d_cov + o_src);
+    const PgCovQuery *d_qry = (const PgCovQuery *)(pg->d_cov + o_qry);
+    int *d_flags = (int *)(pg->d_cov + o_flags);
+    ll_pg_cov_record *d_col = (ll_pg_cov_record *)(pg->d_cov + o_col), *d_rec = (ll_pg_cov_record *)(pg->d_cov + o_rec);
+    double *d_joint = (double *)(pg->d_cov + o_joint), *d_rows = (double *)(pg->d_cov + o_rows);
+    PG_HIP(hipEventRecord(pg->cov_ev[0], st));
+    if (chain) hipLaunchKernelGGL((k_pg_cov_prepare<Edge, LL_PG_PRECOND_CHAIN>), dim3((unsigned)n_qg), dim3(PG_THREADS), 0, st, A, d_graphs, d_flags);
+    else hipLaunchKernelGGL((k_pg_cov_prepare<Edge, LL_PG_PRECOND_BLOCK_JACOBI>), dim3((unsigned)n_qg), dim3(PG_THREADS), 0, st, A, d_graphs, d_flags);
+    PG_HIP(hipEventRecord(pg->cov_ev[1], st));
+    if (n_src > 0) {
+        if (chain) hipLaunchKernelGGL((k_pg_cov_columns<Edge, LL_PG_PRECOND_CHAIN>), dim3((unsigned)(n_src * 6)), dim3(PG_THREADS), 0, st, A, d_src, d_flags,
+                                      d_rows, d_col, co.max_pcg_iterations, co.tolerance);
+        else hipLaunchKernelGGL((k_pg_cov_columns<Edge, LL_PG_PRECOND_BLOCK_JACOBI>), dim3((unsigned)(n_src * 6)), dim3(PG_THREADS), 0, st, A, d_src, d_flags,
+                                d_rows, d_col, co.max_pcg_iterations, co.tolerance);
+    }
+    PG_HIP(hipEventRecord(pg->cov_ev[2], st));
+    hipLaunchKernelGGL(k_pg_cov_gather, dim3((unsigned)Q), dim3(64), 0, st, d_qry, d_src, d_rows, d_col, d_joint, d_rec);
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipMemcpyAsync(pout, pg->d_cov + o_col, down, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));                              /* the ONE synchronisation */
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, pg->cov_ev[0], pg->cov_ev[1]) == hipSuccess) pg->cov_ms[0] = (double)ms;
+    if (hipEventElapsedTime(&ms, pg->cov_ev[1], pg->cov_ev[2]) == hipSuccess) pg->cov_ms[1] = (double)ms;
+
+    /* ---- hand back */
+    const ll_pg_cov_record *cols = (const ll_pg_cov_record *)pout;
+    pg->cov_counts[1] = (long long)n_src;
+    for (size_t c = 0; c < n_src * 6; ++c) pg->cov_counts[2] += cols[c].pcg_iterations;
+    std::memcpy(joint144, pout + (o_joint - o_col), Q * 144 * sizeof(double));
+    if (rec) std::memcpy(rec, pout + (o_rec - o_col), Q * sizeof(ll_pg_cov_record));
+    return LL_OK;
+}
+
+extern "C" int ll_posegraphs_covariances(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                                         const unsigned char *fixed, const ll_pg_edge *edges, int n_queries, const ll_pg_cov_query *q,
+                                         const ll_pg_cov_options *opt, double *joint144, ll_pg_cov_record *rec)
+{
+    return pg_cov_run(pg, n_graphs, node_off, edge_off, poses_w7, fixed, edges, n_queries, q, opt, joint144, rec);
+}
+
+extern "C" int ll_posegraphs_covariances6(ll_posegraphs *pg, int n_graphs, const int *node_off, const int *edge_off, const double *poses_w7,
+                                          const unsigned char *fixed, const ll_pg_edge6 *edges, int n_queries, const ll_pg_cov_query *q,
+                                          const ll_pg_cov_options *opt, double *joint144, ll_pg_cov_record *rec)
+{
+    return pg_cov_run(pg, n_graphs, node_off, edge_off, poses_w7, fixed, edges, n_queries, q, opt, joint144, rec);
+}
+
+/* ms2: device time of the last call's prepare and of its columns; counts3: its queries, its sources, the PCG iterations of all its columns */
+extern "C" int ll_posegraphs_cov_timing(ll_posegraphs *pg, double ms2[2], long long counts3[3])
+{
+    if (!pg) return LL_ERR_ARG;
+    if (ms2) for (int k = 0; k < 2; ++k) ms2[k] = pg->cov_ms[k];
+    if (counts3) for (int k = 0; k < 3; ++k) counts3[k] = pg->cov_counts[k];
+    return LL_OK;
+}
+
+/* ------------------------------------------------------------------ the gate (host arithmetic only; the contract is in the header)
+ * pg_error restated for the host: the unweighted error e of the edge a -> b and its unweighted Jacobians
+ * J_a = [ -A 0 ; 2 R(a)[v]x  -R(a) ], J_b = [ A 0 ; 0 R(a) ] (the formulas at the top of this file). */
+static void pgh_qmul(const double a[4], const double b[4], double o[4])
+{
+    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    o[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
+    o[2] = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
+    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+}
+
+static void pgh_unit(const double *P, double out[7])
+{
+    const double n = std::sqrt((P[0] * P[0] + P[1] * P[1]) + (P[2] * P[2] + P[3] * P[3]));
+    for (int k = 0; k < 4; ++k) out[k] = P[k] / n;
+    for (int k = 4; k < 7; ++k) out[k] = P[k];
+}
+
+static void pgh_matrix(const double q[4], double R[3][3])
+{
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double M[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)},
+                            {2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)},
+                            {2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)}};
+    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) R[a][b] = M[a][b];
+}
+
+static void pgh_error(const double Pi[7], const double Pj[7], const double Z[7], double er[6], double Ji[6][6], double Jj[6][6])
+{
+    const double qzc[4] = {-Z[0], -Z[1], -Z[2], Z[3]}, qic[4] = {-Pi[0], -Pi[1], -Pi[2], Pi[3]};
+    double a[4], qe[4], R[3][3], Rz[3][3];
+    pgh_qmul(qzc, qic, a);
+    pgh_qmul(a, Pj, qe);
+    const double sgn = qe[3] < 0.0 ? -1.0 : 1.0;
+    pgh_matrix(a, R);
+    pgh_matrix(qzc, Rz);                                           /* R(q_z)^T */
+    const double v[3] = {Pj[4] - Pi[4], Pj[5] - Pi[5], Pj[6] - Pi[6]};
+    const double vx[3][3] = {{0.0, -v[2], v[1]}, {v[2], 0.0, -v[0]}, {-v[1], v[0], 0.0}};
+    for (int k = 0; k < 3; ++k) {
+        er[k] = 2.0 * sgn * qe[k];
+        er[3 + k] = ((R[k][0] * v[0] + R[k][1] * v[1]) + R[k][2] * v[2]) - ((Rz[k][0] * Z[4] + Rz[k][1] * Z[5]) + Rz[k][2] * Z[6]);
+    }
+    for (int k = 0; k < 3; ++k) {
+        double ek[4] = {0.0, 0.0, 0.0, 0.0}, ae[4], c[4];
+        ek[k] = 1.0;
+        pgh_qmul(a, ek, ae);
+        pgh_qmul(ae, Pj, c);
+        for (int m = 0; m < 3; ++m) {
+            const double A = 2.0 * sgn * c[m];
+            Ji[m][k] = -A;                   Ji[m][3 + k] = 0.0;
+            Jj[m][k] = A;                    Jj[m][3 + k] = 0.0;
+            Ji[3 + m][k] = 2.0 * ((R[m][0] * vx[0][k] + R[m][1] * vx[1][k]) + R[m][2] * vx[2][k]);
+            Ji[3 + m][3 + k] = -R[m][k];
+            Jj[3 + m][k] = 0.0;              Jj[3 + m][3 + k] = R[m][k];
+        }
+    }
+}
+
+/* L (lower, L L^T = M) of a symmetric 6 x 6; false at a pivot that is not positive and finite */
+static bool pgh_chol6(const double M[6][6], double L[6][6])
+{
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double acc = M[i][j];
+            for (int k = 0; k < j; ++k) acc -= L[i][k] * L[j][k];
+            if (i == j) { if (!(acc > 0.0) || !std::isfinite(acc)) return false; L[i][i] = std::sqrt(acc); }
+            else L[i][j] = acc / L[j][j];
+        }
+    return true;
+}
+
+extern "C" int ll_pg_edge_gate(const double *Pa_w7, const double *Pb_w7, const double *Z_w7, const double *S36, const double joint144[144],
+                               double *chi2, double cov36[36])
+{
+    if (!Pa_w7 || !Pb_w7 || !Z_w7 || !joint144 || !chi2) return LL_ERR_ARG;
+    if (!pg_finite7(Pa_w7, 7) || !pg_finite7(Pb_w7, 7) || !pg_finite7(Z_w7, 7) || !pg_finite7(joint144, 144) || (S36 && !pg_finite7(S36, 36))) return LL_ERR_ARG;
+    if (pg_zero_quat(Pa_w7) || pg_zero_quat(Pb_w7) || pg_zero_quat(Z_w7)) return LL_ERR_ARG;
+    double Pa[7], Pb[7], Z[7], e[6], Ja[6][6], Jb[6][6], Cm[6][6], L[6][6];
+    pgh_unit(Pa_w7, Pa); pgh_unit(Pb_w7, Pb); pgh_unit(Z_w7, Z);
+    pgh_error(Pa, Pb, Z, e, Ja, Jb);
+    for (int m = 0; m < 6; ++m)                                    /* C = J Sigma J^T, J = [J_a J_b] */
+        for (int n = 0; n < 6; ++n) {
+            double s = 0.0;
+            for (int u = 0; u < 12; ++u) {
+                double t = 0.0;
+                for (int w = 0; w < 12; ++w) t += joint144[u * 12 + w] * (w < 6 ? Ja[n][w] : Jb[n][w - 6]);
+                s += (u < 6 ? Ja[m][u] : Jb[m][u - 6]) * t;
+            }
+            Cm[m][n] = s;
+        }
+    if (S36) {                                                     /* + (S^T S)^-1 */
+        double I[6][6], Li[6][6] = {};
+        for (int m = 0; m < 6; ++m) for (int n = 0; n < 6; ++n) { double s = 0.0; for (int k = 0; k < 6; ++k) s += S36[k * 6 + m] * S36[k * 6 + n]; I[m][n] = s; }
+        if (!pgh_chol6(I, L)) return LL_ERR_ARG;
+        for (int c = 0; c < 6; ++c)                                /* L^-1, column by column */
+            for (int i = c; i < 6; ++i) {
+                double acc = i == c ? 1.0 : 0.0;
+                for (int k = c; k < i; ++k) acc -= L[i][k] * Li[k][c];
+                Li[i][c] = acc / L[i][i];
+            }
+        for (int m = 0; m < 6; ++m) for (int n = 0; n < 6; ++n) { double s = 0.0; for (int k = 0; k < 6; ++k) s += Li[k][m] * Li[k][n]; Cm[m][n] += s; }
+    }
+    for (int m = 0; m < 6; ++m) for (int n = m + 1; n < 6; ++n) { const double h = 0.5 * (Cm[m][n] + Cm[n][m]); Cm[m][n] = h; Cm[n][m] = h; }
+    if (!pgh_chol6(Cm, L)) return LL_ERR_ARG;
+    double y[6], c2 = 0.0;                                         /* chi2 = |L^-1 e|^2 */
+    for (int i = 0; i < 6; ++i) {
+        double acc = e[i];
+        for (int k = 0; k < i; ++k) acc -= L[i][k] * y[k];
+        y[i] = acc / L[i][i];
+        c2 += y[i] * y[i];
+    }
+    if (!std::isfinite(c2)) return LL_ERR_ARG;
+    *chi2 = c2;
+    if (cov36) for (int m = 0; m < 6; ++m) for (int n = 0; n < 6; ++n) cov36[m * 6 + n] = Cm[m][n];
     return LL_OK;
 }
