@@ -886,6 +886,80 @@ int  ll_cubemaps_insert_keyframes(ll_cubemaps *cms, const ll_keyframes *kf, cons
                                   long long *added /* [n_ops][2], may be NULL */, long long *dropped /* [n_ops][2], may be NULL */);
 int  ll_cubemaps_insert_timing(const ll_cubemaps *cms, double *ms /* assign, sort+gather, filter, commit */, long long *counts /* points in, touched cubes, points out */);
 
+/* ---------------------------------------------------------------- visibility: which stored points did other frames see through?
+ * A map rebuilt from keyframes holds every point any frame contributed, a car that stood at a junction in one frame included.  A point
+ * is not part of the static world if other frames looked straight through the place where it sits and measured something farther
+ * away: the range-image visibility test of Removert (Kim & Kim, IROS 2020) and of Pomerleau et al. (ICRA 2014) -- not part of the
+ * reference -- over what the store holds: per frame the down-sized corner and surf stacks in the sensor frame, and a pose.  The
+ * evidence is therefore SPARSE; thresholds on real data are the caller's.  An ll_visibility belongs to ONE store (and its context).
+ * THE IMAGE OF A FRAME (width columns over 360 degrees, height rows over el_min_deg .. el_max_deg).  For a point (x, y, z) in the
+ * frame's sensor frame, in f32 with every product and sum rounded, left to right:
+ *   r = sqrtf(x*x + y*y + z*z), used iff r >= min_range && r < max_range (a NaN is dropped);
+ *   a = ll_atan2f(y, x), + 6.2831855f if negative;  col = min(width - 1, (int)(a * ka)), ka = (float)(width / (2 pi));
+ *   h = sqrtf(x*x + y*y), e = ll_atan2f(z, h);  row = (int)floorf((e - el_min) * ke), el_min = (float)((double)el_min_deg * (pi / 180)),
+ *   ke = (float)(height / (((double)el_max_deg - (double)el_min_deg) * (pi / 180))), pi / 180 and 2 pi as doubles; a row outside
+ *   0 .. height - 1 gives no pixel;
+ *   raw[row][col] = the minimum r over the points of BOTH of the frame's clouds in that pixel, +inf when empty -- an integer atomic
+ *   minimum on the float's bits (ranges are positive: the unsigned order is the floats'), so it does not depend on the order of arrival;
+ *   img[row][col] = the minimum of raw over the 3 x 3 pixels around it; columns wrap, rows outside the image are left out.  On sparse
+ *   clouds the point's own pixel is not enough: ground at grazing angles is "seen through" by the pixel beside it.
+ * THE VOTE (margin_abs, margin_rel, radius).  Subject point p of frame A with pose P_A; observer B: another frame of the same op --
+ * "another" by position in the op's list -- with dx*dx + dy*dy + dz*dz <= (double)radius * (double)radius over the poses' translations
+ * in f64, summed left to right, decided on the host.
+ *   w = pointAssociateToMap(P_A, p) as ll_cubemaps_insert_keyframes has it: f64, each coordinate rounded to float once -- the
+ *   numbers the insert bins;
+ *   l = R(q_B)^-1 (w - t_B) in f64 from those floats: v = (double)w - t_B per coordinate, then the conjugate quaternion u = -(qx, qy, qz)
+ *   with qw through the same operations in the same order: uv = u x v (uy*vz - uz*vy, ...), uv += uv,
+ *   l = (float)((v + qw*uv) + u x uv) per coordinate; the pose is never normalised; each coordinate rounded to float once;
+ *   l gives r, row, col as above; no evidence if l has no pixel, r is outside the range window, or d = img_B[row][col] is +inf;
+ *   otherwise m = margin_abs + margin_rel * r (f32):  SEEN THROUGH by B if d > r + m;  HIT if d >= r - m && d <= r + m;  occluded
+ *   otherwise, which is no evidence.
+ * Per stored point two counters, through and hit, over all observers, each saturating at 255.  THE RULE: a point is removed iff
+ * through >= min_through && hit <= max_hit; min_through in 1 .. 256 (256 never removes), max_hit in 0 .. 255 (255 ignores hits); the
+ * default rule is {2, 255}.  A parked car that never moves is static by this test.
+ *   ll_visibility_default_params  360 x 90 over -45 .. +45 degrees, ranges 1 .. 120, margins 0.5 + 0.02 r, radius 40, max_images 256
+ *   ll_visibility_create     width in 8 .. 4096, height in 2 .. 1024, -89 <= el_min_deg < el_max_deg <= 89, max_images in 2 .. 2^16,
+ *                            0 <= min_range < max_range, margins and radius finite and >= 0 (LL_ERR_ARG otherwise, ll_keyframes_last_error
+ *                            of the store).  Two bytes per pool point ((cap_corner + cap_surf) * 2 bytes, zero) and max_images raw and
+ *                            eroded images.  Destroy it before its store.
+ *   ll_visibility_run        every op is one drive: its listed frames observe each other, frame k under poses_w7[k] (NULL: the stored
+ *                            poses).  The counters of the listed frames are made anew (zero for an op with fewer than two frames or
+ *                            no pair within radius); the counters of other frames keep their values; a frame that never took part has
+ *                            zeros and is always kept.  pairs[i]: the ordered (subject, observer) frame pairs of op i.  The host builds
+ *                            the cloud table and the observer lists (CSR over list positions) from the store's table; one upload, one
+ *                            fill, THREE launches whatever n_ops is (k_vis_image, k_vis_erode, k_vis_vote), ONE synchronisation.  No
+ *                            floating-point atomic: a frame's counters are the same bits alone, in any batch and in any order of ops.
+ *   ll_visibility_counts     frame's counters, [n_corner + n_surf][2] bytes (through, hit), corner first; one synchronisation
+ *   ll_visibility_images     raw / img [height][width] of the k-th listed frame, counted across ops, of the LAST run (tests, analysis);
+ *                            one synchronisation
+ *   ll_visibility_reset      all counters zero, the last run forgotten; the object follows the store again after ll_keyframes_reset
+ *   ll_visibility_timing     the last run: ms = images, erode, vote (device events); counts = listed frames, their points, frame pairs
+ *   ll_cubemaps_insert_keyframes_filtered   ll_cubemaps_insert_keyframes with the points the rule removes left out: a removed point
+ *                            gets the key of a point outside the array in k_kf_assign, so every later stage is the plain insert's.
+ *                            removed[i][w] counts them; dropped excludes them; added + dropped + removed = the listed points of the
+ *                            type.  With nothing removed the maps are the plain insert's bytes.  Errors go to ll_cubemaps_last_error.
+ * After ll_keyframes_reset the counters mean nothing: run, counts and the filtered insert return LL_ERR_STATE until
+ * ll_visibility_reset.  Errors, all decided before anything is enqueued; a refused call leaves every counter as it was: LL_ERR_ARG for
+ * a NULL handle or ops, n_ops < 1, n_frames < 0, frames NULL with frames to read, an id outside the store, an id listed twice in one
+ * call (in one op or across ops), a non-finite pose, a rule outside its ranges, a store or visibility object of another store or
+ * context; LL_ERR_CAPACITY for more listed frames than max_images; LL_ERR_HIP as elsewhere.                                         */
+typedef struct ll_visibility ll_visibility;
+typedef struct { int width, height; float el_min_deg, el_max_deg, min_range, max_range, margin_abs, margin_rel, radius; int max_images; } ll_visibility_params;
+typedef struct { int n_frames; const int *frames; const double *poses_w7 /* [n_frames][7], NULL: the stored poses */; } ll_visibility_op;
+typedef struct { int min_through, max_hit; } ll_visibility_rule;
+void ll_visibility_default_params(ll_visibility_params *p);
+int  ll_visibility_create(ll_keyframes *kf, const ll_visibility_params *p, ll_visibility **out);
+void ll_visibility_destroy(ll_visibility *v);
+const char *ll_visibility_last_error(const ll_visibility *v);
+int  ll_visibility_run(ll_visibility *v, const ll_visibility_op *ops, int n_ops, long long *pairs /* [n_ops], may be NULL */);
+int  ll_visibility_counts(ll_visibility *v, int frame, unsigned char *through_hit /* [n_corner + n_surf][2], corner first */);
+int  ll_visibility_images(ll_visibility *v, int k, float *raw, float *img /* [height][width] each, either may be NULL */);
+int  ll_visibility_reset(ll_visibility *v);
+int  ll_visibility_timing(const ll_visibility *v, double *ms /* images, erode, vote */, long long *counts /* frames, points, pairs */);
+int  ll_cubemaps_insert_keyframes_filtered(ll_cubemaps *cms, const ll_keyframes *kf, const ll_visibility *v, const ll_visibility_rule *rule,
+                                           const ll_insert_op *ops, int n_ops, long long *added, long long *dropped,
+                                           long long *removed /* [n_ops][2] each, may be NULL */);
+
 /* ---------------------------------------------------------------- drives: capture while driving, and take a correction
  * ll_drives_set_keyframes(d, kf, every): from the next step on, at the end of a step every lane that ran a frame -- mapping or
  * localising -- whose per-lane frame index (0 at START) is a multiple of every (>= 1) is captured into kf: its stack clouds and its

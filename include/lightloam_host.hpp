@@ -439,6 +439,55 @@ private:
     ll_keyframes *kf_ = nullptr;
 };
 
+/* Visibility (ll_visibility): per point of a Keyframes store how many other frames of its drive saw through it and how many hit it;
+ * LaserMappingSequences::insert_keyframes_filtered leaves the points out that a rule over the two counters removes.  Destroy it
+ * before its store. */
+class Visibility {
+public:
+    struct Counts { std::vector<unsigned char> corner, surf; };   /* [n][2]: through, hit */
+    static ll_visibility_params default_params() { ll_visibility_params p; ll_visibility_default_params(&p); return p; }
+    explicit Visibility(Keyframes &kf) : Visibility(kf, default_params()) {}
+    Visibility(Keyframes &kf, const ll_visibility_params &p) : kf_(&kf), p_(p) {
+        const int rc = ll_visibility_create(kf.get(), &p, &v_);
+        if (rc != LL_OK) throw Error(rc, ll_keyframes_last_error(kf.get()));
+    }
+    ~Visibility() { ll_visibility_destroy(v_); }
+    Visibility(const Visibility &) = delete;
+    Visibility &operator=(const Visibility &) = delete;
+
+    /* every op is one drive whose listed frames observe each other; the ordered frame pairs per op */
+    std::vector<long long> run(const std::vector<ll_visibility_op> &ops) {
+        std::vector<long long> pairs(ops.size(), 0);
+        check(ll_visibility_run(v_, ops.data(), (int)ops.size(), pairs.data()));
+        return pairs;
+    }
+    Counts counts(int frame) {
+        const ll_keyframe_info e = kf_->info(frame);
+        std::vector<unsigned char> all((size_t)2 * (e.n[0] + e.n[1]) + 1, 0);
+        check(ll_visibility_counts(v_, frame, all.data()));
+        Counts c;
+        c.corner.assign(all.begin(), all.begin() + (size_t)2 * e.n[0]);
+        c.surf.assign(all.begin() + (size_t)2 * e.n[0], all.begin() + (size_t)2 * (e.n[0] + e.n[1]));
+        return c;
+    }
+    /* raw / img [height][width] of the k-th listed frame of the last run */
+    void images(int k, std::vector<float> *raw, std::vector<float> *img) {
+        const size_t n = (size_t)p_.width * p_.height;
+        if (raw) raw->assign(n, 0.0f);
+        if (img) img->assign(n, 0.0f);
+        check(ll_visibility_images(v_, k, raw ? raw->data() : nullptr, img ? img->data() : nullptr));
+    }
+    void reset() { check(ll_visibility_reset(v_)); }
+    void timing(double ms[3], long long counts[3]) const { check(ll_visibility_timing(v_, ms, counts)); }
+    const ll_visibility_params &params() const { return p_; }
+    ll_visibility *get() const { return v_; }
+private:
+    void check(int rc) const { if (rc != LL_OK) throw Error(rc, ll_visibility_last_error(v_)); }
+    Keyframes *kf_;
+    ll_visibility_params p_;
+    ll_visibility *v_ = nullptr;
+};
+
 struct MapLayout {
     enum { N_COUNTS = 2 * 4851 };
     int cen[3] = {10, 10, 5};
@@ -579,6 +628,21 @@ public:
         if (added) added->assign(2 * ops.size(), 0);
         if (dropped) dropped->assign(2 * ops.size(), 0);
         return ll_cubemaps_insert_keyframes(cms, kf.get(), ops.data(), (int)ops.size(), added ? added->data() : nullptr, dropped ? dropped->data() : nullptr);
+    }
+    /* ll_cubemaps_insert_keyframes_filtered: the same with the points left out that `rule` removes by vis's counters (through >=
+     * min_through && hit <= max_hit); removed [n_ops][2] when given; added + dropped + removed = the listed points */
+    void insert_keyframes_filtered(const Keyframes &kf, const Visibility &vis, const ll_visibility_rule &rule, const std::vector<ll_insert_op> &ops,
+                                   std::vector<long long> *added = nullptr, std::vector<long long> *dropped = nullptr, std::vector<long long> *removed = nullptr) {
+        const int rc = insert_filtered_into(cms_, kf, vis, rule, ops, added, dropped, removed);
+        if (rc != LL_OK) check(rc);
+    }
+    static int insert_filtered_into(ll_cubemaps *cms, const Keyframes &kf, const Visibility &vis, const ll_visibility_rule &rule, const std::vector<ll_insert_op> &ops,
+                                    std::vector<long long> *added = nullptr, std::vector<long long> *dropped = nullptr, std::vector<long long> *removed = nullptr) {
+        if (added) added->assign(2 * ops.size(), 0);
+        if (dropped) dropped->assign(2 * ops.size(), 0);
+        if (removed) removed->assign(2 * ops.size(), 0);
+        return ll_cubemaps_insert_keyframes_filtered(cms, kf.get(), vis.get(), &rule, ops.data(), (int)ops.size(), added ? added->data() : nullptr,
+                                                     dropped ? dropped->data() : nullptr, removed ? removed->data() : nullptr);
     }
     /* ll_cubemaps_align: op i estimates the transform that takes map ops[i].src's world frame into map ops[i].dst's, starting at
      * ops[i].T_w7 -- laserMapping's optimisation over the whole of both maps, read-only.  T [n_ops][7]; ran [n_ops] and fit [n_ops]

@@ -58,6 +58,8 @@ EXPORTS = [
     "ll_keyframes_create", "ll_keyframes_destroy", "ll_keyframes_last_error", "ll_keyframes_size", "ll_keyframes_reset", "ll_keyframes_info",
     "ll_keyframes_add_cubemaps", "ll_keyframes_add_points", "ll_keyframes_export",
     "ll_cubemaps_insert_keyframes", "ll_cubemaps_insert_timing", "ll_drives_set_keyframes", "ll_drives_correct",
+    "ll_visibility_default_params", "ll_visibility_create", "ll_visibility_destroy", "ll_visibility_last_error", "ll_visibility_run",
+    "ll_visibility_counts", "ll_visibility_images", "ll_visibility_reset", "ll_visibility_timing", "ll_cubemaps_insert_keyframes_filtered",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -117,6 +119,23 @@ class KeyframeInfo(C.Structure):
 class InsertOp(C.Structure):
     """ll_insert_op: the listed frames of a Keyframes store go into map dst, frame k under poses_w7[k] (NULL: its stored pose)"""
     _fields_ = [("dst", C.c_int), ("n_frames", C.c_int), ("frames", C.c_void_p), ("poses_w7", C.c_void_p), ("reset", C.c_int), ("cen", C.c_int * 3)]
+
+
+class VisibilityParams(C.Structure):
+    """ll_visibility_params: the range image (width x height over el_min_deg .. el_max_deg, ranges min_range .. max_range), the vote
+    (margin_abs + margin_rel * r, observers within radius) and how many frames one run may list"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("el_min_deg", C.c_float), ("el_max_deg", C.c_float), ("min_range", C.c_float),
+                ("max_range", C.c_float), ("margin_abs", C.c_float), ("margin_rel", C.c_float), ("radius", C.c_float), ("max_images", C.c_int)]
+
+
+class VisibilityOp(C.Structure):
+    """ll_visibility_op: the listed frames of one drive observe each other, frame k under poses_w7[k] (NULL: its stored pose)"""
+    _fields_ = [("n_frames", C.c_int), ("frames", C.c_void_p), ("poses_w7", C.c_void_p)]
+
+
+class VisibilityRule(C.Structure):
+    """ll_visibility_rule: a point is removed iff through >= min_through and hit <= max_hit"""
+    _fields_ = [("min_through", C.c_int), ("max_hit", C.c_int)]
 
 
 class SeqLayout(C.Structure):
@@ -243,6 +262,19 @@ def load_library():
         _lib.ll_cubemaps_insert_timing.argtypes = [C.c_void_p] * 3
         _lib.ll_drives_set_keyframes.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib.ll_drives_correct.argtypes = [C.c_void_p] * 3
+        _lib.ll_visibility_default_params.restype = None
+        _lib.ll_visibility_default_params.argtypes = [C.c_void_p]
+        _lib.ll_visibility_create.argtypes = [C.c_void_p] * 3
+        _lib.ll_visibility_destroy.restype = None
+        _lib.ll_visibility_destroy.argtypes = [C.c_void_p]
+        _lib.ll_visibility_last_error.restype = C.c_char_p
+        _lib.ll_visibility_last_error.argtypes = [C.c_void_p]
+        _lib.ll_visibility_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_visibility_counts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_visibility_images.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.ll_visibility_reset.argtypes = [C.c_void_p]
+        _lib.ll_visibility_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_cubemaps_insert_keyframes_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -647,6 +679,10 @@ class Context:
     def keyframes(self, max_frames, cap_corner, cap_surf):
         """a Keyframes store on this context: up to max_frames frames, cap_corner / cap_surf points per cloud type (ll_keyframes_create)"""
         return Keyframes(self, max_frames, cap_corner, cap_surf)
+
+    def visibility(self, kf, **params):
+        """a Visibility object over the Keyframes store kf (ll_visibility_create); params: fields of visibility_params()"""
+        return Visibility(self, kf, **params)
 
     def algorithmic_bytes(self, first=0, count=1):
         b = [C.c_double(0) for _ in range(4)]
@@ -1168,12 +1204,14 @@ class CubeMaps:
         self._ck(self.lib.ll_cubemaps_merge_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
         return tuple(ms), tuple(int(c) for c in cnt)
 
-    def insert_keyframes(self, kf, ops):
+    def insert_keyframes(self, kf, ops, visibility=None, rule=None):
         """ops: a list of (dst, frames, poses, reset, cen) -- the frames (ids of the Keyframes store kf, in this order; they may repeat)
         go into map dst, frame k under poses[k] ([n, 7]; None: the poses the store holds); reset: dst is first emptied and given the
         centre cen (ignored without reset; None: (10, 10, 5)).  Every cube that received a point is voxel-filtered ONCE over its old
         cloud and all new points (the merge's semantics, not frame-by-frame mapping) -> (added [n_ops, 2], dropped [n_ops, 2]) int64.
-        Everything on the device; three synchronisations whatever len(ops) and the number of frames are"""
+        Everything on the device; three synchronisations whatever len(ops) and the number of frames are.
+        visibility: a Visibility object of kf -- the points its counters and rule ((min_through, max_hit); None: (2, 255)) remove are
+        left out (ll_cubemaps_insert_keyframes_filtered) -> (added, dropped, removed [n_ops, 2])"""
         rec = (InsertOp * max(len(ops), 1))()
         keep = []
         for i, (dst, frames, poses, reset, cen) in enumerate(ops):
@@ -1188,8 +1226,17 @@ class CubeMaps:
             for k, v in enumerate((10, 10, 5) if cen is None else cen):
                 rec[i].cen[k] = int(v)
         added = np.zeros((len(ops), 2), np.int64); dropped = np.zeros((len(ops), 2), np.int64)
-        self._ck(self.lib.ll_cubemaps_insert_keyframes(self.h, kf.h, C.addressof(rec), len(ops), added.ctypes.data, dropped.ctypes.data))
-        return added, dropped
+        if visibility is None:
+            if rule is not None:
+                raise ValueError("a rule needs a Visibility object")
+            self._ck(self.lib.ll_cubemaps_insert_keyframes(self.h, kf.h, C.addressof(rec), len(ops), added.ctypes.data, dropped.ctypes.data))
+            return added, dropped
+        visibility._live()
+        r = VisibilityRule(*((2, 255) if rule is None else (int(rule[0]), int(rule[1]))))
+        removed = np.zeros((len(ops), 2), np.int64)
+        self._ck(self.lib.ll_cubemaps_insert_keyframes_filtered(self.h, kf.h, visibility.h, C.addressof(r), C.addressof(rec), len(ops),
+                                                                added.ctypes.data, dropped.ctypes.data, removed.ctypes.data))
+        return added, dropped, removed
 
     def insert_timing(self):
         """the last insert_keyframes: ((assign ms, sort + gather ms, filter ms, commit ms), (points in, touched cubes, points out))"""
@@ -1322,6 +1369,96 @@ class Keyframes:
         out = np.zeros((max(int(off[-1]), 1), 4), np.float32)
         self._ck(self.lib.ll_keyframes_export(self.h, int(first), count, out.ctypes.data, off.ctypes.data))
         return out[:int(off[-1])], off
+
+
+def visibility_params(**kw):
+    """ll_visibility_default_params with the given fields replaced"""
+    p = VisibilityParams()
+    load_library().ll_visibility_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+class Visibility:
+    """One ll_visibility over a Keyframes store: per stored point how many other frames of its drive saw THROUGH it and how many HIT
+    it (range images of the frames' own clouds, a 3 x 3 minimum, a margin); CubeMaps.insert_keyframes(..., visibility=self) leaves
+    the points out that a rule over the two counters removes"""
+
+    def __init__(self, ctx, kf, **params):
+        self.ctx = ctx; self.lib = ctx.lib; self.kf = kf
+        self.params = visibility_params(**params)
+        self.h = C.c_void_p()
+        rc = self.lib.ll_visibility_create(kf.h, C.byref(self.params), C.byref(self.h))
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_keyframes_last_error(kf.h).decode())
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ll_visibility_destroy(self.h)        # reads nothing of the store: the order in which a Context closes its children is free
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_visibility_last_error(self.h).decode())
+
+    def _live(self):
+        if not getattr(self, "h", None) or not getattr(self.kf, "h", None):
+            raise LightLoamError(-7, "the Visibility object or its Keyframes store is closed")
+
+    def run(self, ops):
+        """ops: a list of (frames, poses) -- the frames of one drive (ids of the store, each at most once per call) observe each other,
+        frame k under poses[k] ([n, 7]; None: the stored poses) -> pairs [n_ops] int64, the ordered (subject, observer) frame pairs.
+        The listed frames' counters are made anew, the others keep theirs.  Three launches, one synchronisation"""
+        self._live()
+        rec = (VisibilityOp * max(len(ops), 1))()
+        keep = []
+        for i, (frames, poses) in enumerate(ops):
+            f = np.ascontiguousarray(frames, np.int32).reshape(-1)
+            p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+            if p is not None and len(p) != len(f):
+                raise ValueError("poses must have one row per listed frame")
+            keep += [f, p]
+            rec[i].n_frames = len(f); rec[i].frames = f.ctypes.data
+            rec[i].poses_w7 = None if p is None else p.ctypes.data
+        pairs = np.zeros(max(len(ops), 1), np.int64)
+        self._ck(self.lib.ll_visibility_run(self.h, C.addressof(rec), len(ops), pairs.ctypes.data))
+        return pairs[:len(ops)]
+
+    def counts(self, frame):
+        """(corner [n_corner, 2], surf [n_surf, 2]) uint8: (through, hit) of every point of the frame, each saturating at 255"""
+        self._live()
+        e = self.kf.info(frame)
+        out = np.zeros((max(e["n"][0] + e["n"][1], 1), 2), np.uint8)
+        self._ck(self.lib.ll_visibility_counts(self.h, int(frame), out.ctypes.data))
+        return out[:e["n"][0]], out[e["n"][0]:e["n"][0] + e["n"][1]]
+
+    def images(self, k):
+        """(raw, img) [height, width] float32 of the k-th listed frame, counted across ops, of the last run; +inf: empty"""
+        shape = (self.params.height, self.params.width)
+        raw = np.zeros(shape, np.float32); img = np.zeros(shape, np.float32)
+        self._ck(self.lib.ll_visibility_images(self.h, int(k), raw.ctypes.data, img.ctypes.data))
+        return raw, img
+
+    def reset(self):
+        """all counters zero; needed after Keyframes.reset before the object is used again"""
+        self._live()
+        self._ck(self.lib.ll_visibility_reset(self.h))
+
+    def timing(self):
+        """the last run: ((images ms, erode ms, vote ms), (listed frames, their points, frame pairs))"""
+        ms = np.zeros(3); cnt = np.zeros(3, np.int64)
+        self._ck(self.lib.ll_visibility_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
+        return tuple(ms), tuple(int(c) for c in cnt)
 
 
 class PlacesParams(C.Structure):

@@ -63,6 +63,17 @@ __device__ __forceinline__ void cm_assign_one(const float4 *stk, int n, const do
     }
     cm_wave_count(cube, addcnt);
 }
+/* the last segment whose first tile is <= t: the tables of the tiled kernels (map merge, keyframe insert, visibility) */
+template <typename S>
+__device__ __forceinline__ int mm_find(const S *seg, int nseg, unsigned t)
+{
+    int lo = 0, hi = nseg;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned)__builtin_amdgcn_readfirstlane((int)seg[mid].tile0) <= t) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 #define CM_GID_SHIFT 20                  /* global id = position in the valid list << 20 | position in the cube */
 
 /* map export (ll_map_export.hip): one non-empty cloud of the output.  dst: its first point in the output; tile0: the tiles of
@@ -101,7 +112,25 @@ struct ll_keyframes {
     std::vector<ll_keyframe_info> tab;
     LLMapExport X;
     std::string err;
+    unsigned long long n_reset = 0;               /* ll_keyframes_reset calls: what an ll_visibility's counters were made under */
     float4 *region(int w) const { return pool + (w ? cap[0] : 0); }
+};
+/* visibility (ll_visibility.hip): per pool point of ONE store two bytes (through, hit) at the point's pool index (the surf region
+ * begins at cap[0]), max_images raw and eroded range images, the table pair of a run's upload (X), the events around the three
+ * launches; last: the store ids of the last run's listed frames by list position; epoch: kf->n_reset when the counters were made */
+struct ll_visibility {
+    ll_ctx *ctx = nullptr;
+    ll_keyframes *kf = nullptr;
+    ll_visibility_params p;
+    unsigned long long epoch = 0;
+    unsigned char *d_cnt = nullptr;
+    float *d_raw = nullptr, *d_img = nullptr;
+    LLMapExport X;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<int> last;
+    double ms[3] = {0.0, 0.0, 0.0};               /* the last run: images, erode, vote (events) */
+    long long counts[3] = {0, 0, 0};              /* listed frames, their points, ordered frame pairs */
+    std::string err;
 };
 /* map alignment (ll_map_align.hip): what an aligning object keeps between calls -- one device buffer grown to the need (search
  * tables, cell-ordered dst points, flat src stacks, per-op fit results, residual blocks and partial sums), the events around the
@@ -147,6 +176,9 @@ struct ll_cubemap : CmTables {                   /* the pair tables (ll_cubemap_
 void cm_run_moves(ll_cubemap *cm, int w, const std::vector<CmPiece> &moves);
 
 #define LL_HIDDEN __attribute__((visibility("hidden")))
+/* ll_visibility.hip, for the filtered keyframe insert: may v's counters be read for kf's points?  LL_OK, or LL_ERR_ARG (another
+ * store) / LL_ERR_STATE (the store was reset since) with *why filled */
+LL_HIDDEN int llvis_check(const ll_visibility *v, const ll_keyframes *kf, std::string *why);
 /* ll_keyframes.hip, for ll_drives.hip: room for n_frames more frames of at most max_pts[w] points each?  LL_OK or LL_ERR_CAPACITY (kf->err set) */
 LL_HIDDEN int llkf_room(ll_keyframes *kf, int n_frames, const int max_pts[2]);
 /* ll_map_export.hip: the tile size of this call; the segments of one map in output order (returns its points; segs == nullptr:

@@ -52,6 +52,7 @@ extern "C" int ll_keyframes_reset(ll_keyframes *kf)
 {
     if (!kf) return LL_ERR_ARG;
     kf->tab.clear(); kf->top[0] = kf->top[1] = 0;
+    ++kf->n_reset;                                                /* an ll_visibility's counters mean nothing from here on */
     return LL_OK;
 }
 

@@ -28,6 +28,11 @@
  * lie in the store's pool, with a pose per SEGMENT; a record's flat order is its listed frames back to back.  Everything from
  * k_mm_cstart to the commit is mm_run, which both entry points call; an op may ask for its dst to be emptied first, which mm_run
  * does once the capacity decision has passed and takes back if the call fails before its commit.
+ *
+ * ll_cubemaps_insert_keyframes_filtered is the same call with k_kf_assign<true>: a point that the rule removes by its two visibility
+ * counters (ll_visibility.hip; read at the point's pool index) gets key 4851 like a point outside the array, and the removed points
+ * per record are counted behind the count tables -- so everything from k_mm_cstart on is untouched, and `dropped` is the outside
+ * bin minus the removed ones.
  */
 #include "ll_cubemap.h"
 #include <chrono>
@@ -47,19 +52,16 @@ struct MmChunk { int first, cnt, rec, pad; };
 struct MmCopy { const float4 *src; const int *index; float4 *dst; int cnt; unsigned tile0; };   /* dst[i] = index ? src[index[i]] : src[i] */
 
 /* ------------------------------------------------------------------ kernels */
-template <typename S>
-__device__ __forceinline__ int mm_find(const S *seg, int nseg, unsigned t)
-{
-    int lo = 0, hi = nseg;                                        /* the last segment whose first tile is <= t */
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((unsigned)__builtin_amdgcn_readfirstlane((int)seg[mid].tile0) <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+/* the filtered keyframe insert: the store's pool, the visibility counters (two bytes per pool point: through, hit), the rule, and
+ * removed[record] */
+struct KfFilter { const float4 *pool; const unsigned char *vis; int min_through, max_hit; int *removed; };
 
-/* tile `tile` of a source cloud of cnt points whose first point has the flat index dst, under the pose Tsrc and the centre of record rec */
-__device__ __forceinline__ void mm_assign_tile(const float4 *src, int dst, int cnt, int tile, const double *Tsrc, const MmRec *recs, int rec, float4 *tp, int *keys, int *addcnt)
+/* tile `tile` of a source cloud of cnt points whose first point has the flat index dst, under the pose Tsrc and the centre of record rec.
+ * FILTER: a point the rule removes (through >= min_through && hit <= max_hit, its counters at its pool index) gets the "outside
+ * the array" key like a dropped point and is counted in removed[rec] with one add per wave */
+template <bool FILTER>
+__device__ __forceinline__ void mm_assign_tile(const float4 *src, int dst, int cnt, int tile, const double *Tsrc, const MmRec *recs, int rec, float4 *tp, int *keys, int *addcnt,
+                                               const KfFilter *F = nullptr)
 {
     const MmRec &R = recs[rec];
     const int first = tile * MM_TILE, n = min(MM_TILE, cnt - first);
@@ -70,6 +72,19 @@ __device__ __forceinline__ void mm_assign_tile(const float4 *src, int dst, int c
     float4 po[MM_TILE / 256];
 #pragma unroll
     for (int k = 0; k < MM_TILE / 256; ++k) po[k] = src[first + min(k * 256 + (int)threadIdx.x, n - 1)];   /* every load before the first store */
+    bool gone[MM_TILE / 256] = {};
+    if (FILTER) {
+        const uchar2 *vis = (const uchar2 *)F->vis + (src - F->pool) + first;
+        int n_gone = 0;
+#pragma unroll
+        for (int k = 0; k < MM_TILE / 256; ++k) {
+            const int i = k * 256 + (int)threadIdx.x;
+            const uchar2 th = vis[min(i, n - 1)];
+            gone[k] = i < n && (int)th.x >= F->min_through && (int)th.y <= F->max_hit;
+            n_gone += __popcll(__ballot(gone[k]));
+        }
+        if ((threadIdx.x & 63) == 0 && n_gone > 0) atomicAdd(&F->removed[rec], n_gone);
+    }
 #pragma unroll
     for (int k = 0; k < MM_TILE / 256; ++k) {
         const int i = k * 256 + (int)threadIdx.x;
@@ -83,6 +98,7 @@ __device__ __forceinline__ void mm_assign_tile(const float4 *src, int dst, int c
             int ci, cj, ck;
             cube = cm_cube_of(sx, sy, sz, cen, &ci, &cj, &ck);
             if (cube < 0) cube = CM_N;                            /* outside the array: a bin of its own */
+            if (FILTER && gone[k]) cube = CM_N;                   /* removed: the same bin, told apart by removed[rec] */
             keys[dst + first + i] = cube;
         }
         cm_wave_count(cube, count);                               /* one add per wave and cube */
@@ -92,16 +108,18 @@ __device__ __forceinline__ void mm_assign_tile(const float4 *src, int dst, int c
 __global__ __launch_bounds__(256) void k_mm_assign(const MmSeg *seg, int nseg, const MmRec *recs, float4 *tp, int *keys, int *addcnt)
 {
     const MmSeg s = seg[mm_find(seg, nseg, blockIdx.x)];
-    mm_assign_tile(s.src, s.dst, s.cnt, (int)(blockIdx.x - s.tile0), recs[s.rec].T, recs, s.rec, tp, keys, addcnt);
+    mm_assign_tile<false>(s.src, s.dst, s.cnt, (int)(blockIdx.x - s.tile0), recs[s.rec].T, recs, s.rec, tp, keys, addcnt);
 }
 
 /* keyframe insert: the same for one tile of one (frame, type) cloud where it lies in the store's pool; the pose is its SEGMENT's --
  * every listed frame has its own -- and the record (op, type) gives the centre and the count table.  A record's flat order is its
- * frames back to back, so the chunks of the counting sort below run across frame boundaries */
-__global__ __launch_bounds__(256) void k_kf_assign(const KfSeg *seg, int nseg, const MmRec *recs, float4 *tp, int *keys, int *addcnt)
+ * frames back to back, so the chunks of the counting sort below run across frame boundaries.  FILTER = false is the plain insert
+ * (F is not read); FILTER = true is ll_cubemaps_insert_keyframes_filtered */
+template <bool FILTER>
+__global__ __launch_bounds__(256) void k_kf_assign(const KfSeg *seg, int nseg, const MmRec *recs, float4 *tp, int *keys, int *addcnt, KfFilter F)
 {
     const KfSeg *s = seg + mm_find(seg, nseg, blockIdx.x);
-    mm_assign_tile(s->src, s->dst, s->cnt, (int)(blockIdx.x - s->tile0), s->T, recs, s->rec, tp, keys, addcnt);
+    mm_assign_tile<FILTER>(s->src, s->dst, s->cnt, (int)(blockIdx.x - s->tile0), s->T, recs, s->rec, tp, keys, addcnt, &F);
 }
 
 /* cstart[r][b] = addcnt[r][0] + .. + addcnt[r][b - 1]: one workgroup per record */
@@ -263,6 +281,7 @@ struct MmJob {
     long long N = 0;
     std::function<bool()> stage;                                  /* the caller's segment table into the call's arena; false: failed */
     std::function<void(const MmRec *d_recs, float4 *d_tp, int *d_keys, int *d_addcnt, hipStream_t st)> assign;
+    bool filtered = false;                                        /* the assign stage also counts removed points: nrec ints behind the count tables */
     double *ms = nullptr; long long *counts = nullptr;            /* [4], [3] of LLMapMerge */
 };
 
@@ -291,7 +310,7 @@ static void mm_reset(ll_cubemaps *cms, const MmOp &o)
 
 /* everything after the refusals that need no look at a point: workspace, the assign stage, then from k_mm_cstart to the commit --
  * count read-back, capacity decision, plan, gather, filter, commit */
-static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropped)
+static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropped, long long *removed = nullptr)
 {
     LLMapMerge &G = llcms_merge_state(cms);
     ll_ctx *ctx = llcms_map(cms, 0)->ctx;
@@ -303,6 +322,7 @@ static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropp
     J.ms[0] = J.ms[1] = J.ms[2] = J.ms[3] = 0.0; J.counts[0] = N; J.counts[1] = J.counts[2] = 0;
     if (added) std::fill(added, added + nrec, 0ll);
     if (dropped) std::fill(dropped, dropped + nrec, 0ll);
+    if (removed) std::fill(removed, removed + nrec, 0ll);
     if (N == 0) {                                                 /* empty sources: nothing to move */
         for (const MmOp &o : J.ops) if (o.reset) mm_reset(cms, o);
         return LL_OK;
@@ -315,7 +335,8 @@ static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropp
     }
     MmCarve A{nullptr};                                           /* first the size, then the pointers */
     A.take<float4>((size_t)N); A.take<int>((size_t)N); A.take<int>((size_t)N);
-    A.take<int>((size_t)nrec * MM_BINS); A.take<int>((size_t)nrec * MM_BINS); A.take<int>(chunks.size() * MM_BINS);
+    const size_t n_cnt = (size_t)nrec * MM_BINS + (J.filtered ? (size_t)nrec : 0);
+    A.take<int>(n_cnt); A.take<int>((size_t)nrec * MM_BINS); A.take<int>(chunks.size() * MM_BINS);
     {
         std::string why;
         A.p = mm_reserve(G, 0, A.at, why);
@@ -324,13 +345,13 @@ static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropp
     A.at = 0;
     float4 *d_tp = A.take<float4>((size_t)N);
     int *d_keys = A.take<int>((size_t)N), *d_perm = A.take<int>((size_t)N);
-    int *d_addcnt = A.take<int>((size_t)nrec * MM_BINS), *d_cstart = A.take<int>((size_t)nrec * MM_BINS), *d_H = A.take<int>(chunks.size() * MM_BINS);
+    int *d_addcnt = A.take<int>(n_cnt), *d_cstart = A.take<int>((size_t)nrec * MM_BINS), *d_H = A.take<int>(chunks.size() * MM_BINS);
     llcms_begin(cms);
     const MmRec *d_recs = (const MmRec *)llcms_stage(cms, recs.data(), recs.size() * sizeof(MmRec));
     const MmChunk *d_chunks = (const MmChunk *)llcms_stage(cms, chunks.data(), chunks.size() * sizeof(MmChunk));
     if (!d_recs || !d_chunks || !J.stage()) return LL_ERR_HIP;
     /* ---- stage A: points -> cubes, by-cube order; host: the cubes' new-point counts of every record */
-    MM_HIP(hipMemsetAsync(d_addcnt, 0, (size_t)nrec * MM_BINS * sizeof(int), st));
+    MM_HIP(hipMemsetAsync(d_addcnt, 0, n_cnt * sizeof(int), st));
     MM_HIP(hipEventRecord(G.ev[0], st));
     J.assign(d_recs, d_tp, d_keys, d_addcnt, st);
     MM_HIP(hipEventRecord(G.ev[1], st));
@@ -340,7 +361,7 @@ static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropp
     hipLaunchKernelGGL(k_mm_place, dim3((unsigned)chunks.size()), dim3(64), 0, st, d_chunks, d_recs, (const int *)d_keys, (const int *)d_H, d_perm);
     MM_HIP(hipEventRecord(G.ev[2], st));
     MM_HIP(hipGetLastError());
-    std::vector<int> addcnt((size_t)nrec * MM_BINS);
+    std::vector<int> addcnt(n_cnt);
     {
         int *pin = (int *)ll_pinned_scratch(addcnt.size() * sizeof(int));
         if (!pin) return llcms_fail(cms, LL_ERR_HIP, J.what + "no page-locked scratch");
@@ -361,7 +382,9 @@ static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropp
         long long live = 0;
         for (int c = 0; c < CM_N; ++c) { n_add[r] += a[c]; if (!o.reset) live += dst->cnt[w][c]; }
         if (added) added[r] = n_add[r];
-        if (dropped) dropped[r] = a[CM_N];
+        const int gone = J.filtered ? addcnt[(size_t)nrec * MM_BINS + r] : 0;     /* removed points sit in the outside bin too */
+        if (dropped) dropped[r] = a[CM_N] - gone;
+        if (removed) removed[r] = gone;
         if (live + n_add[r] > (long long)dst->cap_pool)
             return llcms_fail(cms, LL_ERR_CAPACITY, J.what + "op " + std::to_string(r / 2) + " (" + o.who + "): " +
                               std::to_string(live) + " " + mm_type(w) + " points + " + std::to_string(n_add[r]) + " added, pool_points is " + std::to_string(dst->cap_pool));
@@ -545,12 +568,21 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
 }
 
 /* ------------------------------------------------------------------ keyframe insert: one transform per frame through the same stages */
-extern "C" int ll_cubemaps_insert_keyframes(ll_cubemaps *cms, const ll_keyframes *kf, const ll_insert_op *ops, int n_ops, long long *added, long long *dropped)
+/* v == nullptr: the plain insert.  Otherwise the points that `rule` removes by v's counters are left out and counted in removed */
+static int kf_insert(ll_cubemaps *cms, const ll_keyframes *kf, const ll_visibility *v, const ll_visibility_rule *rule, const ll_insert_op *ops, int n_ops,
+                     long long *added, long long *dropped, long long *removed)
 {
     if (!cms) return LL_ERR_ARG;
-    const std::string what = "keyframe insert: ";
+    const std::string what = v ? "filtered keyframe insert: " : "keyframe insert: ";
     if (!kf || !ops || n_ops < 1) return llcms_fail(cms, LL_ERR_ARG, what + "kf or ops is NULL, or n_ops < 1");
     if (kf->ctx != llcms_map(cms, 0)->ctx) return llcms_fail(cms, LL_ERR_ARG, what + "the store belongs to another context");
+    if (v) {
+        if (rule->min_through < 1 || rule->min_through > 256 || rule->max_hit < 0 || rule->max_hit > 255)
+            return llcms_fail(cms, LL_ERR_ARG, what + "the rule is outside its ranges (min_through in 1 .. 256, max_hit in 0 .. 255)");
+        std::string why;
+        const int rc = llvis_check(v, kf, &why);
+        if (rc) return llcms_fail(cms, rc, what + why);
+    }
     const int S = llcms_size(cms), size = (int)kf->tab.size();
     /* ---- every refusal that needs no look at a point: before anything is enqueued */
     std::vector<char> is_dst(S, 0);
@@ -610,10 +642,30 @@ extern "C" int ll_cubemaps_insert_keyframes(ll_cubemaps *cms, const ll_keyframes
     J.N = N;
     const KfSeg *d_segs = nullptr;
     J.stage = [&]() { d_segs = (const KfSeg *)llcms_stage(cms, segs.data(), segs.size() * sizeof(KfSeg)); return d_segs != nullptr; };
+    J.filtered = v != nullptr;
     J.assign = [&](const MmRec *d_recs, float4 *d_tp, int *d_keys, int *d_addcnt, hipStream_t st) {
-        hipLaunchKernelGGL(k_kf_assign, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt);
+        if (v) {
+            const KfFilter F = {kf->pool, v->d_cnt, rule->min_through, rule->max_hit, d_addcnt + (size_t)2 * n_ops * MM_BINS};
+            hipLaunchKernelGGL(k_kf_assign<true>, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt, F);
+        } else {
+            const KfFilter F = {nullptr, nullptr, 0, 0, nullptr};
+            hipLaunchKernelGGL(k_kf_assign<false>, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt, F);
+        }
     };
-    return mm_run(cms, J, added, dropped);
+    return mm_run(cms, J, added, dropped, removed);
+}
+
+extern "C" int ll_cubemaps_insert_keyframes(ll_cubemaps *cms, const ll_keyframes *kf, const ll_insert_op *ops, int n_ops, long long *added, long long *dropped)
+{
+    return kf_insert(cms, kf, nullptr, nullptr, ops, n_ops, added, dropped, nullptr);
+}
+
+extern "C" int ll_cubemaps_insert_keyframes_filtered(ll_cubemaps *cms, const ll_keyframes *kf, const ll_visibility *v, const ll_visibility_rule *rule,
+                                                     const ll_insert_op *ops, int n_ops, long long *added, long long *dropped, long long *removed)
+{
+    if (!cms) return LL_ERR_ARG;
+    if (!v || !rule) return llcms_fail(cms, LL_ERR_ARG, "filtered keyframe insert: the visibility object or the rule is NULL");
+    return kf_insert(cms, kf, v, rule, ops, n_ops, added, dropped, removed);
 }
 
 extern "C" int ll_cubemaps_insert_timing(const ll_cubemaps *cms, double *ms4, long long *counts3)
