@@ -960,6 +960,87 @@ int  ll_cubemaps_insert_keyframes_filtered(ll_cubemaps *cms, const ll_keyframes 
                                            const ll_insert_op *ops, int n_ops, long long *added, long long *dropped,
                                            long long *removed /* [n_ops][2] each, may be NULL */);
 
+/* ---------------------------------------------------------------- bev: from a place match to a guess, by correlative matching
+ * A Scan Context match (ll_places) names the revisited scan and a heading good to a sector; the translation between the two sensor
+ * positions is unknown and is metres on a real revisit, while ll_cubemaps_align and ll_cubemaps_localize_slots are local (a start
+ * inside the 1 m association radius).  ll_bev closes that gap with correlative scan matching on bird's-eye occupancy grids (Olson,
+ * ICRA 2009; the loop-closure matcher of Cartographer, Hess et al., ICRA 2016) -- not part of the reference -- over what an
+ * ll_keyframes store holds.  An ll_bev belongs to ONE store (and its context).  Per op a QUERY (a list of stored frames) is matched
+ * against a TARGET (a list of stored frames) over n_yaws x (2 sh)^2 rigid hypotheses (yaw_j, sx, sy); every score is a count, so
+ * everything below is integers and exact.  All f32 arithmetic has every product and sum rounded, left to right.
+ * A SIDE'S POINTS.  A side is a list of frame ids, the first is the ANCHOR; ids may repeat.  Frame k is under poses_w7[k], or under
+ * its stored pose when the pointer is NULL.  Every point p of both stored clouds of every listed frame, the anchor included:
+ *   w = pointAssociateToMap(P_k, p) as ll_cubemaps_insert_keyframes has it: f64, each coordinate rounded to float once;
+ *   l = R(q_a)^-1 (w - t_a) with the anchor's pose, as the visibility vote spells it (above): f64 from those floats, each coordinate
+ *   rounded to float once.  A point with a non-finite l coordinate is dropped before any conversion to integer.
+ * CELLS AND LAYERS.  inv = (float)(1.0 / (double)cell), invz = (float)(1.0 / (double)z_layer);
+ *   fx = floorf(x * inv), fy = floorf(y * inv), fl = floorf((z - z_min) * invz); every range test is made on the floats, then
+ *   converted: a point HAS A LAYER iff 0 <= fl <= 7 (eight layers), and is INSIDE THE SQUARE iff -half <= fx, fy <= half - 1.
+ * TARGET.  A byte per cell, [2 half][2 half]: bit fl of cell (fy + half, fx + half) is set for every target point that has a layer
+ *   and lies inside the square (a 32-bit integer atomic OR: order-free).
+ * QUERY.  Per point (x, y, layer) of l at the point's own position in a per-call list; the layer is -1 when the point is dropped or
+ *   has no layer; no compaction.  n_query: the query points with a layer.
+ * HYPOTHESES.  yaw_j = yaw0 + (double)j * yaw_step (host, f64), c_j = (float)cos(yaw_j), s_j = (float)sin(yaw_j) (libm).  For a query
+ *   point with a layer: xr = c*x - s*y, yr = s*x + c*y, the cell (fx, fy) of (xr, yr); USED iff inside the square.
+ * SCORE.  score[j][sy + sh][sx + sh], sx, sy in -sh .. sh - 1: the number of used query points whose bit `layer` is set in target
+ *   cell (fx + sx, fy + sy); a cell outside the grid is empty.
+ * PEAK.  The best hypothesis is the largest score; ties go to the lowest flat index (j, sy, sx).  second: the largest score among
+ *   the hypotheses with |j - j*| > excl_yaw or |sx - sx*| > excl_shift or |sy - sy*| > excl_shift; -1 when there is none.
+ *   second / score is the ambiguity handle -- a corridor or a straight road scores nearly as well one cell along -- and plays the
+ *   role the eigenvalues play for the fine registration; thresholds on real data are the caller's.
+ * RESULT.  yaw = yaw_{j*}; D_w7 = (0, 0, sin(yaw / 2), cos(yaw / 2), (double)sx * (double)cell, (double)sy * (double)cell, 0), host
+ *   f64: p_target ~ D p_query, i.e. D measures P_target_anchor^-1 P_query_anchor in x, y and yaw.  Roll, pitch and z are NOT
+ *   searched: the level-sensor assumption of Scan Context.  The guess for ll_cubemaps_align between two maps is
+ *   T0 = P_c o D o P_q^-1 (ll_bev_guess); the start pose of a lane localising in the candidate's map is P_c o D.
+ * WHY z_min = -1.  With the ground layer in, the sensor-centred ground rings of two scans coincide at ZERO shift whatever the true
+ *   displacement is, and zero shift wins every time (the tests' yard scene: 6 896 hits at zero against 724 at the true displacement).  The
+ *   default drops the ground of a sensor mounted about 1.8 m up; a caller with another mounting height changes z_min.
+ *   ll_bev_default_params  cell 0.5, half 128, shift_half 16, z_min -1, z_layer 1, excl_yaw 1, excl_shift 2, max_ops 64, max_yaws 16,
+ *                          max_points 2^21
+ *   ll_bev_create     cell, z_layer finite and > 0, z_min finite, half in 1 .. 512, shift_half in 1 .. 16, excl_yaw, excl_shift >= 0,
+ *                     max_ops in 1 .. 4096, max_yaws in 1 .. 64, max_points in 1 .. 2^30, and (2 half + 2 shift_half)^2 + 4096 bytes
+ *                     within the 160 KiB of LDS (LL_ERR_ARG otherwise, ll_keyframes_last_error of the store).  Device memory is
+ *                     taken by the first call that needs it and grown to the need.  Destroy it before its store.
+ *   ll_bev_match      n_ops ops, one result each.  The host builds the tile table of the listed clouds, the poses, the op and yaw
+ *                     tables; ONE upload, ONE fill (grids and counts), THREE launches whatever n_ops is -- k_bev_prepare (a workgroup
+ *                     per 1024-point tile of one (op, side, frame, type) cloud where it lies in the store's pool), k_bev_score (a
+ *                     workgroup per (op, yaw), a thread per shift, the op's grid resident in LDS inside a zero border of shift_half
+ *                     cells, the query list staged 1024 entries at a time and walked by every thread) and k_bev_peak (a workgroup
+ *                     per op) --, ONE synchronisation.  No floating-point atomic: an op's volume and result are the same bits
+ *                     alone, at any position of any batch, and on every repetition.  An op whose query or target has no usable
+ *                     point succeeds with score 0 and the best at flat index 0.
+ *   ll_bev_volume     the scores [n_yaws][2 sh][2 sh] of op `op` of the LAST successful call (tests, analysis); one synchronisation
+ *   ll_bev_grid       the target grid [2 half][2 half] of that op
+ *   ll_bev_reset      the last call forgotten; the object follows the store again after ll_keyframes_reset
+ *   ll_bev_timing     the last call: ms = prepare, score, peak (device events); counts = ops, listed points, hypotheses
+ *   ll_bev_guess      T0 = P_c o D o P_q^-1 in the pose_w7 layout, host f64, no device, the poses used as given (unit quaternions
+ *                     are the caller's): A o B = (q_A x q_B, R(q_A) t_B + t_A), the product spelled
+ *                     (aw*bx + ax*bw + ay*bz - az*by, aw*by - ax*bz + ay*bw + az*bx, aw*bz + ax*by - ay*bx + az*bw,
+ *                     aw*bw - ax*bx - ay*by - az*bz), R(q) v as pointAssociateToMap rotates; P^-1 = (q*, -(R(q*) t)); D o P_q^-1
+ *                     first, then P_c o that.  LL_ERR_ARG for a NULL pointer.
+ * Errors of ll_bev_match, all decided before anything is enqueued; a refused call launches nothing and leaves the last call's volume,
+ * grids and timing readable: LL_ERR_ARG for a NULL handle, ops or out, n_ops outside 1 .. max_ops, a side with no frame or a NULL
+ * list, an id outside the store, a non-finite pose (given or stored), a non-finite yaw0, yaw_step or yaw_j, n_yaws outside
+ * 1 .. max_yaws; LL_ERR_CAPACITY for more listed points (both sides, all ops) than max_points; LL_ERR_STATE for match, volume and
+ * grid after ll_keyframes_reset until ll_bev_reset or a new object; LL_ERR_ARG for a volume or grid of an op the last call did not
+ * have; LL_ERR_HIP as elsewhere (the buffer cannot be grown: the last call is then forgotten).                                       */
+typedef struct ll_bev ll_bev;
+typedef struct { float cell; int half, shift_half; float z_min, z_layer; int excl_yaw, excl_shift, max_ops, max_yaws; long long max_points; } ll_bev_params;
+typedef struct { int n_target; const int *target; const double *target_poses_w7 /* [n_target][7], NULL: the stored poses */;
+                 int n_query;  const int *query;  const double *query_poses_w7 /* [n_query][7], NULL: the stored poses */;
+                 double yaw0, yaw_step; int n_yaws; } ll_bev_op;
+typedef struct { int score, second, iyaw, sx, sy, n_query; double yaw; double D_w7[7]; } ll_bev_result;
+void ll_bev_default_params(ll_bev_params *p);
+int  ll_bev_create(ll_keyframes *kf, const ll_bev_params *p, ll_bev **out);
+void ll_bev_destroy(ll_bev *b);
+const char *ll_bev_last_error(const ll_bev *b);
+int  ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_result *out /* [n_ops] */);
+int  ll_bev_volume(ll_bev *b, int op, int *scores /* [n_yaws][2 sh][2 sh] */);
+int  ll_bev_grid(ll_bev *b, int op, unsigned char *cells /* [2 half][2 half] */);
+int  ll_bev_reset(ll_bev *b);
+int  ll_bev_timing(const ll_bev *b, double *ms /* prepare, score, peak */, long long *counts /* ops, listed points, hypotheses */);
+int  ll_bev_guess(const double *Pc_w7, const double *D_w7, const double *Pq_w7, double *T0_w7);
+
 /* ---------------------------------------------------------------- drives: capture while driving, and take a correction
  * ll_drives_set_keyframes(d, kf, every): from the next step on, at the end of a step every lane that ran a frame -- mapping or
  * localising -- whose per-lane frame index (0 at START) is a multiple of every (>= 1) is captured into kf: its stack clouds and its

@@ -488,6 +488,58 @@ private:
     ll_visibility *v_ = nullptr;
 };
 
+/* Bev (ll_bev): correlative matching of bird's-eye occupancy grids over a Keyframes store -- from a place match (the revisited frame,
+ * a heading good to a sector) to the 3-DoF transform D that starts an align (guess) or a localising lane.  Destroy it before its
+ * store. */
+class Bev {
+public:
+    static ll_bev_params default_params() { ll_bev_params p; ll_bev_default_params(&p); return p; }
+    explicit Bev(Keyframes &kf) : Bev(kf, default_params()) {}
+    Bev(Keyframes &kf, const ll_bev_params &p) : p_(p) {
+        const int rc = ll_bev_create(kf.get(), &p, &b_);
+        if (rc != LL_OK) throw Error(rc, ll_keyframes_last_error(kf.get()));
+    }
+    ~Bev() { ll_bev_destroy(b_); }
+    Bev(const Bev &) = delete;
+    Bev &operator=(const Bev &) = delete;
+
+    /* one result per op; one upload, one fill, three launches, one synchronisation whatever ops.size() is */
+    std::vector<ll_bev_result> match(const std::vector<ll_bev_op> &ops) {
+        std::vector<ll_bev_result> out(ops.size());
+        check(ll_bev_match(b_, ops.data(), (int)ops.size(), out.data()));
+        n_yaws_.resize(ops.size());
+        for (size_t i = 0; i < ops.size(); ++i) n_yaws_[i] = ops[i].n_yaws;
+        return out;
+    }
+    /* the scores [n_yaws][2 sh][2 sh] of op `op` of the last match */
+    std::vector<int> volume(int op) {
+        const size_t n = op >= 0 && (size_t)op < n_yaws_.size() ? (size_t)n_yaws_[op] : 1;
+        std::vector<int> v(n * 4 * p_.shift_half * p_.shift_half, 0);
+        check(ll_bev_volume(b_, op, v.data()));
+        return v;
+    }
+    /* the target grid [2 half][2 half] of op `op` of the last match */
+    std::vector<unsigned char> grid(int op) {
+        std::vector<unsigned char> g((size_t)4 * p_.half * p_.half, 0);
+        check(ll_bev_grid(b_, op, g.data()));
+        return g;
+    }
+    void reset() { check(ll_bev_reset(b_)); n_yaws_.clear(); }
+    void timing(double ms[3], long long counts[3]) const { check(ll_bev_timing(b_, ms, counts)); }
+    /* T0 = P_c o D o P_q^-1: the guess of an align of the query's map onto the candidate's */
+    static void guess(const double Pc_w7[7], const double D_w7[7], const double Pq_w7[7], double T0_w7[7]) {
+        const int rc = ll_bev_guess(Pc_w7, D_w7, Pq_w7, T0_w7);
+        if (rc != LL_OK) throw Error(rc, "bev guess: a NULL pointer");
+    }
+    const ll_bev_params &params() const { return p_; }
+    ll_bev *get() const { return b_; }
+private:
+    void check(int rc) const { if (rc != LL_OK) throw Error(rc, ll_bev_last_error(b_)); }
+    ll_bev_params p_;
+    ll_bev *b_ = nullptr;
+    std::vector<int> n_yaws_;
+};
+
 struct MapLayout {
     enum { N_COUNTS = 2 * 4851 };
     int cen[3] = {10, 10, 5};

@@ -60,6 +60,8 @@ EXPORTS = [
     "ll_cubemaps_insert_keyframes", "ll_cubemaps_insert_timing", "ll_drives_set_keyframes", "ll_drives_correct",
     "ll_visibility_default_params", "ll_visibility_create", "ll_visibility_destroy", "ll_visibility_last_error", "ll_visibility_run",
     "ll_visibility_counts", "ll_visibility_images", "ll_visibility_reset", "ll_visibility_timing", "ll_cubemaps_insert_keyframes_filtered",
+    "ll_bev_default_params", "ll_bev_create", "ll_bev_destroy", "ll_bev_last_error", "ll_bev_match", "ll_bev_volume", "ll_bev_grid", "ll_bev_reset",
+    "ll_bev_timing", "ll_bev_guess",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -136,6 +138,27 @@ class VisibilityOp(C.Structure):
 class VisibilityRule(C.Structure):
     """ll_visibility_rule: a point is removed iff through >= min_through and hit <= max_hit"""
     _fields_ = [("min_through", C.c_int), ("max_hit", C.c_int)]
+
+
+class BevParams(C.Structure):
+    """ll_bev_params: the grid (cell metres, 2 half cells a side about the anchor's sensor, eight layers of z_layer from z_min), the
+    search (shifts -shift_half .. shift_half - 1), the exclusion window of `second`, and the limits of one call"""
+    _fields_ = [("cell", C.c_float), ("half", C.c_int), ("shift_half", C.c_int), ("z_min", C.c_float), ("z_layer", C.c_float), ("excl_yaw", C.c_int),
+                ("excl_shift", C.c_int), ("max_ops", C.c_int), ("max_yaws", C.c_int), ("max_points", C.c_longlong)]
+
+
+class BevOp(C.Structure):
+    """ll_bev_op: the query frames against the target frames (the first of a list is its anchor; frame k under its row of the poses,
+    NULL: its stored pose) over the yaws yaw0 + j * yaw_step, j < n_yaws"""
+    _fields_ = [("n_target", C.c_int), ("target", C.c_void_p), ("target_poses_w7", C.c_void_p), ("n_query", C.c_int), ("query", C.c_void_p),
+                ("query_poses_w7", C.c_void_p), ("yaw0", C.c_double), ("yaw_step", C.c_double), ("n_yaws", C.c_int)]
+
+
+class BevResult(C.Structure):
+    """ll_bev_result: the best hypothesis (iyaw, sx, sy) and its score, the best score outside the exclusion window (-1: none), the
+    query points with a layer, the yaw and D_w7 with p_target ~ D p_query"""
+    _fields_ = [("score", C.c_int), ("second", C.c_int), ("iyaw", C.c_int), ("sx", C.c_int), ("sy", C.c_int), ("n_query", C.c_int), ("yaw", C.c_double),
+                ("D_w7", C.c_double * 7)]
 
 
 class SeqLayout(C.Structure):
@@ -274,6 +297,19 @@ def load_library():
         _lib.ll_visibility_images.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.ll_visibility_reset.argtypes = [C.c_void_p]
         _lib.ll_visibility_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_bev_default_params.restype = None
+        _lib.ll_bev_default_params.argtypes = [C.c_void_p]
+        _lib.ll_bev_create.argtypes = [C.c_void_p] * 3
+        _lib.ll_bev_destroy.restype = None
+        _lib.ll_bev_destroy.argtypes = [C.c_void_p]
+        _lib.ll_bev_last_error.restype = C.c_char_p
+        _lib.ll_bev_last_error.argtypes = [C.c_void_p]
+        _lib.ll_bev_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_bev_volume.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_bev_grid.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_bev_reset.argtypes = [C.c_void_p]
+        _lib.ll_bev_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_bev_guess.argtypes = [C.c_void_p] * 4
         _lib.ll_cubemaps_insert_keyframes_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     return _lib
 
@@ -683,6 +719,10 @@ class Context:
     def visibility(self, kf, **params):
         """a Visibility object over the Keyframes store kf (ll_visibility_create); params: fields of visibility_params()"""
         return Visibility(self, kf, **params)
+
+    def bev(self, kf, **params):
+        """a Bev object over the Keyframes store kf (ll_bev_create); params: fields of bev_params()"""
+        return Bev(self, kf, **params)
 
     def algorithmic_bytes(self, first=0, count=1):
         b = [C.c_double(0) for _ in range(4)]
@@ -1458,6 +1498,113 @@ class Visibility:
         """the last run: ((images ms, erode ms, vote ms), (listed frames, their points, frame pairs))"""
         ms = np.zeros(3); cnt = np.zeros(3, np.int64)
         self._ck(self.lib.ll_visibility_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
+        return tuple(ms), tuple(int(c) for c in cnt)
+
+
+def bev_params(**kw):
+    """ll_bev_default_params with the given fields replaced"""
+    p = BevParams()
+    load_library().ll_bev_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def bev_guess(Pc, D, Pq):
+    """ll_bev_guess: T0 = P_c o D o P_q^-1 [7], the guess of CubeMaps.align((dst = the candidate's map, src = the query's map, T0));
+    P_c, P_q: the anchors' poses in their maps, D: BevResult.D_w7.  Host arithmetic: needs no device"""
+    a = [np.ascontiguousarray(x, np.float64).reshape(7) for x in (Pc, D, Pq)]
+    T = np.zeros(7)
+    rc = load_library().ll_bev_guess(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, T.ctypes.data)
+    if rc != LL_OK:
+        raise LightLoamError(rc, "bev_guess: a NULL pointer")
+    return T
+
+
+class Bev:
+    """One ll_bev over a Keyframes store: correlative matching of bird's-eye occupancy grids, from a place match (the revisited
+    frame and a heading good to a sector) to the 3-DoF transform that starts CubeMaps.align or a localising lane"""
+
+    def __init__(self, ctx, kf, **params):
+        self.ctx = ctx; self.lib = ctx.lib; self.kf = kf
+        self.params = bev_params(**params)
+        self.h = C.c_void_p()
+        rc = self.lib.ll_bev_create(kf.h, C.byref(self.params), C.byref(self.h))
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_keyframes_last_error(kf.h).decode())
+        self._n_yaws = []
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ll_bev_destroy(self.h)               # reads nothing of the store: the order in which a Context closes its children is free
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_bev_last_error(self.h).decode())
+
+    def _live(self):
+        if not getattr(self, "h", None) or not getattr(self.kf, "h", None):
+            raise LightLoamError(-7, "the Bev object or its Keyframes store is closed")
+
+    def match(self, ops):
+        """ops: a list of (target, target_poses, query, query_poses, yaw0, yaw_step, n_yaws) -- frame ids of the store, the first of a
+        list is its anchor; poses [n, 7] or None for the stored ones -> a BevResult array [n_ops].  One upload, one fill, three launches,
+        one synchronisation whatever len(ops) is"""
+        self._live()
+        rec = (BevOp * max(len(ops), 1))()
+        keep = []
+        for i, (target, tposes, query, qposes, yaw0, yaw_step, n_yaws) in enumerate(ops):
+            for side, ids, poses in (("target", target, tposes), ("query", query, qposes)):
+                f = np.ascontiguousarray(ids, np.int32).reshape(-1)
+                p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+                if p is not None and len(p) != len(f):
+                    raise ValueError("poses must have one row per listed frame")
+                keep += [f, p]
+                setattr(rec[i], "n_" + side, len(f)); setattr(rec[i], side, f.ctypes.data if len(f) else None)
+                setattr(rec[i], side + "_poses_w7", None if p is None else p.ctypes.data)
+            rec[i].yaw0 = float(yaw0); rec[i].yaw_step = float(yaw_step); rec[i].n_yaws = int(n_yaws)
+        out = (BevResult * max(len(ops), 1))()
+        self._ck(self.lib.ll_bev_match(self.h, C.addressof(rec), len(ops), C.addressof(out)))
+        self._n_yaws = [int(o[6]) for o in ops]
+        return out
+
+    def volume(self, op):
+        """the scores [n_yaws, 2 sh, 2 sh] int32 of op `op` of the last match (index: yaw, sy + sh, sx + sh)"""
+        self._live()
+        S = 2 * self.params.shift_half
+        n = self._n_yaws[op] if 0 <= int(op) < len(self._n_yaws) else 1
+        out = np.zeros((n, S, S), np.int32)
+        self._ck(self.lib.ll_bev_volume(self.h, int(op), out.ctypes.data))
+        return out
+
+    def grid(self, op):
+        """the target grid [2 half, 2 half] uint8 of op `op` of the last match: bit l of cell (fy + half, fx + half) is layer l"""
+        self._live()
+        G = 2 * self.params.half
+        out = np.zeros((G, G), np.uint8)
+        self._ck(self.lib.ll_bev_grid(self.h, int(op), out.ctypes.data))
+        return out
+
+    def reset(self):
+        """the last match forgotten; needed after Keyframes.reset before the object is used again"""
+        self._live()
+        self._ck(self.lib.ll_bev_reset(self.h))
+        self._n_yaws = []
+
+    def timing(self):
+        """the last match: ((prepare ms, score ms, peak ms), (ops, listed points, hypotheses))"""
+        ms = np.zeros(3); cnt = np.zeros(3, np.int64)
+        self._ck(self.lib.ll_bev_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
         return tuple(ms), tuple(int(c) for c in cnt)
 
 

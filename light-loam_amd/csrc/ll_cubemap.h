@@ -132,6 +132,24 @@ struct ll_visibility {
     long long counts[3] = {0, 0, 0};              /* listed frames, their points, ordered frame pairs */
     std::string err;
 };
+/* correlative BEV matching (ll_bev.hip): ONE device buffer grown to a call's need -- the ops' target grids, the query counts behind
+ * them (one fill zeroes both), the peak records, the score volume, the query list --, the table pair of a call's upload (X), the
+ * events around the three launches, and what ll_bev_volume / ll_bev_grid need of the last successful call; epoch: kf->n_reset at
+ * create / ll_bev_reset */
+struct ll_bev {
+    ll_ctx *ctx = nullptr;
+    ll_keyframes *kf = nullptr;
+    ll_bev_params p;
+    unsigned long long epoch = 0;
+    unsigned char *d_mem = nullptr; size_t cap_mem = 0;
+    size_t at_volume = 0;                         /* of the last call, in d_mem */
+    std::vector<int> last_vbase, last_nyaws;      /* per op of the last call: its first yaw row in the volume, its yaws */
+    LLMapExport X;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double ms[3] = {0.0, 0.0, 0.0};               /* the last call: prepare, score, peak (events) */
+    long long counts[3] = {0, 0, 0};              /* ops, listed points, hypotheses */
+    std::string err;
+};
 /* map alignment (ll_map_align.hip): what an aligning object keeps between calls -- one device buffer grown to the need (search
  * tables, cell-ordered dst points, flat src stacks, per-op fit results, residual blocks and partial sums), the events around the
  * stages (two more per outer iteration), the last call's figures */

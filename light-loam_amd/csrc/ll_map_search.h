@@ -124,6 +124,19 @@ __device__ __forceinline__ void ll_map_to_world(const double *pose, const float4
     sz = (float)(((v[2] + w * uvz) + (ux * uvy - uy * uvx)) + pose[6]);
 }
 
+/* R(q)^-1 (s - t): the conjugate quaternion through ll_map_to_world's operations in their order, the pose used as given
+ * (ll_visibility's vote and ll_bev's prepare take a world point into a frame with it) */
+__device__ __forceinline__ void vis_world_to_frame(const double *pose, float sx, float sy, float sz, float &lx, float &ly, float &lz)
+{
+    const double ux = -pose[0], uy = -pose[1], uz = -pose[2], w = pose[3];
+    const double v[3] = {(double)sx - pose[4], (double)sy - pose[5], (double)sz - pose[6]};
+    double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
+    uvx += uvx; uvy += uvy; uvz += uvz;
+    lx = (float)((v[0] + w * uvx) + (uy * uvz - uz * uvy));
+    ly = (float)((v[1] + w * uvy) + (uz * uvx - ux * uvz));
+    lz = (float)((v[2] + w * uvz) + (ux * uvy - uy * uvx));
+}
+
 /* residual block `pos` of cloud type `which` <- the fit of stack point i (ll_map_fit leaves it in q*, the solves read f*) */
 __device__ __forceinline__ void ll_map_place(const LLMapView &M, int which, int pos, int i)
 {

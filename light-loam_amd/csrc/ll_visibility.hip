@@ -44,18 +44,6 @@ __device__ __forceinline__ int vis_pixel(float x, float y, float z, const VisCfg
     return (int)fr * c.W + col;
 }
 
-/* R(q)^-1 (s - t): the conjugate quaternion through ll_map_to_world's operations in their order, the pose used as given */
-__device__ __forceinline__ void vis_world_to_frame(const double *pose, float sx, float sy, float sz, float &lx, float &ly, float &lz)
-{
-    const double ux = -pose[0], uy = -pose[1], uz = -pose[2], w = pose[3];
-    const double v[3] = {(double)sx - pose[4], (double)sy - pose[5], (double)sz - pose[6]};
-    double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
-    uvx += uvx; uvy += uvy; uvz += uvz;
-    lx = (float)((v[0] + w * uvx) + (uy * uvz - uz * uvy));
-    ly = (float)((v[1] + w * uvy) + (uz * uvx - ux * uvz));
-    lz = (float)((v[2] + w * uvz) + (ux * uvy - uy * uvx));
-}
-
 __global__ __launch_bounds__(256) void k_vis_image(const float4 *__restrict__ pool, const VisSeg *__restrict__ seg, int nseg, VisCfg c, unsigned *raw)
 {
     const VisSeg s = seg[mm_find(seg, nseg, blockIdx.x)];
