@@ -24,7 +24,10 @@
  * ll_bev_match enqueues one table upload, one fill (grids and query counts), the three launches and the copy of the peak records,
  * and synchronises ONCE.
  */
-#include "ll_cubemap.h"
+#include "ll_keyframes.h"
+#include "ll_map_export.h"
+#include "ll_map_search.h"
+#include "ll_tiles.h"
 #include <cmath>
 
 #define BEV_TILE 1024
@@ -40,7 +43,7 @@ struct BevYaw { int op, j; float c, s; };
 __global__ __launch_bounds__(256) void k_bev_prepare(const float4 *__restrict__ pool, const BevSeg *__restrict__ seg, int nseg, const double *__restrict__ poses,
                                                      BevCfg c, unsigned *grids, int *nq, float2 *__restrict__ qxy, signed char *__restrict__ qlay)
 {
-    const BevSeg s = seg[mm_find(seg, nseg, blockIdx.x)];
+    const BevSeg s = seg[ll_tile_find(seg, nseg, blockIdx.x)];
     const int first = (int)(blockIdx.x - s.tile0) * BEV_TILE, n = min(BEV_TILE, s.cnt - first);
     const float4 *src = pool + s.off + first;
     const int kp = __builtin_amdgcn_readfirstlane(s.pose), ka = __builtin_amdgcn_readfirstlane(s.anchor);
@@ -186,7 +189,6 @@ static int bev_kf_err(ll_keyframes *kf, int rc, const std::string &msg) { kf->er
     } while (0)
 
 static size_t bev_lds_bytes(int half, int sh) { const size_t W = (size_t)(2 * half + 2 * sh); return W * W + BEV_CHUNK * 4; }
-static size_t bev_up(size_t x) { return (x + 255) / 256 * 256; }
 
 extern "C" void ll_bev_default_params(ll_bev_params *p)
 {
@@ -247,14 +249,6 @@ extern "C" int ll_bev_reset(ll_bev *b)
     return LL_OK;
 }
 
-template <typename T> static size_t bev_put(std::vector<unsigned char> &blob, const std::vector<T> &a)
-{
-    const size_t at = bev_up(blob.size());
-    blob.resize(at + a.size() * sizeof(T));
-    if (!a.empty()) std::memcpy(blob.data() + at, a.data(), a.size() * sizeof(T));
-    return at;
-}
-
 extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_result *out)
 {
     if (!b) return LL_ERR_ARG;
@@ -294,7 +288,7 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
     std::vector<BevOpDev> optab((size_t)n_ops);
     std::vector<BevYaw> yawtab; yawtab.reserve((size_t)n_rows);
     std::vector<int> vbase((size_t)n_ops), nyaws((size_t)n_ops);
-    unsigned long long tile = 0;
+    LLTiler tiles{BEV_TILE};
     long long n_query_points = 0;
     for (int i = 0; i < n_ops; ++i) {
         const ll_bev_op &o = ops[i];
@@ -310,8 +304,7 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
                 poses.insert(poses.end(), P, P + 7);
                 for (int w = 0; w < 2; ++w) {
                     if (e.n[w] <= 0) continue;
-                    segs.push_back({(w ? kf->cap[0] : 0) + e.offset[w], e.n[w], (unsigned)tile, anchor + f, anchor, i, side ? (int)n_query_points : -1});
-                    tile += (unsigned long long)((e.n[w] + BEV_TILE - 1) / BEV_TILE);
+                    segs.push_back({(w ? kf->cap[0] : 0) + e.offset[w], e.n[w], tiles.take(e.n[w]), anchor + f, anchor, i, side ? (int)n_query_points : -1});
                     if (side) n_query_points += e.n[w];
                 }
             }
@@ -323,11 +316,11 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
             yawtab.push_back({i, j, (float)std::cos(yaw), (float)std::sin(yaw)});
         }
     }
-    if (tile > 0x7fffffffull) return bev_fail(b, LL_ERR_CAPACITY, "bev: too many tiles for one call");
+    if (!tiles.fits()) return bev_fail(b, LL_ERR_CAPACITY, "bev: too many tiles for one call");
     /* ---- the buffer: grids | query counts | peak records | volume | query (x, y) | query layers */
     const size_t grid_bytes = (size_t)G * G, fill_bytes = (size_t)n_ops * grid_bytes + (size_t)n_ops * 4;
-    const size_t at_nq = (size_t)n_ops * grid_bytes, at_rec = bev_up(fill_bytes), at_vol = bev_up(at_rec + (size_t)n_ops * 16);
-    const size_t at_qxy = bev_up(at_vol + (size_t)n_rows * S * S * 4), at_qlay = bev_up(at_qxy + (size_t)n_query_points * 8);
+    const size_t at_nq = (size_t)n_ops * grid_bytes, at_rec = ll_up256(fill_bytes), at_vol = ll_up256(at_rec + (size_t)n_ops * 16);
+    const size_t at_qxy = ll_up256(at_vol + (size_t)n_rows * S * S * 4), at_qlay = ll_up256(at_qxy + (size_t)n_query_points * 8);
     const size_t need = at_qlay + (size_t)n_query_points + 16;
     hipStream_t st = b->ctx->stream;
     BEV_HIP(hipSetDevice(b->ctx->device));
@@ -342,7 +335,7 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
         b->d_mem = (unsigned char *)mem; b->cap_mem = cap;
     }
     std::vector<unsigned char> blob;
-    const size_t at_seg = bev_put(blob, segs), at_pose = bev_put(blob, poses), at_op = bev_put(blob, optab), at_yaw = bev_put(blob, yawtab);
+    const size_t at_seg = ll_blob_put(blob, segs), at_pose = ll_blob_put(blob, poses), at_op = ll_blob_put(blob, optab), at_yaw = ll_blob_put(blob, yawtab);
     const unsigned char *d_blob = (const unsigned char *)llx_stage_bytes(b->X, blob.data(), blob.size(), st, b->err);
     if (!d_blob) return LL_ERR_HIP;
     int *pin = (int *)ll_pinned_scratch((size_t)n_ops * 16);
@@ -358,8 +351,8 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
     ll_ensure_dynamic_lds(k_bev_score, lds, lds_set);
     BEV_HIP(hipMemsetAsync(m, 0, fill_bytes, st));
     BEV_HIP(hipEventRecord(b->ev[0], st));
-    if (tile > 0)
-        hipLaunchKernelGGL(k_bev_prepare, dim3((unsigned)tile), dim3(256), 0, st, (const float4 *)kf->pool, (const BevSeg *)(d_blob + at_seg), (int)segs.size(),
+    if (tiles.next > 0)
+        hipLaunchKernelGGL(k_bev_prepare, dim3((unsigned)tiles.next), dim3(256), 0, st, (const float4 *)kf->pool, (const BevSeg *)(d_blob + at_seg), (int)segs.size(),
                            (const double *)(d_blob + at_pose), c, (unsigned *)m, (int *)(m + at_nq), (float2 *)(m + at_qxy), (signed char *)(m + at_qlay));
     BEV_HIP(hipEventRecord(b->ev[1], st));
     hipLaunchKernelGGL(k_bev_score, dim3((unsigned)n_rows), dim3((unsigned)(S * S)), lds, st, (const unsigned char *)m, (const float2 *)(m + at_qxy),
@@ -371,7 +364,7 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
     BEV_HIP(hipGetLastError());
     BEV_HIP(hipMemcpyAsync(pin, m + at_rec, (size_t)n_ops * 16, hipMemcpyDeviceToHost, st));
     BEV_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < 3; ++k) { float ms = 0.0f; b->ms[k] = hipEventElapsedTime(&ms, b->ev[k], b->ev[k + 1]) == hipSuccess ? (double)ms : 0.0; }
+    for (int k = 0; k < 3; ++k) b->ms[k] = ll_event_ms(b->ev[k], b->ev[k + 1], 0.0);
     b->counts[0] = n_ops; b->counts[1] = n_points; b->counts[2] = n_rows * S * S;
     b->at_volume = at_vol; b->last_vbase = vbase; b->last_nyaws = nyaws;
     for (int i = 0; i < n_ops; ++i) {

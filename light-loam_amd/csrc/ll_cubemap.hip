@@ -43,15 +43,7 @@ __global__ __launch_bounds__(256) void k_cm_assign(const float4 *stack, int n, c
 
 /* ------------------------------------------------------------------ host side */
 template <typename T>
-static bool cm_alloc(ll_cubemap *cm, T *&ptr, size_t count)
-{
-    void *p = nullptr;
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    if (hipMalloc(&p, bytes) != hipSuccess) { cm->err = "hipMalloc failed (" + std::to_string(bytes) + " bytes)"; return false; }
-    cm->allocs.push_back(p);
-    ptr = (T *)p;
-    return true;
-}
+static bool cm_alloc(ll_cubemap *cm, T *&ptr, size_t count) { return ll_dev_alloc(cm->allocs, cm->err, ptr, count, false); }
 
 extern "C" void ll_cubemap_destroy(ll_cubemap *cm)
 {

@@ -21,7 +21,7 @@
  * sequence's and shared: cms_localize), optimize, no update -- three synchronisations; with a fit record, one more knn + compact
  * pass at the final poses and k_cms_fit (ll_localize.hip) before the poses' copy, which then carries the records too.
  */
-#include "ll_cubemap.h"
+#include "ll_cubemaps.h"
 #include "ll_factor_math.h"
 #include "ll_map_neq.h"
 #include "ll_map_search.h"
@@ -178,15 +178,7 @@ struct ll_cubemaps {
     } while (0)
 
 template <typename T>
-static bool cms_alloc(ll_cubemaps *cms, T *&ptr, size_t count)
-{
-    void *p = nullptr;
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    if (hipMalloc(&p, bytes) != hipSuccess) { cms->err = "hipMalloc failed (" + std::to_string(bytes) + " bytes)"; return false; }
-    cms->allocs.push_back(p);
-    ptr = (T *)p;
-    return true;
-}
+static bool cms_alloc(ll_cubemaps *cms, T *&ptr, size_t count) { return ll_dev_alloc(cms->allocs, cms->err, ptr, count, false); }
 
 /* host bytes -> device: through the call's page-locked arena; dst == nullptr: into the arena's device half (returned) */
 static void *cms_stage(ll_cubemaps *cms, const void *src, size_t bytes, void *dst = nullptr)
@@ -607,21 +599,59 @@ static int cms_check_common(ll_cubemaps *cms, const std::vector<int> &run)
     return LL_OK;
 }
 
+/* ---- the slot intake of ll_cubemaps_process_slots, ll_cubemaps_localize_slots_info and cms_slots_dev.  The read-back of the scan
+ * headers between the two halves stays with the caller: cms_slots_dev folds the poses and `extra` into the same synchronisation */
+/* run: the sequences whose slot is not -1.  check_range (the public entry points): a slot outside the batch and a slot used by
+ * two sequences are refused, in that order; without it (ll_drives.hip hands out the slots itself) any negative slot sits out */
+static int cms_running_slots(ll_cubemaps *cms, const int *slots, bool check_range, std::vector<int> &run)
+{
+    const int batch = cms->ctx->p.batch;
+    std::vector<char> used(check_range ? batch : 0, 0);
+    for (int q = 0; q < cms->S; ++q) {
+        const int s = slots[q];
+        if (check_range ? s == -1 : s < 0) continue;
+        if (check_range) {
+            if (s < -1 || s >= batch) { cms->err = "sequence " + std::to_string(q) + ": slot out of range"; return LL_ERR_ARG; }
+            if (used[s]) { cms->err = "sequence " + std::to_string(q) + ": slot " + std::to_string(s) + " is used by two sequences"; return LL_ERR_ARG; }
+            used[s] = 1;
+        }
+        run.push_back(q);
+    }
+    return LL_OK;
+}
+
+/* the headers h[r] of the slots of the running sequences -> their scan clouds: src[w][r], n_in[w][r], and flat[r] = the slot whose
+ * ring-strided less-flat cloud is flattened into place (-1: none).  A status other than 0 is refused; allow_empty (the drives):
+ * LL_ERR_EMPTY runs with empty clouds, and the refusal names the status */
+static int cms_slot_scans(ll_cubemaps *cms, const int *slots, const std::vector<int> &run, const std::vector<ScanHdr> &h, bool allow_empty,
+                          std::vector<const float4 *> src[2], std::vector<int> n_in[2], std::vector<int> &flat)
+{
+    const int R = (int)run.size();
+    const LLView &V = cms->ctx->V;
+    for (int w = 0; w < 2; ++w) { src[w].assign(R, nullptr); n_in[w].assign(R, 0); }
+    flat.assign(R, -1);
+    for (int r = 0; r < R; ++r) {
+        const int s = slots[run[r]];
+        const bool empty = allow_empty && h[r].status == LL_ERR_EMPTY;
+        if (h[r].status != 0 && !empty) {
+            const std::string why = allow_empty ? "the scan registration refused the slot's scan (status " + std::to_string(h[r].status) + ")" : "the slot holds no extracted scan";
+            cms->err = "sequence " + std::to_string(run[r]) + ": " + why;
+            return LL_ERR_STATE;
+        }
+        src[0][r] = V.lsharp + (size_t)s * V.cap_lsharp; n_in[0][r] = empty ? 0 : h[r].n_less_sharp;
+        n_in[1][r] = empty ? 0 : h[r].n_less_flat;
+        if (h[r].lf_strided) { src[1][r] = nullptr; flat[r] = s; } else src[1][r] = V.lflat + (size_t)s * V.LFS;
+    }
+    return LL_OK;
+}
+
 extern "C" int ll_cubemaps_process_slots(ll_cubemaps *cms, const int *slots, double *pose_w7, int *ran)
 {
     if (!cms || !slots || !pose_w7) return LL_ERR_ARG;
     ll_ctx *ctx = cms->ctx;
     std::vector<int> run;
-    std::vector<char> used(ctx->p.batch, 0);
-    for (int q = 0; q < cms->S; ++q) {
-        const int s = slots[q];
-        if (s == -1) continue;
-        if (s < -1 || s >= ctx->p.batch) { cms->err = "sequence " + std::to_string(q) + ": slot out of range"; return LL_ERR_ARG; }
-        if (used[s]) { cms->err = "sequence " + std::to_string(q) + ": slot " + std::to_string(s) + " is used by two sequences"; return LL_ERR_ARG; }
-        used[s] = 1;
-        run.push_back(q);
-    }
-    int rc = cms_check_common(cms, run); if (rc) return rc;
+    int rc = cms_running_slots(cms, slots, true, run); if (rc) return rc;
+    rc = cms_check_common(cms, run); if (rc) return rc;
     if (run.empty()) return LL_OK;
     CMS_HIP(hipSetDevice(ctx->device));
     cms->par ^= 1; cms->ar[cms->par].used = 0;
@@ -634,16 +664,9 @@ extern "C" int ll_cubemaps_process_slots(ll_cubemaps *cms, const int *slots, dou
         rc = cms_sync(cms); if (rc) return rc;
         std::memcpy(h.data(), pin, (size_t)R * sizeof(ScanHdr));
     }
-    std::vector<const float4 *> src[2] = {std::vector<const float4 *>(R), std::vector<const float4 *>(R)};
-    std::vector<int> n_in[2] = {std::vector<int>(R), std::vector<int>(R)}, flat(R, -1);
-    const LLView &V = ctx->V;
-    for (int r = 0; r < R; ++r) {
-        const int s = slots[run[r]];
-        if (h[r].status != 0) { cms->err = "sequence " + std::to_string(run[r]) + ": the slot holds no extracted scan"; return LL_ERR_STATE; }
-        src[0][r] = V.lsharp + (size_t)s * V.cap_lsharp; n_in[0][r] = h[r].n_less_sharp;
-        n_in[1][r] = h[r].n_less_flat;
-        if (h[r].lf_strided) { src[1][r] = nullptr; flat[r] = s; } else src[1][r] = V.lflat + (size_t)s * V.LFS;
-    }
+    std::vector<const float4 *> src[2];
+    std::vector<int> n_in[2], flat;
+    rc = cms_slot_scans(cms, slots, run, h, false, src, n_in, flat); if (rc) return rc;
     return cms_frame(cms, run, src, n_in, flat, pose_w7, ran);
 }
 
@@ -728,16 +751,8 @@ extern "C" int ll_cubemaps_localize_slots_info(ll_cubemaps *cms, const int *slot
     if (info) std::memset(info, 0, (size_t)cms->S * sizeof(ll_pose_info));          /* also for a sequence that sits out, and when the call is refused */
     ll_ctx *ctx = cms->ctx;
     std::vector<int> run;
-    std::vector<char> used(ctx->p.batch, 0);
-    for (int q = 0; q < cms->S; ++q) {
-        const int s = slots[q];
-        if (s == -1) continue;
-        if (s < -1 || s >= ctx->p.batch) { cms->err = "sequence " + std::to_string(q) + ": slot out of range"; return LL_ERR_ARG; }
-        if (used[s]) { cms->err = "sequence " + std::to_string(q) + ": slot " + std::to_string(s) + " is used by two sequences"; return LL_ERR_ARG; }
-        used[s] = 1;
-        run.push_back(q);
-    }
-    int rc = cms_check_read_maps(cms, run, map_of); if (rc) return rc;
+    int rc = cms_running_slots(cms, slots, true, run); if (rc) return rc;
+    rc = cms_check_read_maps(cms, run, map_of); if (rc) return rc;
     if (run.empty()) return LL_OK;
     CMS_HIP(hipSetDevice(ctx->device));
     cms->par ^= 1; cms->ar[cms->par].used = 0;
@@ -750,16 +765,9 @@ extern "C" int ll_cubemaps_localize_slots_info(ll_cubemaps *cms, const int *slot
         rc = cms_sync(cms); if (rc) return rc;
         std::memcpy(h.data(), pin, (size_t)R * sizeof(ScanHdr));
     }
-    std::vector<const float4 *> src[2] = {std::vector<const float4 *>(R), std::vector<const float4 *>(R)};
-    std::vector<int> n_in[2] = {std::vector<int>(R), std::vector<int>(R)}, flat(R, -1);
-    const LLView &V = ctx->V;
-    for (int r = 0; r < R; ++r) {
-        const int s = slots[run[r]];
-        if (h[r].status != 0) { cms->err = "sequence " + std::to_string(run[r]) + ": the slot holds no extracted scan"; return LL_ERR_STATE; }
-        src[0][r] = V.lsharp + (size_t)s * V.cap_lsharp; n_in[0][r] = h[r].n_less_sharp;
-        n_in[1][r] = h[r].n_less_flat;
-        if (h[r].lf_strided) { src[1][r] = nullptr; flat[r] = s; } else src[1][r] = V.lflat + (size_t)s * V.LFS;
-    }
+    std::vector<const float4 *> src[2];
+    std::vector<int> n_in[2], flat;
+    rc = cms_slot_scans(cms, slots, run, h, false, src, n_in, flat); if (rc) return rc;
     return cms_localize(cms, run, map_of, src, n_in, flat, pose_w7, ran, fit, info);
 }
 
@@ -839,8 +847,8 @@ extern "C" int ll_cubemaps_reset(ll_cubemaps *cms, int q)
 }
 
 /* ------------------------------------------------------------------ map export (:2173-2203 for any subset of the sequences)
- * Host bookkeeping: the sizes of the selected clouds.  segs != nullptr: also the segment table of the gather */
-static int cms_export_table(ll_cubemaps *cms, const int *which, long long *offset, int tile_points, unsigned long long *ntiles, std::vector<LLExpSeg> *segs, long long *total)
+ * Host bookkeeping: the sizes of the selected clouds.  T != nullptr: also the segment table of the gather, numbered by T */
+static int cms_export_table(ll_cubemaps *cms, const int *which, long long *offset, LLTiler *T, std::vector<LLExpSeg> *segs, long long *total)
 {
     for (int q = 0; q < cms->S; ++q) {
         if (which[q] < LL_MAP_NONE || which[q] > LL_MAP_ALL) { cms->err = "sequence " + std::to_string(q) + ": which must be LL_MAP_NONE, LL_MAP_SURROUND or LL_MAP_ALL"; return LL_ERR_ARG; }
@@ -849,7 +857,7 @@ static int cms_export_table(ll_cubemaps *cms, const int *which, long long *offse
     long long at = 0;
     for (int q = 0; q < cms->S; ++q) {
         if (offset) offset[q] = at;
-        at += llx_segments(cms->cm[q], which[q], at, tile_points, ntiles, segs);
+        at += llx_segments(cms->cm[q], which[q], at, T, segs);
     }
     if (offset) offset[cms->S] = at;
     *total = at;
@@ -860,7 +868,7 @@ extern "C" int ll_cubemaps_export_sizes(ll_cubemaps *cms, const int *which, long
 {
     if (!cms || !which || !offset) return LL_ERR_ARG;
     long long total = 0;
-    return cms_export_table(cms, which, offset, 0, nullptr, nullptr, &total);
+    return cms_export_table(cms, which, offset, nullptr, nullptr, &total);
 }
 
 extern "C" int ll_cubemaps_export(ll_cubemaps *cms, const int *which, ll_point *out, long long cap, long long *offset)
@@ -868,20 +876,19 @@ extern "C" int ll_cubemaps_export(ll_cubemaps *cms, const int *which, ll_point *
     if (!cms || !which) return LL_ERR_ARG;
     if (cap < 0) { cms->err = "map export: negative capacity"; return LL_ERR_ARG; }
     const auto t0 = std::chrono::steady_clock::now();
-    const int tile_points = llx_tile();
+    LLTiler T{llx_tile()};
     std::vector<LLExpSeg> segs;
-    unsigned long long ntiles = 0;
     long long total = 0;
-    int rc = cms_export_table(cms, which, offset, tile_points, &ntiles, &segs, &total); if (rc) return rc;
+    int rc = cms_export_table(cms, which, offset, &T, &segs, &total); if (rc) return rc;
     if (total > 0 && !out) { cms->err = "map export: out is NULL"; return LL_ERR_ARG; }
     if (total > cap) { cms->err = "map export: " + std::to_string(total) + " points, room for " + std::to_string(cap); return LL_ERR_CAPACITY; }
-    if (ntiles > 0x7fffffffull) { cms->err = "map export: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+    if (!T.fits()) { cms->err = "map export: too many tiles for one launch"; return LL_ERR_CAPACITY; }
     CMS_HIP(hipSetDevice(cms->ctx->device));
     cms->par ^= 1; cms->ar[cms->par].used = 0;                                     /* the last frame's copies may still read the other arena */
     const LLExpSeg *d_segs = nullptr;
     if (total > 0) { d_segs = (const LLExpSeg *)cms_stage(cms, segs.data(), segs.size() * sizeof(LLExpSeg)); if (!d_segs) return LL_ERR_HIP; }
     cms->X.ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    rc = llx_gather(cms->X, cms->ctx, d_segs, segs.size(), ntiles, total, (size_t)cms->S * 2 * cms->cap_pool, tile_points, out, cms->err);
+    rc = llx_gather(cms->X, cms->ctx, d_segs, segs.size(), T.next, total, (size_t)cms->S * 2 * cms->cap_pool, T.per, out, cms->err);
     if (rc == LL_OK) ++cms->syncs;
     return rc;
 }
@@ -923,12 +930,11 @@ extern "C" int ll_cubemaps_import(ll_cubemaps *cms, const int *sel, const ll_poi
     }
     const long long n_up = lo < 0 ? 0 : hi - lo;
     if (n_up > 0 && !points) { cms->err = "map import: points is NULL"; return LL_ERR_ARG; }
-    const int tile_points = llx_tile();
+    LLTiler T{llx_tile()};
     std::vector<LLImpSeg> segs;
-    unsigned long long ntiles = 0;
     for (int q = 0; q < S; ++q)
-        if (sel[q]) llx_import_segments(cms->cm[q], counts + (size_t)q * 2 * CM_N, offset[q] - (lo < 0 ? 0 : lo), tile_points, &ntiles, &segs);
-    if (ntiles > 0x7fffffffull) { cms->err = "map import: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+        if (sel[q]) llx_import_segments(cms->cm[q], counts + (size_t)q * 2 * CM_N, offset[q] - (lo < 0 ? 0 : lo), T, &segs);
+    if (!T.fits()) { cms->err = "map import: too many tiles for one launch"; return LL_ERR_CAPACITY; }
     CMS_HIP(hipSetDevice(cms->ctx->device));
     const bool direct = n_up > 0 && llx_is_device(points);
     float4 *src = direct ? (float4 *)points + lo : nullptr;
@@ -942,7 +948,7 @@ extern "C" int ll_cubemaps_import(ll_cubemaps *cms, const int *sel, const ll_poi
     if (!segs.empty()) { d_segs = (const LLImpSeg *)cms_stage(cms, segs.data(), segs.size() * sizeof(LLImpSeg)); if (!d_segs) return LL_ERR_HIP; }
     /* ---- from here on a failure leaves the selected maps' pools half-written ---- */
     for (int q = 0; q < S; ++q) if (sel[q]) cms->cm[q]->broken = true;
-    int rc = llx_scatter(cms->ctx, d_segs, segs.size(), ntiles, src, direct ? nullptr : (const void *)(points + lo), (size_t)n_up, tile_points, cms->err);
+    int rc = llx_scatter(cms->ctx, d_segs, segs.size(), T.next, src, direct ? nullptr : (const void *)(points + lo), (size_t)n_up, T.per, cms->err);
     if (rc) return rc;
     rc = cms_sync(cms); if (rc) return rc;                                         /* the ONE synchronisation: the caller's points may go away */
     for (int q = 0; q < S; ++q)
@@ -976,9 +982,8 @@ static int cms_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, 
 {
     ll_ctx *ctx = cms->ctx;
     std::vector<int> run;
-    for (int q = 0; q < cms->S; ++q)
-        if (slots[q] >= 0) run.push_back(q);
-    int rc = map_of ? cms_check_read_maps(cms, run, map_of) : cms_check_common(cms, run); if (rc) return rc;
+    int rc = cms_running_slots(cms, slots, false, run); if (rc) return rc;
+    rc = map_of ? cms_check_read_maps(cms, run, map_of) : cms_check_common(cms, run); if (rc) return rc;
     const int R = (int)run.size();
     const size_t pose_bytes = (size_t)cms->S * 7 * sizeof(double), hdr_at = (pose_bytes + extra_bytes + 15) & ~(size_t)15;
     std::vector<ScanHdr> h(R);
@@ -995,21 +1000,10 @@ static int cms_slots_dev(ll_cubemaps *cms, const int *slots, const int *map_of, 
         std::memcpy(h.data(), pin + hdr_at, (size_t)R * sizeof(ScanHdr));
     }
     if (R == 0) return LL_OK;
-    std::vector<const float4 *> src[2] = {std::vector<const float4 *>(R), std::vector<const float4 *>(R)};
-    std::vector<int> n_in[2] = {std::vector<int>(R), std::vector<int>(R)}, flat(R, -1);
-    const LLView &V = ctx->V;
-    for (int r = 0; r < R; ++r) {
-        const int s = slots[run[r]];
-        hdr_out[run[r]] = h[r];
-        if (h[r].status != 0 && h[r].status != LL_ERR_EMPTY) {
-            cms->err = "sequence " + std::to_string(run[r]) + ": the scan registration refused the slot's scan (status " + std::to_string(h[r].status) + ")";
-            return LL_ERR_STATE;
-        }
-        const bool empty = h[r].status == LL_ERR_EMPTY;
-        src[0][r] = V.lsharp + (size_t)s * V.cap_lsharp; n_in[0][r] = empty ? 0 : h[r].n_less_sharp;
-        n_in[1][r] = empty ? 0 : h[r].n_less_flat;
-        if (h[r].lf_strided) { src[1][r] = nullptr; flat[r] = s; } else src[1][r] = V.lflat + (size_t)s * V.LFS;
-    }
+    for (int r = 0; r < R; ++r) hdr_out[run[r]] = h[r];
+    std::vector<const float4 *> src[2];
+    std::vector<int> n_in[2], flat;
+    rc = cms_slot_scans(cms, slots, run, h, true, src, n_in, flat); if (rc) return rc;
     return map_of ? cms_localize(cms, run, map_of, src, n_in, flat, pose_w7, ran, fit, info) : cms_frame(cms, run, src, n_in, flat, pose_w7, ran);
 }
 

@@ -14,7 +14,8 @@
  * of ll_cubemaps_localize_slots in place of the mapping frame; a step runs the mapping lanes' frame, then the localising lanes',
  * and refuses beforehand any command set in which one would write what the other reads.
  */
-#include "ll_cubemap.h"
+#include "ll_cubemaps.h"
+#include "ll_keyframes.h"
 #include "ll_factor_math.h"
 #include <cmath>
 
@@ -153,16 +154,7 @@ struct ll_drives {
     } while (0)
 
 template <typename T>
-static bool drv_alloc(ll_drives *d, T *&ptr, size_t count)
-{
-    void *p = nullptr;
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    if (hipMalloc(&p, bytes) != hipSuccess) { d->err = "hipMalloc failed (" + std::to_string(bytes) + " bytes)"; return false; }
-    d->allocs.push_back(p);
-    if (hipMemset(p, 0, bytes) != hipSuccess) { d->err = "hipMemset failed"; return false; }
-    ptr = (T *)p;
-    return true;
-}
+static bool drv_alloc(ll_drives *d, T *&ptr, size_t count) { return ll_dev_alloc(d->allocs, d->err, ptr, count, true); }
 
 extern "C" void ll_drives_destroy(ll_drives *d)
 {
@@ -674,26 +666,22 @@ extern "C" int ll_drives_save(ll_drives *d, const int *lanes, void *blob, long l
     if (!blob) { d->err = "checkpoint: blob is NULL"; return LL_ERR_ARG; }
     ll_ctx *ctx = d->ctx;
     const LLView &V = ctx->V;
-    const int S = d->S, prev = d->base + (d->row ^ 1) * S, tile_points = llx_tile();
+    const int S = d->S, prev = d->base + (d->row ^ 1) * S;
     /* the host part, and the tables of the one pack launch */
     std::vector<unsigned char> host((size_t)dev_off, 0);
     std::memcpy(host.data(), &h, sizeof(h));
     if (!rec.empty()) std::memcpy(host.data() + sizeof(h), rec.data(), rec.size() * sizeof(CkRecord));
     std::vector<LLExpSeg> segs;
     std::vector<LLCkRec> recs;
-    unsigned long long ntiles = 0;
-    auto seg = [&](const float4 *src, long long at, int cnt) {
-        if (cnt <= 0) return;
-        segs.push_back({src, at, cnt, (unsigned)ntiles});
-        ntiles += (unsigned long long)((cnt + tile_points - 1) / tile_points);
-    };
+    LLTiler tiles{llx_tile()};
+    auto seg = [&](const float4 *src, long long at, int cnt) { if (cnt > 0) segs.push_back({src, at, cnt, tiles.take(cnt)}); };
     for (const CkRecord &R : rec) {
         const int q = R.lane, slot = prev + q;
         const ll_cubemap *cm = llcms_map(d->cms, q);
         for (int w = 0; w < 2; ++w) std::memcpy(host.data() + R.tab_offset + (size_t)w * CM_N * sizeof(int), cm->cnt[w].data(), CM_N * sizeof(int));
         std::memcpy(host.data() + R.tab_offset + CK_COUNTS_BYTES, cm->valid, (size_t)cm->n_valid * sizeof(int));
         long long at = (long long)((R.offset - dev_off) / 16);
-        at += llx_segments(cm, LL_MAP_ALL, at, tile_points, &ntiles, &segs);
+        at += llx_segments(cm, LL_MAP_ALL, at, &tiles, &segs);
         seg(V.sharp + (size_t)slot * V.cap_sharp, at, R.n_feat[0]); at += R.n_feat[0];
         seg(V.lsharp + (size_t)slot * V.cap_lsharp, at, R.n_feat[1]); at += R.n_feat[1];
         seg(V.flat + (size_t)slot * V.cap_flat, at, R.n_feat[2]); at += R.n_feat[2];
@@ -706,7 +694,7 @@ extern "C" int ll_drives_save(ll_drives *d, const int *lanes, void *blob, long l
         C.pose = V.pose + (size_t)slot * 7; C.odom = d->d_odom + (size_t)q * 7; C.m2o = d->d_m2o + (size_t)q * 7; C.fidx = d->d_fidx + q; C.dst_state = at; C.bad = d->d_ck_bad;
         recs.push_back(C);
     }
-    if (ntiles > 0x7fffffffull) { d->err = "checkpoint: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+    if (!tiles.fits()) { d->err = "checkpoint: too many tiles for one launch"; return LL_ERR_CAPACITY; }
     DRV_HIP(hipSetDevice(ctx->device));
     const size_t n_pts = (size_t)((h.total_bytes - dev_off) / 16);
     const bool direct = llx_is_device(blob);
@@ -724,7 +712,7 @@ extern "C" int ll_drives_save(ll_drives *d, const int *lanes, void *blob, long l
     int *bad = (int *)ll_pinned_scratch(sizeof(int));
     if (!bad) { d->err = "no page-locked scratch"; return LL_ERR_HIP; }
     DRV_HIP(hipMemsetAsync(d->d_ck_bad, 0, sizeof(int), ctx->stream));
-    rc = llx_pack(ctx, d_segs, segs.size(), ntiles, d_recs, (int)recs.size(), V.R, tile_points, dst, d->err); if (rc) return rc;
+    rc = llx_pack(ctx, d_segs, segs.size(), tiles.next, d_recs, (int)recs.size(), V.R, tiles.per, dst, d->err); if (rc) return rc;
     DRV_HIP(hipMemcpyAsync(bad, d->d_ck_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if (direct) { if (!llcms_stage_to(d->cms, host.data(), host.size(), blob)) { d->err = llcms_err(d->cms); return LL_ERR_HIP; } }
     else if (n_pts > 0) DRV_HIP(hipMemcpyAsync((unsigned char *)blob + dev_off, dst, n_pts * 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -751,7 +739,7 @@ extern "C" int ll_drives_restore(ll_drives *d, const int *into, const void *blob
     if (h.n_scans != ctx->p.n_scans) { d->err = "checkpoint: n_scans = " + std::to_string(h.n_scans) + ", the context has " + std::to_string(ctx->p.n_scans); return LL_ERR_ARG; }
     if (h.distortion != ctx->p.distortion) { d->err = "checkpoint: distortion = " + std::to_string(h.distortion) + ", the context has " + std::to_string(ctx->p.distortion); return LL_ERR_ARG; }
     if (h.line_res != cm0->leaf[0] || h.plane_res != cm0->leaf[1]) { d->err = "checkpoint: line_res / plane_res differ from the destination's"; return LL_ERR_ARG; }
-    const int S = d->S, prev = d->base + (d->row ^ 1) * S, tile_points = llx_tile();
+    const int S = d->S, prev = d->base + (d->row ^ 1) * S;
     const unsigned char *b = (const unsigned char *)blob;
     std::vector<char> taken(S, 0);
     std::vector<std::vector<int>> tabs(v.rec.size());
@@ -778,19 +766,15 @@ extern "C" int ll_drives_restore(ll_drives *d, const int *into, const void *blob
     if (hi <= lo) return LL_OK;                                                         /* every record skipped */
     std::vector<LLImpSeg> segs;
     std::vector<DrvRestore> tab;
-    unsigned long long ntiles = 0;
-    auto seg = [&](float4 *dst, long long at, int cnt) {
-        if (cnt <= 0) return;
-        segs.push_back({dst, at, cnt, (unsigned)ntiles});
-        ntiles += (unsigned long long)((cnt + tile_points - 1) / tile_points);
-    };
+    LLTiler tiles{llx_tile()};
+    auto seg = [&](float4 *dst, long long at, int cnt) { if (cnt > 0) segs.push_back({dst, at, cnt, tiles.take(cnt)}); };
     for (size_t r = 0; r < v.rec.size(); ++r) {
         const int q = into[r];
         if (q < 0) continue;
         const CkRecord &R = v.rec[r];
         const int slot = prev + q;
         long long at = (long long)((R.offset - lo) / 16);
-        llx_import_segments(llcms_map(d->cms, q), tabs[r].data(), at, tile_points, &ntiles, &segs);
+        llx_import_segments(llcms_map(d->cms, q), tabs[r].data(), at, tiles, &segs);
         at += R.n_pts[0] + R.n_pts[1];
         seg(V.sharp + (size_t)slot * V.cap_sharp, at, R.n_feat[0]); at += R.n_feat[0];
         seg(V.lsharp + (size_t)slot * V.cap_lsharp, at, R.n_feat[1]); at += R.n_feat[1];
@@ -803,7 +787,7 @@ extern "C" int ll_drives_restore(ll_drives *d, const int *into, const void *blob
         T.hdr.n_sharp = R.n_feat[0]; T.hdr.n_less_sharp = R.n_feat[1]; T.hdr.n_flat = R.n_feat[2]; T.hdr.n_less_flat = R.n_feat[3];
         tab.push_back(T);
     }
-    if (ntiles > 0x7fffffffull) { d->err = "checkpoint: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+    if (!tiles.fits()) { d->err = "checkpoint: too many tiles for one launch"; return LL_ERR_CAPACITY; }
     DRV_HIP(hipSetDevice(ctx->device));
     const size_t n_up = (size_t)((hi - lo) / 16);
     std::string why;
@@ -815,7 +799,7 @@ extern "C" int ll_drives_restore(ll_drives *d, const int *into, const void *blob
     if ((!segs.empty() && !d_segs) || !d_tab) { d->err = llcms_err(d->cms); return LL_ERR_HIP; }
     /* ---- from here on a failure loses the lanes being restored ---- */
     for (const DrvRestore &T : tab) { llcms_map(d->cms, T.lane)->broken = true; d->ran_prev[T.lane] = 0; d->reg_n[T.lane] = 0; }
-    rc = llx_scatter(ctx, d_segs, segs.size(), ntiles, src, b + lo, n_up, tile_points, d->err); if (rc) return rc;
+    rc = llx_scatter(ctx, d_segs, segs.size(), tiles.next, src, b + lo, n_up, tiles.per, d->err); if (rc) return rc;
     hipLaunchKernelGGL(k_drives_restore, dim3((unsigned)tab.size()), dim3(64), 0, ctx->stream, d_tab, (const float4 *)src, V.pose, d->d_odom, d->d_m2o, d->d_fidx, V.hdr);
     for (size_t a = 0; a < tab.size();) {                                               /* the slots serve as targets: their search grids, one launch per run of neighbouring lanes */
         size_t e = a + 1;                                                               /* (tab is in record order: a save lists the lanes ascending) */

@@ -1,13 +1,18 @@
 /*
- * ll_internal.h -- what the C-ABI translation units (ll_api.hip, ll_cubemap.hip) share: the context structs behind the
- * opaque handles of include/lightloam_hip.h and the error-return macros.
+ * ll_internal.h -- what every C-ABI translation unit shares: the context and map structs behind the opaque handles ll_ctx and
+ * ll_map of include/lightloam_hip.h, their error-return macros, and the functions of ll_api.hip, ll_mapping.hip and ll_voxel.hip
+ * that the other objects call.  The other handles' structs are in the header of their owner (ll_cubemap.h, ll_keyframes.h) or in
+ * its .hip file.
  */
 #pragma once
 #include "lightloam_hip.h"
 #include "ll_common.h"
+#include "ll_workspace.h"
 #include <string>
 #include <vector>
 #include <cstring>
+
+#define LL_HIDDEN __attribute__((visibility("hidden")))    /* shared between translation units, not exported from the library */
 
 #define LL_PROF_EVENTS 8192
 #define LL_TWO_STREAM_PIECES 4
@@ -95,16 +100,7 @@ struct ll_map {
     } while (0)
 
 template <typename T>
-static inline bool map_alloc(ll_map *m, T *&ptr, size_t count)
-{
-    void *p = nullptr;
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    if (hipMalloc(&p, bytes) != hipSuccess) { m->err = "hipMalloc failed (" + std::to_string(bytes) + " bytes)"; return false; }
-    if (hipMemset(p, 0, bytes) != hipSuccess) { m->err = "hipMemset failed"; (void)hipFree(p); return false; }
-    m->allocs.push_back(p);
-    ptr = (T *)p;
-    return true;
-}
+static inline bool map_alloc(ll_map *m, T *&ptr, size_t count) { return ll_dev_alloc(m->allocs, m->err, ptr, count, true); }
 
 
 LLLmOpt ll_to_dev_opt(const ll_lm_options *opt);

@@ -11,7 +11,8 @@
  *             the cube maps' per-call arena, behind what the frame staged there;
  *   export    one gather into a staging buffer, one copy, one synchronisation (llx_gather).
  */
-#include "ll_cubemap.h"
+#include "ll_keyframes.h"
+#include "ll_cubemaps.h"
 #include <cmath>
 
 static int kf_fail(ll_keyframes *kf, int rc, const std::string &msg) { kf->err = msg; return rc; }
@@ -116,9 +117,8 @@ extern "C" int ll_keyframes_add_cubemaps(ll_keyframes *kf, ll_cubemaps *cms, con
     if (n_new == 0) return LL_OK;
     int rc = kf_room(kf, n_new, need); if (rc) return rc;
     /* ---- the segments: sequence by sequence, corner then surf, each to the top of its region (offsets from the pool's base) */
-    const int tile_points = llx_tile();
+    LLTiler T{llx_tile()};
     std::vector<LLExpSeg> segs;
-    unsigned long long ntiles = 0;
     long long at[2] = {kf->top[0], kf->top[1]};
     for (int q = 0; q < S; ++q) {
         if (!sel[q]) continue;
@@ -126,8 +126,7 @@ extern "C" int ll_keyframes_add_cubemaps(ll_keyframes *kf, ll_cubemaps *cms, con
         for (int w = 0; w < 2; ++w) {
             const int cnt = m->M.n_stk[w];
             if (cnt <= 0) continue;
-            segs.push_back({m->d_stk[w], (w ? kf->cap[0] : 0) + at[w], cnt, (unsigned)ntiles});
-            ntiles += (unsigned long long)((cnt + tile_points - 1) / tile_points);
+            segs.push_back({m->d_stk[w], (w ? kf->cap[0] : 0) + at[w], cnt, T.take(cnt)});
             at[w] += cnt;
         }
     }
@@ -135,7 +134,7 @@ extern "C" int ll_keyframes_add_cubemaps(ll_keyframes *kf, ll_cubemaps *cms, con
         if (hipSetDevice(kf->ctx->device) != hipSuccess) return kf_fail(kf, LL_ERR_HIP, "keyframes: hipSetDevice failed");
         const LLExpSeg *d_segs = (const LLExpSeg *)llcms_stage(cms, segs.data(), segs.size() * sizeof(LLExpSeg));
         if (!d_segs) return kf_fail(kf, LL_ERR_HIP, "keyframes: " + llcms_err(cms));
-        rc = llx_pack(kf->ctx, d_segs, segs.size(), ntiles, nullptr, 0, 0, tile_points, kf->pool, kf->err);
+        rc = llx_pack(kf->ctx, d_segs, segs.size(), T.next, nullptr, 0, 0, T.per, kf->pool, kf->err);
         if (rc) return rc;
     }
     for (int q = 0; q < S; ++q) {
@@ -172,26 +171,22 @@ extern "C" int ll_keyframes_export(ll_keyframes *kf, int first, int count, ll_po
     if (!offsets_out) return kf_fail(kf, LL_ERR_ARG, "keyframes: offsets_out is NULL");
     if (first < 0 || count < 0 || (long long)first + count > (long long)kf->tab.size())
         return kf_fail(kf, LL_ERR_ARG, "keyframes: frames " + std::to_string(first) + " .. + " + std::to_string(count) + " are not in the store (size " + std::to_string(kf->tab.size()) + ")");
-    const int tile_points = llx_tile();
+    LLTiler T{llx_tile()};
     std::vector<LLExpSeg> segs;
-    unsigned long long ntiles = 0;
     long long at = 0;
     for (int f = 0; f < count; ++f) {
         const ll_keyframe_info &e = kf->tab[first + f];
         for (int w = 0; w < 2; ++w) {
             offsets_out[2 * f + w] = at;
-            if (e.n[w] > 0 && points_out) {
-                segs.push_back({kf->region(w) + e.offset[w], at, e.n[w], (unsigned)ntiles});
-                ntiles += (unsigned long long)((e.n[w] + tile_points - 1) / tile_points);
-            }
+            if (e.n[w] > 0 && points_out) segs.push_back({kf->region(w) + e.offset[w], at, e.n[w], T.take(e.n[w])});
             at += e.n[w];
         }
     }
     offsets_out[2 * count] = at;
     if (!points_out || at == 0) return LL_OK;
-    if (ntiles > 0x7fffffffull) return kf_fail(kf, LL_ERR_CAPACITY, "keyframes: too many tiles for one launch");
+    if (!T.fits()) return kf_fail(kf, LL_ERR_CAPACITY, "keyframes: too many tiles for one launch");
     if (hipSetDevice(kf->ctx->device) != hipSuccess) return kf_fail(kf, LL_ERR_HIP, "keyframes: hipSetDevice failed");
     const LLExpSeg *d_segs = llx_stage(kf->X, segs, kf->ctx->stream, kf->err);
     if (!d_segs) return LL_ERR_HIP;
-    return llx_gather(kf->X, kf->ctx, d_segs, segs.size(), ntiles, at, (size_t)(kf->cap[0] + kf->cap[1]), tile_points, points_out, kf->err);
+    return llx_gather(kf->X, kf->ctx, d_segs, segs.size(), T.next, at, (size_t)(kf->cap[0] + kf->cap[1]), T.per, points_out, kf->err);
 }

@@ -5,7 +5,7 @@
  * plain sums of squares of the edge and the plane residuals.  k_cms_info reduces the same blocks once more into the information
  * record (ll_pose_info: the normal equations' H and g there, their eigenvalues, the residual variance).  Nothing here changes a pose or a map.
  */
-#include "ll_cubemap.h"
+#include "ll_cubemaps.h"
 #include "ll_map_neq.h"
 #include "ll_pose_info.h"
 

@@ -35,7 +35,8 @@
  * The host synchronises ONCE per call, for the poses, the records and the block counts: the cube counts and offsets are host
  * bookkeeping, so the launches and the workspace are planned without a read-back.
  */
-#include "ll_cubemap.h"
+#include "ll_cubemaps.h"
+#include "ll_tiles.h"
 #include "ll_factor_math.h"
 #include "ll_map_neq.h"
 #include "ll_map_search.h"
@@ -58,17 +59,6 @@ struct AlGrid { const int *c2s; int cen[3]; int pad; };
 /* what an op has beyond its LLMapView: the two dst clouds, its rows of the block table per type, its first chunk of k_al_eval */
 struct AlOp { int grid[2], blk0[2], nblk[2], chunk0, pad; };
 
-template <typename S>
-__device__ __forceinline__ int al_find(const S *seg, int nseg, unsigned t)
-{
-    int lo = 0, hi = nseg;                                        /* the last segment whose first tile is <= t */
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((unsigned)__builtin_amdgcn_readfirstlane((int)seg[mid].tile0) <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 /* the cell of a map point inside its cube; a coordinate that is no number, or lies beyond the cube, goes to an edge cell */
 __device__ __forceinline__ int al_local(float x, int wc)
 {
@@ -82,7 +72,7 @@ __device__ __forceinline__ int al_cell(const float4 p, const int wc[3])
 
 __global__ __launch_bounds__(256) void k_al_count(const AlSeg *seg, int nseg, int *T)
 {
-    const AlSeg s = seg[al_find(seg, nseg, blockIdx.x)];
+    const AlSeg s = seg[ll_tile_find(seg, nseg, blockIdx.x)];
     const int first = (int)(blockIdx.x - s.tile0) * AL_TILE, n = min(AL_TILE, s.cnt - first);
     float4 po[AL_TILE / 256];
 #pragma unroll
@@ -115,7 +105,7 @@ __global__ __launch_bounds__(256) void k_al_scan(int *T, const int *slot_base)
 /* afterwards T[c + 1] has advanced from the first point of cell c to its end, the first point of cell c + 1 */
 __global__ __launch_bounds__(256) void k_al_scatter(const AlSeg *seg, int nseg, int *T, float4 *sorted)
 {
-    const AlSeg s = seg[al_find(seg, nseg, blockIdx.x)];
+    const AlSeg s = seg[ll_tile_find(seg, nseg, blockIdx.x)];
     if (s.slot < 0) return;
     const int first = (int)(blockIdx.x - s.tile0) * AL_TILE, n = min(AL_TILE, s.cnt - first);
     float4 po[AL_TILE / 256];
@@ -350,11 +340,6 @@ void llal_free(LLMapAlign &A)
     A = LLMapAlign();
 }
 
-struct AlCarve {
-    unsigned char *p; size_t at = 0;
-    template <typename T> T *take(size_t count) { T *r = p ? (T *)(p + at) : nullptr; at += (count * sizeof(T) + 255) / 256 * 256; return r; }
-};
-
 #define AL_HIP(call)                                                                         \
     do {                                                                                     \
         hipError_t e_ = (call);                                                              \
@@ -461,7 +446,7 @@ extern "C" int ll_cubemaps_align_info(ll_cubemaps *cms, const ll_merge_op *ops, 
     float4 *d_sorted = nullptr, *d_flat = nullptr;
     double *d_res = nullptr, *d_part = nullptr, *d_lm = nullptr;
     std::vector<LLMapView> views(O);
-    AlCarve W{A.d_mem};
+    LLCarve W{A.d_mem};
     for (int pass = 0; pass < 2; ++pass) {                         /* first the size, then the pointers */
         W.at = 0;
         d_T = W.take<int>((size_t)n_slot * AL_TAB);
@@ -502,7 +487,7 @@ extern "C" int ll_cubemaps_align_info(ll_cubemaps *cms, const ll_merge_op *ops, 
     std::vector<AlSeg> segs;
     std::vector<int> slot_base((size_t)n_slot), c2s(grids.size() * (size_t)CM_N, -1);
     std::vector<AlGrid> dgrids(grids.size());
-    unsigned long long tile = 0, tile_dst = 0;
+    LLTiler tiles{AL_TILE};
     for (size_t g = 0; g < grids.size(); ++g) {
         const ll_cubemap *cm = llcms_map(cms, grids[g].map);
         const int w = grids[g].w;
@@ -511,17 +496,16 @@ extern "C" int ll_cubemaps_align_info(ll_cubemaps *cms, const ll_merge_op *ops, 
             const int cnt = cm->cnt[w][c];
             if (cnt <= 0) continue;
             AlSeg s;
-            s.src = cm->pool[w][cm->cur[w]] + cm->off[w][c]; s.flat = nullptr; s.cnt = cnt; s.base = base; s.at = (int)grids[g].first; s.slot = slot; s.tile0 = (unsigned)tile;
+            s.src = cm->pool[w][cm->cur[w]] + cm->off[w][c]; s.flat = nullptr; s.cnt = cnt; s.base = base; s.at = (int)grids[g].first; s.slot = slot; s.tile0 = tiles.take(cnt);
             s.wc[0] = c % CM_W - cm->cen[0]; s.wc[1] = (c / CM_W) % CM_H - cm->cen[1]; s.wc[2] = c / (CM_W * CM_H) - cm->cen[2];
             segs.push_back(s);
             slot_base[slot] = (int)grids[g].first + base; c2s[g * CM_N + c] = slot;
-            tile += (unsigned long long)((cnt + AL_TILE - 1) / AL_TILE);
             base += cnt; ++slot;
         }
         for (int k = 0; k < 3; ++k) dgrids[g].cen[k] = cm->cen[k];
         dgrids[g].pad = 0;
     }
-    tile_dst = tile;
+    const unsigned long long tile_dst = tiles.next;                /* the dst cubes come first: k_al_scatter's grid */
     const size_t nseg_dst = segs.size();
     for (const AlCloud &sc : stacks) {
         const ll_cubemap *cm = llcms_map(cms, sc.map);
@@ -530,14 +514,13 @@ extern "C" int ll_cubemaps_align_info(ll_cubemaps *cms, const ll_merge_op *ops, 
             const int cnt = cm->cnt[sc.w][c];
             if (cnt <= 0) continue;
             AlSeg s;
-            s.src = cm->pool[sc.w][cm->cur[sc.w]] + cm->off[sc.w][c]; s.flat = d_flat + sc.first; s.cnt = cnt; s.base = base; s.at = 0; s.slot = -1; s.tile0 = (unsigned)tile;
+            s.src = cm->pool[sc.w][cm->cur[sc.w]] + cm->off[sc.w][c]; s.flat = d_flat + sc.first; s.cnt = cnt; s.base = base; s.at = 0; s.slot = -1; s.tile0 = tiles.take(cnt);
             s.wc[0] = s.wc[1] = s.wc[2] = 0;
             segs.push_back(s);
-            tile += (unsigned long long)((cnt + AL_TILE - 1) / AL_TILE);
             base += cnt;
         }
     }
-    if (tile > 0x7fffffffull) return llcms_fail(cms, LL_ERR_CAPACITY, "map align: too many tiles for one launch");
+    if (!tiles.fits()) return llcms_fail(cms, LL_ERR_CAPACITY, "map align: too many tiles for one launch");
     llcms_begin(cms);
     const AlSeg *d_segs = (const AlSeg *)llcms_stage(cms, segs.data(), segs.size() * sizeof(AlSeg));
     const int *d_slot_base = (const int *)llcms_stage(cms, slot_base.data(), slot_base.size() * sizeof(int));
@@ -559,7 +542,7 @@ extern "C" int ll_cubemaps_align_info(ll_cubemaps *cms, const ll_merge_op *ops, 
     size_t e = 0;
     AL_HIP(hipEventRecord(A.ev[e++], st));
     AL_HIP(hipMemsetAsync(d_T, 0, (size_t)n_slot * AL_TAB * sizeof(int), st));
-    hipLaunchKernelGGL(k_al_count, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_T);
+    hipLaunchKernelGGL(k_al_count, dim3((unsigned)tiles.next), dim3(256), 0, st, d_segs, (int)segs.size(), d_T);
     hipLaunchKernelGGL(k_al_scan, dim3((unsigned)n_slot), dim3(256), 0, st, d_T, d_slot_base);
     hipLaunchKernelGGL(k_al_scatter, dim3((unsigned)tile_dst), dim3(256), 0, st, d_segs, (int)nseg_dst, d_T, d_sorted);
     AL_HIP(hipEventRecord(A.ev[e++], st));
@@ -595,7 +578,7 @@ extern "C" int ll_cubemaps_align_info(ll_cubemaps *cms, const ll_merge_op *ops, 
     if (!pin) return llcms_fail(cms, LL_ERR_HIP, "map align: no page-locked scratch");
     AL_HIP(hipMemcpyAsync(pin, d_res, res_doubles * sizeof(double), hipMemcpyDeviceToHost, st));
     const int rc = llcms_sync(cms); if (rc) return rc;
-    auto span = [&](size_t a, size_t b) { float ms = 0.0f; return hipEventElapsedTime(&ms, A.ev[a], A.ev[b]) == hipSuccess ? (double)ms : 0.0; };
+    auto span = [&](size_t a, size_t b) { return ll_event_ms(A.ev[a], A.ev[b], 0.0); };
     A.ms[0] = span(0, 1);
     for (int it = 0; it < n_outer; ++it) { A.ms[1] += span(1 + 2 * (size_t)it, 2 + 2 * (size_t)it); A.ms[2] += span(2 + 2 * (size_t)it, 3 + 2 * (size_t)it); }
     A.ms[3] = span(1 + 2 * (size_t)n_outer, 2 + 2 * (size_t)n_outer);

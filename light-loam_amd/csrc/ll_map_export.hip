@@ -12,35 +12,25 @@
  * workgroup waits on another.
  */
 #include "ll_cubemap.h"
+#include "ll_tiles.h"
 #include <chrono>
 #include <cstdlib>
 
-/* point K * 256 + tid of a tile of n >= 1 points: the loads of all U points are issued before the first store (a clamped index
- * instead of a branch between them; the recursion keeps the U values in registers) */
-typedef float llx_f4 __attribute__((ext_vector_type(4)));
-typedef llx_f4 __attribute__((address_space(1))) llx_gf4;    /* the pointers come out of a table: said to be global, not flat */
-template <int U, int K>
-__device__ __forceinline__ void llx_copy_tile(const llx_gf4 *src, llx_gf4 *out, int n, int tid)
-{
-    const int i = K * 256 + tid;
-    const llx_f4 v = src[min(i, n - 1)];
-    if constexpr (K + 1 < U) llx_copy_tile<U, K + 1>(src, out, n, tid);
-    if (i < n) out[i] = v;
-}
-
-/* one tile = 256 lanes x U points */
+/* one tile = 256 lanes x U points (ll_copy_tile, ll_tiles.h).  The three kernels of this file keep ll_tile_find's loop written out:
+ * called as a function the compiler emits its one commutative add (lo + hi) with the operands the other way round, and these
+ * kernels' code is kept instruction for instruction */
 template <int U>
 __global__ __launch_bounds__(256) void k_map_export(const LLExpSeg *seg, int nseg, float4 *dst)
 {
     const unsigned t = blockIdx.x;
-    int lo = 0, hi = nseg;                                    /* the last segment whose first tile is <= t */
+    int lo = 0, hi = nseg;                                    /* ll_tile_find's loop, written out (see above) */
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if ((unsigned)__builtin_amdgcn_readfirstlane((int)seg[mid].tile0) <= t) lo = mid; else hi = mid;
     }
     const LLExpSeg s = seg[lo];
     const int first = (int)(t - s.tile0) * (256 * U);
-    llx_copy_tile<U, 0>((const llx_gf4 *)(s.src + first), (llx_gf4 *)(dst + s.dst + first), min(256 * U, s.cnt - first), (int)threadIdx.x);
+    ll_copy_tile<U, 0>((const ll_gf4 *)(s.src + first), (ll_gf4 *)(dst + s.dst + first), min(256 * U, s.cnt - first), (int)threadIdx.x);
 }
 
 /* points per tile: 1024 (four loads in flight per lane) unless LIGHTLOAM_EXPORT_TILE names another of the built sizes (A/B runs:
@@ -51,9 +41,9 @@ int llx_tile()
     return 1024;
 }
 
-/* the clouds of `cm` that `which` selects, in output order from point dst0 on; *tile: the running number of tiles.  Returns the
- * number of points; segs == nullptr: sizes only */
-long long llx_segments(const ll_cubemap *cm, int which, long long dst0, int tile_points, unsigned long long *tile, std::vector<LLExpSeg> *segs)
+/* the clouds of `cm` that `which` selects, in output order from point dst0 on, numbered by T.  Returns the number of points;
+ * T == nullptr: sizes only */
+long long llx_segments(const ll_cubemap *cm, int which, long long dst0, LLTiler *T, std::vector<LLExpSeg> *segs)
 {
     long long at = dst0;
     const int n = which == LL_MAP_ALL ? CM_N : which == LL_MAP_SURROUND ? cm->n_valid : 0;
@@ -62,10 +52,7 @@ long long llx_segments(const ll_cubemap *cm, int which, long long dst0, int tile
         for (int w = 0; w < 2; ++w) {
             const int cnt = cm->cnt[w][c];
             if (cnt <= 0) continue;
-            if (segs) {
-                segs->push_back({cm->pool[w][cm->cur[w]] + cm->off[w][c], at, cnt, (unsigned)*tile});
-                *tile += (unsigned long long)((cnt + tile_points - 1) / tile_points);
-            }
+            if (T) segs->push_back({cm->pool[w][cm->cur[w]] + cm->off[w][c], at, cnt, T->take(cnt)});
             at += cnt;
         }
     }
@@ -147,9 +134,8 @@ int llx_gather(LLMapExport &X, ll_ctx *ctx, const LLExpSeg *d_segs, size_t nseg,
     if (e == hipSuccess) e = hipEventRecord(X.ev[2], st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { err = std::string("map export: ") + hipGetErrorString(e); return LL_ERR_HIP; }
-    float ms = 0.0f;
-    X.ms[1] = hipEventElapsedTime(&ms, X.ev[0], X.ev[1]) == hipSuccess ? (double)ms : -1.0;
-    X.ms[2] = hipEventElapsedTime(&ms, X.ev[1], X.ev[2]) == hipSuccess ? (double)ms : -1.0;
+    X.ms[1] = ll_event_ms(X.ev[0], X.ev[1], -1.0);
+    X.ms[2] = ll_event_ms(X.ev[1], X.ev[2], -1.0);
     X.points = total; X.segments = (long long)nseg; X.tiles = (long long)ntiles;
     return LL_OK;
 }
@@ -173,21 +159,21 @@ void llx_timing(const LLMapExport &X, double *ms3, long long *counts3)
  * The input is the byte layout an LL_MAP_ALL export writes (cubes 0 .. 4850, per cube the corner cloud, then the surf cloud); the
  * host knows every size from `counts`, lists the non-empty clouds as segments in INPUT order and deals the work in the same
  * fixed tiles: a workgroup takes one tile of one segment, found by the same binary search over the segments' first tiles
- * (scalar loads), and copies it with llx_copy_tile -- one dwordx4 load and one dwordx4 store per lane per point, every load of
+ * (scalar loads), and copies it with ll_copy_tile -- one dwordx4 load and one dwordx4 store per lane per point, every load of
  * the tile before its first store.  The corner and surf clouds of a cube are neighbours in the input and go to two different
  * pools: the de-interleave is in the segments' destinations.  No atomics, no LDS, no workgroup waits on another. */
 template <int U>
 __global__ __launch_bounds__(256) void k_map_import(const LLImpSeg *seg, int nseg, const float4 *src)
 {
     const unsigned t = blockIdx.x;
-    int lo = 0, hi = nseg;                                    /* the last segment whose first tile is <= t */
+    int lo = 0, hi = nseg;                                    /* ll_tile_find's loop, written out (see above) */
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if ((unsigned)__builtin_amdgcn_readfirstlane((int)seg[mid].tile0) <= t) lo = mid; else hi = mid;
     }
     const LLImpSeg s = seg[lo];
     const int first = (int)(t - s.tile0) * (256 * U);
-    llx_copy_tile<U, 0>((const llx_gf4 *)(src + s.src + first), (llx_gf4 *)(s.dst + first), min(256 * U, s.cnt - first), (int)threadIdx.x);
+    ll_copy_tile<U, 0>((const ll_gf4 *)(src + s.src + first), (ll_gf4 *)(s.dst + first), min(256 * U, s.cnt - first), (int)threadIdx.x);
 }
 
 /* the checkpoint pack launch: workgroups [0, ntiles) are k_map_export's tiles; behind them R + 1 workgroups per record -- ring r
@@ -206,7 +192,7 @@ __global__ __launch_bounds__(256) void k_ckpt_pack(const LLExpSeg *seg, int nseg
         }
         const LLExpSeg s = seg[lo];
         const int first = (int)(t - s.tile0) * (256 * U);
-        llx_copy_tile<U, 0>((const llx_gf4 *)(s.src + first), (llx_gf4 *)(dst + s.dst + first), min(256 * U, s.cnt - first), tid);
+        ll_copy_tile<U, 0>((const ll_gf4 *)(s.src + first), (ll_gf4 *)(dst + s.dst + first), min(256 * U, s.cnt - first), tid);
         return;
     }
     t -= ntiles;
@@ -230,7 +216,7 @@ int llx_pack(ll_ctx *ctx, const LLExpSeg *d_segs, size_t nseg, unsigned long lon
 {
     const unsigned long long nb = ntiles + (unsigned long long)nrec * (unsigned)(R + 1);
     if (nb == 0) return LL_OK;
-    if (nb > 0x7fffffffull) { err = "checkpoint: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+    if (!ll_grid_fits(nb)) { err = "checkpoint: too many tiles for one launch"; return LL_ERR_CAPACITY; }
     const dim3 grid((unsigned)nb), block(256);
     hipStream_t st = ctx->stream;
     switch (tile_points) {
@@ -273,7 +259,7 @@ int llx_import_check(const ll_cubemap *cm, const int *cen3, const int *counts, c
     return LL_OK;
 }
 
-void llx_import_segments(const ll_cubemap *cm, const int *counts, long long src0, int tile_points, unsigned long long *tile, std::vector<LLImpSeg> *segs)
+void llx_import_segments(const ll_cubemap *cm, const int *counts, long long src0, LLTiler &T, std::vector<LLImpSeg> *segs)
 {
     long long at = src0;
     size_t top[2] = {0, 0};
@@ -281,8 +267,7 @@ void llx_import_segments(const ll_cubemap *cm, const int *counts, long long src0
         for (int w = 0; w < 2; ++w) {
             const int cnt = counts[(size_t)w * CM_N + c];
             if (cnt <= 0) continue;
-            segs->push_back({cm->pool[w][0] + top[w], at, cnt, (unsigned)*tile});
-            *tile += (unsigned long long)((cnt + tile_points - 1) / tile_points);
+            segs->push_back({cm->pool[w][0] + top[w], at, cnt, T.take(cnt)});
             at += cnt; top[w] += (size_t)cnt;
         }
 }
@@ -345,19 +330,18 @@ extern "C" int ll_cubemap_export(ll_cubemap *cm, int which, ll_point *out, long 
     if (which < LL_MAP_NONE || which > LL_MAP_ALL || cap < 0) { cm->err = "map export: bad arguments"; return LL_ERR_ARG; }
     if (which != LL_MAP_NONE && cm->broken) { cm->err = "the cube map is unusable: an earlier ll_cubemap_update failed half-way"; return LL_ERR_STATE; }
     const auto t0 = std::chrono::steady_clock::now();
-    const int tile_points = llx_tile();
+    LLTiler T{llx_tile()};
     std::vector<LLExpSeg> segs;
-    unsigned long long ntiles = 0;
-    const long long total = llx_segments(cm, which, 0, tile_points, &ntiles, &segs);
+    const long long total = llx_segments(cm, which, 0, &T, &segs);
     if (n) *n = total;
     if (total > 0 && !out) { cm->err = "map export: out is NULL"; return LL_ERR_ARG; }
     if (total > cap) { cm->err = "map export: " + std::to_string(total) + " points, room for " + std::to_string(cap); return LL_ERR_CAPACITY; }
-    if (ntiles > 0x7fffffffull) { cm->err = "map export: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+    if (!T.fits()) { cm->err = "map export: too many tiles for one launch"; return LL_ERR_CAPACITY; }
     CM_HIP(hipSetDevice(cm->ctx->device));
     const LLExpSeg *d_segs = nullptr;
     if (total > 0) { d_segs = llx_stage(cm->X, segs, cm->ctx->stream, cm->err); if (!d_segs) return LL_ERR_HIP; }
     cm->X.ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return llx_gather(cm->X, cm->ctx, d_segs, segs.size(), ntiles, total, 2 * cm->cap_pool, tile_points, out, cm->err);
+    return llx_gather(cm->X, cm->ctx, d_segs, segs.size(), T.next, total, 2 * cm->cap_pool, T.per, out, cm->err);
 }
 
 extern "C" int ll_cubemap_layout(ll_cubemap *cm, int *cen3, int *counts, int *valid, int *n_valid)
@@ -377,11 +361,10 @@ extern "C" int ll_cubemap_import(ll_cubemap *cm, const ll_point *points, long lo
     std::string why;
     int rc = llx_import_check(cm, cen3, counts, valid, n_valid, n, why);
     if (rc) { cm->err = "map import: " + why; return rc; }
-    const int tile_points = llx_tile();
+    LLTiler T{llx_tile()};
     std::vector<LLImpSeg> segs;
-    unsigned long long ntiles = 0;
-    llx_import_segments(cm, counts, 0, tile_points, &ntiles, &segs);
-    if (ntiles > 0x7fffffffull) { cm->err = "map import: too many tiles for one launch"; return LL_ERR_CAPACITY; }
+    llx_import_segments(cm, counts, 0, T, &segs);
+    if (!T.fits()) { cm->err = "map import: too many tiles for one launch"; return LL_ERR_CAPACITY; }
     CM_HIP(hipSetDevice(cm->ctx->device));
     const bool direct = n > 0 && llx_is_device(points);
     float4 *src = direct ? (float4 *)points : nullptr;
@@ -392,7 +375,7 @@ extern "C" int ll_cubemap_import(ll_cubemap *cm, const ll_point *points, long lo
         if (!d_segs) return LL_ERR_HIP;
     }
     cm->broken = true;                                        /* until the scatter has landed */
-    rc = llx_scatter(cm->ctx, d_segs, segs.size(), ntiles, src, direct ? nullptr : points, (size_t)n, tile_points, cm->err);
+    rc = llx_scatter(cm->ctx, d_segs, segs.size(), T.next, src, direct ? nullptr : points, (size_t)n, T.per, cm->err);
     if (rc) return rc;
     CM_HIP(hipStreamSynchronize(cm->ctx->stream));
     llx_import_commit(cm, cen3, counts, valid, n_valid);

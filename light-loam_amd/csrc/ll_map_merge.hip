@@ -34,7 +34,9 @@
  * per record are counted behind the count tables -- so everything from k_mm_cstart on is untouched, and `dropped` is the outside
  * bin minus the removed ones.
  */
-#include "ll_cubemap.h"
+#include "ll_cubemaps.h"
+#include "ll_keyframes.h"
+#include "ll_tiles.h"
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -107,7 +109,7 @@ __device__ __forceinline__ void mm_assign_tile(const float4 *src, int dst, int c
 
 __global__ __launch_bounds__(256) void k_mm_assign(const MmSeg *seg, int nseg, const MmRec *recs, float4 *tp, int *keys, int *addcnt)
 {
-    const MmSeg s = seg[mm_find(seg, nseg, blockIdx.x)];
+    const MmSeg s = seg[ll_tile_find(seg, nseg, blockIdx.x)];
     mm_assign_tile<false>(s.src, s.dst, s.cnt, (int)(blockIdx.x - s.tile0), recs[s.rec].T, recs, s.rec, tp, keys, addcnt);
 }
 
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(256) void k_mm_assign(const MmSeg *seg, int nseg, c
 template <bool FILTER>
 __global__ __launch_bounds__(256) void k_kf_assign(const KfSeg *seg, int nseg, const MmRec *recs, float4 *tp, int *keys, int *addcnt, KfFilter F)
 {
-    const KfSeg *s = seg + mm_find(seg, nseg, blockIdx.x);
+    const KfSeg *s = seg + ll_tile_find(seg, nseg, blockIdx.x);
     mm_assign_tile<FILTER>(s->src, s->dst, s->cnt, (int)(blockIdx.x - s->tile0), s->T, recs, s->rec, tp, keys, addcnt, &F);
 }
 
@@ -196,15 +198,13 @@ __global__ __launch_bounds__(64) void k_mm_place(const MmChunk *chunks, const Mm
     }
 }
 
-typedef float mm_f4 __attribute__((ext_vector_type(4)));
-typedef mm_f4 __attribute__((address_space(1))) mm_gf4;          /* the pointers come out of a table: said to be global, not flat */
 __global__ __launch_bounds__(256) void k_mm_gather(const MmCopy *ops, int nops)
 {
-    const MmCopy o = ops[mm_find(ops, nops, blockIdx.x)];
+    const MmCopy o = ops[ll_tile_find(ops, nops, blockIdx.x)];
     const int first = (int)(blockIdx.x - o.tile0) * MM_TILE, n = min(MM_TILE, o.cnt - first);
-    const mm_gf4 *src = (const mm_gf4 *)o.src;
-    mm_gf4 *dst = (mm_gf4 *)o.dst + first;
-    mm_f4 v[MM_TILE / 256];
+    const ll_gf4 *src = (const ll_gf4 *)o.src;
+    ll_gf4 *dst = (ll_gf4 *)o.dst + first;
+    ll_f4 v[MM_TILE / 256];
     if (o.index) {
         int idx[MM_TILE / 256];
 #pragma unroll
@@ -243,11 +243,6 @@ static unsigned char *mm_reserve(LLMapMerge &G, int k, size_t bytes, std::string
     return G.d_mem[k];
 }
 
-struct MmCarve {
-    unsigned char *p; size_t at = 0;
-    template <typename T> T *take(size_t count) { T *r = p ? (T *)(p + at) : nullptr; at += (count * sizeof(T) + 255) / 256 * 256; return r; }
-};
-
 static const char *mm_type(int w) { return w ? "surf" : "corner"; }
 
 #define MM_HIP(call)                                                                         \
@@ -258,13 +253,13 @@ static const char *mm_type(int w) { return w ? "surf" : "corner"; }
 
 static int mm_gather(ll_cubemaps *cms, const std::string &what, std::vector<MmCopy> &ops, hipStream_t st)
 {
-    unsigned long long tile = 0;
-    for (MmCopy &o : ops) { o.tile0 = (unsigned)tile; tile += (unsigned long long)((o.cnt + MM_TILE - 1) / MM_TILE); }
+    LLTiler T{MM_TILE};
+    for (MmCopy &o : ops) o.tile0 = T.take(o.cnt);
     if (ops.empty()) return LL_OK;
-    if (tile > 0x7fffffffull) return llcms_fail(cms, LL_ERR_CAPACITY, what + "too many tiles for one launch");
+    if (!T.fits()) return llcms_fail(cms, LL_ERR_CAPACITY, what + "too many tiles for one launch");
     const MmCopy *d = (const MmCopy *)llcms_stage(cms, ops.data(), ops.size() * sizeof(MmCopy));
     if (!d) return LL_ERR_HIP;
-    hipLaunchKernelGGL(k_mm_gather, dim3((unsigned)tile), dim3(256), 0, st, d, (int)ops.size());
+    hipLaunchKernelGGL(k_mm_gather, dim3((unsigned)T.next), dim3(256), 0, st, d, (int)ops.size());
     return LL_OK;
 }
 
@@ -333,7 +328,7 @@ static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropp
             if (hipEventCreate(&G.ev[k]) != hipSuccess) { for (int j = 0; j < k; ++j) (void)hipEventDestroy(G.ev[j]); return llcms_fail(cms, LL_ERR_HIP, J.what + "hipEventCreate failed"); }
         G.have_ev = true;
     }
-    MmCarve A{nullptr};                                           /* first the size, then the pointers */
+    LLCarve A{nullptr};                                           /* first the size, then the pointers */
     A.take<float4>((size_t)N); A.take<int>((size_t)N); A.take<int>((size_t)N);
     const size_t n_cnt = (size_t)nrec * MM_BINS + (J.filtered ? (size_t)nrec : 0);
     A.take<int>(n_cnt); A.take<int>((size_t)nrec * MM_BINS); A.take<int>(chunks.size() * MM_BINS);
@@ -419,7 +414,7 @@ static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropp
     int *d_nout = nullptr;
     LLVoxWork W[2];
     {
-        MmCarve B{nullptr};
+        LLCarve B{nullptr};
         unsigned char *vox[2] = {nullptr, nullptr};
         for (int pass = 0; pass < 2; ++pass) {
             B.at = 0;
@@ -496,7 +491,7 @@ static int mm_run(ll_cubemaps *cms, MmJob &J, long long *added, long long *dropp
     MM_HIP(hipGetLastError());
     rc = llcms_sync(cms); if (rc) return rc;                      /* the copy has landed: the maps are whole again, the events can be read */
     for (int i = 0; i < n_ops; ++i) llcms_map(cms, J.ops[i].dst)->broken = false;
-    auto span = [&](int a, int b) { float ms = 0.0f; return hipEventElapsedTime(&ms, G.ev[a], G.ev[b]) == hipSuccess ? (double)ms : 0.0; };
+    auto span = [&](int a, int b) { return ll_event_ms(G.ev[a], G.ev[b], 0.0); };
     J.ms[0] = span(0, 1); J.ms[1] = span(1, 2) + span(3, 4); J.ms[2] = span(4, 5); J.ms[3] = span(6, 7);
     J.counts[2] = n_out_all;
     return LL_OK;
@@ -536,7 +531,7 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
     J.what = "map merge: "; J.ms = G.ms; J.counts = G.counts;
     J.recs.resize(2 * n_ops);
     std::vector<MmSeg> segs;
-    unsigned long long tile = 0;
+    LLTiler tiles{MM_TILE};
     long long N = 0;
     for (int i = 0; i < n_ops; ++i) {
         const ll_cubemap *src = llcms_map(cms, ops[i].src), *dst = llcms_map(cms, ops[i].dst);
@@ -550,8 +545,7 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
                 const int cnt = src->cnt[w][c];
                 if (cnt <= 0) continue;
                 if (N + n + cnt > (1ll << 30)) return llcms_fail(cms, LL_ERR_CAPACITY, "map merge: more than 2^30 source points in one call");
-                segs.push_back({src->pool[w][src->cur[w]] + src->off[w][c], (int)(N + n), cnt, (unsigned)tile, 2 * i + w});
-                tile += (unsigned long long)((cnt + MM_TILE - 1) / MM_TILE);
+                segs.push_back({src->pool[w][src->cur[w]] + src->off[w][c], (int)(N + n), cnt, tiles.take(cnt), 2 * i + w});
                 n += cnt;
             }
             mm_close_record(R, 2 * i + w, N, n, J.chunks);
@@ -562,7 +556,7 @@ extern "C" int ll_cubemaps_merge(ll_cubemaps *cms, const ll_merge_op *ops, int n
     const MmSeg *d_segs = nullptr;
     J.stage = [&]() { d_segs = (const MmSeg *)llcms_stage(cms, segs.data(), segs.size() * sizeof(MmSeg)); return d_segs != nullptr; };
     J.assign = [&](const MmRec *d_recs, float4 *d_tp, int *d_keys, int *d_addcnt, hipStream_t st) {
-        hipLaunchKernelGGL(k_mm_assign, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt);
+        hipLaunchKernelGGL(k_mm_assign, dim3((unsigned)tiles.next), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt);
     };
     return mm_run(cms, J, added, dropped);
 }
@@ -611,7 +605,7 @@ static int kf_insert(ll_cubemaps *cms, const ll_keyframes *kf, const ll_visibili
     J.what = what; J.ms = G.ins_ms; J.counts = G.ins_counts;
     J.recs.resize(2 * n_ops);
     std::vector<KfSeg> segs;
-    unsigned long long tile = 0;
+    LLTiler tiles{MM_TILE};
     long long N = 0;
     for (int i = 0; i < n_ops; ++i) {
         const ll_insert_op &o = ops[i];
@@ -627,18 +621,17 @@ static int kf_insert(ll_cubemaps *cms, const ll_keyframes *kf, const ll_visibili
                 const int cnt = e.n[w];
                 if (cnt <= 0) continue;
                 if (N + n + cnt > (1ll << 30)) return llcms_fail(cms, LL_ERR_CAPACITY, what + "more than 2^30 source points in one call");
-                KfSeg s = {kf->region(w) + e.offset[w], (int)(N + n), cnt, (unsigned)tile, 2 * i + w, {}};
+                KfSeg s = {kf->region(w) + e.offset[w], (int)(N + n), cnt, tiles.take(cnt), 2 * i + w, {}};
                 const double *P = o.poses_w7 ? o.poses_w7 + (size_t)f * 7 : e.pose_w7;
                 for (int k = 0; k < 7; ++k) s.T[k] = P[k];
                 segs.push_back(s);
-                tile += (unsigned long long)((cnt + MM_TILE - 1) / MM_TILE);
                 n += cnt;
             }
             mm_close_record(R, 2 * i + w, N, n, J.chunks);
             N += n;
         }
     }
-    if (tile > 0x7fffffffull) return llcms_fail(cms, LL_ERR_CAPACITY, what + "too many tiles for one launch");
+    if (!tiles.fits()) return llcms_fail(cms, LL_ERR_CAPACITY, what + "too many tiles for one launch");
     J.N = N;
     const KfSeg *d_segs = nullptr;
     J.stage = [&]() { d_segs = (const KfSeg *)llcms_stage(cms, segs.data(), segs.size() * sizeof(KfSeg)); return d_segs != nullptr; };
@@ -646,10 +639,10 @@ static int kf_insert(ll_cubemaps *cms, const ll_keyframes *kf, const ll_visibili
     J.assign = [&](const MmRec *d_recs, float4 *d_tp, int *d_keys, int *d_addcnt, hipStream_t st) {
         if (v) {
             const KfFilter F = {kf->pool, v->d_cnt, rule->min_through, rule->max_hit, d_addcnt + (size_t)2 * n_ops * MM_BINS};
-            hipLaunchKernelGGL(k_kf_assign<true>, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt, F);
+            hipLaunchKernelGGL(k_kf_assign<true>, dim3((unsigned)tiles.next), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt, F);
         } else {
             const KfFilter F = {nullptr, nullptr, 0, 0, nullptr};
-            hipLaunchKernelGGL(k_kf_assign<false>, dim3((unsigned)tile), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt, F);
+            hipLaunchKernelGGL(k_kf_assign<false>, dim3((unsigned)tiles.next), dim3(256), 0, st, d_segs, (int)segs.size(), d_recs, d_tp, d_keys, d_addcnt, F);
         }
     };
     return mm_run(cms, J, added, dropped, removed);

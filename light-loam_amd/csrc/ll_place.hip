@@ -435,8 +435,6 @@ static int pl_gram(ll_places *db, int q0, int nq, int c0, int nc)
     return LL_OK;
 }
 
-static double pl_span(hipEvent_t a, hipEvent_t b) { float ms = 0.0f; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (double)ms : 0.0; }
-
 extern "C" int ll_places_distances(ll_places *db, int q0, int nq, int c0, int nc, float *dist, unsigned char *shift)
 {
     if (!db) return LL_ERR_ARG;
@@ -454,7 +452,7 @@ extern "C" int ll_places_distances(ll_places *db, int q0, int nq, int c0, int nc
     PL_HIP(hipMemcpyAsync(dist, db->d_dist, pairs * sizeof(float), hipMemcpyDeviceToHost, st));
     PL_HIP(hipMemcpyAsync(shift, db->d_shift, pairs, hipMemcpyDeviceToHost, st));
     PL_HIP(hipStreamSynchronize(st));                              /* the ONE synchronisation */
-    db->ms[1] = pl_span(db->ev[2], db->ev[3]);
+    db->ms[1] = ll_event_ms(db->ev[2], db->ev[3], 0.0);
     return LL_OK;
 }
 
@@ -490,7 +488,7 @@ extern "C" int ll_places_match(ll_places *db, int q0, int nq, int c0, int nc, co
     PL_HIP(hipMemcpyAsync(pin, db->d_sel, sel_bytes, hipMemcpyDeviceToHost, st));
     PL_HIP(hipStreamSynchronize(st));                              /* the ONE synchronisation */
     std::memcpy(id, pin, n_out * 4); std::memcpy(dist, pin + n_out * 4, n_out * 4); std::memcpy(shift, pin + n_out * 8, n_out);
-    db->ms[1] = pl_span(db->ev[2], db->ev[3]); db->ms[2] = pl_span(db->ev[3], db->ev[4]);
+    db->ms[1] = ll_event_ms(db->ev[2], db->ev[3], 0.0); db->ms[2] = ll_event_ms(db->ev[3], db->ev[4], 0.0);
     return LL_OK;
 }
 
@@ -502,7 +500,7 @@ extern "C" int ll_places_timing(ll_places *db, double *ms3, long long *counts2)
     if (db->add_pending) {
         PL_HIP(hipSetDevice(db->ctx->device));
         PL_HIP(hipEventSynchronize(db->ev[1]));
-        db->ms[0] = pl_span(db->ev[0], db->ev[1]);
+        db->ms[0] = ll_event_ms(db->ev[0], db->ev[1], 0.0);
         db->add_pending = false;
     }
     if (ms3) for (int k = 0; k < 3; ++k) ms3[k] = db->ms[k];

@@ -1271,8 +1271,7 @@ static int pg_run(ll_posegraphs *pg, bool solve, int n_graphs, const int *node_o
     const int *pstat = (const int *)(pout + pg_up8(down));
     if (chain) PG_HIP(hipMemcpyAsync((void *)pstat, A.cstat, stat_bytes, hipMemcpyDeviceToHost, st));
     PG_HIP(hipStreamSynchronize(st));                              /* the ONE synchronisation */
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, pg->ev[0], pg->ev[1]) == hipSuccess) pg->ms[solve ? 1 : 0] = (double)ms;
+    pg->ms[solve ? 1 : 0] = ll_event_ms(pg->ev[0], pg->ev[1], pg->ms[solve ? 1 : 0]);
 
     /* ---- hand back */
     const double *nodes = (const double *)pout;
@@ -1568,9 +1567,7 @@ static int pg_cov_run(ll_posegraphs *pg, int n_graphs, const int *node_off, cons
     PG_HIP(hipGetLastError());
     PG_HIP(hipMemcpyAsync(pout, pg->d_cov + o_col, down, hipMemcpyDeviceToHost, st));
     PG_HIP(hipStreamSynchronize(st));                              /* the ONE synchronisation */
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, pg->cov_ev[0], pg->cov_ev[1]) == hipSuccess) pg->cov_ms[0] = (double)ms;
-    if (hipEventElapsedTime(&ms, pg->cov_ev[1], pg->cov_ev[2]) == hipSuccess) pg->cov_ms[1] = (double)ms;
+    for (int k = 0; k < 2; ++k) pg->cov_ms[k] = ll_event_ms(pg->cov_ev[k], pg->cov_ev[k + 1], pg->cov_ms[k]);
 
     /* ---- hand back */
     const ll_pg_cov_record *cols = (const ll_pg_cov_record *)pout;

@@ -19,7 +19,10 @@
  * ll_visibility_run enqueues one table upload, one fill of raw and the three launches, and synchronises ONCE (the page-locked table
  * is free again, the events can be read).
  */
-#include "ll_cubemap.h"
+#include "ll_keyframes.h"
+#include "ll_map_export.h"
+#include "ll_map_search.h"
+#include "ll_tiles.h"
 #include <cmath>
 
 #define VIS_TILE 1024
@@ -46,7 +49,7 @@ __device__ __forceinline__ int vis_pixel(float x, float y, float z, const VisCfg
 
 __global__ __launch_bounds__(256) void k_vis_image(const float4 *__restrict__ pool, const VisSeg *__restrict__ seg, int nseg, VisCfg c, unsigned *raw)
 {
-    const VisSeg s = seg[mm_find(seg, nseg, blockIdx.x)];
+    const VisSeg s = seg[ll_tile_find(seg, nseg, blockIdx.x)];
     const int first = (int)(blockIdx.x - s.tile0) * VIS_TILE, n = min(VIS_TILE, s.cnt - first);
     const float4 *src = pool + s.off + first;
     unsigned *im = raw + (size_t)s.k * ((size_t)c.W * c.H);
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(256) void k_vis_vote(const float4 *__restrict__ poo
                                                   const int *__restrict__ obs_start, const int *__restrict__ obs, VisCfg c, const float *__restrict__ img,
                                                   unsigned char *cnt)
 {
-    const VisSeg s = seg[mm_find(seg, nseg, blockIdx.x)];
+    const VisSeg s = seg[ll_tile_find(seg, nseg, blockIdx.x)];
     const int first = (int)(blockIdx.x - s.tile0) * VIS_TILE, n = min(VIS_TILE, s.cnt - first);
     const float4 *src = pool + s.off + first;
     const int ka = __builtin_amdgcn_readfirstlane(s.k);
@@ -215,14 +218,6 @@ extern "C" int ll_visibility_reset(ll_visibility *v)
     return LL_OK;
 }
 
-template <typename T> static size_t vis_put(std::vector<unsigned char> &blob, const std::vector<T> &a)
-{
-    const size_t at = (blob.size() + 255) / 256 * 256;
-    blob.resize(at + a.size() * sizeof(T));
-    if (!a.empty()) std::memcpy(blob.data() + at, a.data(), a.size() * sizeof(T));
-    return at;
-}
-
 extern "C" int ll_visibility_run(ll_visibility *v, const ll_visibility_op *ops, int n_ops, long long *pairs)
 {
     if (!v) return LL_ERR_ARG;
@@ -252,7 +247,7 @@ extern "C" int ll_visibility_run(ll_visibility *v, const ll_visibility_op *ops, 
     std::vector<VisSeg> segs;
     std::vector<double> poses((size_t)L * 7);
     std::vector<int> obs_start((size_t)L + 1, 0), obs, listed((size_t)L);
-    unsigned long long tile = 0;
+    LLTiler tiles{VIS_TILE};
     long long n_points = 0, n_pairs = 0;
     const double rad2 = (double)v->p.radius * (double)v->p.radius;
     int k0 = 0;
@@ -265,8 +260,7 @@ extern "C" int ll_visibility_run(ll_visibility *v, const ll_visibility_op *ops, 
             listed[k0 + f] = o.frames[f];
             for (int w = 0; w < 2; ++w) {
                 if (e.n[w] <= 0) continue;
-                segs.push_back({(w ? kf->cap[0] : 0) + e.offset[w], e.n[w], (unsigned)tile, k0 + f, 0});
-                tile += (unsigned long long)((e.n[w] + VIS_TILE - 1) / VIS_TILE);
+                segs.push_back({(w ? kf->cap[0] : 0) + e.offset[w], e.n[w], tiles.take(e.n[w]), k0 + f, 0});
                 n_points += e.n[w];
             }
         }
@@ -285,14 +279,14 @@ extern "C" int ll_visibility_run(ll_visibility *v, const ll_visibility_op *ops, 
         n_pairs += np;
         k0 += o.n_frames;
     }
-    if (obs.size() > 0x7fffffffull || tile > 0x7fffffffull) return vis_fail(v, LL_ERR_CAPACITY, "visibility: too many frame pairs or tiles for one call");
+    if (!ll_grid_fits(obs.size()) || !tiles.fits()) return vis_fail(v, LL_ERR_CAPACITY, "visibility: too many frame pairs or tiles for one call");
     v->last = listed;
     v->ms[0] = v->ms[1] = v->ms[2] = 0.0;
     v->counts[0] = L; v->counts[1] = n_points; v->counts[2] = n_pairs;
     if (L == 0) return LL_OK;
     if (obs.empty()) obs.push_back(0);                              /* never read: keeps the table's last part non-empty */
     std::vector<unsigned char> blob;
-    const size_t at_seg = vis_put(blob, segs), at_pose = vis_put(blob, poses), at_start = vis_put(blob, obs_start), at_obs = vis_put(blob, obs);
+    const size_t at_seg = ll_blob_put(blob, segs), at_pose = ll_blob_put(blob, poses), at_start = ll_blob_put(blob, obs_start), at_obs = ll_blob_put(blob, obs);
     hipStream_t st = v->ctx->stream;
     VIS_HIP(hipSetDevice(v->ctx->device));
     const unsigned char *d_blob = (const unsigned char *)llx_stage_bytes(v->X, blob.data(), blob.size(), st, v->err);
@@ -302,17 +296,17 @@ extern "C" int ll_visibility_run(ll_visibility *v, const ll_visibility_op *ops, 
     const VisSeg *d_seg = (const VisSeg *)(d_blob + at_seg);
     VIS_HIP(hipMemsetD32Async((hipDeviceptr_t)v->d_raw, (int)VIS_INF_BITS, (size_t)L * HW, st));
     VIS_HIP(hipEventRecord(v->ev[0], st));
-    if (tile > 0) hipLaunchKernelGGL(k_vis_image, dim3((unsigned)tile), dim3(256), 0, st, (const float4 *)kf->pool, d_seg, (int)segs.size(), c, (unsigned *)v->d_raw);
+    if (tiles.next > 0) hipLaunchKernelGGL(k_vis_image, dim3((unsigned)tiles.next), dim3(256), 0, st, (const float4 *)kf->pool, d_seg, (int)segs.size(), c, (unsigned *)v->d_raw);
     VIS_HIP(hipEventRecord(v->ev[1], st));
     hipLaunchKernelGGL(k_vis_erode, dim3((unsigned)L, (unsigned)((HW + 255) / 256)), dim3(256), 0, st, (const unsigned *)v->d_raw, (unsigned *)v->d_img, c.W, c.H);
     VIS_HIP(hipEventRecord(v->ev[2], st));
-    if (tile > 0)
-        hipLaunchKernelGGL(k_vis_vote, dim3((unsigned)tile), dim3(256), 0, st, (const float4 *)kf->pool, d_seg, (int)segs.size(), (const double *)(d_blob + at_pose),
+    if (tiles.next > 0)
+        hipLaunchKernelGGL(k_vis_vote, dim3((unsigned)tiles.next), dim3(256), 0, st, (const float4 *)kf->pool, d_seg, (int)segs.size(), (const double *)(d_blob + at_pose),
                            (const int *)(d_blob + at_start), (const int *)(d_blob + at_obs), c, (const float *)v->d_img, v->d_cnt);
     VIS_HIP(hipEventRecord(v->ev[3], st));
     VIS_HIP(hipGetLastError());
     VIS_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < 3; ++k) { float ms = 0.0f; if (hipEventElapsedTime(&ms, v->ev[k], v->ev[k + 1]) == hipSuccess) v->ms[k] = (double)ms; }
+    for (int k = 0; k < 3; ++k) v->ms[k] = ll_event_ms(v->ev[k], v->ev[k + 1], v->ms[k]);
     return LL_OK;
 }
 
