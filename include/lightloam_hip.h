@@ -1041,6 +1041,66 @@ int  ll_bev_reset(ll_bev *b);
 int  ll_bev_timing(const ll_bev *b, double *ms /* prepare, score, peak */, long long *counts /* ops, listed points, hypotheses */);
 int  ll_bev_guess(const double *Pc_w7, const double *D_w7, const double *Pq_w7, double *T0_w7);
 
+/* ---------------------------------------------------------------- entropy: how crisp is the cloud of these frames under these poses?
+ * Ground truth free: a trajectory that lays the same wall down twice, 20 cm apart, makes thick point neighbourhoods, the corrected
+ * one thin ones.  Mean map entropy (Droeschel, Stueckler & Behnke, ICRA 2014; Razlaw, Droeschel, Holz & Behnke, 2015) and mean plane
+ * variance from the covariance of every point's fixed-radius neighbourhood -- not part of the reference -- over what an ll_keyframes
+ * store holds.  The cube maps cannot show this (a double wall inside one voxel becomes one centroid).  An ll_entropy belongs to ONE
+ * store (and its context).  WHAT IT IS NOT: it rewards any thinning, so compare trajectories over the same points only; thresholds on
+ * real data are the caller's.
+ * AN OP is (n_frames, frames, poses_w7) as an ll_visibility_op.  Its cloud is every corner and surf point of its listed frames, each
+ * w = pointAssociateToMap(P_frame, p) as ll_cubemaps_insert_keyframes has it (f64, each coordinate rounded to float once).  Ops are
+ * independent clouds: an id may occur once per op and in several ops (the same frames before and after a pose-graph solve, in one
+ * call).  Every listed frame has a list position k counted across the ops, as ll_visibility_images counts it.
+ * PER POINT q, in f32 with every operation rounded on its own:
+ *   cell = radius * 1.03125f;  c = floorf(w / cell) per coordinate;  q is OUTSIDE if a coordinate of w is not finite or a c is not in
+ *   -65536 .. 65535: nn = 0, h = pv = NaN, and it is nobody's neighbour;
+ *   the neighbours of q are all points p of the same op that are not outside, q included, with d = p - q per coordinate and
+ *   d2 = (dx*dx + dy*dy) + dz*dz <= radius * radius;
+ *   over them, in f64 from those f32 d:  n,  S1 = sum d,  S2 = sum d d^T (products in f64: exact), in the order: cell rows dz, then
+ *   dy ascending, a row's cells by x, a cell's points in list order;
+ *   Sigma = S2 / n - (S1 / n)(S1 / n)^T entry by entry; its eigenvalues l0 <= l1 <= l2 by a cyclic Jacobi of 8 sweeps in f64;
+ *   n >= min_neighbours: VALID, pv = (float)max(l0, 0), h = (float)(0.5 * (3 ln(2 pi e) + ln max(l0, f) + ln max(l1, f) + ln max(l2, f))),
+ *   f = (double)lambda_floor;  otherwise SPARSE: nn set, h = pv = NaN.  nn is read as uint16 saturating at 65535.
+ * PER OP an ll_entropy_rec: n_points = n_valid + n_sparse + n_outside;  n_pairs = the sum of the unsaturated nn of valid and sparse
+ * points;  sum_h, sum_pv = f64 sums of the STORED f32 values of the valid points, in a fixed shape: per 1024-point tile of a (frame,
+ * type) cloud thread t of 256 adds points t, t + 256, t + 512, t + 768 in that order from 0.0 and the 256 partials fold by halves
+ * (t += t + 128, t += t + 64, ...); then the op's tiles in list order from 0.0;  mme = sum_h / n_valid, mpv = sum_pv / n_valid (0 when
+ * n_valid is 0).  Nothing atomic, every sum in a fixed order: a point's values and an op's record are the same bits alone, in any
+ * batch and at any op position.
+ *   ll_entropy_default_params  radius 0.5, min_neighbours 6, lambda_floor 1e-6 (1 mm sigma), max_points 2^20
+ *   ll_entropy_create     radius in (0, 8] (its f32 square at least 2^-100), min_neighbours >= 4 (fewer points have a singular
+ *                         covariance), lambda_floor > 0 and finite, max_points in 1 .. 2^27 (LL_ERR_ARG otherwise,
+ *                         ll_keyframes_last_error of the store).  The workspace, about 200 bytes per point, is sized from
+ *                         max_points here and never grows.  Destroy it before its store.
+ *   ll_entropy_run        at most 1024 ops; rec [n_ops].  The host builds the cloud table from the store's table; one upload and
+ *                         keys, the stable sort by cell, heads + scan + cells, rows, moments, tile sums, op sums.  Host
+ *                         synchronisations, whatever the numbers of ops and frames: TWO (the occupied-cell count that sizes the per-cell
+ *                         launches; the records), plus the sort's read-back above 65536 points; ll_entropy_timing counts them.  A call
+ *                         without a point launches nothing.
+ *   ll_entropy_values     h, pv, nn [n_corner + n_surf] of the k-th listed frame of the LAST run, corner first; each may be NULL; one
+ *                         synchronisation
+ *   ll_entropy_reset      the last run forgotten; the object follows the store again after ll_keyframes_reset
+ *   ll_entropy_timing     the last run: ms = keys, sort + cells, rows, moments, sums (device events); counts = listed frames, their
+ *                         points, occupied cells, neighbour pairs, host synchronisations
+ * After ll_keyframes_reset run and values return LL_ERR_STATE until ll_entropy_reset.  Errors, all decided before anything is enqueued;
+ * a refused call leaves the last run's values readable and unchanged: LL_ERR_ARG for a NULL handle, ops or rec, n_ops < 1, n_frames < 0,
+ * frames NULL with frames to read, an id outside the store, an id twice in one op, a non-finite pose (given or stored), a k the last
+ * run did not have; LL_ERR_CAPACITY for more than 1024 ops or more listed points than max_points; LL_ERR_HIP as elsewhere.          */
+typedef struct ll_entropy ll_entropy;
+typedef struct { float radius; int min_neighbours; float lambda_floor; long long max_points; } ll_entropy_params;
+typedef struct { int n_frames; const int *frames; const double *poses_w7 /* [n_frames][7], NULL: the stored poses */; } ll_entropy_op;
+typedef struct { long long n_points, n_valid, n_sparse, n_outside, n_pairs; double sum_h, sum_pv, mme, mpv; } ll_entropy_rec;
+void ll_entropy_default_params(ll_entropy_params *p);
+int  ll_entropy_create(ll_keyframes *kf, const ll_entropy_params *p, ll_entropy **out);
+void ll_entropy_destroy(ll_entropy *en);
+const char *ll_entropy_last_error(const ll_entropy *en);
+int  ll_entropy_run(ll_entropy *en, const ll_entropy_op *ops, int n_ops, ll_entropy_rec *rec /* [n_ops] */);
+int  ll_entropy_values(ll_entropy *en, int k, float *h, float *pv, unsigned short *nn /* [n_corner + n_surf] each, each may be NULL */);
+int  ll_entropy_reset(ll_entropy *en);
+int  ll_entropy_timing(const ll_entropy *en, double *ms /* [5] keys, sort + cells, rows, moments, sums */,
+                       long long *counts /* [5] frames, points, occupied cells, neighbour pairs, synchronisations */);
+
 /* ---------------------------------------------------------------- drives: capture while driving, and take a correction
  * ll_drives_set_keyframes(d, kf, every): from the next step on, at the end of a step every lane that ran a frame -- mapping or
  * localising -- whose per-lane frame index (0 at START) is a multiple of every (>= 1) is captured into kf: its stack clouds and its

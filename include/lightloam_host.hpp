@@ -540,6 +540,55 @@ private:
     std::vector<int> n_yaws_;
 };
 
+/* Entropy (ll_entropy): mean map entropy and mean plane variance of the cloud that listed frames of a Keyframes store make under
+ * listed poses -- the same frames before and after a pose-graph solve in one call.  It rewards any thinning: compare trajectories
+ * over the same points only.  Destroy it before its store. */
+class Entropy {
+public:
+    struct Values { std::vector<float> h, pv; std::vector<unsigned short> nn; };   /* [n_corner + n_surf], corner first */
+    static ll_entropy_params default_params() { ll_entropy_params p; ll_entropy_default_params(&p); return p; }
+    explicit Entropy(Keyframes &kf) : Entropy(kf, default_params()) {}
+    Entropy(Keyframes &kf, const ll_entropy_params &p) : kf_(&kf), p_(p) {
+        const int rc = ll_entropy_create(kf.get(), &p, &e_);
+        if (rc != LL_OK) throw Error(rc, ll_keyframes_last_error(kf.get()));
+    }
+    ~Entropy() { ll_entropy_destroy(e_); }
+    Entropy(const Entropy &) = delete;
+    Entropy &operator=(const Entropy &) = delete;
+
+    /* one record per op; two synchronisations (and the sort's read-back above 65536 points) whatever ops.size() is */
+    std::vector<ll_entropy_rec> run(const std::vector<ll_entropy_op> &ops) {
+        std::vector<ll_entropy_rec> rec(ops.size());
+        check(ll_entropy_run(e_, ops.data(), (int)ops.size(), rec.data()));
+        sizes_.clear();
+        for (size_t i = 0; i < ops.size(); ++i)
+            for (int f = 0; f < ops[i].n_frames; ++f) {
+                const ll_keyframe_info e = kf_->info(ops[i].frames[f]);
+                sizes_.push_back((size_t)e.n[0] + (size_t)e.n[1]);
+            }
+        return rec;
+    }
+    /* the k-th listed frame, counted across ops, of the last run */
+    Values values(int k) {
+        const size_t n = k >= 0 && (size_t)k < sizes_.size() ? sizes_[k] : 0;
+        Values v;
+        v.h.assign(n + 1, 0.0f); v.pv.assign(n + 1, 0.0f); v.nn.assign(n + 1, 0);
+        check(ll_entropy_values(e_, k, v.h.data(), v.pv.data(), v.nn.data()));
+        v.h.resize(n); v.pv.resize(n); v.nn.resize(n);
+        return v;
+    }
+    void reset() { check(ll_entropy_reset(e_)); sizes_.clear(); }
+    void timing(double ms[5], long long counts[5]) const { check(ll_entropy_timing(e_, ms, counts)); }
+    const ll_entropy_params &params() const { return p_; }
+    ll_entropy *get() const { return e_; }
+private:
+    void check(int rc) const { if (rc != LL_OK) throw Error(rc, ll_entropy_last_error(e_)); }
+    Keyframes *kf_;
+    ll_entropy_params p_;
+    ll_entropy *e_ = nullptr;
+    std::vector<size_t> sizes_;
+};
+
 struct MapLayout {
     enum { N_COUNTS = 2 * 4851 };
     int cen[3] = {10, 10, 5};

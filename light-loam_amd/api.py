@@ -62,6 +62,8 @@ EXPORTS = [
     "ll_visibility_counts", "ll_visibility_images", "ll_visibility_reset", "ll_visibility_timing", "ll_cubemaps_insert_keyframes_filtered",
     "ll_bev_default_params", "ll_bev_create", "ll_bev_destroy", "ll_bev_last_error", "ll_bev_match", "ll_bev_volume", "ll_bev_grid", "ll_bev_reset",
     "ll_bev_timing", "ll_bev_guess",
+    "ll_entropy_default_params", "ll_entropy_create", "ll_entropy_destroy", "ll_entropy_last_error", "ll_entropy_run", "ll_entropy_values",
+    "ll_entropy_reset", "ll_entropy_timing",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -159,6 +161,23 @@ class BevResult(C.Structure):
     query points with a layer, the yaw and D_w7 with p_target ~ D p_query"""
     _fields_ = [("score", C.c_int), ("second", C.c_int), ("iyaw", C.c_int), ("sx", C.c_int), ("sy", C.c_int), ("n_query", C.c_int), ("yaw", C.c_double),
                 ("D_w7", C.c_double * 7)]
+
+
+class EntropyParams(C.Structure):
+    """ll_entropy_params: the neighbourhood (radius, at least min_neighbours points), the floor under an eigenvalue inside the
+    logarithm, and how many points one run may list"""
+    _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_int), ("lambda_floor", C.c_float), ("max_points", C.c_longlong)]
+
+
+class EntropyOp(C.Structure):
+    """ll_entropy_op: the cloud of the listed frames, frame k under poses_w7[k] (NULL: its stored pose)"""
+    _fields_ = [("n_frames", C.c_int), ("frames", C.c_void_p), ("poses_w7", C.c_void_p)]
+
+
+class EntropyRec(C.Structure):
+    """ll_entropy_rec: an op's points by kind, the neighbour pairs, the sums of the stored h and pv of the valid points, their means"""
+    _fields_ = [("n_points", C.c_longlong), ("n_valid", C.c_longlong), ("n_sparse", C.c_longlong), ("n_outside", C.c_longlong),
+                ("n_pairs", C.c_longlong), ("sum_h", C.c_double), ("sum_pv", C.c_double), ("mme", C.c_double), ("mpv", C.c_double)]
 
 
 class SeqLayout(C.Structure):
@@ -310,6 +329,17 @@ def load_library():
         _lib.ll_bev_reset.argtypes = [C.c_void_p]
         _lib.ll_bev_timing.argtypes = [C.c_void_p] * 3
         _lib.ll_bev_guess.argtypes = [C.c_void_p] * 4
+        _lib.ll_entropy_default_params.restype = None
+        _lib.ll_entropy_default_params.argtypes = [C.c_void_p]
+        _lib.ll_entropy_create.argtypes = [C.c_void_p] * 3
+        _lib.ll_entropy_destroy.restype = None
+        _lib.ll_entropy_destroy.argtypes = [C.c_void_p]
+        _lib.ll_entropy_last_error.restype = C.c_char_p
+        _lib.ll_entropy_last_error.argtypes = [C.c_void_p]
+        _lib.ll_entropy_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_entropy_values.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.ll_entropy_reset.argtypes = [C.c_void_p]
+        _lib.ll_entropy_timing.argtypes = [C.c_void_p] * 3
         _lib.ll_cubemaps_insert_keyframes_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     return _lib
 
@@ -723,6 +753,10 @@ class Context:
     def bev(self, kf, **params):
         """a Bev object over the Keyframes store kf (ll_bev_create); params: fields of bev_params()"""
         return Bev(self, kf, **params)
+
+    def entropy(self, kf, **params):
+        """an Entropy object over the Keyframes store kf (ll_entropy_create); params: fields of entropy_params()"""
+        return Entropy(self, kf, **params)
 
     def algorithmic_bytes(self, first=0, count=1):
         b = [C.c_double(0) for _ in range(4)]
@@ -1605,6 +1639,96 @@ class Bev:
         """the last match: ((prepare ms, score ms, peak ms), (ops, listed points, hypotheses))"""
         ms = np.zeros(3); cnt = np.zeros(3, np.int64)
         self._ck(self.lib.ll_bev_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
+        return tuple(ms), tuple(int(c) for c in cnt)
+
+
+def entropy_params(**kw):
+    """ll_entropy_default_params with the given fields replaced"""
+    p = EntropyParams()
+    load_library().ll_entropy_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+class Entropy:
+    """One ll_entropy over a Keyframes store: mean map entropy and mean plane variance of the cloud that listed frames make under
+    listed poses, from the covariance of every point's fixed-radius neighbourhood.  It rewards any thinning: compare trajectories over
+    the same points only"""
+
+    def __init__(self, ctx, kf, **params):
+        self.ctx = ctx; self.lib = ctx.lib; self.kf = kf
+        self.params = entropy_params(**params)
+        self.h = C.c_void_p()
+        self._sizes = []
+        rc = self.lib.ll_entropy_create(kf.h, C.byref(self.params), C.byref(self.h))
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_keyframes_last_error(kf.h).decode())
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ll_entropy_destroy(self.h)           # reads nothing of the store: the order in which a Context closes its children is free
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_entropy_last_error(self.h).decode())
+
+    def _live(self):
+        if not getattr(self, "h", None) or not getattr(self.kf, "h", None):
+            raise LightLoamError(-7, "the Entropy object or its Keyframes store is closed")
+
+    def run(self, ops):
+        """ops: a list of (frames, poses) -- the cloud of the listed frames (ids of the store, each at most once per op; the same id may
+        stand in several ops), frame k under poses[k] ([n, 7]; None: the stored poses) -> a list of EntropyRec, one per op.  Two
+        synchronisations, plus the sort's read-back above 65536 points"""
+        self._live()
+        rec = (EntropyOp * max(len(ops), 1))()
+        keep = []; sizes = []
+        for i, (frames, poses) in enumerate(ops):
+            f = np.ascontiguousarray(frames, np.int32).reshape(-1)
+            p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+            if p is not None and len(p) != len(f):
+                raise ValueError("poses must have one row per listed frame")
+            keep += [f, p]
+            rec[i].n_frames = len(f); rec[i].frames = f.ctypes.data
+            rec[i].poses_w7 = None if p is None else p.ctypes.data
+        out = (EntropyRec * max(len(ops), 1))()
+        self._ck(self.lib.ll_entropy_run(self.h, C.addressof(rec), len(ops), C.addressof(out)))
+        for i, (frames, _) in enumerate(ops):
+            sizes += [self.kf.info(int(f))["n"] for f in np.asarray(frames, np.int64).reshape(-1)]
+        self._sizes = sizes
+        return [out[i] for i in range(len(ops))]
+
+    def values(self, k):
+        """(h, pv, nn) of the k-th listed frame, counted across ops, of the last run: float32, float32, uint16 [n_corner + n_surf],
+        corner first; NaN where a point is sparse (nn < min_neighbours) or outside (nn == 0)"""
+        self._live()
+        n = sum(self._sizes[k]) if 0 <= int(k) < len(self._sizes) else 0
+        h = np.zeros(max(n, 1), np.float32); pv = np.zeros(max(n, 1), np.float32); nn = np.zeros(max(n, 1), np.uint16)
+        self._ck(self.lib.ll_entropy_values(self.h, int(k), h.ctypes.data, pv.ctypes.data, nn.ctypes.data))
+        return h[:n], pv[:n], nn[:n]
+
+    def reset(self):
+        """the last run forgotten; needed after Keyframes.reset before the object is used again"""
+        self._live()
+        self._ck(self.lib.ll_entropy_reset(self.h))
+        self._sizes = []
+
+    def timing(self):
+        """the last run: ((keys, sort + cells, rows, moments, sums) ms, (listed frames, their points, occupied cells, neighbour pairs,
+        host synchronisations))"""
+        ms = np.zeros(5); cnt = np.zeros(5, np.int64)
+        self._ck(self.lib.ll_entropy_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
         return tuple(ms), tuple(int(c) for c in cnt)
 
 
