@@ -44,7 +44,12 @@ __device__ __forceinline__ bool ll_xcd_map2(int id, int per_scan, int count, int
 #define LL_FWAVES_SPLIT 7     /* workgroups per CU (= waves per SIMD) of the 9-row instantiation: 66 registers, no scratch, 19-22 KB of LDS.  Six are
                                * 4 % slower, eight (64 registers, fits at the S64 capacity) 3 % slower: DESIGN.md 14.7 */
 #endif
-#define LL_NLIST 176      /* per segment slots: sharp[6][2] lsharp[6][20] flat[6][4] + counters[6][3] */
+#ifndef LL_RUN_LANES
+#define LL_RUN_LANES 1        /* an open voxel run is continued through the registers of this many following lanes of its wave before it
+                               * goes to memory for the rest.  1: the next lane only, by the DPP shift.  8 (lanes +2 .. +8 by ds_bpermute) was
+                               * measured 0.08 ms SLOWER per 16384 S64 scans (14.11 against 14.03 ms, docs/rounds/r09.md): not the default */
+#endif
+#define LL_NLIST 176     /* per segment slots: sharp[6][2] lsharp[6][20] flat[6][4] + counters[6][3] */
 
 struct FeatLds {
     unsigned *k32;             /* [mr] sort key (voxel index) */
@@ -305,6 +310,32 @@ __device__ __forceinline__ void ll_ring_features_ring(const LLView &V, int s, in
     FeatLds L = ll_carve(ll_smem, ring_hi);
     float *fs = (float *)(L.sc + 32);                                 /* 24 floats: per-wave bounds */
     LL_PHASE_BEGIN();
+    /* The ring's points are requested FIRST: which ones depends on (off, nr) only, and this is the workgroup's longest memory trip --
+     * the lists, the bitmap's LDS atomics and both of their barriers are built while the points travel (they used to stand in front).
+     * The segment points go to the sort as they lie, in the sort's own (wave, row, lane) order -- coalesced rows, no compaction
+     * scan, no trip through LDS: a less-sharp pick (not less-flat, :361-367) just carries the all-ones key that the padding
+     * of the last row carries and ends up behind the m real records. */
+    /* Record g IS the ring's point g (local index): the five points in front of the first segment are records that never become
+     * less-flat.  A wave's load instruction then covers 64 points from a multiple of 64 = eight whole 128-byte lines; with the
+     * records starting at the first segment point (80 bytes into a line) every instruction straddled a ninth line that the next
+     * one asked for again -- and this chip's L2 sends EVERY request for a line that is still on its way across the fabric
+     * (profiles/r05_fetch_granule.txt): 14 % more lines fetched than the ring has. */
+    const int nrec = Lseg + 5;
+    const int nrows_w = active ? (nrec + LL_BLOCK - 1) / LL_BLOCK : 0;       /* rows per wave, uniform; a ring without a segment loads nothing */
+    const int wbase = __builtin_amdgcn_readfirstlane(tid >> 6) * nrows_w * 64;
+    float px[ROWS], py[ROWS], pz[ROWS];
+    /* The header's vector loads (the earlier rings' counts, this ring's lists: predicated, requested with the header) land HERE, once:
+     * left in flight behind the ring's loads, the lists' first use below waited for every point of the ring (their number is not known
+     * to the wait-count pass), and each later reuse of their registers again. */
+    __builtin_amdgcn_s_waitcnt(0x0f70);                                      /* vmcnt(0) */
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) {
+        const int g = wbase + k * 64 + lane;
+        if (k < nrows_w && g >= 5 && g < nrec) {
+            const float4 p = cloud[off + g];
+            px[k] = p.x; py[k] = p.y; pz[k] = p.z;
+        }
+    }
     /* the pick's lists of this ring: local indices + per-segment counts -> L.lists; the less-sharp picks (label 1 / 2) -> bitmap:
      * less-flat = every segment point that is not one of them (:361-367) */
     if (tid < 174) L.lists[tid] = (int)rec_v;
@@ -349,28 +380,6 @@ __device__ __forceinline__ void ll_ring_features_ring(const LLView &V, int s, in
         int m = 0;
         bool sorted_ok = false;
         {
-            /* The segment points go to the sort as they lie, in the sort's own (wave, row, lane) order -- coalesced rows, no compaction
-             * scan, no trip through LDS: a less-sharp pick (not less-flat, :361-367) just carries the all-ones key that the padding
-             * of the last row carries and ends up behind the m real records. */
-            /* Record g IS the ring's point g (local index): the five points in front of the first segment are records that never become
-             * less-flat.  A wave's load instruction then covers 64 points from a multiple of 64 = eight whole 128-byte lines; with the
-             * records starting at the first segment point (80 bytes into a line) every instruction straddled a ninth line that the next
-             * one asked for again -- and this chip's L2 sends EVERY request for a line that is still on its way across the fabric
-             * (profiles/r05_fetch_granule.txt): 14 % more lines fetched than the ring has. */
-            const int nrec = Lseg + 5;
-            const int nrows_w = (nrec + LL_BLOCK - 1) / LL_BLOCK;                   /* rows per wave, uniform */
-            const int wbase = __builtin_amdgcn_readfirstlane(tid >> 6) * nrows_w * 64;
-            float px[ROWS], py[ROWS], pz[ROWS];
-            unsigned mem = 0;                                                        /* bit k: record wbase + k * 64 + lane is less-flat */
-#pragma unroll
-            for (int k = 0; k < ROWS; ++k) {
-                const int g = wbase + k * 64 + lane;
-                if (k < nrows_w && g >= 5 && g < nrec) {
-                    const float4 p = cloud[off + g];
-                    px[k] = p.x; py[k] = p.y; pz[k] = p.z;
-                    if (!ll_bit(L.picked, g)) mem |= 1u << k;
-                }
-            }
             /* The picked points of the three small lists are fetched HERE, behind the row's own loads: their lines are on their way into the
              * L2 (every pick is a segment point) -- at the end of the workgroup, ~20 us later, half of them had left it again and came
              * over the fabric a third time.  Entry t of each list belongs to thread t from here to its store: parked in LDS meanwhile. */
@@ -381,6 +390,15 @@ __device__ __forceinline__ void ll_ring_features_ring(const LLView &V, int s, in
             if (hv0) q0 = cloud[off + L.lists[tid]];
             if (hv1) q1 = cloud[off + L.lists[12 + tid]];
             if (hv2) q2 = cloud[off + L.lists[132 + tid]];
+            unsigned mem = 0;                                                        /* bit k: record wbase + k * 64 + lane is less-flat */
+#pragma unroll
+            for (int k = 0; k < ROWS; ++k) {
+                const int g = wbase + k * 64 + lane;
+                if (k < nrows_w && g >= 5 && g < nrec && !ll_bit(L.picked, g)) mem |= 1u << k;
+            }
+            /* One unconditional wait where the points are first used: behind predicated loads the wait-count pass otherwise waits
+             * inside each block that uses a row and counts the row's registers as in flight at the joins (r08.md 8.1). */
+            __builtin_amdgcn_s_waitcnt(0x0f70);                                      /* vmcnt(0) */
             float mnx = INFINITY, mny = INFINITY, mnz = INFINITY, mxx = -INFINITY, mxy = -INFINITY, mxz = -INFINITY;
 #pragma unroll
             for (int k = 0; k < ROWS; ++k)
@@ -535,6 +553,27 @@ __device__ __forceinline__ void ll_ring_features_ring(const LLView &V, int s, in
                         if (cn && u < c_n) { sx += qx; sy += qy; sz += qz; si += qw; ++cn; }
                     }
 #undef LL_SHL1
+                /* A run that took ALL of a full next lane goes on through lanes +2, +3, ... of its wave: their leading points are in
+                 * registers too and come over by ds_bpermute, in sorted order, up to the first lane that has a run head.  The loop is
+                 * wave-uniform and ends as soon as no lane has a run to continue; past LL_RUN_LANES lanes, or the wave, memory (below). */
+                int taken = c_n;                                                    /* points of the open run consumed beyond b1 */
+                bool go = cn && lane < 63 && hm_n == 0u && cnt_n == perm;
+#pragma unroll 1
+                for (int d = 2; d <= LL_RUN_LANES && __any(go); ++d) {
+                    const int src = lane + d;
+                    const unsigned hm_d = (unsigned)__shfl((int)headm, src);
+                    const int cnt_d = __shfl(b1 - b0, src);
+                    go = go && src < 64;
+                    const int c_d = go ? (hm_d ? __ffs((int)hm_d) - 1 : cnt_d) : 0;
+#pragma unroll
+                    for (int u = 0; u < ROWS; ++u)
+                        if (u < perm) {
+                            const float qx = __shfl(pt[u].x, src), qy = __shfl(pt[u].y, src), qz = __shfl(pt[u].z, src), qw = __shfl(pt[u].w, src);
+                            if (u < c_d) { sx += qx; sy += qy; sz += qz; si += qw; ++cn; }
+                        }
+                    taken += c_d;
+                    go = go && hm_d == 0u && cnt_d == perm;
+                }
                 /* the centroids of the runs that ended inside the range leave now, in voxel order, for the ring's own row (:376: lessFlatScanDS
                  * appended ring after ring): their registers are free for the points the open run still has to fetch */
 #pragma unroll
@@ -546,7 +585,7 @@ __device__ __forceinline__ void ll_ring_features_ring(const LLView &V, int s, in
                      * that sweeps the ground close to the sensor puts ten points into a voxel, its runs span several threads, and the
                      * workgroup waited at the next barrier for the longest of these chains: a fifth of its time.) */
                     const unsigned vid = L.k32[b1 - 1];
-                    for (int e = b1 + c_n; e < m; e += 4) {
+                    for (int e = b1 + taken; e < m; e += 4) {
                         unsigned kk[4]; int ii[4];
 #pragma unroll
                         for (int u = 0; u < 4; ++u) { kk[u] = (e + u < m) ? L.k32[e + u] : ~vid; ii[u] = (e + u < m) ? (int)L.k16[e + u] : 0; }
