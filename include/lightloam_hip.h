@@ -1333,6 +1333,80 @@ int  ll_posegraphs_cov_timing(ll_posegraphs *pg, double ms2[2], long long counts
 int  ll_pg_edge_gate(const double *Pa_w7, const double *Pb_w7, const double *Z_w7, const double *S36, const double joint144[144],
                      double *chi2, double cov36[36]);
 
+/* ---------------------------------------------------------------- pcm: pairwise-consistent sets of loop-closure candidates
+ * A revisit yields tens to thousands of candidate loop edges, some from look-alike places.  ll_pcm keeps a large mutually consistent set
+ * of them BEFORE any enters a graph: pairwise consistency maximisation (Mangelson, Dominic, Eustice & Vasudevan, ICRA 2018) in the
+ * threshold form of Kimera-RPGO's PcmSimple -- not part of the reference.  Two candidates are consistent if the cycle through both and
+ * the trajectory between their endpoints closes.  Order of use: ll_pcm over all candidates, then ll_pg_edge_gate or a Huber width on the
+ * survivors.  WHAT IT IS NOT: thresholds, not a Mahalanobis test (the measured information of ll_pose_info is not used); a greedy
+ * clique, not the maximum one; and the nodes must be in trajectory order for L, below, to mean path length.  The default thresholds are
+ * conventions (twice a 1 % drift), not measurements: thresholds on real data are the caller's.
+ * A GRAPH of a call is N poses P in pose_w7, in trajectory order, and C <= 4096 candidates (i, j, Z_w7), Z measuring P_i^-1 P_j, i and j
+ * local to the graph.  Only the poses are used, no edges.  The layout of a call is that of ll_posegraphs_*: node_off and cand_off have
+ * n_graphs + 1 ascending entries from 0.
+ * THE HOST, in plain f64 C before the upload: every quaternion (poses and Z) normalised, n = sqrt((x*x + y*y) + (z*z + w*w)), each
+ * component / n;  the path length per graph, s[0] = 0, s[n+1] = s[n] + sqrt((dx*dx + dy*dy) + dz*dz) of the translations.
+ * FROM THERE only + - * and comparisons in f64, every operation rounded on its own (ll_pcm_math.h is the text, shared by the kernels
+ * and ll_pcm_host), so a decision has no sqrt and no division in it:
+ *   a (x) b, quaternions (x, y, z, w):  x = aw*bx + ax*bw + ay*bz - az*by;  y = aw*by - ax*bz + ay*bw + az*bx;
+ *                                       z = aw*bz + ax*by - ay*bx + az*bw;  w = aw*bw - ax*bx - ay*by - az*bz   (sums left to right)
+ *   R(q) v:  r00 = 1 - 2*(y*y + z*z), r01 = 2*(x*y - z*w), r02 = 2*(x*z + y*w);  r10 = 2*(x*y + z*w), r11 = 1 - 2*(x*x + z*z),
+ *            r12 = 2*(y*z - x*w);  r20 = 2*(x*z - y*w), r21 = 2*(y*z + x*w), r22 = 1 - 2*(x*x + y*y);  row k = (rk0*v0 + rk1*v1) + rk2*v2
+ *   a o b = (q_a (x) q_b, R(q_a) t_b + t_a);   inv(a) = (q_a*, -(R(q_a*) t_a)),  q* = (-x, -y, -z, w)
+ *   per candidate c:   B_c = Z_c o inv(P_jc);   Ai_c = (P_jc o inv(Z_c)) o inv(P_ic)
+ *   per unordered pair, always evaluated as (c, d) with c < d:   E = (B_c o Ai_d) o P_ic  -- the cycle Z_c X(jc, jd) Z_d^-1 X(id, ic) in
+ *   the body frame of i_c (the world-frame form Ai_d^-1 Ai_c would carry a lever arm of the world coordinates in its translation);
+ *   rot2 = 4*((vx*vx + vy*vy) + vz*vz) of vec(q_E);  trans2 = (tx*tx + ty*ty) + tz*tz;  L = |s[ic] - s[id]| + |s[jc] - s[jd]|;
+ *   ar = rot_tol + rot_rate*L;  at = trans_tol + trans_rate*L;
+ *   CONSISTENT iff rot2 <= ar*ar && trans2 <= at*at and rot2, trans2, ar*ar, at*at are all finite (x - x == 0): huge finite inputs make
+ *   an inconsistent pair, never a NaN decision.  The adjacency is symmetric by construction, its diagonal zero.
+ * THE SELECTION, a deterministic greedy clique (Pattabiraman et al.'s heuristic as PCM uses it, every start tried): deg[c] = the
+ * consistent partners of c;  the order is (deg descending, index ascending);  for every start v: M = {v}, U = N(v); while U is not
+ * empty, u = the member of U earliest in the order, M += u, U = U & N(u);  the winner is the largest M, ties to the start earliest in the
+ * order.  selected[c] = membership of the winner.  C == 0: nothing selected, start = -1; an isolated best gives a clique of 1 -- what
+ * size means "confirmed" is the caller's.  An implementation may skip starts that cannot win; that changes work, never the result.
+ * A BIT MATRIX of a graph is C rows of ceil(C / 64) 64-bit words, bit d % 64 of word d / 64 of row c standing for (c, d), in original
+ * candidate order; the matrices of a call lie back to back.
+ *   ll_pcm_default_params  rot_tol 0.05 rad, trans_tol 0.5 m, rot_rate 2e-4 rad/m, trans_rate 0.02
+ *   ll_pcm_create      buffers for calls of at most max_graphs (1 .. 65535) graphs with max_nodes_total nodes and max_candidates_total
+ *                      candidates in all (about 270 B per candidate); LL_ERR_ARG otherwise (ll_last_error(ctx)).  The bit matrices (16 B
+ *                      per word of a call) are allocated at the first call and grown on demand.  Destroy it before its context.
+ *   ll_pcm_run         selected [cands] (1: in the winner), degree [cands] (may be NULL), rec [n_graphs] (may be NULL); params NULL: the
+ *                      defaults.  One upload, seven launches and a small clear whatever the number of graphs, ONE synchronisation.
+ *   ll_pcm_select      the selection alone on caller-supplied bit matrices: for direct tests and for callers with a consistency test of
+ *                      their own (as ll_posegraphs_chain_solve serves the chain solver)
+ *   ll_pcm_adjacency   the bit matrix of one graph of the last run (or select) in original candidate order; one synchronisation;
+ *                      LL_ERR_STATE before any call
+ *   ll_pcm_timing      the last call: ms[5] = prepare, adjacency, order (degrees, ranks, the matrix in rank order), clique, pick (device
+ *                      events; the first two are 0 after a select); counts[4] = graphs, candidates, pairs evaluated (C*C per graph: both
+ *                      triangles), clique steps taken.  Either may be NULL.
+ *   ll_pcm_host        one graph entirely on the host, needs no device: words_out (may be NULL), selected, degree (may be NULL), rec (may
+ *                      be NULL) as ll_pcm_run gives them, bit for bit
+ * A graph's matrix, selection, degrees and record have the same bits alone, in any batch and at any position: every index is relative
+ * to the graph, the only atomics are integer, and none of them reaches a result.  Errors are decided on the host before anything is
+ * enqueued and leave the outputs untouched; ll_pcm_last_error names the graph and the candidate.  LL_ERR_ARG: a NULL pointer, offsets
+ * that do not ascend from 0, i or j outside the graph, i == j, a non-finite pose, Z or parameter, a negative parameter, a zero
+ * quaternion; for select a matrix that is not symmetric, has a diagonal bit or a bit at or beyond C.  LL_ERR_CAPACITY: more than 4096
+ * candidates in one graph, a call beyond a create-time total.  LL_ERR_HIP: the bit matrices could not be allocated.  n_graphs == 0 or
+ * no candidate at all is LL_OK and launches nothing.                                                                              */
+typedef struct ll_pcm ll_pcm;
+typedef struct { double rot_tol, trans_tol, rot_rate, trans_rate; } ll_pcm_params;
+typedef struct { int i, j; double Z_w7[7]; } ll_pcm_candidate;        /* i, j local to the graph */
+typedef struct { int n_candidates, n_selected, start /* original index, -1: none */, max_degree; long long n_consistent_pairs; } ll_pcm_record;
+void ll_pcm_default_params(ll_pcm_params *p);
+int  ll_pcm_create(ll_ctx *ctx, int max_graphs, int max_nodes_total, int max_candidates_total, ll_pcm **out);
+void ll_pcm_destroy(ll_pcm *pcm);
+const char *ll_pcm_last_error(const ll_pcm *pcm);
+int  ll_pcm_run(ll_pcm *pcm, int n_graphs, const int *node_off, const int *cand_off, const double *poses_w7,
+                const ll_pcm_candidate *candidates, const ll_pcm_params *params, unsigned char *selected /* [cands] */,
+                int *degree /* [cands], may be NULL */, ll_pcm_record *rec /* [n_graphs], may be NULL */);
+int  ll_pcm_select(ll_pcm *pcm, int n_graphs, const int *cand_off, const unsigned long long *words, unsigned char *selected,
+                   int *degree, ll_pcm_record *rec);
+int  ll_pcm_adjacency(ll_pcm *pcm, int graph, unsigned long long *words_out);
+int  ll_pcm_timing(const ll_pcm *pcm, double *ms /* [5] */, long long *counts /* [4] */);
+int  ll_pcm_host(int n_nodes, const double *poses_w7, int n_candidates, const ll_pcm_candidate *candidates, const ll_pcm_params *params,
+                 unsigned long long *words_out, unsigned char *selected, int *degree, ll_pcm_record *rec);
+
 /* ---------------------------------------------------------------- whole hot path
  * One pass: extract + associate + vote + normal equations + one GN step for slots [first, first+count),
  * everything device-resident, no host synchronisation inside.  `vote_enable` as above.                   */

@@ -1256,6 +1256,97 @@ private:
     std::vector<unsigned char> fixed_;
 };
 
+/* Pcm (ll_pcm): the pairwise-consistent set of loop-closure candidates of many graphs side by side -- over ALL candidates of a revisit,
+ * before the gate or a Huber width see the survivors.  A Graph holds poses [N][7] in trajectory order and candidates whose i, j index
+ * its own poses and whose Z measures P_i^-1 P_j.  Thresholds, not a Mahalanobis test; a greedy clique, not the maximum one.  Destroy it
+ * before its Context. */
+class Pcm {
+public:
+    struct Graph { std::vector<double> poses; std::vector<ll_pcm_candidate> candidates; };
+    struct Result { std::vector<std::vector<unsigned char>> selected; std::vector<std::vector<int>> degree; std::vector<ll_pcm_record> rec; };
+    Pcm(Context &c, int max_graphs, int max_nodes_total, int max_candidates_total) {
+        c.check(ll_pcm_create(c.get(), max_graphs, max_nodes_total, max_candidates_total, &p_));
+    }
+    ~Pcm() { ll_pcm_destroy(p_); }
+    Pcm(const Pcm &) = delete;
+    Pcm &operator=(const Pcm &) = delete;
+
+    static ll_pcm_params default_params() { ll_pcm_params p; ll_pcm_default_params(&p); return p; }
+    static size_t words(size_t n_candidates) { return (n_candidates + 63) / 64; }
+    static ll_pcm_candidate candidate(int i, int j, const double Z[7]) {
+        ll_pcm_candidate c;
+        c.i = i; c.j = j;
+        for (int k = 0; k < 7; ++k) c.Z_w7[k] = Z[k];
+        return c;
+    }
+    /* a pose-graph edge is a candidate as it is */
+    static ll_pcm_candidate candidate(const ll_pg_edge &e) { return candidate(e.i, e.j, e.Z_w7); }
+    static ll_pcm_candidate candidate(const ll_pg_edge6 &e) { return candidate(e.i, e.j, e.Z_w7); }
+
+    /* ONE synchronisation whatever graphs.size() is */
+    Result run(const std::vector<Graph> &graphs, const ll_pcm_params *params = nullptr) {
+        std::vector<int> node_off(1, 0), cand_off(1, 0);
+        std::vector<double> poses; std::vector<ll_pcm_candidate> cands;
+        for (const Graph &g : graphs) {
+            poses.insert(poses.end(), g.poses.begin(), g.poses.end());
+            cands.insert(cands.end(), g.candidates.begin(), g.candidates.end());
+            node_off.push_back((int)(poses.size() / 7)); cand_off.push_back((int)cands.size());
+        }
+        std::vector<unsigned char> sel(cands.size() + 1); std::vector<int> deg(cands.size() + 1);
+        Result r; r.rec.resize(graphs.size());
+        check(ll_pcm_run(p_, (int)graphs.size(), node_off.data(), cand_off.data(), poses.data(), cands.data(), params, sel.data(), deg.data(), r.rec.data()));
+        split(cand_off, sel, deg, r);
+        return r;
+    }
+    /* the selection alone; matrices[g]: C rows of words(C) 64-bit words, bit d % 64 of word d / 64 of row c standing for (c, d) */
+    Result select(const std::vector<std::vector<unsigned long long>> &matrices, const std::vector<int> &n_candidates) {
+        std::vector<int> cand_off(1, 0);
+        std::vector<unsigned long long> all;
+        for (size_t g = 0; g < matrices.size(); ++g) {
+            if (matrices[g].size() != (size_t)n_candidates[g] * words((size_t)n_candidates[g])) throw Error(LL_ERR_ARG, "Pcm::select: a matrix of C rows has C * words(C) words");
+            all.insert(all.end(), matrices[g].begin(), matrices[g].end());
+            cand_off.push_back(cand_off.back() + n_candidates[g]);
+        }
+        std::vector<unsigned char> sel((size_t)cand_off.back() + 1); std::vector<int> deg((size_t)cand_off.back() + 1);
+        Result r; r.rec.resize(matrices.size());
+        check(ll_pcm_select(p_, (int)matrices.size(), cand_off.data(), all.data(), sel.data(), deg.data(), r.rec.data()));
+        split(cand_off, sel, deg, r);
+        return r;
+    }
+    /* the bit matrix of graph g of the last run or select, n_candidates rows in original order */
+    std::vector<unsigned long long> adjacency(int g, int n_candidates) {
+        std::vector<unsigned long long> w((size_t)n_candidates * words((size_t)n_candidates) + 1);
+        check(ll_pcm_adjacency(p_, g, w.data()));
+        w.pop_back();
+        return w;
+    }
+    void timing(double ms[5], long long counts[4]) const { check(ll_pcm_timing(p_, ms, counts)); }
+    /* one graph on the host, no device */
+    static int host(const Graph &g, const ll_pcm_params *params, std::vector<unsigned long long> *words_out, std::vector<unsigned char> &selected,
+                    std::vector<int> *degree, ll_pcm_record *rec) {
+        const size_t C = g.candidates.size();
+        selected.assign(C + 1, 0);
+        if (words_out) words_out->assign(C * words(C) + 1, 0ull);
+        if (degree) degree->assign(C + 1, 0);
+        const int rc = ll_pcm_host((int)(g.poses.size() / 7), g.poses.data(), (int)C, g.candidates.data(), params, words_out ? words_out->data() : nullptr,
+                                   selected.data(), degree ? degree->data() : nullptr, rec);
+        selected.resize(C);
+        if (words_out) words_out->pop_back();
+        if (degree) degree->resize(C);
+        return rc;
+    }
+    ll_pcm *get() const { return p_; }
+private:
+    void check(int rc) const { if (rc != LL_OK) throw Error(rc, ll_pcm_last_error(p_)); }
+    static void split(const std::vector<int> &off, const std::vector<unsigned char> &sel, const std::vector<int> &deg, Result &r) {
+        for (size_t g = 0; g + 1 < off.size(); ++g) {
+            r.selected.emplace_back(sel.begin() + off[g], sel.begin() + off[g + 1]);
+            r.degree.emplace_back(deg.begin() + off[g], deg.begin() + off[g + 1]);
+        }
+    }
+    ll_pcm *p_ = nullptr;
+};
+
 }  // namespace lightloam
 
 /* ------------------------------------------------------------------------------------------------------------------

@@ -64,6 +64,8 @@ EXPORTS = [
     "ll_bev_timing", "ll_bev_guess",
     "ll_entropy_default_params", "ll_entropy_create", "ll_entropy_destroy", "ll_entropy_last_error", "ll_entropy_run", "ll_entropy_values",
     "ll_entropy_reset", "ll_entropy_timing",
+    "ll_pcm_default_params", "ll_pcm_create", "ll_pcm_destroy", "ll_pcm_last_error", "ll_pcm_run", "ll_pcm_select", "ll_pcm_adjacency",
+    "ll_pcm_timing", "ll_pcm_host",
 ]
 
 MAP_NONE, MAP_SURROUND, MAP_ALL = -1, 0, 1
@@ -178,6 +180,19 @@ class EntropyRec(C.Structure):
     """ll_entropy_rec: an op's points by kind, the neighbour pairs, the sums of the stored h and pv of the valid points, their means"""
     _fields_ = [("n_points", C.c_longlong), ("n_valid", C.c_longlong), ("n_sparse", C.c_longlong), ("n_outside", C.c_longlong),
                 ("n_pairs", C.c_longlong), ("sum_h", C.c_double), ("sum_pv", C.c_double), ("mme", C.c_double), ("mpv", C.c_double)]
+
+
+class PcmParams(C.Structure):
+    """ll_pcm_params: a pair of candidates is consistent if its cycle closes within rot_tol + rot_rate * L radians and trans_tol +
+    trans_rate * L metres, L the path length between the two candidates' endpoints"""
+    _fields_ = [("rot_tol", C.c_double), ("trans_tol", C.c_double), ("rot_rate", C.c_double), ("trans_rate", C.c_double)]
+
+
+class PcmRecord(C.Structure):
+    """ll_pcm_record: a graph's candidates, the size of the selected set, the start it grew from (original index, -1: none), the largest
+    degree and the consistent pairs"""
+    _fields_ = [("n_candidates", C.c_int), ("n_selected", C.c_int), ("start", C.c_int), ("max_degree", C.c_int),
+                ("n_consistent_pairs", C.c_longlong)]
 
 
 class SeqLayout(C.Structure):
@@ -340,6 +355,18 @@ def load_library():
         _lib.ll_entropy_values.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.ll_entropy_reset.argtypes = [C.c_void_p]
         _lib.ll_entropy_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_pcm_default_params.restype = None
+        _lib.ll_pcm_default_params.argtypes = [C.c_void_p]
+        _lib.ll_pcm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.ll_pcm_destroy.restype = None
+        _lib.ll_pcm_destroy.argtypes = [C.c_void_p]
+        _lib.ll_pcm_last_error.restype = C.c_char_p
+        _lib.ll_pcm_last_error.argtypes = [C.c_void_p]
+        _lib.ll_pcm_run.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        _lib.ll_pcm_select.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        _lib.ll_pcm_adjacency.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.ll_pcm_timing.argtypes = [C.c_void_p] * 3
+        _lib.ll_pcm_host.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
         _lib.ll_cubemaps_insert_keyframes_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     return _lib
 
@@ -757,6 +784,10 @@ class Context:
     def entropy(self, kf, **params):
         """an Entropy object over the Keyframes store kf (ll_entropy_create); params: fields of entropy_params()"""
         return Entropy(self, kf, **params)
+
+    def pcm(self, max_graphs, max_nodes_total, max_candidates_total):
+        """a Pcm object on this context (ll_pcm_create): pairwise-consistent sets of loop-closure candidates"""
+        return Pcm(self, max_graphs, max_nodes_total, max_candidates_total)
 
     def algorithmic_bytes(self, first=0, count=1):
         b = [C.c_double(0) for _ in range(4)]
@@ -1730,6 +1761,157 @@ class Entropy:
         ms = np.zeros(5); cnt = np.zeros(5, np.int64)
         self._ck(self.lib.ll_entropy_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
         return tuple(ms), tuple(int(c) for c in cnt)
+
+
+PCM_CANDIDATE = np.dtype([("i", "i4"), ("j", "i4"), ("Z_w7", "f8", (7,))])       # ll_pcm_candidate as a numpy record
+PCM_MAX_CANDIDATES = 4096
+
+
+def pcm_params(**kw):
+    """ll_pcm_default_params (0.05 rad, 0.5 m, 2e-4 rad/m, 0.02: conventions, not measurements) with the given fields replaced"""
+    p = PcmParams()
+    load_library().ll_pcm_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def pcm_candidates(cands):
+    """a PCM_CANDIDATE record array from one, or from tuples starting with (i, j, Z[7], ...): a pose-graph edge tuple passes as it is"""
+    if isinstance(cands, np.ndarray) and cands.dtype == PCM_CANDIDATE:
+        return np.ascontiguousarray(cands).reshape(-1)
+    if isinstance(cands, np.ndarray) and cands.dtype in (PG_EDGE, PG_EDGE6):
+        out = np.zeros(len(cands), PCM_CANDIDATE)
+        out["i"] = cands["i"]; out["j"] = cands["j"]; out["Z_w7"] = cands["Z_w7"]
+        return out
+    out = np.zeros(len(cands), PCM_CANDIDATE)
+    for k, e in enumerate(cands):
+        out[k] = (int(e[0]), int(e[1]), np.asarray(e[2], np.float64).reshape(7))
+    return out
+
+
+def pcm_words(C_):
+    """words per row of a graph's bit matrix"""
+    return (int(C_) + 63) // 64
+
+
+def pcm_pack_bits(adj):
+    """a bool [C, C] matrix as the uint64 [C, ceil(C / 64)] bit matrix of ll_pcm_select (bit d % 64 of word d // 64 stands for d)"""
+    a = np.asarray(adj, bool)
+    n = len(a); W = pcm_words(n)
+    pad = np.zeros((n, W * 64), np.uint8); pad[:, :n] = a
+    return np.ascontiguousarray(np.packbits(pad, axis=1, bitorder="little")).view("<u8").reshape(n, W)
+
+
+def pcm_unpack_bits(words, C_):
+    """the bool [C, C] matrix of a uint64 [C, W] bit matrix"""
+    w = np.ascontiguousarray(words, "<u8").reshape(int(C_), -1)
+    return np.unpackbits(w.view(np.uint8), axis=1, bitorder="little")[:, :int(C_)].astype(bool)
+
+
+def pcm_host(poses, candidates, params=None):
+    """ll_pcm_host: one graph entirely on the host, no device -> (words uint64 [C, W], selected bool [C], degree int32 [C], PcmRecord)"""
+    p = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+    c = pcm_candidates(candidates)
+    n = len(c); W = pcm_words(n)
+    words = np.zeros((n, W), np.uint64); sel = np.zeros(max(n, 1), np.uint8); deg = np.zeros(max(n, 1), np.int32)
+    rec = PcmRecord()
+    rc = load_library().ll_pcm_host(len(p), p.ctypes.data, n, c.ctypes.data, None if params is None else C.addressof(params),
+                                    words.ctypes.data, sel.ctypes.data, deg.ctypes.data, C.addressof(rec))
+    if rc != LL_OK:
+        raise LightLoamError(rc, "pcm_host: a NULL or non-finite input, an index outside the graph, i == j, a zero quaternion, a negative "
+                                 "parameter, or more than 4096 candidates")
+    return words, sel[:n].astype(bool), deg[:n], rec
+
+
+class Pcm:
+    """One ll_pcm: the pairwise-consistent set of loop-closure candidates of many graphs side by side.  A graph is (poses [N, 7] in
+    trajectory order, candidates); a candidate is any tuple starting with (i, j, Z[7], ...), i and j local to the graph, Z measuring
+    P_i^-1 P_j.  Thresholds, not a Mahalanobis test; a greedy clique, not the maximum one"""
+
+    def __init__(self, ctx, max_graphs, max_nodes_total, max_candidates_total):
+        self.ctx = ctx; self.lib = ctx.lib
+        self.h = C.c_void_p()
+        self._sizes = []
+        rc = self.lib.ll_pcm_create(ctx.h, int(max_graphs), int(max_nodes_total), int(max_candidates_total), C.byref(self.h))
+        if rc != LL_OK:
+            raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ll_pcm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != LL_OK:
+            raise LightLoamError(rc, self.lib.ll_pcm_last_error(self.h).decode())
+
+    def _split(self, off, sel, deg, rec):
+        G = len(off) - 1
+        return ([sel[off[g]:off[g + 1]].astype(bool) for g in range(G)], [deg[off[g]:off[g + 1]].copy() for g in range(G)], [rec[g] for g in range(G)])
+
+    def run(self, graphs, params=None):
+        """(selected [bool [C_g]], degree [int32 [C_g]], records [PcmRecord]) per graph.  params: a PcmParams (pcm_params(...)).  ONE
+        synchronisation"""
+        node_off = [0]; cand_off = [0]; poses = []; cands = []
+        for g in graphs:
+            p = np.ascontiguousarray(g[0], np.float64).reshape(-1, 7); c = pcm_candidates(g[1])
+            poses.append(p); cands.append(c)
+            node_off.append(node_off[-1] + len(p)); cand_off.append(cand_off[-1] + len(c))
+        no = np.array(node_off, np.int32); co = np.array(cand_off, np.int32)
+        P = np.ascontiguousarray(np.concatenate(poses)) if poses else np.zeros((0, 7))
+        Cd = np.ascontiguousarray(np.concatenate(cands)) if cands else np.zeros(0, PCM_CANDIDATE)
+        n = int(co[-1])
+        sel = np.zeros(max(n, 1), np.uint8); deg = np.zeros(max(n, 1), np.int32); rec = (PcmRecord * max(len(graphs), 1))()
+        self._ck(self.lib.ll_pcm_run(self.h, len(graphs), _ptr(no), _ptr(co), _ptr(P), _ptr(Cd), None if params is None else C.addressof(params),
+                                     _ptr(sel), _ptr(deg), C.addressof(rec)))
+        self._sizes = [int(co[g + 1] - co[g]) for g in range(len(graphs))]
+        return self._split(co, sel, deg, rec)
+
+    def select(self, matrices):
+        """the selection alone on supplied adjacency matrices, each a bool [C, C] array or a uint64 [C, ceil(C / 64)] bit matrix -> what
+        run returns"""
+        words = []; cand_off = [0]
+        for m in matrices:
+            m = np.asarray(m)
+            w = pcm_pack_bits(m) if m.dtype != np.uint64 else np.ascontiguousarray(m).reshape(len(m), -1)
+            if len(w) and w.shape[1] != pcm_words(len(w)):
+                raise ValueError("a bit matrix of C rows has ceil(C / 64) words per row")
+            words.append(w.reshape(-1)); cand_off.append(cand_off[-1] + len(w))
+        co = np.array(cand_off, np.int32)
+        Wd = np.ascontiguousarray(np.concatenate(words)) if words else np.zeros(0, np.uint64)
+        n = int(co[-1])
+        sel = np.zeros(max(n, 1), np.uint8); deg = np.zeros(max(n, 1), np.int32); rec = (PcmRecord * max(len(matrices), 1))()
+        self._ck(self.lib.ll_pcm_select(self.h, len(matrices), _ptr(co), _ptr(Wd) if len(Wd) else None, _ptr(sel), _ptr(deg), C.addressof(rec)))
+        self._sizes = [int(co[g + 1] - co[g]) for g in range(len(matrices))]
+        return self._split(co, sel, deg, rec)
+
+    def adjacency_words(self, g):
+        """the uint64 [C, ceil(C / 64)] bit matrix of graph g of the last run or select, in original candidate order"""
+        n = self._sizes[g] if 0 <= int(g) < len(self._sizes) else 0
+        w = np.zeros((n, pcm_words(n)), np.uint64)
+        self._ck(self.lib.ll_pcm_adjacency(self.h, int(g), w.ctypes.data if w.size else None))
+        return w
+
+    def adjacency(self, g):
+        """the consistency matrix of graph g of the last run or select as bool [C, C]"""
+        w = self.adjacency_words(g)
+        return pcm_unpack_bits(w, len(w)) if len(w) else np.zeros((0, 0), bool)
+
+    def timing(self):
+        """the last call: {"ms": [prepare, adjacency, order, clique, pick] (device events), "graphs", "candidates", "pairs", "clique_steps"}"""
+        ms = np.zeros(5); cnt = np.zeros(4, np.int64)
+        self._ck(self.lib.ll_pcm_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
+        return {"ms": ms.tolist(), "graphs": int(cnt[0]), "candidates": int(cnt[1]), "pairs": int(cnt[2]), "clique_steps": int(cnt[3])}
 
 
 class PlacesParams(C.Structure):
