@@ -227,8 +227,9 @@ def test_hot_path_matches_staged(case_down, odo):
 
 @pytest.mark.parametrize("max_ring_points", [4608, 8192])
 def test_long_ring_capacity_path(api, orc, synth, max_ring_points):
-    """max_ring_points above 2304 switches the feature kernel to its 18-row / 32-row instantiation (more records per
-    thread in the pick and the voxel sort); the published clouds must not change."""
+    """max_ring_points above 2304 adds the tier launches of the feature kernels (the 8-, 12- and 22-row instantiations of the pick:
+    rings of up to 3072, 4608 and 8192 points, more records per thread in the pick and the voxel sort); the published clouds must
+    not change."""
     cfg = synth.default_cfg(64)
     scan = synth.scan(cfg, 3)
     ref = orc.extract(scan, orc.params(64))
@@ -275,7 +276,7 @@ def _assert_extract_equal(api, orc, scan, rings, what, max_ring_points=2304, **p
 
 
 @pytest.mark.parametrize("lengths", [
-    # VLP-16 rings (elevation -15 + 2 k deg); lengths beyond 2304 go on the work lists of the 12- / 18-row tier launches (ll_organize.hip:
+    # VLP-16 rings (elevation -15 + 2 k deg); lengths beyond 2304 go on the work lists of the 8- / 12- / 22-row tier launches (ll_organize.hip:
     # ll_tier_append), the others are extracted by the main launch; every ring writes its own row, the totals come from k_build_grid
     pytest.param([2600, 900, 1200, 0, 3500, 1800, 2305, 2304, 700, 0, 1500, 3073, 3072, 1000, 800, 2900], id="last ring long"),
     pytest.param([4400, 2400, 2500, 2600, 2700, 2800, 2900, 3000, 3100, 3200, 3300, 3400, 3500, 3600, 3700, 0], id="every ring long, last ring empty"),
@@ -337,7 +338,7 @@ def test_pick_with_exact_curvature_ties(api, orc, step, max_ring):
     """Exactly repeated geometry: every curvature value occurs hundreds of times inside a segment, in many lanes and
     rows of the picking wave.  std::sort leaves equal keys unspecified; the oracle and the device define ascending
     index, so the device's arg-max tie path (second wave reduction on the index) must agree bit for bit.  The finer
-    step makes rings longer than 2304 points: the 18-row instantiation of the feature kernel."""
+    step makes rings longer than 2304 points: the 8-row tier instantiation of the pick (rings of up to 3072 points)."""
     rings = [_square_room_ring(z=round(8.0 * np.tan(np.deg2rad(-15 + 2 * k)) * 32) / 32, step=step) for k in range(16)]
     scan = _ring_scan(rings)
     ref = _assert_extract_equal(api, orc, scan, 16, "ties", minimum_range=0.3, max_ring_points=max_ring)
