@@ -22,6 +22,7 @@
 #ifndef LIGHTLOAM_HIP_H
 #define LIGHTLOAM_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus

@@ -371,6 +371,54 @@ def load_library():
     return _lib
 
 
+class _Handle:
+    """what the classes over one of the library's handles share.  _DESTROY, _ERROR: the names of the handle's destroy and last-error
+    functions; a class with a real difference (a borrowed handle, children to close first) overrides close"""
+    _DESTROY = _ERROR = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.lib, self._DESTROY)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != LL_OK:
+            raise LightLoamError(rc, getattr(self.lib, self._ERROR)(self.h).decode())
+
+    def _timing(self, fn, n_ms, n_counts):
+        """a *_timing function of the library as ((ms, ...), (counts, ...))"""
+        ms = np.zeros(n_ms); cnt = np.zeros(n_counts, np.int64)
+        self._ck(fn(self.h, ms.ctypes.data, cnt.ctypes.data))
+        return tuple(ms), tuple(int(c) for c in cnt)
+
+
+def _struct_params(struct, default_fn, kw):
+    """a parameter struct as the library's default function fills it, with the given fields replaced"""
+    p = struct()
+    default_fn(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _frame_list(ids, poses):
+    """(ids int32 [n], poses float64 [n, 7] or None) of one list of frames of a Keyframes store, as the library takes it; the caller
+    keeps both alive over the call"""
+    f = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+    if p is not None and len(p) != len(f):
+        raise ValueError("poses must have one row per listed frame")
+    return f, p
+
+
 class PinnedStaging:
     """`count` scan slots of `stride_points` points each in ONE page-locked area: what an ingest thread fills and
     ll_upload_scans_async_strided copies with two enqueues"""
@@ -437,8 +485,9 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-class Context:
+class Context(_Handle):
     """One ll_ctx: `batch` scan slots resident in HBM on one GPU."""
+    _DESTROY, _ERROR = "ll_destroy", "ll_last_error"
 
     def __init__(self, params, device=0):
         self.lib = load_library()
@@ -458,18 +507,7 @@ class Context:
                     child.close()
                 except Exception:
                     pass
-            self.lib.ll_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_last_error(self.h).decode())
+        super().close()
 
     @property
     def stream(self):
@@ -795,8 +833,9 @@ class Context:
         return dict(ext=b[0].value, assoc=b[1].value, vote=b[2].value, rj=b[3].value)
 
 
-class Map:
+class Map(_Handle):
     """One ll_map: laserMapping's scan-to-submap optimisation (laserMapping.cpp:1822-2095) on the device of `ctx`."""
+    _DESTROY, _ERROR = "ll_map_destroy", "ll_map_last_error"
 
     def __init__(self, ctx, max_map_corner, max_map_surf, max_scan_corner, max_scan_surf, _borrowed=None):
         self.ctx = ctx; self.lib = ctx.lib
@@ -814,20 +853,9 @@ class Map:
         ctx._children.add(self)
 
     def close(self):
-        if getattr(self, "h", None):
-            if self._owned:
-                self.lib.ll_map_destroy(self.h)
+        if getattr(self, "h", None) and not self._owned:
             self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_map_last_error(self.h).decode())
+        super().close()
 
     @staticmethod
     def _pts(a):
@@ -1003,8 +1031,9 @@ def map_vote_host(ctx, src, tgt):
     return cnt[:n], sel[:n].astype(bool)
 
 
-class CubeMap:
+class CubeMap(_Handle):
     """One ll_cubemap: laserMapping's cube map + per-frame body (laserMapping.cpp:1584-2165) on the device of `ctx`."""
+    _DESTROY, _ERROR = "ll_cubemap_destroy", "ll_cubemap_last_error"
 
     def __init__(self, ctx, max_scan_corner, max_scan_surf, pool_points=1 << 20, line_res=0.4, plane_res=0.8):
         self.ctx = ctx; self.lib = ctx.lib
@@ -1017,21 +1046,6 @@ class CubeMap:
         if rc != LL_OK:
             raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
         ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ll_cubemap_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_cubemap_last_error(self.h).decode())
 
     def set_shard(self, rank, world):
         """Keep only the cubes of `rank` out of `world` (tile-parallel mapping); before the first scan."""
@@ -1118,9 +1132,10 @@ class CubeMap:
         self._ck(self.lib.ll_cubemap_import(self.h, pts.ctypes.data, len(pts), cen.ctypes.data, counts.ctypes.data, v.ctypes.data, len(valid)))
 
 
-class CubeMaps:
+class CubeMaps(_Handle):
     """One ll_cubemaps: n_seq cube maps side by side, frame k of every running sequence in one set of launches per stage.
     Sequence q equals a CubeMap with the same parameters driven by process_slot / process with the same frames, bit for bit."""
+    _DESTROY, _ERROR = "ll_cubemaps_destroy", "ll_cubemaps_last_error"
 
     def __init__(self, ctx, n_seq, max_scan_corner, max_scan_surf, pool_points=1 << 20, line_res=0.4, plane_res=0.8):
         self.ctx = ctx; self.lib = ctx.lib; self.n_seq = int(n_seq)
@@ -1133,21 +1148,6 @@ class CubeMaps:
         if rc != LL_OK:
             raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
         ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ll_cubemaps_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_cubemaps_last_error(self.h).decode())
 
     def _poses(self, pose_w):
         p = np.ascontiguousarray(pose_w, np.float64).reshape(self.n_seq, 7).copy()
@@ -1250,9 +1250,7 @@ class CubeMaps:
 
     def export_timing(self):
         """the last export: ((table build ms, gather ms, copy ms), (points, segments, tiles))"""
-        ms = np.zeros(3); cnt = np.zeros(3, np.int64)
-        self._ck(self.lib.ll_cubemaps_export_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
-        return tuple(ms), tuple(int(c) for c in cnt)
+        return self._timing(self.lib.ll_cubemaps_export_timing, 3, 3)
 
     def layout(self, q):
         """(cen (3,), counts [2, 4851] int32, valid [n_valid] int32) of map q: host bookkeeping, no launch, no synchronisation.
@@ -1305,9 +1303,7 @@ class CubeMaps:
 
     def merge_timing(self):
         """the last merge: ((assign ms, sort + gather ms, filter ms, commit ms), (points in, touched cubes, points out))"""
-        ms = np.zeros(4); cnt = np.zeros(3, np.int64)
-        self._ck(self.lib.ll_cubemaps_merge_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
-        return tuple(ms), tuple(int(c) for c in cnt)
+        return self._timing(self.lib.ll_cubemaps_merge_timing, 4, 3)
 
     def insert_keyframes(self, kf, ops, visibility=None, rule=None):
         """ops: a list of (dst, frames, poses, reset, cen) -- the frames (ids of the Keyframes store kf, in this order; they may repeat)
@@ -1320,10 +1316,7 @@ class CubeMaps:
         rec = (InsertOp * max(len(ops), 1))()
         keep = []
         for i, (dst, frames, poses, reset, cen) in enumerate(ops):
-            f = np.ascontiguousarray(frames, np.int32).reshape(-1)
-            p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
-            if p is not None and len(p) != len(f):
-                raise ValueError("poses must have one row per listed frame")
+            f, p = _frame_list(frames, poses)
             keep += [f, p]
             rec[i].dst = int(dst); rec[i].n_frames = len(f); rec[i].frames = f.ctypes.data
             rec[i].poses_w7 = None if p is None else p.ctypes.data
@@ -1345,9 +1338,7 @@ class CubeMaps:
 
     def insert_timing(self):
         """the last insert_keyframes: ((assign ms, sort + gather ms, filter ms, commit ms), (points in, touched cubes, points out))"""
-        ms = np.zeros(4); cnt = np.zeros(3, np.int64)
-        self._ck(self.lib.ll_cubemaps_insert_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
-        return tuple(ms), tuple(int(c) for c in cnt)
+        return self._timing(self.lib.ll_cubemaps_insert_timing, 4, 3)
 
     def align(self, ops, n_outer=2, opt=None, fit=True, info=False):
         """ops: a list of (dst, src, guess_w7) -- the rigid transform that takes map src's world frame into map dst's, by
@@ -1375,9 +1366,7 @@ class CubeMaps:
 
     def align_timing(self):
         """the last align: ((build ms, search + fit ms, evaluate + solve ms, fit record ms), (stack points, map points, residual blocks))"""
-        ms = np.zeros(4); cnt = np.zeros(3, np.int64)
-        self._ck(self.lib.ll_cubemaps_align_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
-        return tuple(ms), tuple(int(c) for c in cnt)
+        return self._timing(self.lib.ll_cubemaps_align_timing, 4, 3)
 
     def stats(self):
         """(host synchronisations, frames) since create"""
@@ -1398,9 +1387,10 @@ class CubeMaps:
         self._ck(self.lib.ll_cubemaps_reset(self.h, int(q)))
 
 
-class Keyframes:
+class Keyframes(_Handle):
     """One ll_keyframes: the stack clouds (down-sized corner and surf features, sensor frame) and mapped poses of frames, on the device;
     frame ids are 0 .. len(self) - 1 in the order they were added.  CubeMaps.insert_keyframes rebuilds maps from them"""
+    _DESTROY, _ERROR = "ll_keyframes_destroy", "ll_keyframes_last_error"
 
     def __init__(self, ctx, max_frames, cap_corner, cap_surf):
         self.ctx = ctx; self.lib = ctx.lib
@@ -1410,21 +1400,6 @@ class Keyframes:
         if rc != LL_OK:
             raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
         ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ll_keyframes_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_keyframes_last_error(self.h).decode())
 
     def __len__(self):
         return self.lib.ll_keyframes_size(self.h)
@@ -1476,49 +1451,38 @@ class Keyframes:
         return out[:int(off[-1])], off
 
 
-def visibility_params(**kw):
-    """ll_visibility_default_params with the given fields replaced"""
-    p = VisibilityParams()
-    load_library().ll_visibility_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+class _StoreReader(_Handle):
+    """what the classes over an object that follows one Keyframes store share.  _CREATE: the name of the create function, which
+    reports through the store's last error"""
+    _CREATE = None
 
-
-class Visibility:
-    """One ll_visibility over a Keyframes store: per stored point how many other frames of its drive saw THROUGH it and how many HIT
-    it (range images of the frames' own clouds, a 3 x 3 minimum, a margin); CubeMaps.insert_keyframes(..., visibility=self) leaves
-    the points out that a rule over the two counters removes"""
-
-    def __init__(self, ctx, kf, **params):
+    def _follow(self, ctx, kf, params):
         self.ctx = ctx; self.lib = ctx.lib; self.kf = kf
-        self.params = visibility_params(**params)
+        self.params = params
         self.h = C.c_void_p()
-        rc = self.lib.ll_visibility_create(kf.h, C.byref(self.params), C.byref(self.h))
+        rc = getattr(self.lib, self._CREATE)(kf.h, C.byref(self.params), C.byref(self.h))
         if rc != LL_OK:
             raise LightLoamError(rc, self.lib.ll_keyframes_last_error(kf.h).decode())
-        ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ll_visibility_destroy(self.h)        # reads nothing of the store: the order in which a Context closes its children is free
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_visibility_last_error(self.h).decode())
+        ctx._children.add(self)           # destroy reads nothing of the store: the order in which a Context closes its children is free
 
     def _live(self):
         if not getattr(self, "h", None) or not getattr(self.kf, "h", None):
-            raise LightLoamError(-7, "the Visibility object or its Keyframes store is closed")
+            raise LightLoamError(-7, "the %s object or its Keyframes store is closed" % type(self).__name__)
+
+
+def visibility_params(**kw):
+    """ll_visibility_default_params with the given fields replaced"""
+    return _struct_params(VisibilityParams, load_library().ll_visibility_default_params, kw)
+
+
+class Visibility(_StoreReader):
+    """One ll_visibility over a Keyframes store: per stored point how many other frames of its drive saw THROUGH it and how many HIT
+    it (range images of the frames' own clouds, a 3 x 3 minimum, a margin); CubeMaps.insert_keyframes(..., visibility=self) leaves
+    the points out that a rule over the two counters removes"""
+    _CREATE, _DESTROY, _ERROR = "ll_visibility_create", "ll_visibility_destroy", "ll_visibility_last_error"
+
+    def __init__(self, ctx, kf, **params):
+        self._follow(ctx, kf, visibility_params(**params))
 
     def run(self, ops):
         """ops: a list of (frames, poses) -- the frames of one drive (ids of the store, each at most once per call) observe each other,
@@ -1528,10 +1492,7 @@ class Visibility:
         rec = (VisibilityOp * max(len(ops), 1))()
         keep = []
         for i, (frames, poses) in enumerate(ops):
-            f = np.ascontiguousarray(frames, np.int32).reshape(-1)
-            p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
-            if p is not None and len(p) != len(f):
-                raise ValueError("poses must have one row per listed frame")
+            f, p = _frame_list(frames, poses)
             keep += [f, p]
             rec[i].n_frames = len(f); rec[i].frames = f.ctypes.data
             rec[i].poses_w7 = None if p is None else p.ctypes.data
@@ -1561,20 +1522,12 @@ class Visibility:
 
     def timing(self):
         """the last run: ((images ms, erode ms, vote ms), (listed frames, their points, frame pairs))"""
-        ms = np.zeros(3); cnt = np.zeros(3, np.int64)
-        self._ck(self.lib.ll_visibility_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
-        return tuple(ms), tuple(int(c) for c in cnt)
+        return self._timing(self.lib.ll_visibility_timing, 3, 3)
 
 
 def bev_params(**kw):
     """ll_bev_default_params with the given fields replaced"""
-    p = BevParams()
-    load_library().ll_bev_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _struct_params(BevParams, load_library().ll_bev_default_params, kw)
 
 
 def bev_guess(Pc, D, Pq):
@@ -1588,38 +1541,14 @@ def bev_guess(Pc, D, Pq):
     return T
 
 
-class Bev:
+class Bev(_StoreReader):
     """One ll_bev over a Keyframes store: correlative matching of bird's-eye occupancy grids, from a place match (the revisited
     frame and a heading good to a sector) to the 3-DoF transform that starts CubeMaps.align or a localising lane"""
+    _CREATE, _DESTROY, _ERROR = "ll_bev_create", "ll_bev_destroy", "ll_bev_last_error"
 
     def __init__(self, ctx, kf, **params):
-        self.ctx = ctx; self.lib = ctx.lib; self.kf = kf
-        self.params = bev_params(**params)
-        self.h = C.c_void_p()
-        rc = self.lib.ll_bev_create(kf.h, C.byref(self.params), C.byref(self.h))
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_keyframes_last_error(kf.h).decode())
         self._n_yaws = []
-        ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ll_bev_destroy(self.h)               # reads nothing of the store: the order in which a Context closes its children is free
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_bev_last_error(self.h).decode())
-
-    def _live(self):
-        if not getattr(self, "h", None) or not getattr(self.kf, "h", None):
-            raise LightLoamError(-7, "the Bev object or its Keyframes store is closed")
+        self._follow(ctx, kf, bev_params(**params))
 
     def match(self, ops):
         """ops: a list of (target, target_poses, query, query_poses, yaw0, yaw_step, n_yaws) -- frame ids of the store, the first of a
@@ -1630,10 +1559,7 @@ class Bev:
         keep = []
         for i, (target, tposes, query, qposes, yaw0, yaw_step, n_yaws) in enumerate(ops):
             for side, ids, poses in (("target", target, tposes), ("query", query, qposes)):
-                f = np.ascontiguousarray(ids, np.int32).reshape(-1)
-                p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
-                if p is not None and len(p) != len(f):
-                    raise ValueError("poses must have one row per listed frame")
+                f, p = _frame_list(ids, poses)
                 keep += [f, p]
                 setattr(rec[i], "n_" + side, len(f)); setattr(rec[i], side, f.ctypes.data if len(f) else None)
                 setattr(rec[i], side + "_poses_w7", None if p is None else p.ctypes.data)
@@ -1668,55 +1594,23 @@ class Bev:
 
     def timing(self):
         """the last match: ((prepare ms, score ms, peak ms), (ops, listed points, hypotheses))"""
-        ms = np.zeros(3); cnt = np.zeros(3, np.int64)
-        self._ck(self.lib.ll_bev_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
-        return tuple(ms), tuple(int(c) for c in cnt)
+        return self._timing(self.lib.ll_bev_timing, 3, 3)
 
 
 def entropy_params(**kw):
     """ll_entropy_default_params with the given fields replaced"""
-    p = EntropyParams()
-    load_library().ll_entropy_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _struct_params(EntropyParams, load_library().ll_entropy_default_params, kw)
 
 
-class Entropy:
+class Entropy(_StoreReader):
     """One ll_entropy over a Keyframes store: mean map entropy and mean plane variance of the cloud that listed frames make under
     listed poses, from the covariance of every point's fixed-radius neighbourhood.  It rewards any thinning: compare trajectories over
     the same points only"""
+    _CREATE, _DESTROY, _ERROR = "ll_entropy_create", "ll_entropy_destroy", "ll_entropy_last_error"
 
     def __init__(self, ctx, kf, **params):
-        self.ctx = ctx; self.lib = ctx.lib; self.kf = kf
-        self.params = entropy_params(**params)
-        self.h = C.c_void_p()
         self._sizes = []
-        rc = self.lib.ll_entropy_create(kf.h, C.byref(self.params), C.byref(self.h))
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_keyframes_last_error(kf.h).decode())
-        ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ll_entropy_destroy(self.h)           # reads nothing of the store: the order in which a Context closes its children is free
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_entropy_last_error(self.h).decode())
-
-    def _live(self):
-        if not getattr(self, "h", None) or not getattr(self.kf, "h", None):
-            raise LightLoamError(-7, "the Entropy object or its Keyframes store is closed")
+        self._follow(ctx, kf, entropy_params(**params))
 
     def run(self, ops):
         """ops: a list of (frames, poses) -- the cloud of the listed frames (ids of the store, each at most once per op; the same id may
@@ -1726,10 +1620,7 @@ class Entropy:
         rec = (EntropyOp * max(len(ops), 1))()
         keep = []; sizes = []
         for i, (frames, poses) in enumerate(ops):
-            f = np.ascontiguousarray(frames, np.int32).reshape(-1)
-            p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
-            if p is not None and len(p) != len(f):
-                raise ValueError("poses must have one row per listed frame")
+            f, p = _frame_list(frames, poses)
             keep += [f, p]
             rec[i].n_frames = len(f); rec[i].frames = f.ctypes.data
             rec[i].poses_w7 = None if p is None else p.ctypes.data
@@ -1758,9 +1649,7 @@ class Entropy:
     def timing(self):
         """the last run: ((keys, sort + cells, rows, moments, sums) ms, (listed frames, their points, occupied cells, neighbour pairs,
         host synchronisations))"""
-        ms = np.zeros(5); cnt = np.zeros(5, np.int64)
-        self._ck(self.lib.ll_entropy_timing(self.h, ms.ctypes.data, cnt.ctypes.data))
-        return tuple(ms), tuple(int(c) for c in cnt)
+        return self._timing(self.lib.ll_entropy_timing, 5, 5)
 
 
 PCM_CANDIDATE = np.dtype([("i", "i4"), ("j", "i4"), ("Z_w7", "f8", (7,))])       # ll_pcm_candidate as a numpy record
@@ -1769,13 +1658,7 @@ PCM_MAX_CANDIDATES = 4096
 
 def pcm_params(**kw):
     """ll_pcm_default_params (0.05 rad, 0.5 m, 2e-4 rad/m, 0.02: conventions, not measurements) with the given fields replaced"""
-    p = PcmParams()
-    load_library().ll_pcm_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _struct_params(PcmParams, load_library().ll_pcm_default_params, kw)
 
 
 def pcm_candidates(cands):
@@ -1826,10 +1709,11 @@ def pcm_host(poses, candidates, params=None):
     return words, sel[:n].astype(bool), deg[:n], rec
 
 
-class Pcm:
+class Pcm(_Handle):
     """One ll_pcm: the pairwise-consistent set of loop-closure candidates of many graphs side by side.  A graph is (poses [N, 7] in
     trajectory order, candidates); a candidate is any tuple starting with (i, j, Z[7], ...), i and j local to the graph, Z measuring
     P_i^-1 P_j.  Thresholds, not a Mahalanobis test; a greedy clique, not the maximum one"""
+    _DESTROY, _ERROR = "ll_pcm_destroy", "ll_pcm_last_error"
 
     def __init__(self, ctx, max_graphs, max_nodes_total, max_candidates_total):
         self.ctx = ctx; self.lib = ctx.lib
@@ -1839,21 +1723,6 @@ class Pcm:
         if rc != LL_OK:
             raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
         ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ll_pcm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_pcm_last_error(self.h).decode())
 
     def _split(self, off, sel, deg, rec):
         G = len(off) - 1
@@ -1918,9 +1787,10 @@ class PlacesParams(C.Structure):
     _fields_ = [("capacity", C.c_int), ("max_radius", C.c_float), ("z_offset", C.c_float)]
 
 
-class Places:
+class Places(_Handle):
     """One ll_places: Scan Context descriptors (20 rings x 60 sectors) of resident or uploaded scans in HBM, and the exact search of
     every query against every stored place.  Place ids are 0 .. size - 1 in the order they were added."""
+    _DESTROY, _ERROR = "ll_places_destroy", "ll_places_last_error"
 
     DESC = (20, 60)
 
@@ -1937,21 +1807,6 @@ class Places:
         if rc != LL_OK:
             raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
         ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ll_places_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_places_last_error(self.h).decode())
 
     def __len__(self):
         return self.lib.ll_places_size(self.h)
@@ -2155,10 +2010,11 @@ def edge_gate(Pa, Pb, Z, S, joint, with_cov=False):
     return (chi2.value, cov) if with_cov else chi2.value
 
 
-class PoseGraphs:
+class PoseGraphs(_Handle):
     """One ll_posegraphs: many independent SE(3) pose graphs optimised side by side on the device, one workgroup per graph.  A graph
     is the tuple (poses [N, 7], edges, fixed): poses in the pose_w7 layout (world from body), edges as pg_edges takes them (i, j local to
     the graph, Z measures P_i^-1 P_j), fixed None (node 0 is fixed) or N flags."""
+    _DESTROY, _ERROR = "ll_posegraphs_destroy", "ll_posegraphs_last_error"
 
     def __init__(self, ctx, max_graphs, max_nodes_total, max_edges_total):
         self.ctx = ctx; self.lib = ctx.lib
@@ -2167,21 +2023,6 @@ class PoseGraphs:
         if rc != LL_OK:
             raise LightLoamError(rc, ctx.lib.ll_last_error(ctx.h).decode())
         ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ll_posegraphs_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_posegraphs_last_error(self.h).decode())
 
     @staticmethod
     def _pack(graphs):
@@ -2297,10 +2138,11 @@ class DrivesParams(C.Structure):
 IDLE, RUN, START = 0, 1, 2
 
 
-class Drives:
+class Drives(_Handle):
     """One ll_drives: n_lanes lanes, each running one drive at a time through registration -> odometry -> mapping.  Upload lane q's
     raw scan into slots()[q], then step(cmd): IDLE (0), RUN (1: the next frame, only after a step the lane ran) or START (2: frame 0
     of a new drive).  Lane q equals its drive run alone through ll_odometry_frames, WorldPose and a CubeMap, bit for bit."""
+    _DESTROY, _ERROR = "ll_drives_destroy", "ll_drives_last_error"
 
     def __init__(self, ctx, n_lanes, max_scan_corner, max_scan_surf, pool_points=1 << 20, base=0, line_res=0.4, plane_res=0.8,
                  n_outer=3, keep_registered=False):
@@ -2327,21 +2169,6 @@ class Drives:
     def export_maps(self, which):
         """CubeMaps.export of the lanes' maps: (points [N, 4], offset [S + 1]); between any two steps"""
         return self.cubemaps.export(which)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.ll_drives_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != LL_OK:
-            raise LightLoamError(rc, self.lib.ll_drives_last_error(self.h).decode())
 
     def slots(self):
         """[S]: the slot the next step reads each lane's raw scan from"""

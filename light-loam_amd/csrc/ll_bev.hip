@@ -180,13 +180,7 @@ __global__ __launch_bounds__(256) void k_bev_peak(const int *__restrict__ volume
 }
 
 /* ------------------------------------------------------------------ host side */
-static int bev_fail(ll_bev *b, int rc, const std::string &msg) { b->err = msg; return rc; }
-static int bev_kf_err(ll_keyframes *kf, int rc, const std::string &msg) { kf->err = msg; return rc; }   /* create: there is no object yet */
-#define BEV_HIP(call)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return bev_fail(b, LL_ERR_HIP, std::string("bev: " #call ": ") + hipGetErrorString(e_)); \
-    } while (0)
+#define BEV_HIP(call) LL_HIP_CHECK(ll_fail, b, "bev: ", call, #call)
 
 static size_t bev_lds_bytes(int half, int sh) { const size_t W = (size_t)(2 * half + 2 * sh); return W * W + BEV_CHUNK * 4; }
 
@@ -204,20 +198,20 @@ extern "C" int ll_bev_create(ll_keyframes *kf, const ll_bev_params *p, ll_bev **
     if (!std::isfinite(p->cell) || !(p->cell > 0.0f) || !std::isfinite(p->z_layer) || !(p->z_layer > 0.0f) || !std::isfinite(p->z_min) || p->half < 1 || p->half > 512 ||
         p->shift_half < 1 || p->shift_half > 16 || p->excl_yaw < 0 || p->excl_shift < 0 || p->max_ops < 1 || p->max_ops > 4096 || p->max_yaws < 1 || p->max_yaws > 64 ||
         p->max_points < 1 || p->max_points > (1ll << 30))
-        return bev_kf_err(kf, LL_ERR_ARG, "bev: bad parameters (cell, z_layer finite and > 0, z_min finite, half in 1 .. 512, shift_half in 1 .. 16, excl_yaw, excl_shift >= 0, "
+        return llkf_create_err(kf, LL_ERR_ARG, "bev: bad parameters (cell, z_layer finite and > 0, z_min finite, half in 1 .. 512, shift_half in 1 .. 16, excl_yaw, excl_shift >= 0, "
                                           "max_ops in 1 .. 4096, max_yaws in 1 .. 64, max_points in 1 .. 2^30)");
     if (bev_lds_bytes(p->half, p->shift_half) > (size_t)BEV_LDS_MAX)
-        return bev_kf_err(kf, LL_ERR_ARG, "bev: (2 half + 2 shift_half)^2 + 4096 = " + std::to_string(bev_lds_bytes(p->half, p->shift_half)) + " bytes do not fit the 160 KiB of LDS");
+        return llkf_create_err(kf, LL_ERR_ARG, "bev: (2 half + 2 shift_half)^2 + 4096 = " + std::to_string(bev_lds_bytes(p->half, p->shift_half)) + " bytes do not fit the 160 KiB of LDS");
     ll_ctx *ctx = kf->ctx;
-    if (hipSetDevice(ctx->device) != hipSuccess) return bev_kf_err(kf, LL_ERR_HIP, "bev: hipSetDevice failed");
+    if (hipSetDevice(ctx->device) != hipSuccess) return llkf_create_err(kf, LL_ERR_HIP, "bev: hipSetDevice failed");
     ll_bev *b = new ll_bev();
-    b->ctx = ctx; b->kf = kf; b->p = *p; b->epoch = kf->n_reset;
+    b->follow(kf); b->p = *p;
     bool ok = true;
     for (int k = 0; ok && k < 4; ++k) ok = hipEventCreate(&b->ev[k]) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         ll_bev_destroy(b);
-        return bev_kf_err(kf, LL_ERR_HIP, "bev: hipEventCreate failed");
+        return llkf_create_err(kf, LL_ERR_HIP, "bev: hipEventCreate failed");
     }
     *out = b;
     return LL_OK;
@@ -226,19 +220,21 @@ extern "C" int ll_bev_create(ll_keyframes *kf, const ll_bev_params *p, ll_bev **
 extern "C" void ll_bev_destroy(ll_bev *b)
 {
     if (!b) return;
-    if (b->ctx) { (void)hipSetDevice(b->ctx->device); (void)hipStreamSynchronize(b->ctx->stream); }
+    b->release();
     if (b->d_mem) (void)hipFree(b->d_mem);
     for (int k = 0; k < 4; ++k) if (b->ev[k]) (void)hipEventDestroy(b->ev[k]);
-    llx_free(b->X);
     delete b;
 }
 
 extern "C" const char *ll_bev_last_error(const ll_bev *b) { return b ? b->err.c_str() : "null bev"; }
 
-static int bev_stale(ll_bev *b)
+static int bev_stale(ll_bev *b) { return b->stale("bev: the store was reset since the object was made: call ll_bev_reset"); }
+
+/* the two lists of an op: target, query */
+static LLKfList bev_side(const ll_bev_op &o, int side)
 {
-    if (b->epoch == b->kf->n_reset) return LL_OK;
-    return bev_fail(b, LL_ERR_STATE, "bev: the store was reset since the object was made: call ll_bev_reset");
+    if (side) return {o.n_query, o.query, o.query_poses_w7, "query"};
+    return {o.n_target, o.target, o.target_poses_w7, "target"};
 }
 
 extern "C" int ll_bev_reset(ll_bev *b)
@@ -252,34 +248,28 @@ extern "C" int ll_bev_reset(ll_bev *b)
 extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_result *out)
 {
     if (!b) return LL_ERR_ARG;
-    if (!ops || !out) return bev_fail(b, LL_ERR_ARG, "bev: ops or out is NULL");
-    if (n_ops < 1 || n_ops > b->p.max_ops) return bev_fail(b, LL_ERR_ARG, "bev: n_ops = " + std::to_string(n_ops) + " is outside 1 .. max_ops = " + std::to_string(b->p.max_ops));
+    if (!ops || !out) return b->fail(LL_ERR_ARG, "bev: ops or out is NULL");
+    if (n_ops < 1 || n_ops > b->p.max_ops) return b->fail(LL_ERR_ARG, "bev: n_ops = " + std::to_string(n_ops) + " is outside 1 .. max_ops = " + std::to_string(b->p.max_ops));
     const ll_keyframes *kf = b->kf;
+    const ll_keyframe_info *tab = kf->tab.data();
     const int size = (int)kf->tab.size();
     /* ---- every refusal before anything is enqueued */
     long long n_points = 0, n_rows = 0;
     for (int i = 0; i < n_ops; ++i) {
         const ll_bev_op &o = ops[i];
         const std::string who = "bev: op " + std::to_string(i) + ": ";
-        if (o.n_yaws < 1 || o.n_yaws > b->p.max_yaws) return bev_fail(b, LL_ERR_ARG, who + "n_yaws = " + std::to_string(o.n_yaws) + " is outside 1 .. max_yaws = " + std::to_string(b->p.max_yaws));
-        if (!std::isfinite(o.yaw0) || !std::isfinite(o.yaw_step) || !std::isfinite(o.yaw0 + (double)(o.n_yaws - 1) * o.yaw_step)) return bev_fail(b, LL_ERR_ARG, who + "a yaw is not finite");
+        if (o.n_yaws < 1 || o.n_yaws > b->p.max_yaws) return b->fail(LL_ERR_ARG, who + "n_yaws = " + std::to_string(o.n_yaws) + " is outside 1 .. max_yaws = " + std::to_string(b->p.max_yaws));
+        if (!std::isfinite(o.yaw0) || !std::isfinite(o.yaw_step) || !std::isfinite(o.yaw0 + (double)(o.n_yaws - 1) * o.yaw_step)) return b->fail(LL_ERR_ARG, who + "a yaw is not finite");
         for (int side = 0; side < 2; ++side) {
-            const int nf = side ? o.n_query : o.n_target;
-            const int *ids = side ? o.query : o.target;
-            const double *given = side ? o.query_poses_w7 : o.target_poses_w7;
-            const char *name = side ? "query" : "target";
-            if (nf < 1 || !ids) return bev_fail(b, LL_ERR_ARG, who + "the " + name + " side has no frame or its list is NULL");
-            for (int f = 0; f < nf; ++f) {
-                const int id = ids[f];
-                if (id < 0 || id >= size) return bev_fail(b, LL_ERR_ARG, who + name + " frame " + std::to_string(id) + " is not in the store (size " + std::to_string(size) + ")");
-                const double *P = given ? given + (size_t)f * 7 : kf->tab[id].pose_w7;
-                for (int k = 0; k < 7; ++k) if (!std::isfinite(P[k])) return bev_fail(b, LL_ERR_ARG, who + "the pose of " + name + " list entry " + std::to_string(f) + " is not finite");
-                n_points += (long long)kf->tab[id].n[0] + kf->tab[id].n[1];
-            }
+            const LLKfList list = bev_side(o, side);
+            long long pts;
+            if (list.n < 1 || !list.ids) return b->fail(LL_ERR_ARG, who + "the " + list.side + " side has no frame or its list is NULL");
+            if (llkf_check(tab, size, list, LLKF_DUP_ALLOWED, nullptr, i, who, &b->err, &pts)) return LL_ERR_ARG;
+            n_points += pts;
         }
         n_rows += o.n_yaws;
     }
-    if (n_points > b->p.max_points) return bev_fail(b, LL_ERR_CAPACITY, "bev: " + std::to_string(n_points) + " listed points, max_points is " + std::to_string(b->p.max_points));
+    if (n_points > b->p.max_points) return b->fail(LL_ERR_CAPACITY, "bev: " + std::to_string(n_points) + " listed points, max_points is " + std::to_string(b->p.max_points));
     int rc = bev_stale(b); if (rc) return rc;
     /* ---- the tables: clouds (query clouds of an op back to back in the list), poses, ops, yaws */
     const int S = 2 * b->p.shift_half, G = 2 * b->p.half;
@@ -294,18 +284,16 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
         const ll_bev_op &o = ops[i];
         optab[i].qbase = (int)n_query_points; optab[i].vbase = (int)yawtab.size(); optab[i].n_yaws = o.n_yaws;
         for (int side = 0; side < 2; ++side) {
-            const int nf = side ? o.n_query : o.n_target;
-            const int *ids = side ? o.query : o.target;
-            const double *given = side ? o.query_poses_w7 : o.target_poses_w7;
+            const LLKfList list = bev_side(o, side);
             const int anchor = (int)(poses.size() / 7);
-            for (int f = 0; f < nf; ++f) {
-                const ll_keyframe_info &e = kf->tab[ids[f]];
-                const double *P = given ? given + (size_t)f * 7 : e.pose_w7;
+            for (int f = 0; f < list.n; ++f) {
+                const double *P = llkf_pose(tab, list, f);
                 poses.insert(poses.end(), P, P + 7);
                 for (int w = 0; w < 2; ++w) {
-                    if (e.n[w] <= 0) continue;
-                    segs.push_back({(w ? kf->cap[0] : 0) + e.offset[w], e.n[w], tiles.take(e.n[w]), anchor + f, anchor, i, side ? (int)n_query_points : -1});
-                    if (side) n_query_points += e.n[w];
+                    const LLKfCloud cl = llkf_cloud(tab, kf->cap[0], list.ids[f], w);
+                    if (cl.cnt <= 0) continue;
+                    segs.push_back({cl.off, cl.cnt, tiles.take(cl.cnt), anchor + f, anchor, i, side ? (int)n_query_points : -1});
+                    if (side) n_query_points += cl.cnt;
                 }
             }
         }
@@ -316,7 +304,7 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
             yawtab.push_back({i, j, (float)std::cos(yaw), (float)std::sin(yaw)});
         }
     }
-    if (!tiles.fits()) return bev_fail(b, LL_ERR_CAPACITY, "bev: too many tiles for one call");
+    if (!tiles.fits()) return b->fail(LL_ERR_CAPACITY, "bev: too many tiles for one call");
     /* ---- the buffer: grids | query counts | peak records | volume | query (x, y) | query layers */
     const size_t grid_bytes = (size_t)G * G, fill_bytes = (size_t)n_ops * grid_bytes + (size_t)n_ops * 4;
     const size_t at_nq = (size_t)n_ops * grid_bytes, at_rec = ll_up256(fill_bytes), at_vol = ll_up256(at_rec + (size_t)n_ops * 16);
@@ -331,7 +319,7 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
         b->d_mem = nullptr; b->cap_mem = 0;
         const size_t cap = std::max(need, (size_t)1 << 20);
         void *mem = nullptr;
-        if (hipMalloc(&mem, cap) != hipSuccess) { (void)hipGetLastError(); return bev_fail(b, LL_ERR_HIP, "bev: no device memory for " + std::to_string(cap) + " bytes"); }
+        if (hipMalloc(&mem, cap) != hipSuccess) { (void)hipGetLastError(); return b->fail(LL_ERR_HIP, "bev: no device memory for " + std::to_string(cap) + " bytes"); }
         b->d_mem = (unsigned char *)mem; b->cap_mem = cap;
     }
     std::vector<unsigned char> blob;
@@ -339,7 +327,7 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
     const unsigned char *d_blob = (const unsigned char *)llx_stage_bytes(b->X, blob.data(), blob.size(), st, b->err);
     if (!d_blob) return LL_ERR_HIP;
     int *pin = (int *)ll_pinned_scratch((size_t)n_ops * 16);
-    if (!pin) return bev_fail(b, LL_ERR_HIP, "bev: no page-locked scratch");
+    if (!pin) return b->fail(LL_ERR_HIP, "bev: no page-locked scratch");
     b->last_vbase.clear(); b->last_nyaws.clear();                     /* the volume is being overwritten from here on */
     BevCfg c;
     c.half = b->p.half; c.sh = b->p.shift_half; c.zmin = b->p.z_min;
@@ -379,24 +367,18 @@ extern "C" int ll_bev_match(ll_bev *b, const ll_bev_op *ops, int n_ops, ll_bev_r
     return LL_OK;
 }
 
-/* bytes at `at` of the buffer to the host through the page-locked scratch; one synchronisation */
+/* bytes at `at` of the buffer to the host; one synchronisation */
 static int bev_read(ll_bev *b, size_t at, size_t bytes, void *dst)
 {
-    unsigned char *pin = (unsigned char *)ll_pinned_scratch(bytes);
-    if (!pin) return bev_fail(b, LL_ERR_HIP, "bev: no page-locked scratch");
-    hipStream_t st = b->ctx->stream;
-    BEV_HIP(hipSetDevice(b->ctx->device));
-    BEV_HIP(hipMemcpyAsync(pin, b->d_mem + at, bytes, hipMemcpyDeviceToHost, st));
-    BEV_HIP(hipStreamSynchronize(st));
-    std::memcpy(dst, pin, bytes);
-    return LL_OK;
+    const LLKfRange range = {b->d_mem + at, bytes, dst};
+    return b->read("bev: ", &range, 1);
 }
 
 static int bev_last_op(ll_bev *b, int op, const void *dst)
 {
-    if (!dst) return bev_fail(b, LL_ERR_ARG, "bev: the output pointer is NULL");
+    if (!dst) return b->fail(LL_ERR_ARG, "bev: the output pointer is NULL");
     const int rc = bev_stale(b); if (rc) return rc;
-    if (op < 0 || op >= (int)b->last_nyaws.size()) return bev_fail(b, LL_ERR_ARG, "bev: the last call had " + std::to_string(b->last_nyaws.size()) + " ops, there is no op " + std::to_string(op));
+    if (op < 0 || op >= (int)b->last_nyaws.size()) return b->fail(LL_ERR_ARG, "bev: the last call had " + std::to_string(b->last_nyaws.size()) + " ops, there is no op " + std::to_string(op));
     return LL_OK;
 }
 
@@ -418,10 +400,7 @@ extern "C" int ll_bev_grid(ll_bev *b, int op, unsigned char *cells)
 
 extern "C" int ll_bev_timing(const ll_bev *b, double *ms, long long *counts)
 {
-    if (!b) return LL_ERR_ARG;
-    if (ms) for (int k = 0; k < 3; ++k) ms[k] = b->ms[k];
-    if (counts) for (int k = 0; k < 3; ++k) counts[k] = b->counts[k];
-    return LL_OK;
+    return b ? llkf_timing(b->ms, b->counts, 3, ms, counts) : LL_ERR_ARG;
 }
 
 /* ---- T0 = P_c o D o P_q^-1, plain host f64 (the header spells the operations) */

@@ -92,11 +92,7 @@ struct ll_cubemap : CmTables {                   /* the pair tables (ll_cubemap_
     bool has_frame = false;                       /* a frame has run since create / reset / import: the stack clouds are one frame's (the keyframe store) */
 };
 
-#define CM_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) { cm->err = std::string(#call) + ": " + hipGetErrorString(e_); return LL_ERR_HIP; } \
-    } while (0)
+#define CM_HIP(call) LL_HIP_CHECK(ll_fail, cm, "", call, #call)
 
 /* ll_cubemap.hip: a compaction's copies (cm_commit's moves) of type w, out of the pool that was current into the one that is */
 void cm_run_moves(ll_cubemap *cm, int w, const std::vector<CmPiece> &moves);

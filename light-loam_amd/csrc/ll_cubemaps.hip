@@ -171,11 +171,7 @@ struct ll_cubemaps {
     std::string err;
 };
 
-#define CMS_HIP(call)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) { cms->err = std::string(#call) + ": " + hipGetErrorString(e_); return LL_ERR_HIP; } \
-    } while (0)
+#define CMS_HIP(call) LL_HIP_CHECK(ll_fail, cms, "", call, #call)
 
 template <typename T>
 static bool cms_alloc(ll_cubemaps *cms, T *&ptr, size_t count) { return ll_dev_alloc(cms->allocs, cms->err, ptr, count, false); }

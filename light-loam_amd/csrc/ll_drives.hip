@@ -147,11 +147,7 @@ struct ll_drives {
     std::string err;
 };
 
-#define DRV_HIP(call)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) { d->err = std::string(#call) + ": " + hipGetErrorString(e_); return LL_ERR_HIP; } \
-    } while (0)
+#define DRV_HIP(call) LL_HIP_CHECK(ll_fail, d, "", call, #call)
 
 template <typename T>
 static bool drv_alloc(ll_drives *d, T *&ptr, size_t count) { return ll_dev_alloc(d->allocs, d->err, ptr, count, true); }

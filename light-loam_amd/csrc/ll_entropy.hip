@@ -60,23 +60,18 @@ struct EnSeg { long long off, base; int cnt; unsigned tile0; int k, op; };   /* 
 struct EnOpTiles { unsigned t0, t1; };
 struct EnTile { double sum_h, sum_pv; long long pairs; int valid, sparse, outside, pad; };
 
-struct ll_entropy {
-    ll_ctx *ctx = nullptr;
-    ll_keyframes *kf = nullptr;
+struct ll_entropy : LLKfReader {
     ll_entropy_params p;
-    unsigned long long epoch = 0;
     unsigned char *d_mem = nullptr;               /* one allocation, carved at create from max_points */
     LLVoxWork W;                                  /* keys, values, flags, ranks and the sort's and the scan's scratch */
     float4 *d_world = nullptr, *d_spts = nullptr; /* world points by list index, and in sorted order */
     float *d_h = nullptr, *d_pv = nullptr; int *d_nn = nullptr;   /* by list index; nn unsaturated */
     int *d_cs = nullptr; unsigned long long *d_ck = nullptr; int2 *d_rows = nullptr;
     EnTile *d_tile = nullptr; ll_entropy_rec *d_rec = nullptr;
-    LLMapExport X;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<long long> last_base; std::vector<int> last_n0, last_n1;   /* the last run's listed frames by list position */
     double ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};     /* the last run: keys, sort + cells, rows, moments, sums (events) */
     long long counts[5] = {0, 0, 0, 0, 0};        /* listed frames, their points, occupied cells, neighbour pairs, host synchronisations */
-    std::string err;
 };
 
 __device__ __forceinline__ unsigned long long en_key(int op, int cz, int cy, int cx)
@@ -333,13 +328,7 @@ __global__ __launch_bounds__(64) void k_en_op_sums(const EnOpTiles *__restrict__
 }
 
 /* ------------------------------------------------------------------ host side */
-static int en_fail(ll_entropy *v, int rc, const std::string &msg) { v->err = msg; return rc; }
-static int en_kf_err(ll_keyframes *kf, int rc, const std::string &msg) { kf->err = msg; return rc; }   /* create: there is no object yet */
-#define EN_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return en_fail(v, LL_ERR_HIP, std::string("entropy: " #call ": ") + hipGetErrorString(e_)); \
-    } while (0)
+#define EN_HIP(call) LL_HIP_CHECK(ll_fail, v, "entropy: ", call, #call)
 
 extern "C" void ll_entropy_default_params(ll_entropy_params *p)
 {
@@ -365,12 +354,12 @@ extern "C" int ll_entropy_create(ll_keyframes *kf, const ll_entropy_params *p, l
     *out = nullptr;
     if (!(p->radius > 0.0f) || !(p->radius <= 8.0f) || !(p->radius * p->radius >= 0x1p-100f) || p->min_neighbours < 4 || !(p->lambda_floor > 0.0f) ||
         !std::isfinite(p->lambda_floor) || p->max_points < 1 || p->max_points > EN_MAX_POINTS)
-        return en_kf_err(kf, LL_ERR_ARG, "entropy: bad parameters (radius in (0, 8] with a square of at least 2^-100, min_neighbours >= 4, lambda_floor > 0 and finite, "
+        return llkf_create_err(kf, LL_ERR_ARG, "entropy: bad parameters (radius in (0, 8] with a square of at least 2^-100, min_neighbours >= 4, lambda_floor > 0 and finite, "
                                          "max_points in 1 .. 2^27)");
     ll_ctx *ctx = kf->ctx;
-    if (hipSetDevice(ctx->device) != hipSuccess) return en_kf_err(kf, LL_ERR_HIP, "entropy: hipSetDevice failed");
+    if (hipSetDevice(ctx->device) != hipSuccess) return llkf_create_err(kf, LL_ERR_HIP, "entropy: hipSetDevice failed");
     ll_entropy *v = new ll_entropy();
-    v->ctx = ctx; v->kf = kf; v->p = *p; v->epoch = kf->n_reset;
+    v->follow(kf); v->p = *p;
     const size_t cap = (size_t)p->max_points;
     const size_t own = en_carve(v, nullptr, cap), bytes = own + ll_vox_work_bytes((int)cap, 1);
     bool ok = hipMalloc((void **)&v->d_mem, bytes) == hipSuccess;
@@ -378,7 +367,7 @@ extern "C" int ll_entropy_create(ll_keyframes *kf, const ll_entropy_params *p, l
     if (!ok) {
         (void)hipGetLastError();
         ll_entropy_destroy(v);
-        return en_kf_err(kf, LL_ERR_HIP, "entropy: no device memory for " + std::to_string(bytes) + " bytes of workspace");
+        return llkf_create_err(kf, LL_ERR_HIP, "entropy: no device memory for " + std::to_string(bytes) + " bytes of workspace");
     }
     en_carve(v, v->d_mem, cap);
     ll_vox_work_carve(v->d_mem + own, (int)cap, 1, &v->W);
@@ -389,20 +378,15 @@ extern "C" int ll_entropy_create(ll_keyframes *kf, const ll_entropy_params *p, l
 extern "C" void ll_entropy_destroy(ll_entropy *v)
 {
     if (!v) return;
-    if (v->ctx) { (void)hipSetDevice(v->ctx->device); (void)hipStreamSynchronize(v->ctx->stream); }
+    v->release();
     if (v->d_mem) (void)hipFree(v->d_mem);
     for (int k = 0; k < 6; ++k) if (v->ev[k]) (void)hipEventDestroy(v->ev[k]);
-    llx_free(v->X);
     delete v;
 }
 
 extern "C" const char *ll_entropy_last_error(const ll_entropy *v) { return v ? v->err.c_str() : "null entropy"; }
 
-static int en_stale(ll_entropy *v)
-{
-    if (v->epoch == v->kf->n_reset) return LL_OK;
-    return en_fail(v, LL_ERR_STATE, "entropy: the store was reset since the object followed it: call ll_entropy_reset");
-}
+static int en_stale(ll_entropy *v) { return v->stale("entropy: the store was reset since the object followed it: call ll_entropy_reset"); }
 
 extern "C" int ll_entropy_reset(ll_entropy *v)
 {
@@ -416,9 +400,10 @@ extern "C" int ll_entropy_reset(ll_entropy *v)
 extern "C" int ll_entropy_run(ll_entropy *v, const ll_entropy_op *ops, int n_ops, ll_entropy_rec *rec)
 {
     if (!v) return LL_ERR_ARG;
-    if (!ops || n_ops < 1 || !rec) return en_fail(v, LL_ERR_ARG, "entropy: ops or rec is NULL or n_ops < 1");
-    if (n_ops > EN_MAX_OPS) return en_fail(v, LL_ERR_CAPACITY, "entropy: " + std::to_string(n_ops) + " ops, one call takes at most " + std::to_string(EN_MAX_OPS));
+    if (!ops || n_ops < 1 || !rec) return v->fail(LL_ERR_ARG, "entropy: ops or rec is NULL or n_ops < 1");
+    if (n_ops > EN_MAX_OPS) return v->fail(LL_ERR_CAPACITY, "entropy: " + std::to_string(n_ops) + " ops, one call takes at most " + std::to_string(EN_MAX_OPS));
     const ll_keyframes *kf = v->kf;
+    const ll_keyframe_info *tab = kf->tab.data();
     const int size = (int)kf->tab.size();
     /* ---- every refusal before anything is enqueued or a value changes */
     long long L = 0, n_points = 0;
@@ -426,19 +411,13 @@ extern "C" int ll_entropy_run(ll_entropy *v, const ll_entropy_op *ops, int n_ops
     for (int i = 0; i < n_ops; ++i) {
         const ll_entropy_op &o = ops[i];
         const std::string who = "entropy: op " + std::to_string(i) + ": ";
-        if (o.n_frames < 0 || (o.n_frames > 0 && !o.frames)) return en_fail(v, LL_ERR_ARG, who + "n_frames < 0 or frames is NULL");
-        for (int f = 0; f < o.n_frames; ++f) {
-            const int id = o.frames[f];
-            if (id < 0 || id >= size) return en_fail(v, LL_ERR_ARG, who + "frame " + std::to_string(id) + " is not in the store (size " + std::to_string(size) + ")");
-            if (seen[id] == i) return en_fail(v, LL_ERR_ARG, who + "frame " + std::to_string(id) + " is listed twice in this op");
-            seen[id] = i;
-            const double *P = o.poses_w7 ? o.poses_w7 + (size_t)f * 7 : kf->tab[id].pose_w7;
-            for (int k = 0; k < 7; ++k) if (!std::isfinite(P[k])) return en_fail(v, LL_ERR_ARG, who + "the pose of list entry " + std::to_string(f) + " is not finite");
-            n_points += (long long)kf->tab[id].n[0] + kf->tab[id].n[1];
-        }
+        if (o.n_frames < 0 || (o.n_frames > 0 && !o.frames)) return v->fail(LL_ERR_ARG, who + "n_frames < 0 or frames is NULL");
+        long long pts;
+        if (llkf_check(tab, size, {o.n_frames, o.frames, o.poses_w7, ""}, LLKF_DUP_PER_OP, &seen, i, who, &v->err, &pts)) return LL_ERR_ARG;
+        n_points += pts;
         L += o.n_frames;
     }
-    if (n_points > v->p.max_points) return en_fail(v, LL_ERR_CAPACITY, "entropy: " + std::to_string(n_points) + " listed points, max_points is " + std::to_string(v->p.max_points));
+    if (n_points > v->p.max_points) return v->fail(LL_ERR_CAPACITY, "entropy: " + std::to_string(n_points) + " listed points, max_points is " + std::to_string(v->p.max_points));
     int rc = en_stale(v); if (rc) return rc;
     /* ---- the tables: clouds, poses, the ops' tiles */
     std::vector<EnSeg> segs;
@@ -450,15 +429,16 @@ extern "C" int ll_entropy_run(ll_entropy *v, const ll_entropy_op *ops, int n_ops
     for (int i = 0; i < n_ops; ++i) {
         const ll_entropy_op &o = ops[i];
         optab[i].t0 = (unsigned)tiles.next;
+        const LLKfList list = {o.n_frames, o.frames, o.poses_w7, ""};
         for (int f = 0; f < o.n_frames; ++f) {
-            const ll_keyframe_info &e = kf->tab[o.frames[f]];
-            const double *P = o.poses_w7 ? o.poses_w7 + (size_t)f * 7 : e.pose_w7;
+            const double *P = llkf_pose(tab, list, f);
             for (int k = 0; k < 7; ++k) poses[(size_t)(k0 + f) * 7 + k] = P[k];
-            base[k0 + f] = at; n0[k0 + f] = e.n[0]; n1[k0 + f] = e.n[1];
+            base[k0 + f] = at; n0[k0 + f] = tab[o.frames[f]].n[0]; n1[k0 + f] = tab[o.frames[f]].n[1];
             for (int w = 0; w < 2; ++w) {
-                if (e.n[w] <= 0) continue;
-                segs.push_back({(w ? kf->cap[0] : 0) + e.offset[w], at, e.n[w], tiles.take(e.n[w]), k0 + f, i});
-                at += e.n[w];
+                const LLKfCloud c = llkf_cloud(tab, kf->cap[0], o.frames[f], w);
+                if (c.cnt <= 0) continue;
+                segs.push_back({c.off, at, c.cnt, tiles.take(c.cnt), k0 + f, i});
+                at += c.cnt;
             }
         }
         optab[i].t1 = (unsigned)tiles.next;
@@ -477,7 +457,7 @@ extern "C" int ll_entropy_run(ll_entropy *v, const ll_entropy_op *ops, int n_ops
     hipStream_t st = v->ctx->stream;
     EN_HIP(hipSetDevice(v->ctx->device));
     ll_entropy_rec *pin = (ll_entropy_rec *)ll_pinned_scratch((size_t)n_ops * sizeof(ll_entropy_rec) + sizeof(int));
-    if (!pin) return en_fail(v, LL_ERR_HIP, "entropy: no page-locked scratch");
+    if (!pin) return v->fail(LL_ERR_HIP, "entropy: no page-locked scratch");
     const unsigned char *d_blob = (const unsigned char *)llx_stage_bytes(v->X, blob.data(), blob.size(), st, v->err);
     if (!d_blob) return LL_ERR_HIP;
     const EnSeg *d_seg = (const EnSeg *)(d_blob + at_seg);
@@ -490,7 +470,7 @@ extern "C" int ll_entropy_run(ll_entropy *v, const ll_entropy_op *ops, int n_ops
                        W.keys, W.vals, v->d_h, v->d_pv, v->d_nn);
     EN_HIP(hipEventRecord(v->ev[1], st));
     if (ll_sort_pairs_reads_back(n)) ++syncs;
-    if (ll_sort_pairs(W.keys, W.vals, W.tmp_keys, W.tmp_vals, n, W.hist, W.tile_sum, W.or_and, st)) return en_fail(v, LL_ERR_HIP, "entropy: the sort's read-back failed");
+    if (ll_sort_pairs(W.keys, W.vals, W.tmp_keys, W.tmp_vals, n, W.hist, W.tile_sum, W.or_and, st)) return v->fail(LL_ERR_HIP, "entropy: the sort's read-back failed");
     hipLaunchKernelGGL(k_en_heads, dim3(nb), dim3(256), 0, st, (const unsigned long long *)W.keys, (const int *)W.vals, (const float4 *)v->d_world, n, W.flag, v->d_spts);
     ll_copy_d2d(W.rank, W.flag, (size_t)n * sizeof(int), st);
     ll_fill_words(W.rank + n, 1, 0, 0, 1, st);
@@ -505,7 +485,7 @@ extern "C" int ll_entropy_run(ll_entropy *v, const ll_entropy_op *ops, int n_ops
     EN_HIP(hipMemcpyAsync(pin_cells, W.rank + n, sizeof(int), hipMemcpyDeviceToHost, st));
     EN_HIP(hipStreamSynchronize(st)); ++syncs;                       /* the one read that sizes the two launches per cell */
     const int ncell = *pin_cells;
-    if (ncell < 1 || ncell > n) return en_fail(v, LL_ERR_HIP, "entropy: " + std::to_string(ncell) + " cells for " + std::to_string(n) + " points");
+    if (ncell < 1 || ncell > n) return v->fail(LL_ERR_HIP, "entropy: " + std::to_string(ncell) + " cells for " + std::to_string(n) + " points");
     hipLaunchKernelGGL(k_en_rows, dim3((unsigned)(((long long)ncell * 9 + 255) / 256)), dim3(256), 0, st, (const unsigned long long *)v->d_ck, (const int *)v->d_cs, ncell, v->d_rows);
     EN_HIP(hipEventRecord(v->ev[3], st));
     hipLaunchKernelGGL(k_en_moments, dim3((unsigned)ncell), dim3(64), 0, st, (const float4 *)v->d_spts, (const int *)W.vals, (const int *)v->d_cs,
@@ -529,29 +509,19 @@ extern "C" int ll_entropy_run(ll_entropy *v, const ll_entropy_op *ops, int n_ops
 extern "C" int ll_entropy_values(ll_entropy *v, int k, float *h, float *pv, unsigned short *nn)
 {
     if (!v) return LL_ERR_ARG;
-    const int rc = en_stale(v); if (rc) return rc;
-    if (k < 0 || k >= (int)v->last_base.size()) return en_fail(v, LL_ERR_ARG, "entropy: the last run listed " + std::to_string(v->last_base.size()) + " frames, there is no frame " + std::to_string(k));
+    int rc = en_stale(v); if (rc) return rc;
+    if (k < 0 || k >= (int)v->last_base.size()) return v->fail(LL_ERR_ARG, "entropy: the last run listed " + std::to_string(v->last_base.size()) + " frames, there is no frame " + std::to_string(k));
     const size_t n = (size_t)v->last_n0[k] + (size_t)v->last_n1[k];
     if (n == 0 || (!h && !pv && !nn)) return LL_OK;
-    unsigned char *pin = (unsigned char *)ll_pinned_scratch(n * 12);
-    if (!pin) return en_fail(v, LL_ERR_HIP, "entropy: no page-locked scratch");
-    hipStream_t st = v->ctx->stream;
     const long long b = v->last_base[k];
-    EN_HIP(hipSetDevice(v->ctx->device));
-    if (h) EN_HIP(hipMemcpyAsync(pin, v->d_h + b, n * 4, hipMemcpyDeviceToHost, st));
-    if (pv) EN_HIP(hipMemcpyAsync(pin + n * 4, v->d_pv + b, n * 4, hipMemcpyDeviceToHost, st));
-    if (nn) EN_HIP(hipMemcpyAsync(pin + n * 8, v->d_nn + b, n * 4, hipMemcpyDeviceToHost, st));
-    EN_HIP(hipStreamSynchronize(st));
-    if (h) std::memcpy(h, pin, n * 4);
-    if (pv) std::memcpy(pv, pin + n * 4, n * 4);
+    const LLKfRange ranges[3] = {{h ? v->d_h + b : nullptr, n * 4, h}, {pv ? v->d_pv + b : nullptr, n * 4, pv}, {nn ? v->d_nn + b : nullptr, n * 4, nullptr}};
+    const unsigned char *pin;
+    rc = v->read("entropy: ", ranges, 3, &pin); if (rc) return rc;
     if (nn) { const int *c = (const int *)(pin + n * 8); for (size_t i = 0; i < n; ++i) nn[i] = (unsigned short)(c[i] > 65535 ? 65535 : c[i]); }
     return LL_OK;
 }
 
 extern "C" int ll_entropy_timing(const ll_entropy *v, double *ms, long long *counts)
 {
-    if (!v) return LL_ERR_ARG;
-    if (ms) for (int k = 0; k < 5; ++k) ms[k] = v->ms[k];
-    if (counts) for (int k = 0; k < 5; ++k) counts[k] = v->counts[k];
-    return LL_OK;
+    return v ? llkf_timing(v->ms, v->counts, 5, ms, counts) : LL_ERR_ARG;
 }

@@ -64,14 +64,16 @@ struct ll_ctx {
 };
 
 
-#define LL_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                    \
-            return LL_ERR_HIP;                                                               \
-        }                                                                                    \
+/* the one check of a HIP call: on an error, return fail(obj, LL_ERR_HIP, prefix + the call as written + ": " + HIP's text).  `text` is
+ * the alias's own #call: stringified there, before any macro in the call's arguments expands.  ll_fail is the plain fail: obj->err */
+template <typename T>
+static inline int ll_fail(T *obj, int rc, const std::string &msg) { obj->err = msg; return rc; }
+#define LL_HIP_CHECK(fail, obj, prefix, call, text)                                                          \
+    do {                                                                                                     \
+        hipError_t e_ = (call);                                                                              \
+        if (e_ != hipSuccess) return fail(obj, LL_ERR_HIP, std::string(prefix) + text ": " + hipGetErrorString(e_)); \
     } while (0)
+#define LL_HIP(call) LL_HIP_CHECK(ll_fail, ctx, "", call, #call)
 
 struct ll_map {
     ll_ctx *ctx = nullptr;
@@ -93,11 +95,7 @@ struct ll_map {
     std::string err;
 };
 
-#define LLM_HIP(call)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) { m->err = std::string(#call) + ": " + hipGetErrorString(e_); return LL_ERR_HIP; } \
-    } while (0)
+#define LLM_HIP(call) LL_HIP_CHECK(ll_fail, m, "", call, #call)
 
 template <typename T>
 static inline bool map_alloc(ll_map *m, T *&ptr, size_t count) { return ll_dev_alloc(m->allocs, m->err, ptr, count, true); }

@@ -53,7 +53,33 @@ extern "C" int ll_keyframes_reset(ll_keyframes *kf)
 {
     if (!kf) return LL_ERR_ARG;
     kf->tab.clear(); kf->top[0] = kf->top[1] = 0;
-    ++kf->n_reset;                                                /* an ll_visibility's counters mean nothing from here on */
+    ++kf->n_reset;                                                /* what a follower (LLKfReader) kept of the old table means nothing from here on */
+    return LL_OK;
+}
+
+void LLKfReader::release()
+{
+    if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
+    llx_free(X);
+}
+
+#define KFR_HIP(call) LL_HIP_CHECK(ll_fail, this, who, call, #call)
+int LLKfReader::read(const char *who, const LLKfRange *ranges, int n, const unsigned char **pin_out)
+{
+    size_t total = 0;
+    for (int r = 0; r < n; ++r) total += ranges[r].bytes;
+    unsigned char *pin = (unsigned char *)ll_pinned_scratch(total);
+    if (!pin) return fail(LL_ERR_HIP, std::string(who) + "no page-locked scratch");
+    hipStream_t st = ctx->stream;
+    KFR_HIP(hipSetDevice(ctx->device));
+    size_t at = 0;
+    for (int r = 0; r < n; at += ranges[r++].bytes)
+        if (ranges[r].src && ranges[r].bytes) KFR_HIP(hipMemcpyAsync(pin + at, ranges[r].src, ranges[r].bytes, hipMemcpyDeviceToHost, st));
+    KFR_HIP(hipStreamSynchronize(st));
+    at = 0;
+    for (int r = 0; r < n; at += ranges[r++].bytes)
+        if (ranges[r].src && ranges[r].bytes && ranges[r].dst) std::memcpy(ranges[r].dst, pin + at, ranges[r].bytes);
+    if (pin_out) *pin_out = pin;
     return LL_OK;
 }
 

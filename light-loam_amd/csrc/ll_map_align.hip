@@ -340,11 +340,7 @@ void llal_free(LLMapAlign &A)
     A = LLMapAlign();
 }
 
-#define AL_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return llcms_fail(cms, LL_ERR_HIP, std::string("map align: " #call ": ") + hipGetErrorString(e_)); \
-    } while (0)
+#define AL_HIP(call) LL_HIP_CHECK(llcms_fail, cms, "map align: ", call, #call)
 
 /* a map in one role: which of its cubes hold points of type w, and how many in all */
 struct AlCloud { int map, w; long long n, first; int slot0, nslot; };

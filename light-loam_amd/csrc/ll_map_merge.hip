@@ -245,11 +245,7 @@ static unsigned char *mm_reserve(LLMapMerge &G, int k, size_t bytes, std::string
 
 static const char *mm_type(int w) { return w ? "surf" : "corner"; }
 
-#define MM_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return llcms_fail(cms, LL_ERR_HIP, J.what + #call ": " + hipGetErrorString(e_)); \
-    } while (0)
+#define MM_HIP(call) LL_HIP_CHECK(llcms_fail, cms, J.what, call, #call)
 
 static int mm_gather(ll_cubemaps *cms, const std::string &what, std::vector<MmCopy> &ops, hipStream_t st)
 {
@@ -578,6 +574,7 @@ static int kf_insert(ll_cubemaps *cms, const ll_keyframes *kf, const ll_visibili
         if (rc) return llcms_fail(cms, rc, what + why);
     }
     const int S = llcms_size(cms), size = (int)kf->tab.size();
+    const ll_keyframe_info *tab = kf->tab.data();
     /* ---- every refusal that needs no look at a point: before anything is enqueued */
     std::vector<char> is_dst(S, 0);
     for (int i = 0; i < n_ops; ++i) {
@@ -591,11 +588,9 @@ static int kf_insert(ll_cubemaps *cms, const ll_keyframes *kf, const ll_visibili
         if (o.reset)
             for (int k = 0; k < 3; ++k)
                 if (o.cen[k] < -(1 << 24) || o.cen[k] > (1 << 24)) return llcms_fail(cms, LL_ERR_ARG, who + "cen[" + std::to_string(k) + "] = " + std::to_string(o.cen[k]) + " is outside the cube array's reach");
-        for (int f = 0; f < o.n_frames; ++f) {
-            if (o.frames[f] < 0 || o.frames[f] >= size) return llcms_fail(cms, LL_ERR_ARG, who + "frame " + std::to_string(o.frames[f]) + " is not in the store (size " + std::to_string(size) + ")");
-            const double *P = o.poses_w7 ? o.poses_w7 + (size_t)f * 7 : kf->tab[o.frames[f]].pose_w7;
-            for (int k = 0; k < 7; ++k) if (!std::isfinite(P[k])) return llcms_fail(cms, LL_ERR_ARG, who + "the pose of list entry " + std::to_string(f) + " is not finite");
-        }
+        std::string why;
+        long long pts;
+        if (llkf_check(tab, size, {o.n_frames, o.frames, o.poses_w7, ""}, LLKF_DUP_ALLOWED, nullptr, i, who, &why, &pts)) return llcms_fail(cms, LL_ERR_ARG, why);
     }
     for (int i = 0; i < n_ops; ++i)
         if (llcms_map(cms, ops[i].dst)->broken) return llcms_fail(cms, LL_ERR_STATE, what + "op " + std::to_string(i) + ": map " + std::to_string(ops[i].dst) + " is unusable, an earlier update failed half-way");
@@ -610,6 +605,7 @@ static int kf_insert(ll_cubemaps *cms, const ll_keyframes *kf, const ll_visibili
     for (int i = 0; i < n_ops; ++i) {
         const ll_insert_op &o = ops[i];
         const ll_cubemap *dst = llcms_map(cms, o.dst);
+        const LLKfList list = {o.n_frames, o.frames, o.poses_w7, ""};
         J.ops.push_back({o.dst, o.reset, {o.cen[0], o.cen[1], o.cen[2]}, "map " + std::to_string(o.dst) + " <- " + std::to_string(o.n_frames) + " keyframes"});
         for (int w = 0; w < 2; ++w) {
             MmRec &R = J.recs[2 * i + w];
@@ -617,12 +613,12 @@ static int kf_insert(ll_cubemaps *cms, const ll_keyframes *kf, const ll_visibili
             for (int k = 0; k < 3; ++k) R.cen[k] = o.reset ? o.cen[k] : dst->cen[k];
             long long n = 0;
             for (int f = 0; f < o.n_frames; ++f) {
-                const ll_keyframe_info &e = kf->tab[o.frames[f]];
-                const int cnt = e.n[w];
+                const LLKfCloud c = llkf_cloud(tab, kf->cap[0], o.frames[f], w);
+                const int cnt = c.cnt;
                 if (cnt <= 0) continue;
                 if (N + n + cnt > (1ll << 30)) return llcms_fail(cms, LL_ERR_CAPACITY, what + "more than 2^30 source points in one call");
-                KfSeg s = {kf->region(w) + e.offset[w], (int)(N + n), cnt, tiles.take(cnt), 2 * i + w, {}};
-                const double *P = o.poses_w7 ? o.poses_w7 + (size_t)f * 7 : e.pose_w7;
+                KfSeg s = {kf->pool + c.off, (int)(N + n), cnt, tiles.take(cnt), 2 * i + w, {}};
+                const double *P = llkf_pose(tab, list, f);
                 for (int k = 0; k < 7; ++k) s.T[k] = P[k];
                 segs.push_back(s);
                 n += cnt;

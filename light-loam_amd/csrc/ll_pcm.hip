@@ -224,11 +224,7 @@ __global__ __launch_bounds__(256) void k_pcm_pick(const PcmGraph *__restrict__ g
 
 /* ------------------------------------------------------------------ host side */
 static int pcm_fail(ll_pcm *v, int rc, const std::string &msg) { v->err = "pcm: " + msg; return rc; }
-#define PCM_HIP(call)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return pcm_fail(v, LL_ERR_HIP, std::string(#call ": ") + hipGetErrorString(e_)); \
-    } while (0)
+#define PCM_HIP(call) LL_HIP_CHECK(pcm_fail, v, "", call, #call)
 
 extern "C" void ll_pcm_default_params(ll_pcm_params *p)
 {

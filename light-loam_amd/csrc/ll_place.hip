@@ -270,11 +270,7 @@ __global__ __launch_bounds__(256) void k_pl_select(const float *dist, const unsi
 /* ------------------------------------------------------------------ host side */
 static int pl_fail(ll_places *db, int code, const std::string &what) { db->err = what; return code; }
 
-#define PL_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return pl_fail(db, LL_ERR_HIP, std::string("places: " #call ": ") + hipGetErrorString(e_)); \
-    } while (0)
+#define PL_HIP(call) LL_HIP_CHECK(pl_fail, db, "places: ", call, #call)
 
 template <typename T>
 static bool pl_grow(T *&ptr, size_t &cap, size_t bytes)

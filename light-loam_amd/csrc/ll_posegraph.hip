@@ -983,11 +983,7 @@ __global__ __launch_bounds__(64) void k_pg_cov_gather(const PgCovQuery *qry, con
 /* ------------------------------------------------------------------ host side */
 static int pg_fail(ll_posegraphs *pg, int code, const std::string &what) { pg->err = "posegraphs: " + what; return code; }
 
-#define PG_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return pg_fail(pg, LL_ERR_HIP, std::string(#call ": ") + hipGetErrorString(e_)); \
-    } while (0)
+#define PG_HIP(call) LL_HIP_CHECK(pg_fail, pg, "", call, #call)
 
 static size_t pg_up8(size_t b) { return (b + 7) & ~(size_t)7; }
 

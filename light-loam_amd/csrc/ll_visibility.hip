@@ -133,13 +133,8 @@ __global__ __launch_bounds__(256) void k_vis_vote(const float4 *__restrict__ poo
 }
 
 /* ------------------------------------------------------------------ host side */
-static int vis_fail(ll_visibility *v, int rc, const std::string &msg) { v->err = msg; return rc; }
-static int vis_kf_err(ll_keyframes *kf, int rc, const std::string &msg) { kf->err = msg; return rc; }   /* create: there is no object yet */
-#define VIS_HIP(call)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return vis_fail(v, LL_ERR_HIP, std::string("visibility: " #call ": ") + hipGetErrorString(e_)); \
-    } while (0)
+#define VIS_HIP(call) LL_HIP_CHECK(ll_fail, v, "visibility: ", call, #call)
+#define VIS_RESET_SINCE "the store was reset since the counters were made: call ll_visibility_reset"
 
 extern "C" void ll_visibility_default_params(ll_visibility_params *p)
 {
@@ -168,12 +163,12 @@ extern "C" int ll_visibility_create(ll_keyframes *kf, const ll_visibility_params
         !(p->el_max_deg <= 89.0f) || p->max_images < 2 || p->max_images > (1 << 16) || !(p->min_range >= 0.0f) || !(p->max_range > p->min_range) ||
         !std::isfinite(p->max_range) || !(p->margin_abs >= 0.0f) || !(p->margin_rel >= 0.0f) || !std::isfinite(p->margin_abs) ||
         !std::isfinite(p->margin_rel) || !(p->radius >= 0.0f) || !std::isfinite(p->radius))
-        return vis_kf_err(kf, LL_ERR_ARG, "visibility: bad parameters (width in 8 .. 4096, height in 2 .. 1024, -89 <= el_min_deg < el_max_deg <= 89, "
+        return llkf_create_err(kf, LL_ERR_ARG, "visibility: bad parameters (width in 8 .. 4096, height in 2 .. 1024, -89 <= el_min_deg < el_max_deg <= 89, "
                                           "max_images in 2 .. 2^16, 0 <= min_range < max_range, margins and radius finite and >= 0)");
     ll_ctx *ctx = kf->ctx;
-    if (hipSetDevice(ctx->device) != hipSuccess) return vis_kf_err(kf, LL_ERR_HIP, "visibility: hipSetDevice failed");
+    if (hipSetDevice(ctx->device) != hipSuccess) return llkf_create_err(kf, LL_ERR_HIP, "visibility: hipSetDevice failed");
     ll_visibility *v = new ll_visibility();
-    v->ctx = ctx; v->kf = kf; v->p = *p; v->epoch = kf->n_reset;
+    v->follow(kf); v->p = *p;
     const size_t n_cnt = (size_t)(kf->cap[0] + kf->cap[1]) * 2, n_pix = (size_t)p->max_images * p->width * p->height;
     bool ok = hipMalloc((void **)&v->d_cnt, n_cnt) == hipSuccess && hipMalloc((void **)&v->d_raw, n_pix * 4) == hipSuccess &&
               hipMalloc((void **)&v->d_img, n_pix * 4) == hipSuccess;
@@ -182,7 +177,7 @@ extern "C" int ll_visibility_create(ll_keyframes *kf, const ll_visibility_params
     if (!ok) {
         (void)hipGetLastError();
         ll_visibility_destroy(v);
-        return vis_kf_err(kf, LL_ERR_HIP, "visibility: no device memory for " + std::to_string(n_cnt) + " counter bytes and 2 x " + std::to_string(n_pix) + " pixels");
+        return llkf_create_err(kf, LL_ERR_HIP, "visibility: no device memory for " + std::to_string(n_cnt) + " counter bytes and 2 x " + std::to_string(n_pix) + " pixels");
     }
     *out = v;
     return LL_OK;
@@ -191,22 +186,17 @@ extern "C" int ll_visibility_create(ll_keyframes *kf, const ll_visibility_params
 extern "C" void ll_visibility_destroy(ll_visibility *v)
 {
     if (!v) return;
-    if (v->ctx) { (void)hipSetDevice(v->ctx->device); (void)hipStreamSynchronize(v->ctx->stream); }
+    v->release();
     if (v->d_cnt) (void)hipFree(v->d_cnt);
     if (v->d_raw) (void)hipFree(v->d_raw);
     if (v->d_img) (void)hipFree(v->d_img);
     for (int k = 0; k < 4; ++k) if (v->ev[k]) (void)hipEventDestroy(v->ev[k]);
-    llx_free(v->X);
     delete v;
 }
 
 extern "C" const char *ll_visibility_last_error(const ll_visibility *v) { return v ? v->err.c_str() : "null visibility"; }
 
-static int vis_stale(ll_visibility *v)
-{
-    if (v->epoch == v->kf->n_reset) return LL_OK;
-    return vis_fail(v, LL_ERR_STATE, "visibility: the store was reset since the counters were made: call ll_visibility_reset");
-}
+static int vis_stale(ll_visibility *v) { return v->stale("visibility: " VIS_RESET_SINCE); }
 
 extern "C" int ll_visibility_reset(ll_visibility *v)
 {
@@ -221,27 +211,22 @@ extern "C" int ll_visibility_reset(ll_visibility *v)
 extern "C" int ll_visibility_run(ll_visibility *v, const ll_visibility_op *ops, int n_ops, long long *pairs)
 {
     if (!v) return LL_ERR_ARG;
-    if (!ops || n_ops < 1) return vis_fail(v, LL_ERR_ARG, "visibility: ops is NULL or n_ops < 1");
+    if (!ops || n_ops < 1) return v->fail(LL_ERR_ARG, "visibility: ops is NULL or n_ops < 1");
     const ll_keyframes *kf = v->kf;
+    const ll_keyframe_info *tab = kf->tab.data();
     const int size = (int)kf->tab.size();
     /* ---- every refusal before anything is enqueued or a counter changes */
     long long L = 0;
-    std::vector<char> seen(size, 0);
+    std::vector<int> seen(size, -1);
     for (int i = 0; i < n_ops; ++i) {
         const ll_visibility_op &o = ops[i];
         const std::string who = "visibility: op " + std::to_string(i) + ": ";
-        if (o.n_frames < 0 || (o.n_frames > 0 && !o.frames)) return vis_fail(v, LL_ERR_ARG, who + "n_frames < 0 or frames is NULL");
-        for (int f = 0; f < o.n_frames; ++f) {
-            const int id = o.frames[f];
-            if (id < 0 || id >= size) return vis_fail(v, LL_ERR_ARG, who + "frame " + std::to_string(id) + " is not in the store (size " + std::to_string(size) + ")");
-            if (seen[id]) return vis_fail(v, LL_ERR_ARG, who + "frame " + std::to_string(id) + " is listed twice in this call");
-            seen[id] = 1;
-            const double *P = o.poses_w7 ? o.poses_w7 + (size_t)f * 7 : kf->tab[id].pose_w7;
-            for (int k = 0; k < 7; ++k) if (!std::isfinite(P[k])) return vis_fail(v, LL_ERR_ARG, who + "the pose of list entry " + std::to_string(f) + " is not finite");
-        }
+        if (o.n_frames < 0 || (o.n_frames > 0 && !o.frames)) return v->fail(LL_ERR_ARG, who + "n_frames < 0 or frames is NULL");
+        long long pts;
+        if (llkf_check(tab, size, {o.n_frames, o.frames, o.poses_w7, ""}, LLKF_DUP_PER_CALL, &seen, i, who, &v->err, &pts)) return LL_ERR_ARG;
         L += o.n_frames;
     }
-    if (L > (long long)v->p.max_images) return vis_fail(v, LL_ERR_CAPACITY, "visibility: " + std::to_string(L) + " listed frames, max_images is " + std::to_string(v->p.max_images));
+    if (L > (long long)v->p.max_images) return v->fail(LL_ERR_CAPACITY, "visibility: " + std::to_string(L) + " listed frames, max_images is " + std::to_string(v->p.max_images));
     int rc = vis_stale(v); if (rc) return rc;
     /* ---- the tables: clouds, poses, observers (CSR over list positions) */
     std::vector<VisSeg> segs;
@@ -253,15 +238,16 @@ extern "C" int ll_visibility_run(ll_visibility *v, const ll_visibility_op *ops, 
     int k0 = 0;
     for (int i = 0; i < n_ops; ++i) {
         const ll_visibility_op &o = ops[i];
+        const LLKfList list = {o.n_frames, o.frames, o.poses_w7, ""};
         for (int f = 0; f < o.n_frames; ++f) {
-            const ll_keyframe_info &e = kf->tab[o.frames[f]];
-            const double *P = o.poses_w7 ? o.poses_w7 + (size_t)f * 7 : e.pose_w7;
+            const double *P = llkf_pose(tab, list, f);
             for (int k = 0; k < 7; ++k) poses[(size_t)(k0 + f) * 7 + k] = P[k];
             listed[k0 + f] = o.frames[f];
             for (int w = 0; w < 2; ++w) {
-                if (e.n[w] <= 0) continue;
-                segs.push_back({(w ? kf->cap[0] : 0) + e.offset[w], e.n[w], tiles.take(e.n[w]), k0 + f, 0});
-                n_points += e.n[w];
+                const LLKfCloud c = llkf_cloud(tab, kf->cap[0], o.frames[f], w);
+                if (c.cnt <= 0) continue;
+                segs.push_back({c.off, c.cnt, tiles.take(c.cnt), k0 + f, 0});
+                n_points += c.cnt;
             }
         }
         long long np = 0;
@@ -279,7 +265,7 @@ extern "C" int ll_visibility_run(ll_visibility *v, const ll_visibility_op *ops, 
         n_pairs += np;
         k0 += o.n_frames;
     }
-    if (!ll_grid_fits(obs.size()) || !tiles.fits()) return vis_fail(v, LL_ERR_CAPACITY, "visibility: too many frame pairs or tiles for one call");
+    if (!ll_grid_fits(obs.size()) || !tiles.fits()) return v->fail(LL_ERR_CAPACITY, "visibility: too many frame pairs or tiles for one call");
     v->last = listed;
     v->ms[0] = v->ms[1] = v->ms[2] = 0.0;
     v->counts[0] = L; v->counts[1] = n_points; v->counts[2] = n_pairs;
@@ -313,54 +299,37 @@ extern "C" int ll_visibility_run(ll_visibility *v, const ll_visibility_op *ops, 
 extern "C" int ll_visibility_counts(ll_visibility *v, int frame, unsigned char *through_hit)
 {
     if (!v) return LL_ERR_ARG;
-    if (!through_hit) return vis_fail(v, LL_ERR_ARG, "visibility: through_hit is NULL");
+    if (!through_hit) return v->fail(LL_ERR_ARG, "visibility: through_hit is NULL");
     const ll_keyframes *kf = v->kf;
-    if (frame < 0 || frame >= (int)kf->tab.size()) return vis_fail(v, LL_ERR_ARG, "visibility: frame " + std::to_string(frame) + " is not in the store (size " + std::to_string(kf->tab.size()) + ")");
+    long long pts;                                                  /* a list of one: the stored pose is finite, add refuses others */
+    if (llkf_check(kf->tab.data(), (int)kf->tab.size(), {1, &frame, nullptr, ""}, LLKF_DUP_ALLOWED, nullptr, 0, "visibility: ", &v->err, &pts)) return LL_ERR_ARG;
     const int rc = vis_stale(v); if (rc) return rc;
-    const ll_keyframe_info &e = kf->tab[frame];
-    const size_t n0 = (size_t)e.n[0] * 2, n1 = (size_t)e.n[1] * 2;
-    if (n0 + n1 == 0) return LL_OK;
-    unsigned char *pin = (unsigned char *)ll_pinned_scratch(n0 + n1);
-    if (!pin) return vis_fail(v, LL_ERR_HIP, "visibility: no page-locked scratch");
-    hipStream_t st = v->ctx->stream;
-    VIS_HIP(hipSetDevice(v->ctx->device));
-    if (n0) VIS_HIP(hipMemcpyAsync(pin, v->d_cnt + (size_t)e.offset[0] * 2, n0, hipMemcpyDeviceToHost, st));
-    if (n1) VIS_HIP(hipMemcpyAsync(pin + n0, v->d_cnt + (size_t)(kf->cap[0] + e.offset[1]) * 2, n1, hipMemcpyDeviceToHost, st));
-    VIS_HIP(hipStreamSynchronize(st));
-    std::memcpy(through_hit, pin, n0 + n1);
-    return LL_OK;
+    if (pts == 0) return LL_OK;
+    const LLKfCloud c0 = llkf_cloud(kf->tab.data(), kf->cap[0], frame, 0), c1 = llkf_cloud(kf->tab.data(), kf->cap[0], frame, 1);
+    const size_t n0 = (size_t)c0.cnt * 2, n1 = (size_t)c1.cnt * 2;
+    const LLKfRange ranges[2] = {{v->d_cnt + (size_t)c0.off * 2, n0, through_hit}, {v->d_cnt + (size_t)c1.off * 2, n1, through_hit + n0}};
+    return v->read("visibility: ", ranges, 2);
 }
 
 extern "C" int ll_visibility_images(ll_visibility *v, int k, float *raw, float *img)
 {
     if (!v) return LL_ERR_ARG;
-    if (k < 0 || k >= (int)v->last.size()) return vis_fail(v, LL_ERR_ARG, "visibility: the last run listed " + std::to_string(v->last.size()) + " frames, there is no image " + std::to_string(k));
+    if (k < 0 || k >= (int)v->last.size()) return v->fail(LL_ERR_ARG, "visibility: the last run listed " + std::to_string(v->last.size()) + " frames, there is no image " + std::to_string(k));
     const size_t HW = (size_t)v->p.width * v->p.height, bytes = HW * sizeof(float);
     if (!raw && !img) return LL_OK;
-    unsigned char *pin = (unsigned char *)ll_pinned_scratch(2 * bytes);
-    if (!pin) return vis_fail(v, LL_ERR_HIP, "visibility: no page-locked scratch");
-    hipStream_t st = v->ctx->stream;
-    VIS_HIP(hipSetDevice(v->ctx->device));
-    if (raw) VIS_HIP(hipMemcpyAsync(pin, v->d_raw + (size_t)k * HW, bytes, hipMemcpyDeviceToHost, st));
-    if (img) VIS_HIP(hipMemcpyAsync(pin + bytes, v->d_img + (size_t)k * HW, bytes, hipMemcpyDeviceToHost, st));
-    VIS_HIP(hipStreamSynchronize(st));
-    if (raw) std::memcpy(raw, pin, bytes);
-    if (img) std::memcpy(img, pin + bytes, bytes);
-    return LL_OK;
+    const LLKfRange ranges[2] = {{raw ? v->d_raw + (size_t)k * HW : nullptr, bytes, raw}, {img ? v->d_img + (size_t)k * HW : nullptr, bytes, img}};
+    return v->read("visibility: ", ranges, 2);
 }
 
 extern "C" int ll_visibility_timing(const ll_visibility *v, double *ms, long long *counts)
 {
-    if (!v) return LL_ERR_ARG;
-    if (ms) for (int k = 0; k < 3; ++k) ms[k] = v->ms[k];
-    if (counts) for (int k = 0; k < 3; ++k) counts[k] = v->counts[k];
-    return LL_OK;
+    return v ? llkf_timing(v->ms, v->counts, 3, ms, counts) : LL_ERR_ARG;
 }
 
 /* for the filtered insert (ll_map_merge.hip): is v usable with kf?  LL_OK, or the status with *why filled */
 int llvis_check(const ll_visibility *v, const ll_keyframes *kf, std::string *why)
 {
     if (v->kf != kf) { *why = "the visibility object belongs to another store"; return LL_ERR_ARG; }
-    if (v->epoch != kf->n_reset) { *why = "the store was reset since the counters were made: call ll_visibility_reset"; return LL_ERR_STATE; }
+    if (v->epoch != kf->n_reset) { *why = VIS_RESET_SINCE; return LL_ERR_STATE; }
     return LL_OK;
 }
