@@ -27,6 +27,7 @@
 #include "ll_keyframes.h"
 #include "ll_map_export.h"
 #include "ll_map_search.h"
+#include "ll_pose_math.h"
 #include "ll_tiles.h"
 #include <cmath>
 
@@ -403,37 +404,13 @@ extern "C" int ll_bev_timing(const ll_bev *b, double *ms, long long *counts)
     return b ? llkf_timing(b->ms, b->counts, 3, ms, counts) : LL_ERR_ARG;
 }
 
-/* ---- T0 = P_c o D o P_q^-1, plain host f64 (the header spells the operations) */
-static void bev_rotate(const double *q, const double *v, double *r)
-{
-    const double ux = q[0], uy = q[1], uz = q[2], w = q[3];
-    double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
-    uvx += uvx; uvy += uvy; uvz += uvz;
-    r[0] = (v[0] + w * uvx) + (uy * uvz - uz * uvy);
-    r[1] = (v[1] + w * uvy) + (uz * uvx - ux * uvz);
-    r[2] = (v[2] + w * uvz) + (ux * uvy - uy * uvx);
-}
-
-static void bev_compose(const double *A, const double *B, double *out)
-{
-    const double ax = A[0], ay = A[1], az = A[2], aw = A[3], bx = B[0], by = B[1], bz = B[2], bw = B[3];
-    double r[3];
-    bev_rotate(A, B + 4, r);
-    out[0] = aw * bx + ax * bw + ay * bz - az * by;
-    out[1] = aw * by - ax * bz + ay * bw + az * bx;
-    out[2] = aw * bz + ax * by - ay * bx + az * bw;
-    out[3] = aw * bw - ax * bx - ay * by - az * bz;
-    for (int k = 0; k < 3; ++k) out[4 + k] = r[k] + A[4 + k];
-}
-
+/* ---- T0 = P_c o D o P_q^-1, plain host f64 in the Eigen form (the header spells the operations; ll_pose_math.h is their text) */
 extern "C" int ll_bev_guess(const double *Pc_w7, const double *D_w7, const double *Pq_w7, double *T0_w7)
 {
     if (!Pc_w7 || !D_w7 || !Pq_w7 || !T0_w7) return LL_ERR_ARG;
-    double inv[7] = {-Pq_w7[0], -Pq_w7[1], -Pq_w7[2], Pq_w7[3], 0.0, 0.0, 0.0}, r[3], DQ[7], T[7];
-    bev_rotate(inv, Pq_w7 + 4, r);
-    for (int k = 0; k < 3; ++k) inv[4 + k] = -r[k];
-    bev_compose(D_w7, inv, DQ);
-    bev_compose(Pc_w7, DQ, T);
-    for (int k = 0; k < 7; ++k) T0_w7[k] = T[k];
+    double T[7];
+    ll_pose_inverse(Pq_w7, T);
+    ll_pose_compose(D_w7, T, T);
+    ll_pose_compose(Pc_w7, T, T0_w7);
     return LL_OK;
 }

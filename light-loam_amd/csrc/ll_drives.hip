@@ -7,9 +7,9 @@
  *   transformAssociateToMap, laserMapping.cpp:113-117, straight into the cube maps' pose array), the cube-map frame from those
  *   guesses (ll_cubemaps.hip: they come to the host with the slot headers it reads back anyway), k_drives_update
  *   (transformUpdate, :119-123) and, with keep_registered, k_drives_register (pointAssociateToMap of laserCloud, :125-133).
- * The pose arithmetic restates lightloam::WorldPose::compose and LaserMapping::qmul / qrot (lightloam_host.hpp;
- * qrot is ll_rotate of ll_factor_math.h) in their operation order, in double; the library is built with -ffp-contract=off, so it is bit for bit the host's.  No fma(), no
- * reassociation here.
+ * The pose arithmetic is ll_pose_math.h's Eigen form -- ll_qmul, ll_rotate, ll_pose_compose: lightloam::WorldPose::compose and
+ * LaserMapping::qmul / qrot (lightloam_host.hpp) in their operation order, in double; the library is built with -ffp-contract=off,
+ * so it is bit for bit the host's.
  * A lane may instead localise against another lane's frozen map (ll_drives_set_localize): the same chain with the read-only frame
  * of ll_cubemaps_localize_slots in place of the mapping frame; a step runs the mapping lanes' frame, then the localising lanes',
  * and refuses beforehand any command set in which one would write what the other reads.
@@ -18,14 +18,6 @@
 #include "ll_keyframes.h"
 #include "ll_factor_math.h"
 #include <cmath>
-
-/* a * b, LaserMapping::qmul */
-__device__ __forceinline__ void drv_qmul(const double *a, const double *b, double *o)
-{
-    const double ax = a[0], ay = a[1], az = a[2], aw = a[3], bx = b[0], by = b[1], bz = b[2], bw = b[3];
-    o[0] = aw * bx + ax * bw + ay * bz - az * by; o[1] = aw * by - ax * bz + ay * bw + az * bx;
-    o[2] = aw * bz + ax * by - ay * bx + az * bw; o[3] = aw * bw - ax * bx - ay * by - az * bz;
-}
 
 /* per lane: odom [S][7] = q_w_curr, t_w_curr (laserOdometry); m2o [S][7] = q_wmap_wodom, t_wmap_wodom (laserMapping);
  * start [S][7] = what START sets m2o to (ll_drives_set_localize; identity rows for mapping lanes) */
@@ -42,25 +34,13 @@ __global__ __launch_bounds__(64) void k_drives_associate(double *vpose, int firs
         for (int k = 0; k < 7; ++k) slot_pose[k] = pose0[(size_t)q * 7 + k];     /* the warm start of frame 1 (:61-65) */
         fidx[q] = 0;
     } else {                                                                      /* WorldPose::compose (:830-831), kept as the host spells it: W is updated in place, t before q */
-        const double ql[4] = {slot_pose[0], slot_pose[1], slot_pose[2], slot_pose[3]}, tl[3] = {slot_pose[4], slot_pose[5], slot_pose[6]};
-        const double ux = W[0], uy = W[1], uz = W[2], w = W[3];
-        double uv[3] = {uy * tl[2] - uz * tl[1], uz * tl[0] - ux * tl[2], ux * tl[1] - uy * tl[0]};
-        for (int k = 0; k < 3; ++k) uv[k] += uv[k];
-        W[4] += (tl[0] + w * uv[0]) + (uy * uv[2] - uz * uv[1]);
-        W[5] += (tl[1] + w * uv[1]) + (uz * uv[0] - ux * uv[2]);
-        W[6] += (tl[2] + w * uv[2]) + (ux * uv[1] - uy * uv[0]);
-        const double ax = W[0], ay = W[1], az = W[2], aw = W[3], bx = ql[0], by = ql[1], bz = ql[2], bw = ql[3];
-        W[3] = aw * bw - ax * bx - ay * by - az * bz;
-        W[0] = aw * bx + ax * bw + ay * bz - az * by;
-        W[1] = aw * by - ax * bz + ay * bw + az * bx;
-        W[2] = aw * bz + ax * by - ay * bx + az * bw;
+        double r[3];
+        ll_rotate(W, slot_pose + 4, r);
+        for (int k = 0; k < 3; ++k) W[4 + k] += r[k];
+        ll_qmul(W, slot_pose, W);
         fidx[q] += 1;
     }
-    double P[7], r[3];                                                            /* transformAssociateToMap (:113-117) */
-    drv_qmul(M, W, P);
-    ll_rotate(M, W + 4, r);
-    for (int k = 0; k < 3; ++k) P[4 + k] = r[k] + M[4 + k];
-    for (int k = 0; k < 7; ++k) map_pose[(size_t)q * 7 + k] = P[k];
+    ll_pose_compose(M, W, map_pose + (size_t)q * 7);                              /* transformAssociateToMap (:113-117) */
 }
 
 /* transformUpdate (:119-123) from the mapped parameters[] of every running lane */
@@ -73,7 +53,7 @@ __global__ __launch_bounds__(64) void k_drives_update(int S, const int *cmd, con
     const double n2 = qc[0] * qc[0] + qc[1] * qc[1] + qc[2] * qc[2] + qc[3] * qc[3];
     const double inv[4] = {-qc[0] / n2, -qc[1] / n2, -qc[2] / n2, qc[3] / n2};
     double qm[4], r[3];
-    drv_qmul(P, inv, qm);
+    ll_qmul(P, inv, qm);
     ll_rotate(qm, tc, r);
     for (int k = 0; k < 4; ++k) M[k] = qm[k];
     for (int k = 0; k < 3; ++k) M[4 + k] = P[4 + k] - r[k];
@@ -97,18 +77,14 @@ __global__ __launch_bounds__(256) void k_drives_register(LLView V, const DrvReg 
 }
 
 /* ll_drives_correct: the map-to-odom pose of every selected lane left-multiplied by its C (q_C, t_C), spelled as
- * transformAssociateToMap spells its products: q' = q_C * q_m2o, t' = R(q_C) t_m2o + t_C */
+ * transformAssociateToMap spells its products (ll_pose_compose): q' = q_C * q_m2o, t' = R(q_C) t_m2o + t_C */
 __global__ __launch_bounds__(64) void k_drives_correct(int S, const int *sel, const double *C, double *m2o)
 {
     const int q = blockIdx.x * 64 + threadIdx.x;
     if (q >= S || !sel[q]) return;
     const double *Cq = C + (size_t)q * 7;
     double *M = m2o + (size_t)q * 7;
-    double P[7], r[3];
-    drv_qmul(Cq, M, P);
-    ll_rotate(Cq, M + 4, r);
-    for (int k = 0; k < 3; ++k) P[4 + k] = r[k] + Cq[4 + k];
-    for (int k = 0; k < 7; ++k) M[k] = P[k];
+    ll_pose_compose(Cq, M, M);
 }
 
 /* ll_drives_restore: the state of one record out of the uploaded blob -- the slot's pose and header (as ll_upload_features

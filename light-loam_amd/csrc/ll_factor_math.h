@@ -6,21 +6,11 @@
  */
 #pragma once
 #include "ll_common.h"
+#include "ll_pose_math.h"
 
 struct Pose { double q[4], t[3]; };
 
-/* q (x, y, z, w) * v: Eigen's _transformVector, uv = u x v; uv += uv; v + w*uv + u x uv (LaserMapping::qrot on the host) */
-__device__ __forceinline__ void ll_rotate(const double q[4], const double v[3], double out[3])
-{
-    const double ux = q[0], uy = q[1], uz = q[2], w = q[3];
-    double uvx = uy * v[2] - uz * v[1], uvy = uz * v[0] - ux * v[2], uvz = ux * v[1] - uy * v[0];
-    uvx += uvx; uvy += uvy; uvz += uvz;
-    out[0] = (v[0] + w * uvx) + (uy * uvz - uz * uvy);
-    out[1] = (v[1] + w * uvy) + (uz * uvx - ux * uvz);
-    out[2] = (v[2] + w * uvz) + (ux * uvy - uy * uvx);
-}
-
-/* spells ll_rotate out once more: the Jacobian reuses uv (d lp / d w) */
+/* spells ll_rotate (ll_pose_math.h) out once more: the Jacobian reuses uv (d lp / d w) */
 __device__ __forceinline__ void ll_lp_and_jac(const Pose &P, const double v[3], double lp[3], double Jq[3][4])
 {
     const double ux = P.q[0], uy = P.q[1], uz = P.q[2], w = P.q[3];
@@ -218,7 +208,8 @@ __device__ __forceinline__ int ll_chol_solve(const double H[36], const double g[
     return 0;
 }
 
-/* EigenQuaternionManifold::Plus: q+ = [sin|d| d/|d|, cos|d|] (x) q ; t += dt  (laserOdometry.cpp:476-477) */
+/* EigenQuaternionManifold::Plus: q+ = [sin|d| d/|d|, cos|d|] (x) q ; t += dt  (laserOdometry.cpp:476-477).  The product is ll_qmul's,
+ * kept spelled out in place: through ll_qmul the hot path's kernels schedule differently */
 __device__ __forceinline__ void ll_pose_plus(double *pose, const double d[6])
 {
     const double n2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];

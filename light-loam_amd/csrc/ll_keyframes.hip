@@ -13,6 +13,7 @@
  */
 #include "ll_keyframes.h"
 #include "ll_cubemaps.h"
+#include "ll_pose_math.h"
 #include <cmath>
 
 static int kf_fail(ll_keyframes *kf, int rc, const std::string &msg) { kf->err = msg; return rc; }
@@ -109,8 +110,6 @@ int llkf_room(ll_keyframes *kf, int n_frames, const int max_pts[2])
     return kf_room(kf, n_frames, need);
 }
 
-static bool kf_finite7(const double *p) { for (int k = 0; k < 7; ++k) if (!std::isfinite(p[k])) return false; return true; }
-
 /* the new frame's table entry, its clouds at the regions' tops */
 static ll_keyframe_info kf_entry(ll_keyframes *kf, int lane, int frame, const int n[2], const double *pose)
 {
@@ -132,7 +131,7 @@ extern "C" int ll_keyframes_add_cubemaps(ll_keyframes *kf, ll_cubemaps *cms, con
     for (int q = 0; q < S; ++q) {
         if (sel[q] != 0 && sel[q] != 1) return kf_fail(kf, LL_ERR_ARG, "keyframes: sequence " + std::to_string(q) + ": sel must be 0 or 1");
         if (!sel[q]) continue;
-        if (!kf_finite7(pose_w7 + (size_t)q * 7)) return kf_fail(kf, LL_ERR_ARG, "keyframes: sequence " + std::to_string(q) + ": non-finite pose");
+        if (!ll_finite_n(pose_w7 + (size_t)q * 7, 7)) return kf_fail(kf, LL_ERR_ARG, "keyframes: sequence " + std::to_string(q) + ": non-finite pose");
         const ll_cubemap *cm = llcms_map(cms, q);
         if (cm->broken) return kf_fail(kf, LL_ERR_STATE, "keyframes: sequence " + std::to_string(q) + ": unusable, an earlier update failed half-way");
         if (!cm->has_frame) return kf_fail(kf, LL_ERR_STATE, "keyframes: sequence " + std::to_string(q) + " has run no frame since create / reset / import");
@@ -175,7 +174,7 @@ extern "C" int ll_keyframes_add_points(ll_keyframes *kf, const ll_point *corner,
 {
     if (!kf) return LL_ERR_ARG;
     if (!pose_w7 || n_corner < 0 || n_surf < 0 || (n_corner > 0 && !corner) || (n_surf > 0 && !surf)) return kf_fail(kf, LL_ERR_ARG, "keyframes: NULL cloud or pose, or a negative size");
-    if (!kf_finite7(pose_w7)) return kf_fail(kf, LL_ERR_ARG, "keyframes: non-finite pose");
+    if (!ll_finite_n(pose_w7, 7)) return kf_fail(kf, LL_ERR_ARG, "keyframes: non-finite pose");
     const int n[2] = {n_corner, n_surf};
     const long long need[2] = {n_corner, n_surf};
     int rc = kf_room(kf, 1, need); if (rc) return rc;

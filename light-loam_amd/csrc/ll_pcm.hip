@@ -311,9 +311,6 @@ static int pcm_layout(ll_pcm *v, int n_graphs, const int *cand_off, std::vector<
     return LL_OK;
 }
 
-static bool pcm_finite(const double *p, int n) { for (int k = 0; k < n; ++k) if (!std::isfinite(p[k])) return false; return true; }
-static bool pcm_zero_quat(const double *q) { return q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0; }
-
 static bool pcm_params_ok(const ll_pcm_params &p)
 {
     const double t[4] = {p.rot_tol, p.trans_tol, p.rot_rate, p.trans_rate};
@@ -321,28 +318,20 @@ static bool pcm_params_ok(const ll_pcm_params &p)
     return true;
 }
 
-/* plain f64 C: the quaternion normalised as n = sqrt((x*x + y*y) + (z*z + w*w)), each component / n */
-static void pcm_normalise(const double *in, double *out)
-{
-    const double n = std::sqrt((in[0] * in[0] + in[1] * in[1]) + (in[2] * in[2] + in[3] * in[3]));
-    for (int k = 0; k < 4; ++k) out[k] = in[k] / n;
-    for (int k = 4; k < 7; ++k) out[k] = in[k];
-}
-
 /* one graph's poses and candidates checked; msg: what is wrong ("" if nothing) */
 static std::string pcm_check_graph(int n, const double *poses, int C, const ll_pcm_candidate *cand)
 {
     for (int k = 0; k < n; ++k) {
-        if (!pcm_finite(poses + (size_t)k * 7, 7)) return "node " + std::to_string(k) + ": the pose is not finite";
-        if (pcm_zero_quat(poses + (size_t)k * 7)) return "node " + std::to_string(k) + ": zero quaternion";
+        if (!ll_finite_n(poses + (size_t)k * 7, 7)) return "node " + std::to_string(k) + ": the pose is not finite";
+        if (ll_zero_quat(poses + (size_t)k * 7)) return "node " + std::to_string(k) + ": zero quaternion";
     }
     for (int c = 0; c < C; ++c) {
         const ll_pcm_candidate &e = cand[c];
         const std::string cs = "candidate " + std::to_string(c);
         if (e.i < 0 || e.i >= n || e.j < 0 || e.j >= n) return cs + ": a node index lies outside the graph";
         if (e.i == e.j) return cs + ": i == j";
-        if (!pcm_finite(e.Z_w7, 7)) return cs + ": the measurement is not finite";
-        if (pcm_zero_quat(e.Z_w7)) return cs + ": zero quaternion";
+        if (!ll_finite_n(e.Z_w7, 7)) return cs + ": the measurement is not finite";
+        if (ll_zero_quat(e.Z_w7)) return cs + ": zero quaternion";
     }
     return "";
 }
@@ -350,7 +339,7 @@ static std::string pcm_check_graph(int n, const double *poses, int C, const ll_p
 /* normalised poses and the path length s of one graph */
 static void pcm_host_nodes(int n, const double *poses, double *P, double *s)
 {
-    for (int k = 0; k < n; ++k) pcm_normalise(poses + (size_t)k * 7, P + (size_t)k * 7);
+    for (int k = 0; k < n; ++k) ll_pose_unit(poses + (size_t)k * 7, P + (size_t)k * 7);
     for (int k = 0; k < n; ++k) {
         if (k == 0) { s[0] = 0.0; continue; }
         const double dx = P[k * 7 + 4] - P[(k - 1) * 7 + 4], dy = P[k * 7 + 5] - P[(k - 1) * 7 + 5], dz = P[k * 7 + 6] - P[(k - 1) * 7 + 6];
@@ -460,7 +449,7 @@ extern "C" int ll_pcm_run(ll_pcm *v, int n_graphs, const int *node_off, const in
         const int n0 = node_off[g];
         pcm_host_nodes(node_off[g + 1] - n0, poses_w7 + (size_t)n0 * 7, hp + (size_t)n0 * 7, hs + n0);
         for (int c = tab[g].c0; c < tab[g].c0 + tab[g].C; ++c) {
-            pcm_normalise(candidates[c].Z_w7, hc[c].Z);
+            ll_pose_unit(candidates[c].Z_w7, hc[c].Z);
             hc[c].i = n0 + candidates[c].i; hc[c].j = n0 + candidates[c].j;
         }
         maxC = std::max(maxC, tab[g].C);
@@ -564,7 +553,7 @@ extern "C" int ll_pcm_host(int n_nodes, const double *poses_w7, int C, const ll_
     pcm_host_nodes(n_nodes, poses_w7, Pn.data(), s.data());
     for (int c = 0; c < C; ++c) {
         double Z[7];
-        pcm_normalise(candidates[c].Z_w7, Z);
+        ll_pose_unit(candidates[c].Z_w7, Z);
         pcm_prepare(&Pn[(size_t)candidates[c].i * 7], &Pn[(size_t)candidates[c].j * 7], Z, s[candidates[c].i], s[candidates[c].j], &prep[(size_t)c * PCM_PREP]);
     }
     const PcmTol tol = {P.rot_tol, P.trans_tol, P.rot_rate, P.trans_rate};

@@ -1,8 +1,10 @@
 /* ll_pcm_math.h -- the pair arithmetic of ll_pcm (include/lightloam_hip.h states it float by float), once: k_pcm_prepare and
  * k_pcm_adjacency (ll_pcm.hip) and ll_pcm_host run this text, so the CPU tests of ll_pcm_host pin the device's arithmetic.  Only
  * + - * and comparisons in f64, every operation rounded on its own (the build has -ffp-contract=off for host and device).
- * A pose is pose_w7 (qx, qy, qz, qw, tx, ty, tz) with a unit quaternion: the host normalised it. */
+ * A pose is pose_w7 (qx, qy, qz, qw, tx, ty, tz) with a unit quaternion: the host normalised it.  The product and the matrix are
+ * ll_pose_math.h's; compose and inverse here are the MATRIX-form pair (ll_pose_compose / ll_pose_inverse round differently). */
 #pragma once
+#include "ll_pose_math.h"
 
 #define PCM_HD __host__ __device__ __forceinline__
 #define PCM_PREP 23                      /* per candidate: B 7, Ai 7, P_i 7, s_i, s_j */
@@ -10,31 +12,19 @@
 
 struct PcmTol { double rot_tol, trans_tol, rot_rate, trans_rate; };
 
-PCM_HD void pcm_qmul(const double *a, const double *b, double *o)            /* (x, y, z, w): pg_qmul's operation order */
-{
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
-    o[2] = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
-
-/* o = R(q) v: the matrix entry by entry, then every row as (R0 v0 + R1 v1) + R2 v2 */
+/* o = R(q) v in the matrix form: the matrix entry by entry, then every row as (R0 v0 + R1 v1) + R2 v2 */
 PCM_HD void pcm_rotate(const double *q, const double *v, double *o)
 {
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double r00 = 1.0 - 2.0 * (y * y + z * z), r01 = 2.0 * (x * y - z * w), r02 = 2.0 * (x * z + y * w);
-    const double r10 = 2.0 * (x * y + z * w), r11 = 1.0 - 2.0 * (x * x + z * z), r12 = 2.0 * (y * z - x * w);
-    const double r20 = 2.0 * (x * z - y * w), r21 = 2.0 * (y * z + x * w), r22 = 1.0 - 2.0 * (x * x + y * y);
-    o[0] = (r00 * v[0] + r01 * v[1]) + r02 * v[2];
-    o[1] = (r10 * v[0] + r11 * v[1]) + r12 * v[2];
-    o[2] = (r20 * v[0] + r21 * v[1]) + r22 * v[2];
+    double R[3][3];
+    ll_quat_matrix(q, R);
+    ll_mat_apply(R, v, o);
 }
 
 /* a o b = (q_a (x) q_b, R(q_a) t_b + t_a) */
 PCM_HD void pcm_compose(const double *a, const double *b, double *o)
 {
     double r[3];
-    pcm_qmul(a, b, o);
+    ll_qmul(a, b, o);
     pcm_rotate(a, b + 4, r);
     o[4] = r[0] + a[4]; o[5] = r[1] + a[5]; o[6] = r[2] + a[6];
 }

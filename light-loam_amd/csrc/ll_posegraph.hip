@@ -83,59 +83,77 @@ struct ll_posegraphs {
     std::string err;
 };
 
-/* ------------------------------------------------------------------ device: one edge */
-__device__ __forceinline__ void pg_qmul(const double a[4], const double b[4], double o[4])     /* (x, y, z, w) */
+/* ------------------------------------------------------------------ one edge: the kernels' text and ll_pg_edge_gate's
+ * the UNWEIGHTED error er = [2 sgn(w_e) vec(q_e) ; t_e] of an edge at the unit poses (Pi, Pj), with a = qzc (x) q_i*, q_e = a (x) q_j and
+ * t_e = R(a) (t_j - t_i) - R(qzc) t_z; qzc is the unit conjugate of the measurement's quaternion, t_z its translation.  With A != NULL
+ * also what the Jacobians are made of: A (3 x 3, see above), Ra = R(a), v = t_j - t_i.  R(a) v is the matrix form.  z_matrix_form says
+ * which form R(qzc) t_z takes: the kernels have always used the Eigen form and ll_pg_edge_gate the matrix form, and the two round
+ * differently, so each caller keeps its bits */
+LL_HD void pg_error(const double *Pi, const double *Pj, const double *qzc, const double *t_z, bool z_matrix_form, double er[6], double (*A)[3], double (*Ra)[3], double *v)
 {
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
-    o[2] = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
-
-/* the UNWEIGHTED error er = [2 sgn(w_e) vec(q_e) ; t_e] of an edge with measurement Z at (Pi, Pj); with A != NULL also what the
- * Jacobians are made of: A (3 x 3, see above), Ra = R(a), v */
-__device__ __forceinline__ void pg_error(const double *Pi, const double *Pj, const double *Z_w7, double er[6], double (*A)[3], double (*Ra)[3], double *v)
-{
-    const double zn = sqrt((Z_w7[0] * Z_w7[0] + Z_w7[1] * Z_w7[1]) + (Z_w7[2] * Z_w7[2] + Z_w7[3] * Z_w7[3]));
-    const double qzc[4] = {-Z_w7[0] / zn, -Z_w7[1] / zn, -Z_w7[2] / zn, Z_w7[3] / zn};
     const double qic[4] = {-Pi[0], -Pi[1], -Pi[2], Pi[3]};
-    double a[4], qe[4];
-    pg_qmul(qzc, qic, a);
-    pg_qmul(a, Pj, qe);
+    double a[4], qe[4], R[3][3], te[3], tz[3];
+    ll_qmul(qzc, qic, a);
+    ll_qmul(a, Pj, qe);
     const double sgn = qe[3] < 0.0 ? -1.0 : 1.0;
-    const double x = a[0], y = a[1], z = a[2], w = a[3];
-    const double R[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)},
-                            {2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)},
-                            {2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)}};
+    ll_quat_matrix(a, R);
     const double dv[3] = {Pj[4] - Pi[4], Pj[5] - Pi[5], Pj[6] - Pi[6]};
-    double tz[3];
-    ll_rotate(qzc, Z_w7 + 4, tz);                                 /* R(q_z)^T t_z */
+    if (z_matrix_form) { double Rz[3][3]; ll_quat_matrix(qzc, Rz); ll_mat_apply(Rz, t_z, tz); }
+    else ll_rotate(qzc, t_z, tz);
+    for (int k = 0; k < 3; ++k) te[k] = (R[k][0] * dv[0] + R[k][1] * dv[1]) + R[k][2] * dv[2];   /* ll_mat_apply's row, kept in place (below) */
     for (int k = 0; k < 3; ++k) {
         er[k] = 2.0 * sgn * qe[k];
-        er[3 + k] = ((R[k][0] * dv[0] + R[k][1] * dv[1]) + R[k][2] * dv[2]) - tz[k];
+        er[3 + k] = te[k] - tz[k];
     }
     if (!A) return;
     for (int k = 0; k < 3; ++k) {
         double ek[4] = {0.0, 0.0, 0.0, 0.0}, ae[4], c[4];
         ek[k] = 1.0;
-        pg_qmul(a, ek, ae);
-        pg_qmul(ae, Pj, c);
+        ll_qmul(a, ek, ae);
+        ll_qmul(ae, Pj, c);
         for (int m = 0; m < 3; ++m) { A[m][k] = 2.0 * sgn * c[m]; Ra[m][k] = R[m][k]; }
         v[k] = dv[k];
     }
+}
+
+/* the unweighted Jacobians Je_i = [ -A  0 ; 2 R(a)[v]x  -R(a) ], Je_j = [ A  0 ; 0  R(a) ], for ll_pg_edge_gate.  The kernels keep
+ * three lines of this file's arithmetic in place -- this assembly in both pg_edge_linearise, the row of R(a) v in pg_error, the
+ * normalisation on entry: with the shared functions there the device code differs from its predecessor's (at least in the operand
+ * order of some v_mul_f64) and measured outside that code's own run-to-run band in some configurations */
+LL_HD void pg_jacobians(const double (*A)[3], const double (*Ra)[3], const double *v, double (*Jei)[6], double (*Jej)[6])
+{
+    const double vx[3][3] = {{0.0, -v[2], v[1]}, {v[2], 0.0, -v[0]}, {-v[1], v[0], 0.0}};
+    for (int m = 0; m < 3; ++m)
+        for (int k = 0; k < 3; ++k) {
+            Jei[m][k] = -A[m][k];            Jei[m][3 + k] = 0.0;
+            Jej[m][k] = A[m][k];             Jej[m][3 + k] = 0.0;
+            Jei[3 + m][k] = 2.0 * ((Ra[m][0] * vx[0][k] + Ra[m][1] * vx[1][k]) + Ra[m][2] * vx[2][k]);
+            Jei[3 + m][3 + k] = -Ra[m][k];
+            Jej[3 + m][k] = 0.0;             Jej[3 + m][3 + k] = Ra[m][k];
+        }
+}
+
+/* ------------------------------------------------------------------ device: one edge
+ * pg_error of an edge as the graph stores it: Z normalised here, R(q_z)^T t_z in the Eigen form */
+__device__ __forceinline__ void pg_error_z(const double *Pi, const double *Pj, const double *Z_w7, double er[6], double (*A)[3], double (*Ra)[3], double *v)
+{
+    const double zc[4] = {-Z_w7[0], -Z_w7[1], -Z_w7[2], Z_w7[3]};
+    double qzc[4];
+    ll_quat_unit(zc, qzc);
+    pg_error(Pi, Pj, qzc, Z_w7 + 4, false, er, A, Ra, v);
 }
 
 /* the weighted residual r = S er: diag(sqrt_info), or the full matrix row by row, columns ascending */
 __device__ __forceinline__ void pg_residual(const double *Pi, const double *Pj, const ll_pg_edge &e, double r[6], double (*A)[3], double (*Ra)[3], double *v)
 {
     double er[6];
-    pg_error(Pi, Pj, e.Z_w7, er, A, Ra, v);
+    pg_error_z(Pi, Pj, e.Z_w7, er, A, Ra, v);
     for (int k = 0; k < 6; ++k) r[k] = e.sqrt_info[k] * er[k];
 }
 __device__ __forceinline__ void pg_residual(const double *Pi, const double *Pj, const ll_pg_edge6 &e, double r[6], double (*A)[3], double (*Ra)[3], double *v)
 {
     double er[6];
-    pg_error(Pi, Pj, e.Z_w7, er, A, Ra, v);
+    pg_error_z(Pi, Pj, e.Z_w7, er, A, Ra, v);
     for (int m = 0; m < 6; ++m) {
         double s = 0.0;
         for (int k = 0; k < 6; ++k) s += e.S[m * 6 + k] * er[k];
@@ -190,7 +208,7 @@ __device__ __forceinline__ void pg_edge_linearise(const double *Pi, const double
     pg_edge_products(Ji, Jj, r, eH, eg);
 }
 
-/* the full variant: the unweighted Jacobians Je_i = [ -A  0 ; 2 R(a)[v]x  -R(a) ], Je_j = [ A  0 ; 0  R(a) ], then J = w S Je */
+/* the full variant: the unweighted Jacobians Je_i, Je_j as pg_jacobians states them, then J = w S Je */
 __device__ __forceinline__ void pg_edge_linearise(const double *Pi, const double *Pj, const ll_pg_edge6 &e, double *eH, double *eg, double *ecost)
 {
     double r[6], A[3][3], Ra[3][3], v[3], Jei[6][6], Jej[6][6], Ji[6][6], Jj[6][6], c = 0.0;
@@ -577,7 +595,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_solve(PgArgs<Edge> A)
     G.eH = A.eH + (size_t)G.e0 * 108; G.eg = A.eg + (size_t)G.e0 * 12; G.ecost = A.ecost + G.e0;
 
     for (int n = tid; n < G.N; n += PG_THREADS) {                  /* quaternions are normalised on entry */
-        const double *in = A.pose_in + (size_t)(G.n0 + n) * 7;
+        const double *in = A.pose_in + (size_t)(G.n0 + n) * 7;                  /* ll_pose_unit's operations, kept in place */
         const double qn = sqrt((in[0] * in[0] + in[1] * in[1]) + (in[2] * in[2] + in[3] * in[3]));
         for (int k = 0; k < 4; ++k) G.x[(size_t)n * 7 + k] = in[k] / qn;
         for (int k = 4; k < 7; ++k) G.x[(size_t)n * 7 + k] = in[k];
@@ -813,7 +831,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_cov_prepare(PgArgs<Edge> A, c
     PgGraph<Edge> G;
     pg_cov_graph(A, gi, G);
     for (int n = tid; n < G.N; n += PG_THREADS) {                  /* quaternions are normalised on entry */
-        const double *in = A.pose_in + (size_t)(G.n0 + n) * 7;
+        const double *in = A.pose_in + (size_t)(G.n0 + n) * 7;                  /* ll_pose_unit's operations, kept in place */
         const double qn = sqrt((in[0] * in[0] + in[1] * in[1]) + (in[2] * in[2] + in[3] * in[3]));
         for (int k = 0; k < 4; ++k) G.x[(size_t)n * 7 + k] = in[k] / qn;
         for (int k = 4; k < 7; ++k) G.x[(size_t)n * 7 + k] = in[k];
@@ -1095,14 +1113,11 @@ extern "C" int ll_posegraphs_precond_stats(ll_posegraphs *pg, long long counts2[
     return LL_OK;
 }
 
-static bool pg_finite7(const double *p, int n) { for (int k = 0; k < n; ++k) if (!std::isfinite(p[k])) return false; return true; }
-static bool pg_zero_quat(const double *q) { return q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0 && q[3] == 0.0; }
-
 static int pg_check_options(ll_posegraphs *pg, const ll_pg_options &o)
 {
     const double v[10] = {o.eta, o.initial_radius, o.max_radius, o.min_radius, o.min_relative_decrease, o.min_lm_diagonal, o.max_lm_diagonal,
                           o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance};
-    bool ok = o.max_lm_iterations >= 0 && o.max_pcg_iterations >= 1 && pg_finite7(v, 10);
+    bool ok = o.max_lm_iterations >= 0 && o.max_pcg_iterations >= 1 && ll_finite_n(v, 10);
     ok = ok && o.eta > 0.0 && o.eta < 1.0 && o.initial_radius > 0.0 && o.max_radius >= o.initial_radius && o.min_radius >= 0.0 &&
          o.min_relative_decrease >= 0.0 && o.min_relative_decrease < 1.0 && o.min_lm_diagonal > 0.0 && o.max_lm_diagonal >= o.min_lm_diagonal &&
          o.function_tolerance >= 0.0 && o.gradient_tolerance >= 0.0 && o.parameter_tolerance >= 0.0;
@@ -1110,8 +1125,8 @@ static int pg_check_options(ll_posegraphs *pg, const ll_pg_options &o)
                                                 "0 < min_lm_diagonal <= max_lm_diagonal, tolerances >= 0, all finite)");
 }
 
-static bool pg_finite_weights(const ll_pg_edge &e) { return pg_finite7(e.sqrt_info, 6); }
-static bool pg_finite_weights(const ll_pg_edge6 &e) { return pg_finite7(e.S, 36); }
+static bool pg_finite_weights(const ll_pg_edge &e) { return ll_finite_n(e.sqrt_info, 6); }
+static bool pg_finite_weights(const ll_pg_edge6 &e) { return ll_finite_n(e.S, 36); }
 
 /* the checks every call shares, in two parts (a call's own checks of its outputs and options lie between them): the layout ... */
 template <typename Edge>
@@ -1143,8 +1158,8 @@ static int pg_check_graphs(ll_posegraphs *pg, const char *who, int n_graphs, con
         bool any_fixed = !fixed && n > 0;
         for (int k = 0; k < n; ++k) {
             const double *p = poses_w7 + (size_t)(n0 + k) * 7;
-            if (!pg_finite7(p, 7)) return bad(LL_ERR_ARG, gs + ", node " + std::to_string(k) + ": the pose is not finite");
-            if (pg_zero_quat(p)) return bad(LL_ERR_ARG, gs + ", node " + std::to_string(k) + ": zero quaternion");
+            if (!ll_finite_n(p, 7)) return bad(LL_ERR_ARG, gs + ", node " + std::to_string(k) + ": the pose is not finite");
+            if (ll_zero_quat(p)) return bad(LL_ERR_ARG, gs + ", node " + std::to_string(k) + ": zero quaternion");
             if (fixed && fixed[n0 + k]) any_fixed = true;
         }
         if (!any_fixed) return bad(LL_ERR_ARG, gs + " has no fixed node");
@@ -1153,8 +1168,8 @@ static int pg_check_graphs(ll_posegraphs *pg, const char *who, int n_graphs, con
             const std::string es = gs + ", edge " + std::to_string(e - edge_off[g]);
             if (ed.i < 0 || ed.i >= n || ed.j < 0 || ed.j >= n) return bad(LL_ERR_ARG, es + ": a node index lies outside the graph");
             if (ed.i == ed.j) return bad(LL_ERR_ARG, es + ": i == j");
-            if (!pg_finite7(ed.Z_w7, 7) || !pg_finite_weights(ed) || !std::isfinite(ed.huber)) return bad(LL_ERR_ARG, es + ": the measurement or a weight is not finite");
-            if (pg_zero_quat(ed.Z_w7)) return bad(LL_ERR_ARG, es + ": zero quaternion");
+            if (!ll_finite_n(ed.Z_w7, 7) || !pg_finite_weights(ed) || !std::isfinite(ed.huber)) return bad(LL_ERR_ARG, es + ": the measurement or a weight is not finite");
+            if (ll_zero_quat(ed.Z_w7)) return bad(LL_ERR_ARG, es + ": zero quaternion");
         }
     }
     return LL_OK;
@@ -1307,19 +1322,16 @@ extern "C" int ll_posegraphs_solve(ll_posegraphs *pg, int n_graphs, const int *n
 extern "C" int ll_pg_edge_from_info(const ll_pose_info *info, const double *X_w7, double sigma, double floor, double S36[36])
 {
     if (!info || !X_w7 || !S36) return LL_ERR_ARG;
-    if (!pg_finite7(X_w7, 7) || !std::isfinite(sigma) || !std::isfinite(floor) || floor < 0.0 || pg_zero_quat(X_w7)) return LL_ERR_ARG;
+    if (!ll_finite_n(X_w7, 7) || !std::isfinite(sigma) || !std::isfinite(floor) || floor < 0.0 || ll_zero_quat(X_w7)) return LL_ERR_ARG;
     if (info->flags & 1) return LL_ERR_STATE;
     double s2 = sigma * sigma;
     if (!(sigma > 0.0)) {
         if (!(info->sigma2 > 0.0) || !std::isfinite(info->sigma2)) return LL_ERR_STATE;
         s2 = info->sigma2;
     }
-    const double qn = std::sqrt((X_w7[0] * X_w7[0] + X_w7[1] * X_w7[1]) + (X_w7[2] * X_w7[2] + X_w7[3] * X_w7[3]));
-    const double x = X_w7[0] / qn, y = X_w7[1] / qn, z = X_w7[2] / qn, w = X_w7[3] / qn;
-    const double R[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)},
-                            {2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)},
-                            {2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)}};
-    double Mi[6][6] = {}, HM[6][6], L[6][6];
+    double qx[4], R[3][3], Mi[6][6] = {}, HM[6][6], L[6][6];
+    ll_quat_unit(X_w7, qx);
+    ll_quat_matrix(qx, R);
     for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) { Mi[a][b] = 0.5 * R[a][b]; Mi[3 + a][3 + b] = R[a][b]; }
     for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) { double s = 0.0; for (int k = 0; k < 6; ++k) s += info->H[a * 6 + k] * Mi[k][b]; HM[a][b] = s; }
     for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) { double s = 0.0; for (int k = 0; k < 6; ++k) s += Mi[k][a] * HM[k][b]; L[a][b] = s / s2; }
@@ -1382,7 +1394,7 @@ extern "C" int ll_posegraphs_chain_solve(ll_posegraphs *pg, int n_systems, const
     for (int g = 0; g < n_systems; ++g)
         for (int k = node_off[g]; k < node_off[g + 1]; ++k) {
             const bool last = k + 1 == node_off[g + 1];            /* its coupling is not read */
-            if (!pg_finite7(diag36 + (size_t)k * 36, 36) || (!last && !pg_finite7(upper36 + (size_t)k * 36, 36)) || !pg_finite7(rhs6 + (size_t)k * 6, 6))
+            if (!ll_finite_n(diag36 + (size_t)k * 36, 36) || (!last && !ll_finite_n(upper36 + (size_t)k * 36, 36)) || !ll_finite_n(rhs6 + (size_t)k * 6, 6))
                 return bad(LL_ERR_ARG, "system " + std::to_string(g) + ", node " + std::to_string(k - node_off[g]) + ": a block or the right-hand side is not finite");
         }
     if (n_systems == 0) return LL_OK;
@@ -1598,63 +1610,7 @@ extern "C" int ll_posegraphs_cov_timing(ll_posegraphs *pg, double ms2[2], long l
 }
 
 /* ------------------------------------------------------------------ the gate (host arithmetic only; the contract is in the header)
- * pg_error restated for the host: the unweighted error e of the edge a -> b and its unweighted Jacobians
- * J_a = [ -A 0 ; 2 R(a)[v]x  -R(a) ], J_b = [ A 0 ; 0 R(a) ] (the formulas at the top of this file). */
-static void pgh_qmul(const double a[4], const double b[4], double o[4])
-{
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
-    o[2] = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
-
-static void pgh_unit(const double *P, double out[7])
-{
-    const double n = std::sqrt((P[0] * P[0] + P[1] * P[1]) + (P[2] * P[2] + P[3] * P[3]));
-    for (int k = 0; k < 4; ++k) out[k] = P[k] / n;
-    for (int k = 4; k < 7; ++k) out[k] = P[k];
-}
-
-static void pgh_matrix(const double q[4], double R[3][3])
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double M[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)},
-                            {2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)},
-                            {2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)}};
-    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) R[a][b] = M[a][b];
-}
-
-static void pgh_error(const double Pi[7], const double Pj[7], const double Z[7], double er[6], double Ji[6][6], double Jj[6][6])
-{
-    const double qzc[4] = {-Z[0], -Z[1], -Z[2], Z[3]}, qic[4] = {-Pi[0], -Pi[1], -Pi[2], Pi[3]};
-    double a[4], qe[4], R[3][3], Rz[3][3];
-    pgh_qmul(qzc, qic, a);
-    pgh_qmul(a, Pj, qe);
-    const double sgn = qe[3] < 0.0 ? -1.0 : 1.0;
-    pgh_matrix(a, R);
-    pgh_matrix(qzc, Rz);                                           /* R(q_z)^T */
-    const double v[3] = {Pj[4] - Pi[4], Pj[5] - Pi[5], Pj[6] - Pi[6]};
-    const double vx[3][3] = {{0.0, -v[2], v[1]}, {v[2], 0.0, -v[0]}, {-v[1], v[0], 0.0}};
-    for (int k = 0; k < 3; ++k) {
-        er[k] = 2.0 * sgn * qe[k];
-        er[3 + k] = ((R[k][0] * v[0] + R[k][1] * v[1]) + R[k][2] * v[2]) - ((Rz[k][0] * Z[4] + Rz[k][1] * Z[5]) + Rz[k][2] * Z[6]);
-    }
-    for (int k = 0; k < 3; ++k) {
-        double ek[4] = {0.0, 0.0, 0.0, 0.0}, ae[4], c[4];
-        ek[k] = 1.0;
-        pgh_qmul(a, ek, ae);
-        pgh_qmul(ae, Pj, c);
-        for (int m = 0; m < 3; ++m) {
-            const double A = 2.0 * sgn * c[m];
-            Ji[m][k] = -A;                   Ji[m][3 + k] = 0.0;
-            Jj[m][k] = A;                    Jj[m][3 + k] = 0.0;
-            Ji[3 + m][k] = 2.0 * ((R[m][0] * vx[0][k] + R[m][1] * vx[1][k]) + R[m][2] * vx[2][k]);
-            Ji[3 + m][3 + k] = -R[m][k];
-            Jj[3 + m][k] = 0.0;              Jj[3 + m][3 + k] = R[m][k];
-        }
-    }
-}
-
+ * pg_error and pg_jacobians above, the text the solver linearises an edge with, at the normalised poses; R(q_z)^T t_z in the matrix form. */
 /* L (lower, L L^T = M) of a symmetric 6 x 6; false at a pivot that is not positive and finite */
 static bool pgh_chol6(const double M[6][6], double L[6][6])
 {
@@ -1672,11 +1628,13 @@ extern "C" int ll_pg_edge_gate(const double *Pa_w7, const double *Pb_w7, const d
                                double *chi2, double cov36[36])
 {
     if (!Pa_w7 || !Pb_w7 || !Z_w7 || !joint144 || !chi2) return LL_ERR_ARG;
-    if (!pg_finite7(Pa_w7, 7) || !pg_finite7(Pb_w7, 7) || !pg_finite7(Z_w7, 7) || !pg_finite7(joint144, 144) || (S36 && !pg_finite7(S36, 36))) return LL_ERR_ARG;
-    if (pg_zero_quat(Pa_w7) || pg_zero_quat(Pb_w7) || pg_zero_quat(Z_w7)) return LL_ERR_ARG;
-    double Pa[7], Pb[7], Z[7], e[6], Ja[6][6], Jb[6][6], Cm[6][6], L[6][6];
-    pgh_unit(Pa_w7, Pa); pgh_unit(Pb_w7, Pb); pgh_unit(Z_w7, Z);
-    pgh_error(Pa, Pb, Z, e, Ja, Jb);
+    if (!ll_finite_n(Pa_w7, 7) || !ll_finite_n(Pb_w7, 7) || !ll_finite_n(Z_w7, 7) || !ll_finite_n(joint144, 144) || (S36 && !ll_finite_n(S36, 36))) return LL_ERR_ARG;
+    if (ll_zero_quat(Pa_w7) || ll_zero_quat(Pb_w7) || ll_zero_quat(Z_w7)) return LL_ERR_ARG;
+    double Pa[7], Pb[7], Z[7], e[6], A[3][3], Ra[3][3], v[3], Ja[6][6], Jb[6][6], Cm[6][6], L[6][6];
+    ll_pose_unit(Pa_w7, Pa); ll_pose_unit(Pb_w7, Pb); ll_pose_unit(Z_w7, Z);
+    const double qzc[4] = {-Z[0], -Z[1], -Z[2], Z[3]};
+    pg_error(Pa, Pb, qzc, Z + 4, true, e, A, Ra, v);
+    pg_jacobians(A, Ra, v, Ja, Jb);
     for (int m = 0; m < 6; ++m)                                    /* C = J Sigma J^T, J = [J_a J_b] */
         for (int n = 0; n < 6; ++n) {
             double s = 0.0;

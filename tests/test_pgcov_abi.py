@@ -39,7 +39,7 @@ def test_library_exports_the_covariances(api):
         assert name in api.EXPORTS, name
         assert len(getattr(lib, name).argtypes) == n, name
     assert lib.ll_abi_version() == 3                                # functions and structs of their own only
-    for name in ("k_pg_cov_prepare", "k_pg_cov_columns", "k_pg_cov_gather", "pg_cov_run", "pgh_error"):
+    for name in ("k_pg_cov_prepare", "k_pg_cov_columns", "k_pg_cov_gather", "pg_cov_run", "pg_error", "pg_jacobians", "pg_error_z"):
         assert not hasattr(lib, name), name
 
 
